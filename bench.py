@@ -21,7 +21,7 @@ The same JSON line also carries (N = 1):
               sinks (include/nanosim_amd.h: ns_sink_*), to /dev/null and to files on /dev/shm, with and without the error profile
               the reference always writes, next to the measured page-locked device-to-host rate.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -274,6 +274,7 @@ class Workload:
         engine = self.engine
         base = (i * self.world + self.rank) * n
         out = [None, None]
+        self.last_batches = last = [None, None]        # what the step returned (--dump-outputs)
 
         p_al = engine.make_params(seed=SEED, first_read=base, n_reads=n_al, fastq=self.fastq, max_len=self.max_len, emit_errlog=errlog,
                                   kmer_bias=self.kmer, emit_records=records, chimeric=self.chimeric, meta=self.meta)
@@ -282,13 +283,13 @@ class Workload:
 
         def aligned():
             b = self.eng.generate(p_al)
-            out[0] = b.info
+            out[0], last[0] = b.info, b
             if after_aligned:
                 after_aligned(b)
 
         def unaligned(e):
             b = e.generate(p_un)
-            out[1] = b.info
+            out[1], last[1] = b.info, b
             if after_unaligned:
                 after_unaligned(b)
         if not n_un:
@@ -296,10 +297,12 @@ class Workload:
             return out[:1]
         if self.eng_un is None or serial:                      # one engine, one call after the other
             aligned(); unaligned(self.eng)
+            last[0] = None                                     # (the unaligned call reused the aligned batch's buffers)
             return out
         if not self.python_threads:                            # ONE library call per step (ns_generate_step)
             b_al, b_un = self.eng.generate_step(p_al, p_un)
             out[0], out[1] = b_al.info, b_un.info
+            last[0], last[1] = b_al, b_un
             if after_aligned:
                 after_aligned(b_al)
             if after_unaligned:
@@ -591,6 +594,58 @@ def extra_legs(w, a, n, n_al, n_un, steps):
     return out
 
 
+DUMP_READS = 65536             # --dump-outputs: rows of the read table per batch (a seeded sample of the batch's reads)
+DUMP_TEXTS = 1024              # ... reads of that sample whose record (and error-profile) text is written,
+DUMP_TEXT_BYTES = 4096         # ... the first DUMP_TEXT_BYTES bytes of each
+DUMP_LIMIT = 64_000_000
+INFO_FIELDS = ("n_reads", "n_pieces", "n_events", "events_used", "record_bytes", "errlog_bytes", "total_bases", "total_ref_bases",
+               "n_overflow", "spliced_bytes", "n_range_redraws")
+
+
+def dump_outputs(w, d):
+    """--dump-outputs DIR: what the last timed step returned to its caller, as .npy files (float64; text bytes as float32), for an output
+    by output comparison of two builds.  Per batch (<kind> = aligned / unaligned):
+      <kind>_info             the batch's counts (INFO_FIELDS, in that order; no timings)
+      <kind>_read_index       DUMP_READS read indices of the batch, drawn with the bench seed, ascending
+      <kind>_reads_<field>    every field of the read table (nanosim_amd/model.py: READ_DTYPE) at those indices
+      <kind>_records          (DUMP_TEXTS, DUMP_TEXT_BYTES): the record text of the first DUMP_TEXTS sampled reads, -1 past its end
+      <kind>_errlog           the same of the error-profile text (--errlog)
+    --serial: the unaligned worker call reuses the aligned batch's buffers, so only the unaligned batch is written."""
+    import numpy as np
+    from nanosim_amd import model
+    E = w.engine
+    os.makedirs(d, exist_ok=True)
+    files = {}
+    for kind, b in zip(("aligned", "unaligned"), getattr(w, "last_batches", ())):
+        if b is None:
+            continue
+        n = int(b.info.n_reads)
+        files[kind + "_info"] = np.array([float(getattr(b.info, f)) for f in INFO_FIELDS], dtype=np.float64)
+        idx = np.sort(np.random.default_rng(SEED).choice(n, size=min(n, DUMP_READS), replace=False))
+        files[kind + "_read_index"] = idx.astype(np.float64)
+        reads = b.reads()[idx]
+        for f in model.READ_DTYPE.names:
+            files[kind + "_reads_" + f] = reads[f].astype(np.float64)
+        pick = idx[:DUMP_TEXTS]
+        ro, eo = b.record_offsets(np.concatenate([pick, pick + 1]))
+        buf = np.empty(DUMP_TEXT_BYTES, dtype=np.uint8)
+        for name, which, off, total in (("records", E.NS_BUF_RECORDS, ro, int(b.info.record_bytes)),
+                                        ("errlog", E.NS_BUF_ERRLOG, eo, int(b.info.errlog_bytes))):
+            if total == 0:
+                continue
+            txt = np.full((len(pick), DUMP_TEXT_BYTES), -1.0, dtype=np.float32)
+            for r in range(len(pick)):
+                lo, hi = int(off[r]), int(off[len(pick) + r])
+                k = min(hi - lo, DUMP_TEXT_BYTES)
+                txt[r, :k] = b.copy_range(which, lo, buf, k)
+            files["%s_%s" % (kind, name)] = txt
+    nbytes = sum(x.nbytes for x in files.values())
+    assert nbytes <= DUMP_LIMIT, nbytes
+    for name, x in files.items():
+        np.save(os.path.join(d, name + ".npy"), x)
+    return {"dir": d, "files": len(files), "bytes": nbytes}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -624,6 +679,8 @@ def main():
                                                                   "step for the unaligned worker call, instead of ns_generate_step (A/B runs)")
     ap.add_argument("--no-solo-reference", action="store_true", help="N > 1: skip rank 0's single-rank repeat of the timed steps (multi_gpu.single_rank_reference)")
     ap.add_argument("--extras-steps", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (rank 0; a seeded sample, "
+                                                          "at most 64 MB in all): the outputs of two builds can be compared")
     a = ap.parse_args()
     a.aligned_only = a.aligned_only or a.no_genome_run
     genome = "zymo10" if a.metagenome else a.genome
@@ -640,14 +697,16 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if os.environ.get("NS_BENCH_DEVICE") is not None:          # test aid: several ranks on one GPU (gloo only)
         local_rank = int(os.environ["NS_BENCH_DEVICE"])
-    # one rank builds a missing engine, the others wait on the lock and then find it up to date
-    with open(os.path.join(ROOT, ".build.lock"), "w") as lk:
-        fcntl.flock(lk, fcntl.LOCK_EX)
-        try:
-            if not os.path.exists(graft.HIP_OUT):
-                graft.build()
-        finally:
-            fcntl.flock(lk, fcntl.LOCK_UN)
+    # one rank builds a missing engine, the others wait on the lock and then find it up to date; a built tree is only read (it may be
+    # read-only)
+    if not os.path.exists(graft.HIP_OUT):
+        with open(os.path.join(ROOT, ".build.lock"), "w") as lk:
+            fcntl.flock(lk, fcntl.LOCK_EX)
+            try:
+                if not os.path.exists(graft.HIP_OUT):
+                    graft.build()
+            finally:
+                fcntl.flock(lk, fcntl.LOCK_UN)
     from nanosim_amd import engine
 
     dist = None
@@ -673,6 +732,7 @@ def main():
     n = a.reads
     n_al, n_un = w.split(n, a.aligned_only)
     infos, dt, dt_local = timed_steps(w, a, n, n_al, n_un, a.steps, a.warmup, dist, a.errlog)
+    dumped = dump_outputs(w, a.dump_outputs) if a.dump_outputs and rank == 0 else None
     tot_bases = sum(int(x.total_bases) for st in infos for x in st)
     per_rank = None
     if dist is not None:
@@ -699,6 +759,8 @@ def main():
         dist.barrier()
     if rank == 0:
         out = summarise(w, a, infos, dt, n, n_al, n_un, a.steps, a.warmup, world, tot_bases, a.errlog)
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if world > 1:
             out["multi_gpu"] = {"world_size": dist.get_world_size(), "backend": "RCCL (torch.distributed nccl)" if a.dist_backend == "nccl" else a.dist_backend,
                                 "backend_reported": dist.get_backend(),

@@ -348,3 +348,42 @@ def test_bench_metagenome_and_extras_objects():
     assert 0 < d["errlog_on"]["k_errlog_frac"] < 1 and d["errlog_on"]["errlog_bytes_per_read"] > 1000
     r = d["roofline"]
     assert r["frac_kernel_only_bytes"] < r["frac"] < 1
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """--dump-outputs: the same arguments write the same arrays (float32 / float64, within 64 MB); --steps sets the timed steps; the record
+    and error-profile rows are the texts of the sampled reads of the last timed step — the oracle's bytes for those read indices"""
+    import bench
+    from nanosim_amd import synth
+    n, steps, warmup = 100000, 3, 1
+    args = ["--steps", str(steps), "--warmup", str(warmup), "--reads", str(n), "--errlog", "--no-cpu-baseline", "--no-e2e", "--no-configs2",
+            "--no-extras"]
+    runs = [tmp_path / "a", tmp_path / "b"]
+    for d in runs:
+        line = _bench_line(args + ["--dump-outputs", str(d)])
+        assert line["steps"] == steps and line["dump_outputs"]["bytes"] <= 64_000_000
+    names = sorted(os.listdir(runs[0]))
+    assert names == sorted(os.listdir(runs[1])) and "aligned_records.npy" in names and "aligned_errlog.npy" in names
+    assert "unaligned_records.npy" in names
+    for f in names:
+        x, y = np.load(runs[0] / f), np.load(runs[1] / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    prefix = str(tmp_path / "m" / "hg002_like")
+    os.makedirs(os.path.dirname(prefix))
+    synth.write_model(prefix, synth.SynthModelSpec(n_train=1_000_000, seed=bench.SEED), write_pkl=False)
+    mdl = M.load_model(prefix)
+    n_al, _ = mdl.split_counts(n)
+    names_, off, circ = bench.reference_layout("ecoli")
+    ref = M.Reference(names_, bench.reference_bases("ecoli"), off, circ)
+    base = (warmup + steps - 1) * n                                # read indices of the last timed step
+    al = {k: np.load(runs[0] / ("aligned_%s.npy" % k)) for k in ("info", "read_index", "records", "errlog", "reads_seq_len")}
+    assert al["info"][0] == n_al and len(al["read_index"]) == min(n_al, bench.DUMP_READS)
+    for r in (0, 1, len(al["records"]) - 1):
+        i = int(al["read_index"][r])
+        p = E.make_params(seed=bench.SEED, first_read=base + i, n_reads=1, max_len=ref.max_chrom, emit_errlog=True)
+        exp = O.generate(mdl, ref, p, bytes_per_read=1_000_000, events_per_read=50_000)
+        assert int(exp["reads"]["seq_len"][0]) == al["reads_seq_len"][r]
+        for key, img in (("records", exp["records"]), ("errlog", exp["errlog"])):
+            k = min(len(img), bench.DUMP_TEXT_BYTES)
+            row = al[key][r]
+            assert np.array_equal(row[:k], img[:k].astype(np.float32)) and np.all(row[k:] == -1), (key, r)
