@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define NS_ABI_VERSION 6u
+#define NS_ABI_VERSION 7u
 
 /* error codes */
 #define NS_OK 0
@@ -31,6 +31,9 @@ extern "C" {
 #define NS_EHIP (-4)     /* HIP runtime error (see ns_last_error) */
 #define NS_ESTATE (-5)   /* call order violated (no model / no reference / no batch) */
 #define NS_EIO (-6)      /* a file write of an output sink failed (ENOSPC, EBADF ...; see ns_last_error) */
+#define NS_ESTEP_UNALIGNED (-7) /* ns_generate_step (ABI 7): only the UNALIGNED worker call failed, with an error of its own (anything but
+                                 * NS_EHIP, which is returned as such); the aligned batch in info[0] is complete and usable, the cause
+                                 * is in ns_last_error */
 
 /* ---- model tables: the flat form of the globals read_profile() fills (src/simulator.py:247-251) ---- */
 
@@ -298,6 +301,10 @@ int ns_generate(ns_ctx *ctx, const ns_params *params, ns_batch_info *info);
  * pointer may be NULL (that call is skipped and its info zeroed).  The bytes of both batches are those of two ns_generate calls.
  * The unaligned batch's buffers belong to the companion: ns_step_context returns it (created on first use, owned and destroyed by
  * `ctx`; never pass it to ns_destroy) for ns_copy_out / ns_device_ptr / ns_record_offsets / ns_sink_* / ns_io_counters.
+ * Errors: a failed aligned call returns its own code.  A failed unaligned call returns NS_ESTEP_UNALIGNED (ABI 7) — also when
+ * `aligned` is NULL — and info[0] then holds the complete aligned batch (if one was asked for); the unaligned call's own code (NS_EINVAL,
+ * NS_ESTATE, NS_ENOMEM, NS_EIO) is in the ns_last_error text: "unaligned worker call (error <code>): ...".  An NS_EHIP of the unaligned
+ * call is returned unchanged (a HIP error can leave the device unusable for both calls).
  * Added with ABI 6; ns_generate is unchanged. */
 int ns_generate_step(ns_ctx *ctx, const ns_params *aligned, const ns_params *unaligned, ns_batch_info info[2]);
 int ns_step_context(ns_ctx *ctx, ns_ctx **companion);

@@ -2363,6 +2363,9 @@ static int visiting_order(ns_ctx *ctx, const uint32_t *keys, const uint32_t *idx
     uint32_t *hist = (uint32_t *)ctx->ord_bins.p, *cursor = hist + NS_ORD_BINS;
     const unsigned tiles = (unsigned)((n + 1023) / 1024);
     if (!tiles) return NS_OK;
+    // k_order_scan leaves the bins zeroed, but a call that failed between k_order_hist and k_order_scan would not: the cursors of the
+    // next call would then run past the list.  The histogram is zeroed on every call instead of relying on that (8 KB).
+    HIPCHK(hipMemsetAsync(hist, 0, NS_ORD_BINS * 4, st));
     k_order_hist<<<dim3(std::min(tiles, 256u)), dim3(1024), 0, st>>>(keys, (uint32_t)n, hist);
     k_order_scan<<<dim3(1), dim3(1024), 0, st>>>(hist, cursor);
     k_order_deal<<<dim3(tiles), dim3(1024), 0, st>>>(keys, (uint32_t)n, cursor, list);
@@ -3198,6 +3201,8 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
         uint16_t *h_species = (uint16_t *)h_draw;                                  // (once the sum is taken the draws are no longer needed: reuse the staging)
         for (int retry = 0;; ++retry) {
             const size_t np_l = walked ? np : (size_t)np_spec;                     // the reads of this launch
+            // np_spec == 0 (no read's segments fit the V lengths): the walk would assign no read either; it has no effect a later pass
+            // relies on (the quotas are recomputed per pass from cur_bases, its draws are keyed by (pass, segment)), so it is skipped
             if (!np_l) break;
             MetaHist H;
             uint64_t sp_l, po_l;
@@ -3253,6 +3258,9 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
                 np = (size_t)std::min<uint64_t>(np64, m);
                 walked = true;
                 if (np > np_l) return fail(ctx, NS_ESTATE, "metagenome pass: assign_species reached more reads than the pass planned");
+                // fewer reads than launched (every quota used up): the arena of the pass ends behind the events of the first np reads
+                // (a read beyond np that overflowed its capacity still triggers the re-run below, which takes the np reads only)
+                if (np && np < np_l && (rc = read_small(ctx, st, &pass_cap, P.ev_off + np, 8))) return rc;
             }
             if (!np) {                   // every quota is used up: nothing of this launch counts
                 fold_stats(ctx, st);
@@ -3896,8 +3904,8 @@ int ns_generate_step(ns_ctx *ctx, const ns_params *aligned, const ns_params *una
     if (rc) return rc;
     if (!aligned) {
         rc = ns_generate(c, unaligned, &info[1]);
-        if (rc) ctx->err = "unaligned worker call: " + c->err;
-        return rc;
+        if (rc) ctx->err = "unaligned worker call (error " + std::to_string(rc) + "): " + c->err;
+        return rc && rc != NS_EHIP ? NS_ESTEP_UNALIGNED : rc;
     }
     if (!ctx->step) {
         ctx->step = new ns_ctx::StepWorker();
@@ -3915,7 +3923,7 @@ int ns_generate_step(ns_ctx *ctx, const ns_params *aligned, const ns_params *una
     { std::unique_lock<std::mutex> lk(w->mu); w->cv.wait(lk, [w] { return w->done; }); rc_un = w->rc; w->prm = nullptr; w->info = nullptr; }
     c->gate_wait = nullptr;
     if (rc_al) return rc_al;
-    if (rc_un) { ctx->err = "unaligned worker call: " + c->err; return rc_un; }
+    if (rc_un) { ctx->err = "unaligned worker call (error " + std::to_string(rc_un) + "): " + c->err; return rc_un != NS_EHIP ? NS_ESTEP_UNALIGNED : rc_un; }
     return NS_OK;
 }
 

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NANOSIM_AMD_LIB") or os.path.join(_HERE, "libnanosim_amd.so")   # override: A/B builds only
 NS_BUF_RECORDS, NS_BUF_READS, NS_BUF_PIECES, NS_BUF_EVENTS, NS_BUF_ERRLOG, NS_BUF_POLYA, NS_BUF_SPLICED = 0, 1, 2, 3, 4, 5, 6
 NS_SPLICED_BASE = 1 << 56
-NS_EINVAL, NS_ENODEV, NS_ENOMEM, NS_EHIP, NS_ESTATE, NS_EIO = -1, -2, -3, -4, -5, -6
+NS_EINVAL, NS_ENODEV, NS_ENOMEM, NS_EHIP, NS_ESTATE, NS_EIO, NS_ESTEP_UNALIGNED = -1, -2, -3, -4, -5, -6, -7
 NS_KIND_ALIGNED, NS_KIND_UNALIGNED, NS_KIND_PERFECT = 0, 1, 2
 NS_EMIT_SIZES = 2
 KERNEL_NAMES = ("plan(k_nseg+k_lengths+scan+sort)", "k_chain", "k_names", "k_materialise", "k_hp", "k_errlog")
@@ -238,8 +238,8 @@ class Engine:
             self._check(self.L.ns_generate_step(self.ctx, C.byref(aligned) if aligned is not None else None,
                                                 C.byref(unaligned) if unaligned is not None else None, info))
         except EngineError as err:
-            # only the unaligned half failed (the library says which: "unaligned worker call: ..."): the aligned batch is complete
-            if aligned is not None and unaligned is not None and "unaligned worker call:" in str(err):
+            # only the unaligned half failed (NS_ESTEP_UNALIGNED; never a HIP error): the aligned batch is complete
+            if aligned is not None and err.code == NS_ESTEP_UNALIGNED:
                 err.aligned_batch = Batch(self, info[0])
             raise
         return (Batch(self, info[0]) if aligned is not None else None, Batch(un_eng, info[1]) if unaligned is not None else None)

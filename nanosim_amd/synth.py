@@ -224,6 +224,26 @@ def write_fasta(path: str, records: list[tuple[str, np.ndarray]], width: int = 8
                 f.write(b[i:i + width] + b"\n")
 
 
+# Operating points away from the one the record kernels are tuned for (~265 events per 8.4 kb read, mean 8 kb): seeded model specs.
+# The event density follows the mean match length (the match Markov model and the first match), the read length the aligned KDE.
+#   q20_like: ~100 events per 8.4 kb read (long matches: sparse tiles)
+#   r9_like:  ~700 events per 8.4 kb read (most 2 048-byte output tiles past the 63-event limit: the slow-tile queue)
+#   ul_like:  aligned median 35 kb at the default error rates (reads over many tiles, pieces beyond 100 kb)
+OPERATING_POINTS = {
+    "q20_like": dict(seed=20261101, match_scale=3.6),
+    "r9_like": dict(seed=20261102, match_scale=0.35),
+    "ul_like": dict(seed=20261103, match_scale=1.0, aligned_median=35000.0, aligned_sigma=0.5),
+}
+
+
+def operating_point_spec(name: str, n_train: int = 200_000) -> SynthModelSpec:
+    """the SynthModelSpec of a named operating point (OPERATING_POINTS), with its own seed"""
+    op = dict(OPERATING_POINTS[name])
+    k = op.pop("match_scale")
+    base = SynthModelSpec()
+    return SynthModelSpec(n_train=n_train, mm_means=tuple(m * k for m in base.mm_means), fm_mean=base.fm_mean * k, **op)
+
+
 # Reference sets of SURVEY.md §8d (lengths only; content is seeded random)
 ECOLI_LEN = 4_641_652
 CHR1_LEN = 248_956_422

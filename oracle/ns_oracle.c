@@ -1584,6 +1584,18 @@ void nso_case_convert(uint8_t *seq, int64_t n, nso_draw *d, uint32_t seg, uint32
  * inside a pass the reference hands the lengths of a rejected read to the next loop index; here every
  * read keeps its own entry of the sorted list and a rejected read simply waits for the next pass.
  * ---------------------------------------------------------------------------------------------- */
+/* per-pass record of the last nso_generate_meta call (test infrastructure): np_spec = the reads the pass's V lengths can cover
+ * (segment counts in descending order, S:781-782, at most the remaining reads), np = the reads assign_species did assign (fewer when
+ * every quota is used up before the lengths are).  Passes with V == 0 are not recorded. */
+#define NSO_META_PASS_LOG 4096
+static uint64_t g_meta_np_spec[NSO_META_PASS_LOG], g_meta_np[NSO_META_PASS_LOG];
+static uint32_t g_meta_passes;
+uint32_t nso_meta_pass_log(uint64_t *np_spec, uint64_t *np, uint32_t cap) {
+    const uint32_t k = g_meta_passes < cap ? g_meta_passes : cap;
+    for (uint32_t i = 0; i < k; ++i) { np_spec[i] = g_meta_np_spec[i]; np[i] = g_meta_np[i]; }
+    return g_meta_passes;
+}
+
 int nso_generate_meta(const ns_model_tables *t, const uint8_t *bases, const uint64_t *chrom_off, uint32_t nchrom,
                       const uint8_t *circular, const char *names_blob, const nso_meta *mg, const ns_params *prm, nso_out *o,
                       double *species_bases_out) {
@@ -1594,6 +1606,7 @@ int nso_generate_meta(const ns_model_tables *t, const uint8_t *bases, const uint
     o->n_pieces = o->n_events = o->record_bytes = o->errlog_bytes = o->total_bases = o->total_ref_bases = 0;
     const uint64_t n = prm->n_reads;
     int rc = 0;
+    g_meta_passes = 0;
     if (prm->kind == NS_KIND_UNALIGNED) {                /* random species per read, otherwise the genome-mode loop */
         for (uint64_t i = 0; i < n && rc == 0; ++i) rc = gen_read(t, &ref, prm, i, o, NULL, mg, NULL, NULL);
         free((void *)names);
@@ -1645,6 +1658,17 @@ int nso_generate_meta(const ns_model_tables *t, const uint8_t *bases, const uint
         uint32_t w[4];
         philox_at(&db, ST_STRAND, 0, p, 0, 0, w);
         const uint32_t reversed = u32_to_p(w[0]) > t->strandness_rate;                /* S:860 */
+        {                                                                                 /* the pass log: np_spec and np */
+            uint64_t cv = 0, n_spec = 0, n_asg = 0;
+            for (uint64_t i = 0; i < m; ++i) {
+                cv += (uint64_t)segs_sorted[i];
+                if (cv > V) break;
+                ++n_spec;
+                if (cv <= P) ++n_asg;
+            }
+            if (g_meta_passes < NSO_META_PASS_LOG) { g_meta_np_spec[g_meta_passes] = n_spec; g_meta_np[g_meta_passes] = n_asg; }
+            ++g_meta_passes;
+        }
         uint64_t seg_ptr = 0, accepted = 0;
         for (uint64_t i = 0; i < m && rc == 0; ++i) {
             const uint32_t ns = (uint32_t)segs_sorted[i];

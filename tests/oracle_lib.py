@@ -166,7 +166,39 @@ def normalise_bases(bases: np.ndarray) -> np.ndarray:
     return lut[bases]
 
 
-def generate(model, ref, params: NsParams, *, bytes_per_read=40000, events_per_read=4000):
+def sizes_for_model(model, params: NsParams) -> dict:
+    """bytes_per_read / events_per_read / errlog_per_read of the oracle's output buffers for `model` (keyword arguments of generate*): from the largest
+    aligned / unaligned length the model's KDEs can draw (training maximum + 8 bandwidths, capped by max_len) and the mean match length
+    of its match Markov model (unaligned reads: one event per base at most).  The buffers are shared by the batch, so a batch is sized for its mean read and for one read of the
+    largest length; chimeric reads count with up to 4 segments of the mean and one of the largest."""
+    from nanosim_amd.model import NS_KDE_ALIGNED, NS_KDE_HT, NS_KDE_UNALIGNED
+    n = max(1, int(params.n_reads))
+
+    def kde_max(i, log10=False):
+        data, bw = model.kde[i]
+        x = float(np.max(data)) + 8.0 * float(bw)
+        return 10.0 ** x if log10 else x
+
+    def kde_mean(i):
+        return float(np.mean(model.kde[i][0]))
+    lens = [kde_max(NS_KDE_ALIGNED)] + ([kde_max(NS_KDE_UNALIGNED)] if NS_KDE_UNALIGNED in model.kde else [])
+    l_max = min(max(lens), float(params.max_len)) if params.max_len else max(lens)
+    l_mean = max(kde_mean(NS_KDE_ALIGNED), kde_mean(NS_KDE_UNALIGNED) if NS_KDE_UNALIGNED in model.kde else 0.0)
+    ht = kde_max(NS_KDE_HT, log10=True) if NS_KDE_HT in model.kde else 0.0
+    seg = 4.0 if params.chimeric else 1.0
+    bases = (seg * l_mean + ht + 2.0 * l_max / n) * 1.25                 # bases of one read, on average over the batch
+    col = model.match_markov[0] if model.match_markov else model.first_match
+    p = np.diff(np.concatenate([[0.0], np.asarray(col.hi, dtype=np.float64)]))
+    v = (np.concatenate([[col.vlo0], np.asarray(col.vhi, dtype=np.float64)[:-1]]) + np.asarray(col.vhi, dtype=np.float64)) / 2.0
+    mean_match = max(1.0, float((p * v).sum()))
+    # unaligned reads (and chimeric gaps) take the unaligned error list: about one event per two bases whatever the model
+    rate = 1.0 if int(params.kind) == 1 else 3.0 / mean_match
+    events = int(rate * bases) + 256
+    return dict(bytes_per_read=int(bases * (2.0 if params.fastq else 1.0)) + 1024, events_per_read=events,
+                errlog_per_read=events * 128 + 4096)                      # (an error-profile row per event: name, positions, bases)
+
+
+def generate(model, ref, params: NsParams, *, bytes_per_read=40000, events_per_read=4000, errlog_per_read=None):
     """Run the CPU restatement for one batch; returns dict of numpy arrays like the engine's outputs."""
     L = lib()
     t = model.to_c()
@@ -175,7 +207,7 @@ def generate(model, ref, params: NsParams, *, bytes_per_read=40000, events_per_r
     pieces = np.zeros(n * 8 + 64, dtype=PIECE_DTYPE)
     events = np.zeros(n * events_per_read + 1024, dtype=EVENT_DTYPE)
     records = np.zeros(n * bytes_per_read + 4096, dtype=np.uint8)
-    errlog = np.zeros((n * bytes_per_read * 3 + 4096) if params.emit_errlog else 16, dtype=np.uint8)
+    errlog = np.zeros((n * (errlog_per_read or bytes_per_read * 3) + 4096) if params.emit_errlog else 16, dtype=np.uint8)
     o = NsoOut()
     o.reads = reads.ctypes.data; o.pieces = pieces.ctypes.data; o.events = events.ctypes.data
     o.cap_pieces = len(pieces); o.cap_events = len(events)
@@ -217,6 +249,18 @@ def generate_meta(model, meta_ref, abun: dict, abun_inflated, params: NsParams, 
     return dict(reads=reads, pieces=pieces[:o.n_pieces], events=events[:o.n_events], records=records[:o.record_bytes],
                 errlog=errlog[:o.errlog_bytes], total_bases=int(o.total_bases), total_ref_bases=int(o.total_ref_bases),
                 species_bases=sp_bases)
+
+
+def meta_pass_log():
+    """(np_spec, np) per pass of the last generate_meta call: the reads the pass's lengths could cover, and the reads assign_species
+    did assign (np < np_spec: every quota was used up before the lengths were)"""
+    L = lib()
+    L.nso_meta_pass_log.restype = C.c_uint32
+    L.nso_meta_pass_log.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    cap = 4096
+    a, b = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64)
+    k = min(int(L.nso_meta_pass_log(a.ctypes.data, b.ctypes.data, cap)), cap)
+    return a[:k], b[:k]
 
 
 def make_trx(tr, ir=None):

@@ -80,3 +80,13 @@ def test_product_does_not_touch_the_oracle():
             if f.endswith((".py", ".hip", ".h")):
                 txt = open(os.path.join(dirpath, f)).read()
                 assert "ns_oracle" not in txt and "oracle_lib" not in txt and "libns_oracle" not in txt, f
+
+
+def test_error_codes_match_the_header():
+    """the return codes of include/nanosim_amd.h == the constants of nanosim_amd.engine (NS_ESTEP_UNALIGNED: ABI 7)"""
+    src = open(HEADER).read()
+    codes = {k: int(v) for k, v in re.findall(r"#define (NS_E[A-Z_]+) \((-?\d+)\)", src)}
+    assert codes == {k: getattr(engine, k) for k in codes}
+    assert set(codes) == {"NS_EINVAL", "NS_ENODEV", "NS_ENOMEM", "NS_EHIP", "NS_ESTATE", "NS_EIO", "NS_ESTEP_UNALIGNED"}
+    assert len(set(codes.values())) == len(codes)
+    assert int(re.search(r"#define NS_ABI_VERSION (\d+)u", src).group(1)) == model.NS_ABI_VERSION == 7

@@ -155,3 +155,61 @@ def test_many_pass_chimeric_batch_keeps_its_pieces_in_bounds(small_model, setup)
     reads, pieces = b.reads(), b.pieces()
     assert int(reads["n_pieces"].sum()) == len(pieces) == int(b.info.n_pieces)
     assert np.all(reads["piece_off"].astype(np.int64) + reads["n_pieces"] <= len(pieces))
+
+
+QUOTA_TABLES = [(1e6, 1.0, 0.0), (0.0, 0.0, 1.0), (1.0, 1e-300, 1e-300), (5e-324, 5e-324, 0.0),
+                (1.0, 0.002, 0.001)]         # (quotas of about one read length: the walk's fall-backs while the chimeric segments go)
+QUOTA_CASES = [dict(n_reads=300), dict(n_reads=300, emit_errlog=True), dict(n_reads=300, chimeric=True, fastq=True),
+               dict(n_reads=300, chimeric=True, fastq=True, emit_errlog=True), dict(n_reads=200, min_len=3000, max_len=9000, emit_errlog=True)]
+
+
+@pytest.mark.parametrize("table", QUOTA_TABLES)
+def test_gpu_metagenome_extreme_quotas_equal_oracle(small_model, meta_ref, table):
+    """Abundance tables at the edges of the quota walk (tests/test_metagenome.py: with finite quotas np == np_spec in every pass, which
+    the oracle's pass log confirms for each batch here): extreme ratios, species without a share, subnormal abundances.  GPU == oracle
+    with events_used, plus the per-species bases."""
+    abun = dict(zip(meta_ref.species, table))
+    infl = {sp: MG.inflate_abun(abun, sp, small_model.abun_inflation) for sp in abun}
+    e = E.Engine(0)
+    try:
+        e.set_metagenome(meta_ref, abun, infl)
+        e.load_model(small_model)
+        for i, case in enumerate(QUOTA_CASES):
+            p = E.make_params(**dict(dict(seed=0xC0FFEE00 + i, first_read=0, max_len=meta_ref.max_chrom, meta=True), **case))
+            b = e.generate(p)
+            exp = O.generate_meta(small_model, meta_ref, abun, infl if p.chimeric else None, p)
+            np_spec, np_ = O.meta_pass_log()
+            assert np.array_equal(np_spec, np_), case
+            compare(b, exp, p)
+            assert np.array_equal(e.species_bases(), exp["species_bases"]), case
+    finally:
+        e.close()
+
+
+def test_gpu_metagenome_no_finite_quota_fails_and_the_engine_recovers(small_model, meta_ref):
+    """All abundances zero: every quota is 0 / 0, no pass assigns a read (np == 0 < np_spec: the oracle's pass log shows it), and the batch
+    fails on the host at the attempt limit, as the oracle does.  The same engine then gives the right reads with a proper table."""
+    zero = {sp: 0.0 for sp in meta_ref.species}
+    p_bad = E.make_params(seed=0xBAD0, first_read=0, n_reads=20, max_len=meta_ref.max_chrom, meta=True)
+    with pytest.raises(RuntimeError):
+        O.generate_meta(small_model, meta_ref, zero, None, p_bad)
+    np_spec, np_ = O.meta_pass_log()
+    assert len(np_spec) == 1000 and np.all(np_spec > 0) and np.all(np_ == 0)
+    _, samples = MG.read_abundance(os.path.join(META, "abundance.tsv"), meta_ref.species)
+    abun = samples[0]
+    infl = {sp: MG.inflate_abun(abun, sp, small_model.abun_inflation) for sp in abun}
+    e = E.Engine(0)
+    try:
+        e.set_metagenome(meta_ref, zero, None)
+        e.load_model(small_model)
+        with pytest.raises(E.EngineError, match="attempt limit"):
+            e.generate(p_bad)
+        e.set_abundance(meta_ref, abun, infl)
+        for kw in (dict(n_reads=300, emit_errlog=True), dict(n_reads=300, chimeric=True, fastq=True, emit_errlog=True)):
+            p = E.make_params(seed=0xBAD1, first_read=0, max_len=meta_ref.max_chrom, meta=True, **kw)
+            b = e.generate(p)
+            exp = O.generate_meta(small_model, meta_ref, abun, infl if p.chimeric else None, p)
+            compare(b, exp, p)
+            assert np.array_equal(e.species_bases(), exp["species_bases"])
+    finally:
+        e.close()
