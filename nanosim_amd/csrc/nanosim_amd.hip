@@ -264,8 +264,8 @@ __global__ void __launch_bounds__(SMALL ? 64 : 256, SMALL ? 7 : 1) k_lengths(Gen
     int32_t remainder = 0; double ratio = 0;
     if (prm.trx && kind == NS_KIND_ALIGNED) {                                          // S:1073-1076, 1203-1204: one draw per read, no filter
         const double x = ns_pow10m1(kde_sample(A.m.kde[NS_KDE_HT], ns_draw(key, ST_HT, 0, a, 0, 0)));
-        const int64_t r64 = (int64_t)x;
-        remainder = r64 < 0 ? 0 : r64 > 0x3fffffff ? 0x3fffffff : (int32_t)r64;
+        const int64_t r64 = ns_f64_to_i64_sat(x);
+        remainder = r64 < 0 ? 0 : r64 > NS_LEN_DRAW_MAX ? (int32_t)NS_LEN_DRAW_MAX : (int32_t)r64;
         ratio = kde_sample(A.m.kde[NS_KDE_RATIO], ns_draw(key, ST_RATIO, 0, a, 0, 0));
         if (ratio > 1) ratio = 1;
         if (ratio < 0) ratio = 0;
@@ -275,7 +275,11 @@ __global__ void __launch_bounds__(SMALL ? 64 : 256, SMALL ? 7 : 1) k_lengths(Gen
         for (; j < NS_KDE_RETRY; ++j) {
             u32x4 w = ns_draw(key, ST_HT, 0, a, j, 0);
             double x = ns_pow10m1(kde_sample(A.m.kde[NS_KDE_HT], w));
-            if (x >= 0) { remainder = A.meta ? (int32_t)rint(x) : (int32_t)x; break; }      // S:1351 int() / S:901 int(round())
+            if (x >= 0) {                                                                   // S:1351 int() / S:901 int(round()), saturated
+                const int64_t r64 = ns_f64_to_i64_sat(A.meta ? rint(x) : x);                // as in transcriptome mode (x reaches 1e304)
+                remainder = r64 > NS_LEN_DRAW_MAX ? (int32_t)NS_LEN_DRAW_MAX : (int32_t)r64;
+                break;
+            }
         }
         for (j = 0; j < NS_KDE_RETRY; ++j) {
             u32x4 w = ns_draw(key, ST_RATIO, 0, a, j, 0);
@@ -558,7 +562,7 @@ __global__ void __launch_bounds__(COOP ? 64 : NS_CHAIN_BLOCK_BIG, COOP ? (LDS_TA
                     if (!spliced) {                                  // extract_read_trx (S:1683-1691): uniform start inside the transcript
                         const u32x4 wp = ns_draw(key, ST_POS, sid, a, 0, 0);
                         const uint64_t span = (uint64_t)(trx_len - (int64_t)p.ref_len) + 1;
-                        pos = (uint64_t)(u53_to_p(wp.x, wp.y) * (double)span);
+                        pos = (uint64_t)(u53_to_p(wp.x, wp.y) * (double)span);   // (in [0, span]: p < 1)
                         if (pos >= span) pos = span - 1;
                     }
                 }
@@ -854,7 +858,7 @@ __global__ void __launch_bounds__(256) k_meta_words(GenArgs A, uint2 *out, uint6
 // int(round(length)) of the assigned lengths (S:871), on the device copy of the sorted list
 __global__ void __launch_bounds__(256) k_meta_round(const double *__restrict__ x, int32_t *__restrict__ out, uint64_t n) {
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n) out[j] = (int32_t)rint(x[j]);
+    if (j < n) out[j] = (int32_t)rint(x[j]);        // (x passed MetaLenFilter: 0 < x <= max_len <= the longest chromosome < 2^31)
 }
 struct MetaLenFilter {           // S:857 (0 < x <= max_l) / S:841 (--perfect: min_l <= x <= max_l)
     double lo, hi; bool lo_inclusive;

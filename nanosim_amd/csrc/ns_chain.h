@@ -40,7 +40,7 @@ NS_DEV int32_t ecdf_lookup_g(const double *__restrict__ hi, const V *__restrict_
     const double hs = hi[s], hp = hi[sm], vs = (double)vhi[s], vp = (double)vhi[sm];
     const double plo = s ? hp : 0.0;
     const double vlo = s ? vp : vlo0;
-    return (int32_t)floor((p - plo) / (hs - plo) * (vs - vlo) + vlo);
+    return (int32_t)floor((p - plo) / (hs - plo) * (vs - vlo) + vlo);     // (between vlo and vs: the column's values, int32 by ns_pack)
 }
 
 // mixture run length (mm:41-63) on integer thresholds: component by u_mix < T(weight), value = 1 + #{j : p > cdf[j]} by walking
@@ -251,7 +251,7 @@ NS_DEV int32_t ecdf_lookup_gv(const uint64_t *__restrict__ GV, uint32_t n, const
     if (s >= n) { s = n - 1; p = hi_g[s]; }
     const uint32_t sm = s ? s - 1 : 0;
     const double hs = hi_g[s], plo = s ? hi_g[sm] : 0.0, vs = vhi_g[s], vlo = s ? vhi_g[sm] : vlo0;
-    return (int32_t)floor((p - plo) / (hs - plo) * (vs - vlo) + vlo);
+    return (int32_t)floor((p - plo) / (hs - plo) * (vs - vlo) + vlo);     // (between vlo and vs: the column's values, int32 by ns_pack)
 }
 
 // the same walk on the PREFIX of a column (the LDS image, ns_pack.h): answers for a unit-wide or narrow segment inside the prefix; false: the

@@ -83,8 +83,8 @@ struct DevRef {
 
 // ---- table look-ups ------------------------------------------------------------------------------------
 // ECDF look-up of S:1845-1849 / S:1895-1898: segment with lo < p <= hi, linear interpolation, floor.
-__device__ __forceinline__ int64_t ecdf_lookup(const double *__restrict__ hi, const double *__restrict__ vhi,
-                                               uint32_t n, double vlo0, double p) {
+NS_DEV int64_t ecdf_lookup(const double *__restrict__ hi, const double *__restrict__ vhi,
+                           uint32_t n, double vlo0, double p) {
     uint32_t lo_i = 0, hi_i = n;
     while (lo_i < hi_i) {
         uint32_t mid = (lo_i + hi_i) >> 1;
@@ -94,10 +94,10 @@ __device__ __forceinline__ int64_t ecdf_lookup(const double *__restrict__ hi, co
     if (s >= n) { s = n - 1; p = hi[s]; }
     double plo = s ? hi[s - 1] : 0.0;
     double vlo = s ? vhi[s - 1] : vlo0;
-    return (int64_t)floor((p - plo) / (hi[s] - plo) * (vhi[s] - vlo) + vlo);
+    return (int64_t)floor((p - plo) / (hi[s] - plo) * (vhi[s] - vlo) + vlo);     // (between vlo and vhi[s]: the table's own values)
 }
 
-__device__ __forceinline__ int64_t table_value(const double *__restrict__ cdf, uint32_t n, double p) {
+NS_DEV int64_t table_value(const double *__restrict__ cdf, uint32_t n, double p) {
     uint32_t lo = 0, hi = n;
     while (lo < hi) {
         uint32_t mid = (lo + hi) >> 1;
@@ -136,7 +136,7 @@ NS_DEV int trans_pick_u(const uint64_t *row, uint32_t u) {
 // ---- lengths ---------------------------------------------------------------------------------------------
 // KernelDensity.sample (call site S:235): i = floor(U*n); x = N(data[i], bw)
 __device__ __forceinline__ double kde_sample(const ns_kde &k, const u32x4 &w) {
-    uint64_t i = (uint64_t)(u53_to_p(w.x, w.y) * (double)k.n);
+    uint64_t i = (uint64_t)(u53_to_p(w.x, w.y) * (double)k.n);        // (0 < p < 1: the product lies in [0, n])
     if (i >= k.n) i = k.n - 1;
     return fma(k.bw, ns_norminv(u32_to_p(w.z)), k.data[i]);
 }
@@ -160,20 +160,23 @@ __device__ inline bool seg_length(const DevModel &m, const ns_params &prm, const
         }
         bool keep = (prm.kind == NS_KIND_PERFECT) ? ((double)prm.min_len <= x && x <= (double)prm.max_len)
                                                   : (0 < x && x <= (double)prm.max_len);
-        if (keep) { out = (int64_t)x; return true; }
+        if (keep) { out = (int64_t)x; return true; }                            // (0 < x <= max_len < 2^63: in range)
     }
     return false;
 }
 __device__ inline int64_t gap_length(const DevModel &m, const ns_key &key, uint32_t g, uint32_t epoch) {   // S:1298-1299
     u32x4 w = ns_draw(key, ST_GAPLEN, g, epoch, 0, 0);
-    int64_t gi = (int64_t)ns_pow10m1(kde_sample(m.kde[NS_KDE_GAP], w));
+    int64_t gi = ns_f64_to_i64_sat(ns_pow10m1(kde_sample(m.kde[NS_KDE_GAP], w)));
     return gi < 0 ? 0 : gi;
 }
 __device__ inline int64_t unaligned_length(const DevModel &m, const ns_params &prm, const ns_key &key, uint32_t a) {
     u32x4 w = ns_draw(key, ST_ULEN, 0, a, 0, 0);                                                    // S:1494-1495,1499
     double x = prm.use_lognormal ? ns_exp(fma(prm.sd_len, ns_norminv(u32_to_p(w.z)), ns_log(prm.median_len)))
                                  : kde_sample(m.kde[NS_KDE_UNALIGNED], w);
-    return (int64_t)x;
+    // -sd 20 reaches ns_exp's 1e304.  An unaligned read is never shorter than its drawn length (S:1503: middle_ref), so a draw above
+    // max_len (or 0x3fffffff) is no valid draw: -1, rejected by the length filter without walking it
+    const int64_t v = ns_len_draw(x);
+    return v > prm.max_len ? -1 : v;
 }
 
 // extract_read, genome branches (S:1750-1781)
@@ -182,7 +185,7 @@ __device__ inline bool extract_pos(const DevRef &ref, int64_t length, const ns_k
     uint64_t genome_len = ref.chrom_off[ref.nchrom];
     for (uint32_t j = 0; j < NS_POS_RETRY; ++j) {
         u32x4 w = ns_draw(key, ST_POS, seg, attempt, j, 0);
-        uint64_t ref_pos = (uint64_t)(u53_to_p(w.x, w.y) * (double)(genome_len + 1));
+        uint64_t ref_pos = (uint64_t)(u53_to_p(w.x, w.y) * (double)(genome_len + 1));   // (in [0, genome_len + 1]: p < 1)
         if (ref_pos > genome_len) ref_pos = genome_len;
         if (ref.circular[0]) { chrom = 0; pos = ref_pos; return true; }
         if (length > 0 && ref.nchrom > 8) {
@@ -224,10 +227,10 @@ __device__ inline int64_t kde2d_cond(const DevModel &m, double L, const ns_key &
     if (hi > lo) {
         for (uint32_t j = 0; j < NS_KDE_RETRY; ++j) {
             const u32x4 w = ns_draw(key, ST_REFLEN, 0, attempt, j, sub);
-            uint64_t i = lo + (uint64_t)(u53_to_p(w.x, w.y) * (double)(hi - lo));
+            uint64_t i = lo + (uint64_t)(u53_to_p(w.x, w.y) * (double)(hi - lo));   // (in [0, hi - lo]: p < 1)
             if (i >= hi) i = hi - 1;
             const double dd = (L - x[i]) / h;
-            if (u32_to_p(w.z) <= ns_exp(-0.5 * dd * dd)) return (int64_t)fma(h, ns_norminv(u32_to_p(w.w)), y[i]);
+            if (u32_to_p(w.z) <= ns_exp(-0.5 * dd * dd)) return ns_f64_to_i64_sat(fma(h, ns_norminv(u32_to_p(w.w)), y[i]));
         }
     }
     uint64_t a = 0, b = n;
@@ -235,7 +238,7 @@ __device__ inline int64_t kde2d_cond(const DevModel &m, double L, const ns_key &
     uint64_t i = a >= n ? n - 1 : a;
     if (a > 0 && a < n && L - x[a - 1] <= x[a] - L) i = a - 1;
     const u32x4 w = ns_draw(key, ST_REFLEN, 0, attempt, NS_KDE_RETRY, sub);
-    return (int64_t)fma(h, ns_norminv(u32_to_p(w.w)), y[i]);
+    return ns_f64_to_i64_sat(fma(h, ns_norminv(u32_to_p(w.w)), y[i]));
 }
 // extract_read("transcriptome", length) (S:1695-1703): a uniformly drawn transcript that is longer than the read, uniform start
 __device__ inline bool extract_pos_trx_any(const DevRef &ref, int64_t length, const ns_key &key, uint32_t seg, uint32_t attempt,
@@ -246,7 +249,7 @@ __device__ inline bool extract_pos_trx_any(const DevRef &ref, int64_t length, co
         const uint64_t cl = ref.chrom_off[c + 1] - ref.chrom_off[c];
         if ((uint64_t)length < cl) {
             const uint64_t span = cl - (uint64_t)length + 1;
-            uint64_t rp = (uint64_t)(u53_to_p(w.y, w.z) * (double)span);
+            uint64_t rp = (uint64_t)(u53_to_p(w.y, w.z) * (double)span);          // (in [0, span]: p < 1)
             if (rp >= span) rp = span - 1;
             chrom = c; pos = rp;
             return true;
@@ -283,7 +286,7 @@ __device__ inline bool extract_pos_meta(const DevRef &ref, const uint32_t *__res
         clen = ref.chrom_off[c + 1] - ref.chrom_off[c];
     }
     const uint64_t span = ref.circular[c] ? clen + 1 : clen - (uint64_t)length + 1;     // randint(0, len) / randint(0, len - length)
-    uint64_t rp = (uint64_t)(u53_to_p(wb.x, wb.y) * (double)span);
+    uint64_t rp = (uint64_t)(u53_to_p(wb.x, wb.y) * (double)span);             // (in [0, span]: p < 1)
     if (rp >= span) rp = span - 1;
     chrom = c; pos = rp;
     return true;

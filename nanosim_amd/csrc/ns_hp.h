@@ -95,7 +95,7 @@ __device__ __forceinline__ uint32_t hp_new_size(const DevModel &m, const ns_key 
     u32x4 w = ns_draw(key, ST_HPLEN, sid, a, s, 0);
     double x = fma(sigma, ns_norminv(u32_to_p(w.x)), mu);
     if (x < 0) x = 0;
-    return (uint32_t)(int64_t)rint(x);
+    return (uint32_t)ns_f64_to_i64_sat(rint(x));       // (x >= 0; sizes of 2^32 and more: a model no training run gives)
 }
 // The events that turn the run [s0, s0 + L) of `base` into its re-sampled form (mutate_homo, S:657-700), in ascending position,
 // handed to put(pos, type, len, word); returns their number.  New base x of the run (0 <= x < size):

@@ -64,7 +64,7 @@ __device__ inline IrPlan ir_walk(const DevIr &ir, uint32_t trx, uint32_t length,
     if (!pl.any) return pl;
     const uint32_t hi = min(trx_len - length, len_before);                 // S:162: random.randint(0, min(ref_len - length, len_before))
     const u32x4 wp = ns_draw(key, ST_POS, 0, a, 0, 0);
-    uint64_t sp64 = (uint64_t)(u53_to_p(wp.x, wp.y) * (double)((uint64_t)hi + 1));
+    uint64_t sp64 = (uint64_t)(u53_to_p(wp.x, wp.y) * (double)((uint64_t)hi + 1));      // (in [0, hi + 1]: p < 1)
     uint32_t start_pos = sp64 > hi ? hi : (uint32_t)sp64;
     uint32_t remaining = length;
     state = IR_ST_START; k = 0;

@@ -157,6 +157,23 @@ NS_HD double ns_norminv(double p) {
 
 NS_HD double ns_pow10m1(double x) { return ns_exp(x * 2.302585092994046) - 1.0; }
 
+// Float-to-integer conversion with a result for every input: C's truncation wherever that is defined, INT64_MAX / INT64_MIN above /
+// below the int64 range, 0 for NaN.  An out-of-range (int64_t)x is undefined, and x86 (cvttsd2si: INT64_MIN) and gfx950 (v_cvt_*_f64
+// on the two halves: saturated halves) resolve it differently; the oracle restates this helper (nso_f64_to_i64_sat).
+NS_HD int64_t ns_f64_to_i64_sat(double x) {
+    if (!(x == x)) return 0;
+    if (x >= 9223372036854775808.0) return INT64_MAX;
+    if (x < -9223372036854775808.0) return INT64_MIN;
+    return (int64_t)x;
+}
+// A drawn length above NS_LEN_DRAW_MAX (0x3fffffff, the field of ns_piece.ref_len the planner keeps) is no valid draw: -1, which every
+// length filter rejects.
+#define NS_LEN_DRAW_MAX 0x3fffffffll
+NS_HD int64_t ns_len_draw(double x) {
+    const int64_t v = ns_f64_to_i64_sat(x);
+    return v > NS_LEN_DRAW_MAX ? -1 : v;
+}
+
 // ---- event record packing: {pos:32 | len:12 | type:2 | shift+2^17:18} ------------------------------------
 #define NS_EV_LEN_MAX 4095u
 #define NS_EV_SHIFT_BIAS 131072

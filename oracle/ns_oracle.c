@@ -155,6 +155,32 @@ double nso_norminv(double p) {
     return num * q / den;
 }
 
+/* float -> int64 with a result for every input (ns_rng.h ns_f64_to_i64_sat): C's truncation where that is defined, saturated above
+ * and below the int64 range, 0 for NaN.  A plain (int64_t)x out of range is undefined, and x86 and gfx950 resolve it differently. */
+int64_t nso_f64_to_i64_sat(double x) {
+    if (!(x == x)) return 0;
+    if (x >= 9223372036854775808.0) return INT64_MAX;
+    if (x < -9223372036854775808.0) return INT64_MIN;
+    return (int64_t)x;
+}
+/* a drawn length above NSO_LEN_DRAW_MAX is no valid draw: -1 (ns_len_draw) */
+#define NSO_LEN_DRAW_MAX 0x3fffffffll
+static int64_t len_draw(double x) {
+    const int64_t v = nso_f64_to_i64_sat(x);
+    return v > NSO_LEN_DRAW_MAX ? -1 : v;
+}
+/* edge counters for the tests (tests/test_gpu_extremes.py proves its cases reach their edge): not thread-safe, reset by the caller */
+enum { NSO_EDGE_ULEN_LONG = 0,    /* unaligned length draws above max_len or 0x3fffffff (no valid draw) */
+       NSO_EDGE_ULEN_HUGE = 1,    /* ... of 2^31 or more (where a plain cast differs between x86 and gfx950) */
+       NSO_EDGE_REM_SAT = 2,      /* head/tail remainders saturated at 0x3fffffff */
+       NSO_EDGE_REM_HUGE = 3,     /* ... drawn at 2^31 or more */
+       NSO_EDGE_LEN_HUGE = 4,     /* aligned / --perfect length draws of 2^31 or more (rejected by the max_len filter) */
+       NSO_EDGE_N = 8 };
+static uint64_t nso_edges[NSO_EDGE_N];
+void nso_edge_counts(uint64_t *out, int reset) {
+    for (int i = 0; i < NSO_EDGE_N; ++i) { if (out) out[i] = nso_edges[i]; if (reset) nso_edges[i] = 0; }
+}
+
 /* ------------------------------------------------------------------------------------------------
  * table look-ups
  * ---------------------------------------------------------------------------------------------- */
@@ -577,7 +603,7 @@ int64_t nso_mutate_homo(const ns_model_tables *t, const uint8_t *in, const uint8
         if (d->mode) x = tape_z(d);                                   /* np.random.normal(mu, sigma) recorded from the reference */
         else { uint32_t ww[4]; philox_at(d, ST_HPLEN, seg, attempt, (uint32_t)s, 0, ww); x = fma(sigma, nso_norminv(u32_to_p(ww[0])), mu); }
         if (x < 0) x = 0;                                             /* S:652-654 */
-        const int64_t size = (int64_t)nearbyint(x);                   /* int(round(.)), S:665 */
+        const int64_t size = nso_f64_to_i64_sat(nearbyint(x));        /* int(round(.)), S:665 */
         if (w + size > out_cap) return -1;
         int64_t first_mis = -1;
         for (int64_t i = 0; i < size; ++i) {
@@ -895,7 +921,7 @@ int64_t nso_kde2d_cond(const ns_model_tables *t, double L, nso_draw *d, uint32_t
             uint64_t i = lo + (uint64_t)(u53_to_p(w[0], w[1]) * (double)(hi - lo));
             if (i >= hi) i = hi - 1;
             const double dd = (L - x[i]) / h;
-            if (u32_to_p(w[2]) <= nso_exp(-0.5 * dd * dd)) return (int64_t)fma(h, nso_norminv(u32_to_p(w[3])), y[i]);
+            if (u32_to_p(w[2]) <= nso_exp(-0.5 * dd * dd)) return nso_f64_to_i64_sat(fma(h, nso_norminv(u32_to_p(w[3])), y[i]));
         }
     }
     uint64_t a = 0, b = n;
@@ -903,7 +929,7 @@ int64_t nso_kde2d_cond(const ns_model_tables *t, double L, nso_draw *d, uint32_t
     uint64_t i = a >= n ? n - 1 : a;
     if (a > 0 && a < n && L - x[a - 1] <= x[a] - L) i = a - 1;
     philox_at(d, ST_REFLEN, 0, attempt, NSO_KDE_RETRY, sub, w);
-    return (int64_t)fma(h, nso_norminv(u32_to_p(w[3])), y[i]);
+    return nso_f64_to_i64_sat(fma(h, nso_norminv(u32_to_p(w[3])), y[i]));
 }
 
 /* extract_read("transcriptome", length) (S:1695-1703): a uniformly drawn transcript that is longer than the read, uniform start */
@@ -985,7 +1011,10 @@ static int gen_read(const ns_model_tables *t, const nso_ref *ref, const ns_param
             philox_at(&d, ST_ULEN, 0, a, 0, 0, w);
             double x = prm->use_lognormal ? nso_exp(fma(prm->sd_len, nso_norminv(u32_to_p(w[2])), nso_log(prm->median_len)))
                                           : kde_sample(&t->kde[NS_KDE_UNALIGNED], w);
-            ref_len[0] = (int64_t)x;
+            ref_len[0] = len_draw(x);                                     /* above max_len: -1, rejected below unwalked */
+            if (ref_len[0] > prm->max_len) ref_len[0] = -1;
+            if (ref_len[0] < 0 && x > 0) ++nso_edges[NSO_EDGE_ULEN_LONG];
+            if (x >= 2147483648.0) ++nso_edges[NSO_EDGE_ULEN_HUGE];
         } else if (tx) {                                                  /* transcriptome, S:1082-1105: planned by trx_block */
             if (!tr) return -40;
             trx_chrom = tr->chrom;
@@ -996,7 +1025,7 @@ static int gen_read(const ns_model_tables *t, const nso_ref *ref, const ns_param
             for (uint32_t g = 0; g + 1 < nseg; ++g) {
                 philox_at(&d, ST_GAPLEN, g, a, 0, 0, w);
                 double x = pow10m1(kde_sample(&t->kde[NS_KDE_GAP], w));
-                int64_t gi = (int64_t)x; gap_len[g] = gi < 0 ? 0 : gi;
+                int64_t gi = nso_f64_to_i64_sat(x); gap_len[g] = gi < 0 ? 0 : gi;
             }
         } else {
             for (uint32_t s = 0; s < nseg && ok; ++s) {                   /* S:1285-1296,1309 */
@@ -1016,6 +1045,7 @@ static int gen_read(const ns_model_tables *t, const nso_ref *ref, const ns_param
                         if (rem < 0) continue;
                         x = tot - rem;
                     }
+                    if (x >= 2147483648.0) ++nso_edges[NSO_EDGE_LEN_HUGE];
                     int keep = (kind == NS_KIND_PERFECT) ? ((double)prm->min_len <= x && x <= (double)prm->max_len)
                                                          : (0 < x && x <= (double)prm->max_len);
                     if (keep) { ref_len[s] = (int64_t)x; break; }
@@ -1025,15 +1055,17 @@ static int gen_read(const ns_model_tables *t, const nso_ref *ref, const ns_param
             for (uint32_t g = 0; g + 1 < nseg; ++g) {                      /* S:1298-1299 */
                 philox_at(&d, ST_GAPLEN, g, epoch, 0, 0, w);
                 double x = pow10m1(kde_sample(&t->kde[NS_KDE_GAP], w));
-                int64_t gi = (int64_t)x; gap_len[g] = gi < 0 ? 0 : gi;
+                int64_t gi = nso_f64_to_i64_sat(x); gap_len[g] = gi < 0 ? 0 : gi;
             }
         }
         int64_t remainder = 0; double ratio = 0; int reversed;
         if (tx && kind == NS_KIND_ALIGNED) {                               /* S:1073-1076, 1203-1204: one draw per read, no filter */
             philox_at(&d, ST_HT, 0, a, 0, 0, w);
             double x = pow10m1(kde_sample(&t->kde[NS_KDE_HT], w));
-            remainder = (int64_t)x;                                        /* int(): towards zero */
+            remainder = nso_f64_to_i64_sat(x);                             /* int(): towards zero */
+            if (x >= 2147483648.0) ++nso_edges[NSO_EDGE_REM_HUGE];
             if (remainder < 0) remainder = 0;
+            if (remainder > NSO_LEN_DRAW_MAX) { remainder = NSO_LEN_DRAW_MAX; ++nso_edges[NSO_EDGE_REM_SAT]; }
             philox_at(&d, ST_RATIO, 0, a, 0, 0, w);
             ratio = kde_sample(&t->kde[NS_KDE_RATIO], w);
             if (ratio > 1) ratio = 1;
@@ -1044,7 +1076,12 @@ static int gen_read(const ns_model_tables *t, const nso_ref *ref, const ns_param
             for (; j < NSO_KDE_RETRY; ++j) {
                 philox_at(&d, ST_HT, 0, a, j, 0, w);
                 double x = pow10m1(kde_sample(&t->kde[NS_KDE_HT], w));
-                if (x >= 0) { remainder = mr ? (int64_t)nearbyint(x) : (int64_t)x; break; }      /* S:1351 / S:901 */
+                if (x >= 0) {                                              /* S:1351 / S:901 */
+                    remainder = nso_f64_to_i64_sat(mr ? nearbyint(x) : x);
+                    if (x >= 2147483648.0) ++nso_edges[NSO_EDGE_REM_HUGE];
+                    if (remainder > NSO_LEN_DRAW_MAX) { remainder = NSO_LEN_DRAW_MAX; ++nso_edges[NSO_EDGE_REM_SAT]; }
+                    break;
+                }
             }
             if (j == NSO_KDE_RETRY) remainder = 0;
             for (j = 0; j < NSO_KDE_RETRY; ++j) {
@@ -1556,6 +1593,45 @@ double nso_kde_sample(const double *data, uint64_t n, double bw, uint32_t w0, ui
     return kde_sample(&k, w);
 }
 double nso_pow10m1(double x) { return pow10m1(x); }
+/* one scalar primitive over n inputs (tests/test_math_probe.py: the same ops as tests/math_probe.hip).  in / out: 8-byte elements,
+ * read as double, or as uint64 for the draw ops (NORMINV_U: u = low 32 bits; U53: a = high, b = low 32 bits).  Returns 0, -1 for an
+ * unknown op. */
+enum { NSO_OP_LOG = 0, NSO_OP_EXP = 1, NSO_OP_NORMINV_U = 2, NSO_OP_POW10M1 = 3, NSO_OP_U53 = 4, NSO_OP_THR_LT = 5, NSO_OP_THR_GT = 6,
+       NSO_OP_F64_I64 = 7, NSO_OP_NORMINV = 8, NSO_OP_LEN_DRAW = 9 };
+int nso_eval_batch(int op, const void *in, void *out, uint64_t n) {
+    const double *xd = (const double *)in; const uint64_t *xu = (const uint64_t *)in;
+    double *od = (double *)out; int64_t *oi = (int64_t *)out; uint64_t *ou = (uint64_t *)out;
+    switch (op) {
+    case NSO_OP_LOG: for (uint64_t i = 0; i < n; ++i) od[i] = nso_log(xd[i]); break;
+    case NSO_OP_EXP: for (uint64_t i = 0; i < n; ++i) od[i] = nso_exp(xd[i]); break;
+    case NSO_OP_NORMINV_U: for (uint64_t i = 0; i < n; ++i) od[i] = nso_norminv(u32_to_p((uint32_t)xu[i])); break;
+    case NSO_OP_POW10M1: for (uint64_t i = 0; i < n; ++i) od[i] = pow10m1(xd[i]); break;
+    case NSO_OP_U53: for (uint64_t i = 0; i < n; ++i) od[i] = u53_to_p((uint32_t)(xu[i] >> 32), (uint32_t)xu[i]); break;
+    case NSO_OP_THR_LT:                                   /* the integer form of p < t: #{u : u32_to_p(u) < t} */
+        for (uint64_t i = 0; i < n; ++i) {
+            const double t = xd[i];
+            if (!(t > 0.0)) { ou[i] = 0; continue; }
+            if (t >= 1.0) { ou[i] = 1ull << 32; continue; }
+            const double y = ceil(t * 4294967296.0 - 0.5);
+            ou[i] = y <= 0.0 ? 0ull : (uint64_t)y;
+        }
+        break;
+    case NSO_OP_THR_GT:                                   /* the integer form of p > t: the least u with u32_to_p(u) > t */
+        for (uint64_t i = 0; i < n; ++i) {
+            const double t = xd[i];
+            if (t < 0.0) { ou[i] = 0; continue; }
+            if (t >= 1.0) { ou[i] = 1ull << 32; continue; }
+            const double y = floor(t * 4294967296.0 - 0.5) + 1.0;
+            ou[i] = y <= 0.0 ? 0ull : (uint64_t)y;
+        }
+        break;
+    case NSO_OP_F64_I64: for (uint64_t i = 0; i < n; ++i) oi[i] = nso_f64_to_i64_sat(xd[i]); break;
+    case NSO_OP_NORMINV: for (uint64_t i = 0; i < n; ++i) od[i] = nso_norminv(xd[i]); break;
+    case NSO_OP_LEN_DRAW: for (uint64_t i = 0; i < n; ++i) oi[i] = len_draw(xd[i]); break;
+    default: return -1;
+    }
+    return 0;
+}
 uint8_t nso_qual_value(const ns_model_tables *t, int cls, uint32_t h) { return qual_value(t, cls, h); }
 int nso_extract_pos(const uint64_t *chrom_off, uint32_t nchrom, const uint8_t *circular, int64_t length,
                     uint64_t seed, uint64_t read, uint32_t seg, uint32_t attempt, uint32_t *chrom, uint64_t *pos) {
@@ -1648,6 +1724,7 @@ int nso_generate_meta(const ns_model_tables *t, const uint8_t *bases, const uint
                 double rem = pow10m1(kde_sample(&t->kde[NS_KDE_HT], w2));
                 x = rem < 0 ? -1.0 : tot - rem;
             }
+            if (x >= 2147483648.0) ++nso_edges[NSO_EDGE_LEN_HUGE];
             if (perfect ? ((double)prm->min_len <= x && x <= (double)prm->max_len) : (0 < x && x <= (double)prm->max_len)) lens[V++] = x;   /* S:841 / S:857 */
         }
         if (V == 0) { free(lens); continue; }                                          /* S:858-859 */

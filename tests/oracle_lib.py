@@ -80,6 +80,9 @@ def lib():
         L.nso_exp.restype = C.c_double; L.nso_exp.argtypes = [C.c_double]
         L.nso_norminv.restype = C.c_double; L.nso_norminv.argtypes = [C.c_double]
         L.nso_pow10m1.restype = C.c_double; L.nso_pow10m1.argtypes = [C.c_double]
+        L.nso_f64_to_i64_sat.restype = C.c_int64; L.nso_f64_to_i64_sat.argtypes = [C.c_double]
+        L.nso_eval_batch.restype = C.c_int; L.nso_eval_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.nso_edge_counts.restype = None; L.nso_edge_counts.argtypes = [C.c_void_p, C.c_int]
         L.nso_ecdf_lookup.restype = C.c_int64
         L.nso_ecdf_lookup.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint32, C.c_double, C.c_double]
         L.nso_table_value.restype = C.c_int64
