@@ -12,16 +12,21 @@ Other workloads (not the headline; one line each): --genome chr1 --fastq --kmer-
 configs[3] (3.1 Gb reference, chimeric reads: the 8-GPU genome split); --metagenome = configs[4] (zymo10-like community of 10 species,
 one metagenome worker call per step).  --gpus N without a launcher starts the N ranks itself (torch.distributed.run on 127.0.0.1).
 
-The same JSON line also carries (N = 1):
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: nothing else.  With --full the same JSON
+line also carries (N = 1):
   "serial"    the same steps with both worker calls one after the other on ONE engine context (NS_SERIAL=1 of the CLI);
   "errlog_on" the same steps with the error profile the reference always writes (S:2006-2008) formatted on the device as well — what
               the CLI's worker calls cost on the device — and k_errlog's own store rate as a fraction of HBM peak;
   "configs2"  BASELINE configs[2] — chr1-size reference, FASTQ, -hp -k 5 — a few steps of the same protocol, with its own roofline;
   "e2e"       the END-TO-END legs of SURVEY section 8(d): generation + device-to-host copy + file writes through the engine's output
               sinks (include/nanosim_amd.h: ns_sink_*), to /dev/null and to files on /dev/shm, with and without the error profile
-              the reference always writes, next to the measured page-locked device-to-host rate.
+              the reference always writes, next to the measured page-locked device-to-host rate;
+  "chr1_fasta", "trained_shape"  (default workload only) the headline's FASTA workload on the chr1-size reference, and with its chain
+              tables in the shape of a trained model;
+  "cpu_baseline"  the C restatement of the reference (oracle/) on every host core, on a sample of the same workload;
+and, N > 1, "multi_gpu.single_rank_reference": rank 0 repeating the timed steps alone.  The --no-* options drop single objects of --full.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--dump-outputs DIR] [--full]
 """
 import argparse
 import json
@@ -681,6 +686,9 @@ def main():
     ap.add_argument("--extras-steps", type=int, default=3)
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (rank 0; a seeded sample, "
                                                           "at most 64 MB in all): the outputs of two builds can be compared")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure the serial / errlog_on / e2e / configs2 / chr1_fasta / "
+                                                        "trained_shape objects, the CPU baseline and (N > 1) the single-rank reference; "
+                                                        "without it a run does only what the headline needs")
     a = ap.parse_args()
     a.aligned_only = a.aligned_only or a.no_genome_run
     genome = "zymo10" if a.metagenome else a.genome
@@ -749,7 +757,7 @@ def main():
         per_rank = [{"rank": r, "ms_per_step": float(x[0].item()), "aligned_device_ms": float(x[1].item())} for r, x in enumerate(allr)]
 
     solo = None
-    if dist is not None and not a.no_solo_reference:
+    if dist is not None and a.full and not a.no_solo_reference:
         # the same binary, the same workload, ONE rank busy: rank 0 repeats the timed steps while the others wait at the barrier — what the
         # N-rank value is an efficiency of (weak scaling: value / (N x this))
         if rank == 0:
@@ -770,20 +778,20 @@ def main():
                                 "single_rank_reference": solo,
                                 "scaling_efficiency": out["value"] / (world * solo["value"]) if solo else None,
                                 "ranks_on_one_gpu": os.environ.get("NS_BENCH_DEVICE") is not None}
-        if world == 1 and not a.no_extras and w.eng_un is not None and n_un:
+        if a.full and world == 1 and not a.no_extras and w.eng_un is not None and n_un:
             try:
                 out.update(extra_legs(w, a, n, n_al, n_un, a.extras_steps))
             except Exception as ex:
                 out["serial"] = {"error": repr(ex)}
-        if world == 1 and not a.no_e2e and w.eng_un is not None and not w.meta:
+        if a.full and world == 1 and not a.no_e2e and w.eng_un is not None and not w.meta:
             try:
                 out["e2e"] = {"d2h_pinned": d2h_rate(w), **e2e_legs(w, n, a.e2e_steps, a.e2e_dir)}
             except Exception as ex:                 # the headline must not depend on the state of /dev/shm
                 out["e2e"] = {"error": repr(ex)}
-        if not a.no_cpu_baseline and world == 1 and not w.meta:
+        if a.full and not a.no_cpu_baseline and world == 1 and not w.meta:
             out["cpu_baseline"] = cpu_baseline(w.mdl, w.ref_host, engine, a.cpu_sample, a.fastq, a.kmer_bias, w.chimeric)
     w.close()
-    if rank == 0 and world == 1 and default_cfg and not a.no_configs2:
+    if a.full and rank == 0 and world == 1 and default_cfg and not a.no_configs2:
         # on the same GPU, same protocol: BASELINE configs[2] (chr1-size linear reference, FASTQ + base qualities + homopolymers), and the
         # headline's FASTA workload on that reference — 249 Mb do not fit the L2 / Infinity Cache the 4.6 Mb of configs[1] live in, so this
         # is the record kernel's roofline with its source bytes coming from HBM

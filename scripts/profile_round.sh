@@ -9,7 +9,7 @@ mkdir -p $O; cd /tmp; export TMPDIR=/tmp; ulimit -c 0
 run_cfg() {
   key=$1; shift; ARGS="$@"
   [ -n "$SKIP_BENCH" ] || timeout 900 python $R/bench.py $EXTRA $ARGS > $O/bench_$key.log 2>&1
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$key -o s -- python $R/bench.py --no-cpu-baseline --no-e2e --no-configs2 $ARGS > $O/bench_${key}_under_rocprof.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$key -o s -- python $R/bench.py --full --no-cpu-baseline --no-e2e --no-configs2 $ARGS > $O/bench_${key}_under_rocprof.log 2>&1
   B="python $R/bench.py --steps 1 --warmup 1 --reads 200000 --no-cpu-baseline --no-e2e --no-configs2 --aligned-only $ARGS"
   timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_${key}/fetch -o p -- $B > /dev/null 2>&1
   timeout 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_${key}/write -o p -- $B > /dev/null 2>&1
@@ -20,9 +20,9 @@ run_cfg() {
 # SKIP_BENCH=1: only the rocprofv3 passes (the plain bench line of the configuration exists already)
 CFGS=${CFGS:-"ecoli_fasta chr1_fasta chr1_fastq_k5 ecoli_fastq"}      # CFGS="ecoli_fastq" bash scripts/profile_round.sh r03: one configuration only
 want() { case " $CFGS " in *" $1 "*) return 0;; esac; return 1; }
-EXTRA="${EXTRA_FIRST:-}"       # the default command: the line the driver records (with its e2e legs and its configs2 object); EXTRA_FIRST="--no-e2e" skips the /dev/shm legs
+EXTRA="--full ${EXTRA_FIRST:-}"       # the default command with --full: its e2e legs and its configs2 object; EXTRA_FIRST="--no-e2e" skips the end-to-end file legs
 want ecoli_fasta && run_cfg ecoli_fasta
-EXTRA="--no-e2e --no-configs2"
+EXTRA="--full --no-e2e --no-configs2"
 want chr1_fasta && run_cfg chr1_fasta --genome chr1
 want chr1_fastq_k5 && run_cfg chr1_fastq_k5 --genome chr1 --fastq --kmer-bias 5
 want ecoli_fastq && run_cfg ecoli_fastq --fastq

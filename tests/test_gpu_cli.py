@@ -330,7 +330,7 @@ def _bench_line(args, env_extra=None, timeout=900):
 
 def test_bench_gpus_2_launches_its_own_ranks_on_one_gpu():
     """`bench.py --gpus N` WITHOUT torchrun starts N ranks itself; here 2 ranks on the one GPU of the box over gloo"""
-    d = _bench_line(["--gpus", "2", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1", "--reads", "100000"], {"NS_BENCH_DEVICE": "0"})
+    d = _bench_line(["--gpus", "2", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1", "--reads", "100000", "--full"], {"NS_BENCH_DEVICE": "0"})
     assert d["n_gpus"] == 2 and d["multi_gpu"]["world_size"] == 2 and d["multi_gpu"]["collectives_in_timed_region"] == 0
     assert len(d["multi_gpu"]["per_rank"]) == 2 and d["multi_gpu"]["reference_broadcast_ms"] > 0
     assert d["value"] > 0 and d["scaling"] == "weak" and d["config"]["reads_per_step_per_gpu"] == 100000
@@ -341,13 +341,20 @@ def test_bench_gpus_2_launches_its_own_ranks_on_one_gpu():
 
 
 def test_bench_metagenome_and_extras_objects():
-    """configs[4] as a bench workload, and the `serial` / `errlog_on` objects of the default line (here at a reduced size)"""
-    d = _bench_line(["--metagenome", "--steps", "2", "--warmup", "1", "--reads", "200000", "--no-cpu-baseline", "--no-e2e"])
+    """configs[4] as a bench workload, and the `serial` / `errlog_on` objects of a --full line (here at a reduced size)"""
+    d = _bench_line(["--metagenome", "--steps", "2", "--warmup", "1", "--reads", "200000", "--full", "--no-cpu-baseline", "--no-e2e"])
     assert "zymo10_like" in d["config"]["workload"] and d["value"] > 0 and d["n_gpus"] == 1
     assert d["serial"]["value"] > 0 and d["errlog_on"]["value"] > 0 and d["errlog_on"]["k_errlog_ms"] > 0
     assert 0 < d["errlog_on"]["k_errlog_frac"] < 1 and d["errlog_on"]["errlog_bytes_per_read"] > 1000
     r = d["roofline"]
     assert r["frac_kernel_only_bytes"] < r["frac"] < 1
+
+
+def test_bench_plain_line_is_the_headline_alone():
+    """without --full a run times its steps and prints the headline: none of the objects that take runs of their own"""
+    d = _bench_line(["--steps", "1", "--warmup", "1", "--reads", "100000"])
+    assert d["value"] > 0 and d["steps"] == 1 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "reads/s"
+    assert not {"serial", "errlog_on", "e2e", "cpu_baseline", "configs2", "chr1_fasta", "trained_shape", "multi_gpu"} & set(d)
 
 
 def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
