@@ -2132,6 +2132,31 @@ struct DevBuf {
     size_t cap = 0;
 };
 
+// the environment knobs of the library, read once when the context is created (read_knobs)
+struct Knobs {
+    uint32_t dbg = 0;                            // NS_DEBUG_SKIP: phase-ablation bits for profiling only (results are wrong when set)
+    uint32_t coop_min = 16384, coop_shift = 10;  // cooperative chain for the longest n>>shift reads of batches >= min (NS_COOP_MIN, NS_COOP_SHIFT);
+                                                 // 10^6 reads, chain ms at shift 9 / 10 / 11 / 12: 4.18 / 3.63 / 3.90 / 4.32
+    uint32_t ucoop_shift = 0;                    // unaligned reads: the longest n>>shift of a batch take the wave-per-read list, the rest the thread-per-read one (NS_UCOOP_SHIFT; 0: all)
+    bool ucoop_k1 = false, no_piece_threads = false, exact_order = false;     // NS_UCOOP_K=1, NS_NO_PIECE_THREADS, NS_EXACT_ORDER
+    uint32_t tail_bits = 0; int chain_block = 0;  // NS_TAIL_BITS, NS_CHAIN_BLOCK: override ns_load_model's choices (0: none)
+    double cap_rate_scale = 0; int hp_cap_shift = 0;  // test knobs NS_CAP_RATE_SCALE, NS_HP_CAP_SHIFT (> 0: a fraction of the planned capacity)
+};
+
+static void read_knobs(Knobs &k) {
+    if (const char *d = getenv("NS_DEBUG_SKIP")) k.dbg = (uint32_t)atoi(d);
+    if (const char *d = getenv("NS_COOP_MIN")) k.coop_min = (uint32_t)atoi(d);
+    if (const char *d = getenv("NS_COOP_SHIFT")) k.coop_shift = (uint32_t)atoi(d) & 31u;
+    if (const char *d = getenv("NS_UCOOP_SHIFT")) k.ucoop_shift = (uint32_t)atoi(d) & 31u;
+    if (const char *d = getenv("NS_UCOOP_K")) k.ucoop_k1 = atoi(d) == 1;
+    k.no_piece_threads = getenv("NS_NO_PIECE_THREADS") != nullptr;
+    k.exact_order = getenv("NS_EXACT_ORDER") != nullptr;
+    if (const char *d = getenv("NS_TAIL_BITS")) k.tail_bits = (uint32_t)atoi(d) & 31u;
+    if (const char *d = getenv("NS_CHAIN_BLOCK")) k.chain_block = atoi(d);
+    if (const char *d = getenv("NS_CAP_RATE_SCALE")) k.cap_rate_scale = atof(d);
+    if (const char *d = getenv("NS_HP_CAP_SHIFT")) k.hp_cap_shift = atoi(d);
+}
+
 struct ns_ctx {
     int device = 0;
     hipStream_t stream = nullptr, stream2 = nullptr;   // stream2: cooperative chain of the longest reads, concurrent with the bulk
@@ -2146,11 +2171,7 @@ struct ns_ctx {
     std::vector<void *> ref_allocs;
     double cap_rate = 0.1;
     uint64_t ref_nbases = 0;
-    uint32_t dbg = 0;          // NS_DEBUG_SKIP: phase-ablation bits for profiling only (results are wrong when set)
-    uint32_t coop_min = 16384, coop_shift = 10;  // cooperative chain for the longest n>>shift reads of batches >= min (env: NS_COOP_MIN, NS_COOP_SHIFT);
-                                                 // 10^6 reads, chain ms at shift 9 / 10 / 11 / 12: 4.18 / 3.63 / 3.90 / 4.32
-    bool ucoop_lds = true;                       // ... with the run-length tables in LDS (k_chain<true, true>; env NS_UCOOP_LDS=0: from global memory, as until round 5)
-    uint32_t ucoop_shift = 0;                    // unaligned reads: the longest n>>shift of a batch take the wave-per-read list, the rest the thread-per-read one (env: NS_UCOOP_SHIFT; 0: all)
+    Knobs knob;
     // planning + result buffers
     DevBuf l_cap, l_off, p_need, p_off;
     DevBuf n_pieces, piece_off, ev_cap, ev_off, rec_len, rec_off, err_len, err_off, name_len;
@@ -2197,8 +2218,8 @@ struct ns_ctx {
     ns_ctx *owner = nullptr;          // ... which is this one: every call on the companion takes the owner's tables as they are NOW (lend_tables)
     // the step gate: the companion holds its first chain launch until the owner's aligned call has launched its own chain — the aligned
     // call's planning kernels then run in 0.29 ms instead of 0.72 ms behind the unaligned chain's grid (same box: 9.9-10.1 -> 9.6-9.85 ms
-    // per step, profiles/r05/ab_step_gate.log; NS_STEP_GATE=0: off).  Creating the companion's streams with the device's highest priority
-    // changed nothing (9.57 / 9.67 against 9.60 / 9.67).
+    // per step, profiles/r05/ab_step_gate.log).  Companion streams of the highest priority changed nothing (9.57 / 9.67 against 9.60 / 9.67;
+    // profiles/r06/ab_step_companion.log: the unaligned call ends a millisecond earlier, the aligned one as much later; low priority starves it).
     std::atomic<int> gate{0};
     std::atomic<int> *gate_signal = nullptr, *gate_wait = nullptr;
     struct StepWorker;
@@ -2214,7 +2235,6 @@ struct ns_ctx::StepWorker {
     bool done = false, quit = false;
 };
 
-static int fail(ns_ctx *c, int code, const std::string &msg);
 // the tables of a step companion (ns_generate_step) are its owner's
 #define NS_NOT_ON_COMPANION(c) do { if ((c) && (c)->borrowed) return fail((c), NS_ESTATE, "this is a step companion: set reference, model and mode tables on the context that owns it"); } while (0)
 static int fail(ns_ctx *c, int code, const std::string &msg) {
@@ -2241,6 +2261,12 @@ static int ensure(ns_ctx *ctx, DevBuf &b, size_t bytes) {
                                         std::to_string(fr >> 20) + " MiB free of " + std::to_string(tot >> 20) + ")");
     }
     b.cap = want;
+    return NS_OK;
+}
+
+struct Need { DevBuf &b; size_t bytes; };
+static int ensure_all(ns_ctx *ctx, std::initializer_list<Need> need) {      // ensure() for each (buffer, bytes), in order, up to the first failure
+    for (const Need &x : need) if (int rc = ensure(ctx, x.b, x.bytes)) return rc;
     return NS_OK;
 }
 
@@ -2291,29 +2317,10 @@ uint32_t ns_abi_version(void) { return NS_ABI_VERSION; }
 // (Until round 6 a background context sent all but the longest eighth of its unaligned reads to the thread-per-read chain: the wave-per-read
 // one was 2.65 ms of serialized atomics then and slowed the other call's chain.  At 1.45 ms it ends the unaligned call of a step after 3.6
 // instead of 7.7 ms and leaves the record kernel alone — 0.53 instead of 0.48 of the roofline inside a step, the step itself 2 % longer:
-// profiles/r06/ab_step_companion.log, call 39.  NS_UCOOP_SHIFT=3 brings the split back.)
-int ns_set_background(ns_ctx *ctx, int on) {
-    if (!ctx) return NS_EINVAL;
-    (void)on;
-    ctx->ucoop_shift = 0u;
-    if (const char *d = getenv("NS_UCOOP_SHIFT")) ctx->ucoop_shift = (uint32_t)atoi(d) & 31u;
-    return NS_OK;
-}
+// profiles/r06/ab_step_companion.log, call 39.  NS_UCOOP_SHIFT=3 at ns_create brings the split back.)  `on` has no effect (ABI 6 keeps the call).
+int ns_set_background(ns_ctx *ctx, int /*on*/) { return ctx ? NS_OK : NS_EINVAL; }
 
-// prio: 0 = the default stream priority, 1 / -1 = the highest / lowest the device offers (NS_STEP_PRIO, for the step companion's streams:
-// an A/B knob).  Streams of another priority come from another pool of hardware queues — the runtime shares GPU_MAX_HW_QUEUES = 4 among the
-// streams of ONE priority, so with the companion's streams on top of the owner's the two chain kernels of its call share a queue and run one
-// after the other.  Measured (profiles/r06/ab_step_companion.log): high priority ends the unaligned call a millisecond earlier and the
-// aligned one as much later, low priority starves it, eight queues at the default priority change nothing: the default stays.
-static int create_stream(hipStream_t *s, int prio) {
-    int least = 0, greatest = 0;
-    if (prio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least &&
-        hipStreamCreateWithPriority(s, hipStreamNonBlocking, prio > 0 ? greatest : least) == hipSuccess) return 0;
-    return hipStreamCreateWithFlags(s, hipStreamNonBlocking) == hipSuccess ? 0 : -1;
-}
-static int create_ctx(int device, ns_ctx **out, int prio);
-int ns_create(int device, ns_ctx **out) { return create_ctx(device, out, 0); }
-static int create_ctx(int device, ns_ctx **out, int prio) {
+int ns_create(int device, ns_ctx **out) {
     if (!out) return NS_EINVAL;
     *out = nullptr;
     int n = 0;
@@ -2322,26 +2329,20 @@ static int create_ctx(int device, ns_ctx **out, int prio) {
     ns_ctx *ctx = new ns_ctx();
     ctx->device = device;
     // (ns_destroy releases whatever exists of a half-built context: null handles are skipped)
-    if (hipSetDevice(device) != hipSuccess || create_stream(&ctx->stream, prio)) {
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
         ctx->stream = nullptr;
         ns_destroy(ctx);
         return NS_EHIP;
     }
-    for (auto &e : ctx->evt) e = nullptr;
     bool ok = true;
     for (auto &e : ctx->evt)
         if (ok && hipEventCreate(&e) != hipSuccess) { e = nullptr; ok = false; }
     ctx->evt_ok = true;              // (the events that exist are destroyed with the context)
-    if (!ok || create_stream(&ctx->stream2, prio) ||
+    if (!ok || hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming) != hipSuccess) { ns_destroy(ctx); return NS_EHIP; }
     if (hipHostMalloc((void **)&ctx->pin_small, 1024, hipHostMallocDefault) != hipSuccess) { ctx->pin_small = nullptr; ns_destroy(ctx); return NS_ENOMEM; }
-    ctx->evt_ok = true;
-    if (const char *d = getenv("NS_DEBUG_SKIP")) ctx->dbg = (uint32_t)atoi(d);
-    if (const char *d = getenv("NS_COOP_MIN")) ctx->coop_min = (uint32_t)atoi(d);
-    if (const char *d = getenv("NS_COOP_SHIFT")) ctx->coop_shift = (uint32_t)atoi(d) & 31u;
-    if (const char *d = getenv("NS_UCOOP_SHIFT")) ctx->ucoop_shift = (uint32_t)atoi(d) & 31u;
-    if (const char *d = getenv("NS_UCOOP_LDS")) ctx->ucoop_lds = atoi(d) != 0;
+    read_knobs(ctx->knob);
     *out = ctx;
     return NS_OK;
 }
@@ -2353,7 +2354,7 @@ static int create_ctx(int device, ns_ctx **out, int prio) {
 static int visiting_order(ns_ctx *ctx, const uint32_t *keys, const uint32_t *idx, size_t n, uint32_t *list) {
     hipStream_t st = ctx->stream;
     int rc;
-    if (getenv("NS_EXACT_ORDER")) {
+    if (ctx->knob.exact_order) {
         size_t tmp = 0;
         HIPCHK(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tmp, keys, (uint32_t *)ctx->sort_key_out.p, idx, list, (int)n, 0, 32, st));
         if ((rc = ensure(ctx, ctx->scan_tmp, tmp))) return rc;
@@ -2559,15 +2560,13 @@ int ns_load_model(ns_ctx *ctx, const ns_model_tables *t) {
         double rate = 1.0 / (mean_match_min > 0.5 ? mean_match_min + 0.5 : 1.0);
         ctx->cap_rate = rate * 1.5 > 2.0 ? 2.0 : rate * 1.5;
         // test knob (tests/test_gpu_parity.py): a planned rate below the model's forces the event-capacity overflow and its re-plan
-        if (const char *d = getenv("NS_CAP_RATE_SCALE")) { const double f = atof(d); if (f > 0.0) ctx->cap_rate *= f; }
+        if (ctx->knob.cap_rate_scale > 0.0) ctx->cap_rate *= ctx->knob.cap_rate_scale;
 
         // ---- pack the chain tables into one blob of 8-byte words (its first part is copied to LDS by k_chain): ns_pack.h ----
         std::vector<uint64_t> blob;
         ChainTab &ct = m.ct;
         bool whole = true;
-        uint32_t force_bits = 0;
-        if (const char *d = getenv("NS_TAIL_BITS")) force_bits = (uint32_t)atoi(d) & 31u;
-        ns_pack_chain_tables(t, nseg, ct, blob, whole, force_bits);
+        ns_pack_chain_tables(t, nseg, ct, blob, whole, ctx->knob.tail_bits);
         if ((rc = upload(ctx, pool, blob.data(), blob.size(), &m.chain_blob))) return rc;
         ctx->lds_bytes = (size_t)ct.n_words_lds * 8;
         // (the packer sizes the image — hot prefixes of the match-length columns — for 24 / 32 / 45 KB: five / four / three workgroups of 256
@@ -2576,7 +2575,8 @@ int ns_load_model(ns_ctx *ctx, const ns_model_tables *t) {
         // workgroup size of the thread-per-read chain: 256 threads while five workgroups (image + 8 KB of staging) fit a CU's 160 KB, else
         // NS_CHAIN_BLOCK_BIG threads on one image while image + staging stays inside the 64 KB a launch may ask for
         ctx->chain_block = (ctx->lds_bytes + 8192 <= 32768 || ctx->lds_bytes + NS_CHAIN_BLOCK_BIG * 32u > 65536) ? NS_CHAIN_BLOCK : NS_CHAIN_BLOCK_BIG;
-        if (const char *d = getenv("NS_CHAIN_BLOCK")) { const int v = atoi(d); if (v >= 64 && v <= NS_CHAIN_BLOCK_BIG && v % 64 == 0) ctx->chain_block = (uint32_t)v; }
+        const int v = ctx->knob.chain_block;
+        if (v >= 64 && v <= NS_CHAIN_BLOCK_BIG && v % 64 == 0) ctx->chain_block = (uint32_t)v;
         double vmax = 0;
         for (uint32_t k2 = 0; k2 < nseg; ++k2) if (t->mm_vhi[k2] > vmax) vmax = t->mm_vhi[k2];
         ctx->coop_ok = t->mm_nbins <= COOP_MAX_BINS && vmax < 65535.0;   // the cooperative chain keeps match lengths in 16 bits
@@ -2637,11 +2637,11 @@ static int scan_u32(ns_ctx *ctx, const uint32_t *in, uint32_t *out, size_t n) {
 
 
 // ---------------------------------------------------------------------------------------------------------
-// metagenome (src/simulator.py:758-811, 814-1040)
+// the steps of a worker call (ns_generate)
 // ---------------------------------------------------------------------------------------------------------
 // copy phase, slow tiles, payload: the three kernels that write the sequence (and quality) lines of a batch
-static int launch_materialise(ns_ctx *ctx, const GenArgs &A, size_t n, bool fastq, uint64_t event_slots, hipEvent_t names_done = nullptr,
-                              const uint32_t *order = nullptr, int mode = MAT_REF, uint64_t total_bases = 0) {
+static int launch_materialise(ns_ctx *ctx, const GenArgs &A, size_t n, bool fastq, const uint32_t *order = nullptr, int mode = MAT_REF,
+                              uint64_t total_bases = 0) {
     hipStream_t st = ctx->stream;
     if (A.prm.kind == NS_KIND_UNALIGNED) {
         // work list: stretches per read + scan (list_b / list_c are free once the passes are done); the grid is bounded from the batch's
@@ -2656,7 +2656,6 @@ static int launch_materialise(ns_ctx *ctx, const GenArgs &A, size_t n, bool fast
         if (int rc = scan_u32(ctx, cnt, seg_off, n + 1)) return rc;
         const uint64_t bound = total_bases / NS_DENSE_SEG + n + 1;
         if (bound > 0x7fffffffull) return fail(ctx, NS_EINVAL, "unaligned batch too large for one launch of the record kernel (split it)");
-        if (names_done) HIPCHK(hipStreamWaitEvent(st, names_done, 0));
         // FASTQ: the bases here, the quality lines in k_qualities (one class for the whole read, S:1521: no class words) — drawn inside the
         // dense kernel they came through the per-value look-up in global memory: 1.25 against 0.7 ms per 50 000 reads
         k_materialise_dense<false><<<dim3((unsigned)bound), dim3(64), 0, st>>>(A, seg_off);
@@ -2667,8 +2666,6 @@ static int launch_materialise(ns_ctx *ctx, const GenArgs &A, size_t n, bool fast
         }
         return NS_OK;
     }
-    (void)event_slots;                        // (the letter words are drawn in the tile prologue: event_word, ns_materialise.h)
-    if (names_done) HIPCHK(hipStreamWaitEvent(st, names_done, 0));
     for (int round = 0;; ++round) {
         size_t cap = ctx->slow_q.cap >= 16 + sizeof(SlowTile) ? (ctx->slow_q.cap - 16) / sizeof(SlowTile) : 0;
         if (cap < n / 4 + 4096) {
@@ -2683,20 +2680,19 @@ static int launch_materialise(ns_ctx *ctx, const GenArgs &A, size_t n, bool fast
         sq.cap = (uint32_t)(cap > 0xffffffffull ? 0xffffffffull : cap);
         if (!(ctx->sq_zeroed && round == 0)) HIPCHK(hipMemsetAsync(sq.count, 0, 4, st));
         ctx->sq_zeroed = false;
-        const uint32_t *wd = nullptr;               // (MAT_HP_FINAL reads A.hp_wd; the other modes draw the letter words: event_word)
-        if (ctx->dbg & 1024u) order = nullptr;          // (profiling: reads in index order)
+        if (ctx->knob.dbg & 1024u) order = nullptr;     // (profiling: reads in index order)
         const dim3 grid_q((unsigned)((n + NS_MATQ_WAVES - 1) / NS_MATQ_WAVES)), blk_q(64 * NS_MATQ_WAVES), grid_1((unsigned)n), blk_1(64);
-        const uint32_t *order_b = (ctx->dbg & 2048u) ? order : nullptr;      // (the record kernel: reads in index order)
+        const uint32_t *order_b = (ctx->knob.dbg & 2048u) ? order : nullptr; // (the record kernel: reads in index order)
         if (round == 0) HIPCHK(hipEventRecord(ctx->evt[12], st));            // the record kernel itself (ns_batch_info.ms_kernel[NS_K_RECORD_KERNEL])
         if (mode == MAT_REF) {
-            if (fastq) k_materialise<true, MAT_REF><<<grid_1, blk_1, 0, st>>>(A, wd, ctx->dbg, sq, order_b);
-            else k_materialise<false, MAT_REF><<<grid_1, blk_1, 0, st>>>(A, wd, ctx->dbg, sq, order_b);
+            if (fastq) k_materialise<true, MAT_REF><<<grid_1, blk_1, 0, st>>>(A, nullptr, ctx->knob.dbg, sq, order_b);
+            else k_materialise<false, MAT_REF><<<grid_1, blk_1, 0, st>>>(A, nullptr, ctx->knob.dbg, sq, order_b);
         } else if (mode == MAT_HP_SCRATCH) {
-            if (fastq) k_materialise<true, MAT_HP_SCRATCH><<<grid_1, blk_1, 0, st>>>(A, wd, ctx->dbg, sq, nullptr);
-            else k_materialise<false, MAT_HP_SCRATCH><<<grid_1, blk_1, 0, st>>>(A, wd, ctx->dbg, sq, nullptr);
+            if (fastq) k_materialise<true, MAT_HP_SCRATCH><<<grid_1, blk_1, 0, st>>>(A, nullptr, ctx->knob.dbg, sq, nullptr);
+            else k_materialise<false, MAT_HP_SCRATCH><<<grid_1, blk_1, 0, st>>>(A, nullptr, ctx->knob.dbg, sq, nullptr);
         } else {
-            if (fastq) k_materialise<true, MAT_HP_FINAL><<<grid_1, blk_1, 0, st>>>(A, wd, ctx->dbg, sq, order_b);
-            else k_materialise<false, MAT_HP_FINAL><<<grid_1, blk_1, 0, st>>>(A, wd, ctx->dbg, sq, nullptr);
+            if (fastq) k_materialise<true, MAT_HP_FINAL><<<grid_1, blk_1, 0, st>>>(A, nullptr, ctx->knob.dbg, sq, order_b);
+            else k_materialise<false, MAT_HP_FINAL><<<grid_1, blk_1, 0, st>>>(A, nullptr, ctx->knob.dbg, sq, nullptr);
         }
         HIPCHK(hipGetLastError());
         if (round == 0) { HIPCHK(hipEventRecord(ctx->evt[13], st)); ctx->rec_timed = true; }
@@ -2735,20 +2731,19 @@ static int launch_materialise(ns_ctx *ctx, const GenArgs &A, size_t n, bool fast
 // -k stage 1 on the reads of `A` (A.prm.n_reads of them): filter the events inside homopolymers (S:1920-1947), write the pieces before
 // mutate_homo to the scratch buffer, turn mutate_homo (S:618-706) into an edit list per piece + final lengths, and apply the final
 // length check (stats[5] = reads that failed it)
-static int hp_stage1(ns_ctx *ctx, const ns_params *prm, GenArgs &A, size_t n, uint64_t tot_pieces, uint64_t event_slots,
-                     unsigned long long *stats, double *ms_hp) {
+static int hp_stage1(ns_ctx *ctx, const ns_params *prm, GenArgs &A, size_t n, uint64_t tot_pieces, unsigned long long *stats, double *ms_hp) {
     hipStream_t st = ctx->stream;
     const dim3 blk(256), grid_t((unsigned)((n + 1 + 255) / 256));
     int rc;
     float ms = 0;
     HIPCHK(hipEventRecord(ctx->evt[9], st));
-    if ((rc = ensure(ctx, ctx->hp_len, (size_t)tot_pieces * 4 + 64)) || (rc = ensure(ctx, ctx->hp_nev, (size_t)tot_pieces * 4 + 64)) ||
-        (rc = ensure(ctx, ctx->hp_nrun, (size_t)tot_pieces * 4 + 64))) return rc;
+    if ((rc = ensure_all(ctx, {{ctx->hp_len, (size_t)tot_pieces * 4 + 64}, {ctx->hp_nev, (size_t)tot_pieces * 4 + 64},
+                               {ctx->hp_nrun, (size_t)tot_pieces * 4 + 64}, {ctx->hp_pcnt, (n + 1) * 4}, {ctx->hp_pord, (n + 1) * 4}})))
+        return rc;
     A.hp_len = (uint32_t *)ctx->hp_len.p; A.hp_nev = (uint32_t *)ctx->hp_nev.p;
-    if ((rc = ensure(ctx, ctx->hp_pcnt, (n + 1) * 4)) || (rc = ensure(ctx, ctx->hp_pord, (n + 1) * 4))) return rc;
     A.hp_pcnt = (uint32_t *)ctx->hp_pcnt.p; A.hp_pord = (const uint32_t *)ctx->hp_pord.p;
     A.hp_bm = nullptr;
-    if (prm->kmer_bias >= 2 && prm->kmer_bias <= 16 && !getenv("NS_NO_HP_BITMAP")) {
+    if (prm->kmer_bias >= 2 && prm->kmer_bias <= 16) {               // (k > 16: the windowed walk over the reference)
         if (ctx->hp_bm_k != prm->kmer_bias) {           // once per (reference, k)
             const uint64_t nb = ctx->ref_nbases, nthreads = (nb + 3) / 4;
             if ((rc = ensure(ctx, ctx->hp_bm, (size_t)nthreads + 64))) return rc;
@@ -2767,7 +2762,7 @@ static int hp_stage1(ns_ctx *ctx, const ns_params *prm, GenArgs &A, size_t n, ui
     // (the second record pass reads the scratch pieces with unaligned 16-byte loads that may start before / end behind a piece)
     if ((rc = ensure(ctx, ctx->scr, (size_t)scr_bytes + 2 * NS_REF_PAD + 64))) return rc;
     A.scr = (uint8_t *)ctx->scr.p + NS_REF_PAD;
-    if ((rc = launch_materialise(ctx, A, n, prm->fastq != 0, event_slots, nullptr, nullptr, MAT_HP_SCRATCH))) return rc;
+    if ((rc = launch_materialise(ctx, A, n, prm->fastq != 0, nullptr, MAT_HP_SCRATCH))) return rc;
     if (ctx->hp_cap_k != prm->kmer_bias) {      // event capacity per scratch byte: 8x the density of runs >= k in a random sequence
         double rate = 6.0;
         for (uint32_t j = 1; j < prm->kmer_bias && rate > 1e-6; ++j) rate *= 0.25;
@@ -2775,12 +2770,12 @@ static int hp_stage1(ns_ctx *ctx, const ns_params *prm, GenArgs &A, size_t n, ui
         while (sh < 16 && rate * (double)(2u << sh) <= 1.0) ++sh;
         ctx->hp_shift = sh; ctx->hp_pad = 64; ctx->hp_cap_k = prm->kmer_bias;
         // test knob: NS_HP_CAP_SHIFT=s plans 2^-s of that capacity and one slot of slack per piece, so that the stage's own overflow path runs
-        if (const char *d = getenv("NS_HP_CAP_SHIFT")) { const int s = atoi(d); if (s > 0) { ctx->hp_shift = std::min<uint32_t>(16u, sh + (uint32_t)s); ctx->hp_pad = 1; } }
+        if (const int s = ctx->knob.hp_cap_shift; s > 0) { ctx->hp_shift = std::min<uint32_t>(16u, sh + (uint32_t)s); ctx->hp_pad = 1; }
     }
     for (int retry = 0;; ++retry) {
         A.hp_shift = ctx->hp_shift; A.hp_pad = ctx->hp_pad;
         const size_t slots = (size_t)(scr_bytes >> A.hp_shift) + (size_t)A.hp_pad * (tot_pieces + 1) + 64;
-        if ((rc = ensure(ctx, ctx->hp_ev, slots * sizeof(ns_event))) || (rc = ensure(ctx, ctx->hp_wd, slots * 4)) || (rc = ensure(ctx, ctx->hp_runs, slots * 8))) return rc;
+        if ((rc = ensure_all(ctx, {{ctx->hp_ev, slots * sizeof(ns_event)}, {ctx->hp_wd, slots * 4}, {ctx->hp_runs, slots * 8}}))) return rc;
         A.hp_ev = (ns_event *)ctx->hp_ev.p; A.hp_wd = (uint32_t *)ctx->hp_wd.p;
         if (!A.meta || A.key_pos) HIPCHK(hipMemsetAsync((unsigned long long *)ctx->stats.p + 1, 0, sizeof(unsigned long long), st));   // (kept across metagenome passes)
         HIPCHK(hipMemsetAsync((unsigned long long *)ctx->stats.p + 5, 0, sizeof(unsigned long long), st));
@@ -2801,6 +2796,92 @@ static int hp_stage1(ns_ctx *ctx, const ns_params *prm, GenArgs &A, size_t n, ui
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipEventElapsedTime(&ms, ctx->evt[9], ctx->evt[10]));
     *ms_hp += ms;
+    return NS_OK;
+}
+
+// what a planner (genome_passes, meta_passes, trx_passes) leaves for the record stage
+struct Plan {
+    uint64_t tot_pieces = 0, tot_cap = 0;     // pieces of the batch, event slots handed out
+    unsigned long long stats[8] = {};         // the counters after the last pass (k_stats_fold)
+    double ms_hp = 0;                         // time of the -k stage
+};
+
+// the thread-per-read chain over A's list on `st`: the tables in LDS (events staged there too) unless the batch is --perfect
+static int launch_chain(ns_ctx *ctx, const GenArgs &A, hipStream_t st) {
+    const bool lds = ctx->lds_tables && A.prm.kind != NS_KIND_PERFECT;
+    const uint32_t cb = lds ? ctx->chain_block : NS_CHAIN_BLOCK;
+    const dim3 grid((A.list_n + cb - 1) / cb), blk(cb);
+    if (A.list_n && lds) k_chain<true, false><<<grid, blk, ctx->lds_bytes + (A.ev_stage ? cb * 32u : 0u), st>>>(A);
+    else if (A.list_n) k_chain<false, false><<<grid, blk, 0, st>>>(A);
+    HIPCHK(hipGetLastError());
+    return NS_OK;
+}
+
+// the wave-per-read chain over B's list on the second stream, forked from `st`; the caller joins it (ev_join) behind its own launches
+static int launch_chain_coop(ns_ctx *ctx, GenArgs B, hipStream_t st) {
+    HIPCHK(hipEventRecord(ctx->ev_fork, st));
+    HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+    const size_t mix = (size_t)B.m.ct.n_words_mix * 8;
+    // unaligned reads: the run-length tables in LDS (k_chain<true, true>; the image must fit next to nothing else: 64 KB)
+    if (B.prm.kind == NS_KIND_UNALIGNED && ctx->lds_tables && mix <= 64u * 1024u)
+        k_chain<true, true><<<dim3(B.list_n), dim3(64), mix, ctx->stream2>>>(B);
+    else { B.coop_mix = mix <= 32u * 1024u ? 1u : 0u;
+           k_chain<false, true><<<dim3(B.list_n), dim3(64), B.coop_mix ? mix : 0, ctx->stream2>>>(B); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
+    return NS_OK;
+}
+
+// the end of a chain pass (evt[3] .. evt[4]): fold the counters, read them back, add the chain's time.  A read that outgrew its event
+// capacity (rare): counted, and `again` with twice the planned rates — the caller restores what the pass changed and repeats it
+static int end_pass(ns_ctx *ctx, GenArgs &A, int retry, unsigned long long *stats, double &ms_chain, ns_batch_info *info, bool &again) {
+    fold_stats(ctx, ctx->stream);
+    if (int rc = read_small(ctx, ctx->stream, stats, ctx->stats.p, 8 * sizeof(unsigned long long))) return rc;
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ctx->evt[3], ctx->evt[4])); ms_chain += ms;
+    again = (stats[0] & NS_OVER_MASK) != 0;
+    if (!again) return NS_OK;
+    info->n_overflow += stats[0] & NS_OVER_MASK;
+    if (retry >= 6) return fail(ctx, NS_ENOMEM, "event capacity overflow persists after 6 retries");
+    A.cap_rate *= 2.0; A.cap_gap_mul *= 2;
+    return NS_OK;
+}
+
+static int attempt_limit(ns_ctx *ctx) {
+    return fail(ctx, NS_EINVAL, "some reads found no acceptable length within the attempt limit "
+                                "(min_len/max_len too narrow for this model, or its reads do not fit the event record: runs <= 4095 bases, "
+                                "insertion / deletion balance within +-131071 bases per segment)");
+}
+
+// metagenome / transcriptome: A writes the final arrays (what the record kernels read); the view returned writes the per-pass arrays of
+// the same kernels
+static GenArgs pass_views(ns_ctx *ctx, GenArgs &A) {
+    A.f_reads = (ns_read *)ctx->reads.p; A.f_pieces = (ns_piece *)ctx->pieces.p; A.f_name_len = (uint16_t *)ctx->name_len.p;
+    A.f_rec_len = (uint64_t *)ctx->rec_len.p; A.f_err_len = (uint64_t *)ctx->err_len.p;
+    A.key_pos_w = (uint32_t *)ctx->key_pos.p;
+    GenArgs P = A;
+    P.reads = (ns_read *)ctx->t_reads.p; P.pieces = (ns_piece *)ctx->t_pieces.p; P.name_len = (uint16_t *)ctx->t_name_len.p;
+    P.rec_len = (uint64_t *)ctx->t_rec_len.p; P.err_len = (uint64_t *)ctx->t_err_len.p;
+    P.accept = (uint64_t *)ctx->accept.p; P.accept_scan = (uint64_t *)ctx->accept_scan.p;
+    P.list = nullptr;
+    P.cap_rate = ctx->cap_rate;
+    return P;
+}
+
+// intron retention: the splice arena — slot offsets, then the copy from the genome (before anything reads the pieces' bases)
+static int ir_splice(ns_ctx *ctx, GenArgs &A, size_t n) {
+    int rc;
+    if ((rc = scan_u64(ctx, A.ir_need, (uint64_t *)ctx->ir_off.p, n + 1))) return rc;
+    uint64_t arena_bytes = 0;
+    if ((rc = read_small(ctx, ctx->stream, &arena_bytes, (uint64_t *)ctx->ir_off.p + n, 8))) return rc;
+    if ((rc = ensure(ctx, ctx->spliced, (size_t)arena_bytes + 64))) return rc;
+    A.ir.arena = (uint8_t *)ctx->spliced.p; A.ir.arena_off = (const uint64_t *)ctx->ir_off.p;
+    A.ref.spliced = (const uint8_t *)ctx->spliced.p;
+    ctx->spliced_bytes = arena_bytes;
+    if (arena_bytes) {
+        k_ir_splice<<<dim3((unsigned)((n + NS_WPB - 1) / NS_WPB)), dim3(64 * NS_WPB), 0, ctx->stream>>>(A);
+        HIPCHK(hipGetLastError());
+    }
     return NS_OK;
 }
 
@@ -2913,9 +2994,9 @@ int ns_species_bases(ns_ctx *ctx, double *out) {
     return NS_OK;
 }
 
-// assign_species (S:758-811): the species of every segment of a pass, by greedy quota.  lens: the filtered length list of the
-// pass (in draw order); on return the list in assignment order (chimeric segments first, the rest descending).  Draws keyed by
-// the batch: Philox(ST_SPECIES, attempt = pass, idx = segment pointer): word 0 = random.choice, word 1 = random.uniform(0, 100).
+// ---------------------------------------------------------------------------------------------------------
+// metagenome (src/simulator.py:758-811, 814-1040)
+// ---------------------------------------------------------------------------------------------------------
 // assign_species (S:758-811): the species of every segment of a pass, by greedy quota — a sequential walk, on the host.  `lens`: the
 // filtered length list in assignment order (chimeric segments first in draw order, the rest descending — sorted on the device);
 // `to_add`: sum(length_list) taken left to right over the list in draw order; `words`: the draws of every segment pointer.
@@ -3053,27 +3134,17 @@ __global__ void __launch_bounds__(256) k_meta_layout(MetaHist H, uint32_t np, ui
 
 // the passes of one metagenome worker: every pass draws fresh lengths for the reads still missing, assigns species and tries
 // each read once; accepted reads take consecutive numbers
-static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, GenArgs &A, uint64_t &tot_pieces, uint64_t &tot_cap,
-                       unsigned long long *stats) {
+static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, GenArgs &A, Plan &pl) {
     const size_t n = (size_t)prm->n_reads;
+    unsigned long long *stats = pl.stats;
     const uint32_t ns = ctx->nspecies;
     hipStream_t st = ctx->stream;
     const dim3 blk(256);
     int rc;
-    float ms = 0;
     HIPCHK(hipMemsetAsync(ctx->stats.p, 0, NS_STATS_BYTES, st));
     HIPCHK(hipEventRecord(ctx->evt[1], st));
     k_nseg<<<dim3((unsigned)((n + 1 + 255) / 256)), blk, 0, st>>>(A);       // num_segment (S:825-828); zeroes the scan sentinels
     HIPCHK(hipGetLastError());
-    const bool trace = getenv("NS_META_TRACE") != nullptr;      // host-side section timing of the passes (stderr)
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto lap = [&](const char *what, std::chrono::steady_clock::time_point &t) {
-        if (!trace) return;
-        auto t2 = now();
-        fprintf(stderr, "[meta] %-22s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t2 - t).count());
-        t = t2;
-    };
-    auto tt = now();
     // num_segment (k_nseg) stays on the device: the passes need its histogram over the reads still missing, 65 counters per pass
     if ((rc = ensure(ctx, ctx->meta_num, 16 + (NS_MAX_SEG + 1) * 8))) return rc;
     unsigned long long *d_hist = (unsigned long long *)((uint8_t *)ctx->meta_num.p + 16);
@@ -3085,34 +3156,19 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
         return read_small(ctx, st, hist, d_hist, (NS_MAX_SEG + 1) * 8);
     };
     if ((rc = seg_hist(0))) return rc;
-    lap("k_nseg + histogram", tt);
-    tot_pieces = 0;
-    uint64_t tot_seg = 0;
+    uint64_t tot_pieces = 0, tot_seg = 0;
     for (uint32_t v = 1; v <= NS_MAX_SEG; ++v) { tot_pieces += (2ull * v - 1ull) * hist[v]; tot_seg += (uint64_t)v * hist[v]; }
-    if ((rc = ensure(ctx, ctx->pieces, tot_pieces * sizeof(ns_piece) + 64)) || (rc = ensure(ctx, ctx->t_pieces, tot_pieces * sizeof(ns_piece) + 64)) ||
-        (rc = ensure(ctx, ctx->t_reads, n * sizeof(ns_read))) || (rc = ensure(ctx, ctx->t_name_len, (n + 1) * 2)) ||
-        (rc = ensure(ctx, ctx->t_rec_len, (n + 1) * 8)) || (rc = ensure(ctx, ctx->t_err_len, (n + 1) * 8)) ||
-        (rc = ensure(ctx, ctx->accept, (n + 1) * 8)) || (rc = ensure(ctx, ctx->accept_scan, (n + 1) * 8)) ||
-        (rc = ensure(ctx, ctx->key_pos, (n + 1) * 4)) || (rc = ensure(ctx, ctx->draw_x, (tot_seg + 1) * 8)) ||
-        (rc = ensure(ctx, ctx->m_segptr, (n + 1) * 4)) || (rc = ensure(ctx, ctx->m_len, (tot_seg + 1) * 4)) ||
-        (rc = ensure(ctx, ctx->m_species, (tot_seg + 1) * 2)) || (rc = ensure(ctx, ctx->species_bases, (size_t)ns * 8 * NS_STATS_WAYS)))
+    if ((rc = ensure_all(ctx, {{ctx->pieces, tot_pieces * sizeof(ns_piece) + 64}, {ctx->t_pieces, tot_pieces * sizeof(ns_piece) + 64},
+                               {ctx->t_reads, n * sizeof(ns_read)}, {ctx->t_name_len, (n + 1) * 2}, {ctx->t_rec_len, (n + 1) * 8}, {ctx->t_err_len, (n + 1) * 8},
+                               {ctx->accept, (n + 1) * 8}, {ctx->accept_scan, (n + 1) * 8}, {ctx->key_pos, (n + 1) * 4}, {ctx->draw_x, (tot_seg + 1) * 8},
+                               {ctx->m_segptr, (n + 1) * 4}, {ctx->m_len, (tot_seg + 1) * 4}, {ctx->m_species, (tot_seg + 1) * 2},
+                               {ctx->species_bases, (size_t)ns * 8 * NS_STATS_WAYS}})))
         return rc;
     HIPCHK(hipMemsetAsync(ctx->species_bases.p, 0, (size_t)ns * 8 * NS_STATS_WAYS, st));
-    lap("nseg loop + buffers", tt);
-    // final arrays (what the record kernels read) and the per-pass views of the same kernels
-    A.f_reads = (ns_read *)ctx->reads.p; A.f_pieces = (ns_piece *)ctx->pieces.p; A.f_name_len = (uint16_t *)ctx->name_len.p;
-    A.f_rec_len = (uint64_t *)ctx->rec_len.p; A.f_err_len = (uint64_t *)ctx->err_len.p;
-    A.key_pos_w = (uint32_t *)ctx->key_pos.p;
     A.species_bases = (unsigned long long *)ctx->species_bases.p;
-    GenArgs P = A;
-    P.reads = (ns_read *)ctx->t_reads.p; P.pieces = (ns_piece *)ctx->t_pieces.p; P.name_len = (uint16_t *)ctx->t_name_len.p;
-    P.rec_len = (uint64_t *)ctx->t_rec_len.p; P.err_len = (uint64_t *)ctx->t_err_len.p;
-    P.accept = (uint64_t *)ctx->accept.p; P.accept_scan = (uint64_t *)ctx->accept_scan.p;
+    GenArgs P = pass_views(ctx, A);
     P.draw_x = (double *)ctx->draw_x.p;
     P.m_segptr = (const uint32_t *)ctx->m_segptr.p; P.m_len = (const int32_t *)ctx->m_len.p; P.m_species = (const uint16_t *)ctx->m_species.p;
-    P.list = nullptr;
-    P.cap_rate = ctx->cap_rate;
-    const bool lds = ctx->lds_tables && prm->kind != NS_KIND_PERFECT;
     const bool perfect = prm->kind == NS_KIND_PERFECT;      // S:838-842, 879-910: no errors, no head/tail, the quotas are never updated
     const ns_key bkey{(uint32_t)prm->seed, (uint32_t)(prm->seed >> 32), (uint32_t)prm->first_read, (uint32_t)(prm->first_read >> 32)};
     std::vector<double> cur_bases(ns, 0.0);
@@ -3122,24 +3178,17 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
     unsigned long long good_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // counters after the last complete pass
     bool first_pass = true;
     for (uint32_t p = 0; passed < n; ++p) {
-        if (p >= NS_MAX_ATTEMPT)
-            return fail(ctx, NS_EINVAL, "some reads found no acceptable length within the attempt limit "
-                                        "(min_len/max_len too narrow for this model, or its reads do not fit the event record: runs <= 4095 bases, "
-                                            "insertion / deletion balance within +-131071 bases per segment)");
+        if (p >= NS_MAX_ATTEMPT) return attempt_limit(ctx);
         const uint64_t m = n - passed;
         if (p && (rc = seg_hist(passed))) return rc;                               // num_segment[passed:], S:1034 — as a histogram: the reads
                                                                                    // are taken by descending segment count (S:760)
         uint64_t D = 0;
         for (uint32_t v = 1; v <= NS_MAX_SEG; ++v) D += (uint64_t)v * hist[v];
-        lap("histogram", tt);
         P.attempt = p; P.draw_n = D;
         k_meta_draw<<<dim3((unsigned)((D + 255) / 256)), blk, 0, st>>>(P);         // S:852
         HIPCHK(hipGetLastError());
-        lap("setup/alloc", tt);
-        if ((rc = ensure_pin(ctx, ctx->pin_a, (D + 1) * 8)) || (rc = ensure_pin(ctx, ctx->pin_b, (D + 1) * 8)) ||
-            (rc = ensure_pin(ctx, ctx->pin_c, (D + 1) * 8)) || (rc = ensure(ctx, ctx->draw_sel, (D + 1) * 8)) ||
-            (rc = ensure(ctx, ctx->draw_sorted, (D + 1) * 8)) || (rc = ensure(ctx, ctx->meta_words, (D + 1) * 8)) ||
-            false)
+        if ((rc = ensure_pin(ctx, ctx->pin_a, (D + 1) * 8)) || (rc = ensure_pin(ctx, ctx->pin_b, (D + 1) * 8)) || (rc = ensure_pin(ctx, ctx->pin_c, (D + 1) * 8)) ||
+            (rc = ensure_all(ctx, {{ctx->draw_sel, (D + 1) * 8}, {ctx->draw_sorted, (D + 1) * 8}, {ctx->meta_words, (D + 1) * 8}})))
             return rc;
         double *h_draw = (double *)ctx->pin_a.p;
         // the filter (S:857; --perfect: S:841) on the device, order kept; sum(length_list) (S:767) is taken left to right, as Python
@@ -3154,7 +3203,6 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
         }
         int v_sel = 0;
         if ((rc = read_small(ctx, st, &v_sel, ctx->meta_num.p, 4))) return rc;
-        lap("draw + filter", tt);
         const uint64_t V = (uint64_t)v_sel;
         if (!V) continue;                                                          // S:858-859
         uint64_t chim = 0;
@@ -3226,7 +3274,6 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
             if (!walked) {               // S:767: sum(length_list), left to right as Python adds (~1 ms per 10^6 values) — while the device sorts and plans
                 HIPCHK(hipEventSynchronize(ev_draws));
                 for (uint64_t j = 0; j < V; ++j) to_add += h_draw[j];
-                lap("sum(length_list)", tt);
             }
             if ((rc = read_small(ctx, st, &pass_cap, P.ev_off + np_l, 8))) return rc;   // also: the sorted lengths and the words have reached the host
             if ((rc = ensure_keep(ctx, ctx->events, (size_t)(ev_base + pass_cap) * sizeof(ns_event) + 64, (size_t)ev_base * sizeof(ns_event)))) return rc;
@@ -3236,29 +3283,18 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
             if (first_pass && retry == 0) { HIPCHK(hipEventRecord(ctx->evt[2], st)); first_pass = false; }
             // the pass positions are (nearly) sorted by descending length: the head of the list goes to the cooperative chain
             uint32_t n_coop = 0;
-            if (ctx->coop_ok && !perfect && np_l >= ctx->coop_min) n_coop = (uint32_t)(np_l >> ctx->coop_shift);
+            if (ctx->coop_ok && !perfect && np_l >= ctx->knob.coop_min) n_coop = (uint32_t)(np_l >> ctx->knob.coop_shift);
             GenArgs Q = P;
             if (n_coop) {
                 GenArgs B = P; B.list_n = n_coop; B.list_base = 0;
-                HIPCHK(hipEventRecord(ctx->ev_fork, st));
-                HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-                B.coop_mix = (size_t)B.m.ct.n_words_mix * 8 <= 32u * 1024u ? 1u : 0u;
-                k_chain<false, true><<<dim3(n_coop), dim3(64), B.coop_mix ? (size_t)B.m.ct.n_words_mix * 8 : 0, ctx->stream2>>>(B);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
+                if ((rc = launch_chain_coop(ctx, B, st))) return rc;
                 Q.list_base = n_coop; Q.list_n = (uint32_t)np_l - n_coop;
             }
-            const uint32_t cb = lds ? ctx->chain_block : NS_CHAIN_BLOCK;
-            const dim3 grid_pc((unsigned)((Q.list_n + cb - 1) / cb)), blk_c(cb);
-            if (lds) k_chain<true, false><<<grid_pc, blk_c, ctx->lds_bytes + (Q.ev_stage ? cb * 32u : 0u), st>>>(Q);
-            else k_chain<false, false><<<grid_pc, blk_c, 0, st>>>(Q);
-            HIPCHK(hipGetLastError());
+            if ((rc = launch_chain(ctx, Q, st))) return rc;
             if (n_coop) HIPCHK(hipStreamWaitEvent(st, ctx->ev_join, 0));
             HIPCHK(hipEventRecord(ctx->evt[4], st));
             if (!walked) {               // ---- the host's walk over the quotas, next to the chain kernels
-                const uint64_t P_seg = assign_species_host(ctx, h_sorted, V, to_add, h_words, hist, cur_bases, h_species, &np64);   // S:866-867
-                (void)P_seg;
-                lap("assign_species", tt);
+                assign_species_host(ctx, h_sorted, V, to_add, h_words, hist, cur_bases, h_species, &np64);   // S:866-867
                 np = (size_t)std::min<uint64_t>(np64, m);
                 walked = true;
                 if (np > np_l) return fail(ctx, NS_ESTATE, "metagenome pass: assign_species reached more reads than the pass planned");
@@ -3278,14 +3314,10 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
             P.list_n = (uint32_t)np;
             k_meta_tail<<<dim3((unsigned)((np + 255) / 256)), blk, 0, st>>>(P);
             HIPCHK(hipGetLastError());
-            fold_stats(ctx, st);
-            if ((rc = read_small(ctx, st, stats, ctx->stats.p, 8 * sizeof(unsigned long long)))) return rc;
-            HIPCHK(hipEventElapsedTime(&ms, ctx->evt[3], ctx->evt[4])); ms_chain += ms;
-            if (!(stats[0] & NS_OVER_MASK)) break;
-            // a read outgrew its event capacity (rare): the lists of the pass are repeated with twice the capacity
-            info->n_overflow += stats[0] & NS_OVER_MASK;
-            if (retry >= 6) return fail(ctx, NS_ENOMEM, "event capacity overflow persists after 6 retries");
-            P.cap_rate *= 2.0; P.cap_gap_mul *= 2;
+            bool again = false;
+            if ((rc = end_pass(ctx, P, retry, stats, ms_chain, info, again))) return rc;
+            if (!again) break;
+            // (the lists of the pass are repeated with twice the capacity, on the counters of the last complete pass)
             HIPCHK(hipMemcpyAsync(ctx->stats.p, good_stats, 8 * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
         }
         if (!np) continue;
@@ -3294,7 +3326,7 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
             GenArgs H = P;
             H.prm.n_reads = np;                      // bound of the thread-per-read kernels of the stage
             double ms_hp = 0;
-            if ((rc = hp_stage1(ctx, prm, H, np, tot_pieces, ev_base + pass_cap, stats, &ms_hp))) return rc;
+            if ((rc = hp_stage1(ctx, prm, H, np, tot_pieces, stats, &ms_hp))) return rc;
             info->ms_kernel[NS_K_HP] += ms_hp;
             stats[5] = 0;
         } else if (prm->emit_errlog) {     // sizes of the error-profile rows of the reads this pass accepted (k_meta_commit adds the read numbers)
@@ -3315,7 +3347,6 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
         HIPCHK(hipMemcpyAsync(&acc, P.accept_scan + np, 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(sb.data(), ctx->species_bases.p, (size_t)ns * 8 * NS_STATS_WAYS, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        lap("plan/chain/commit", tt);
         for (uint32_t s = 0; s < ns && !perfect; ++s) {
             unsigned long long tot = 0;
             for (uint32_t w = 0; w < NS_STATS_WAYS; ++w) tot += sb[(size_t)w * ns + s];
@@ -3329,10 +3360,14 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
     A.pieces = (ns_piece *)ctx->pieces.p;
     A.key_pos = (const uint32_t *)ctx->key_pos.p;
     A.m_species = P.m_species; A.m_segptr = P.m_segptr;
-    tot_pieces = pieces_passed;
-    tot_cap = ev_base;
+    pl.tot_pieces = pieces_passed;
+    pl.tot_cap = ev_base;
     ctx->last_species_bases = cur_bases;
     info->ms_kernel[NS_K_EVENTS] = ms_chain;
+    if (A.hp) {         // the passes validated the final lengths; the stage runs once more on the reads in their final order
+        pl.ms_hp = info->ms_kernel[NS_K_HP];
+        if ((rc = hp_stage1(ctx, prm, A, n, pl.tot_pieces, stats, &pl.ms_hp))) return rc;
+    }
     return NS_OK;
 }
 
@@ -3341,14 +3376,13 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
 // the candidate table), and the survivors that belong to the batch move to their slots.  Too few picks for a full table, or too few
 // survivors in a block, repeats the planning with more picks / a longer table (deterministic: a pick is keyed by (block, pick), a
 // candidate by (block, candidate)).
-static int trx_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, GenArgs &A, uint64_t &tot_pieces, uint64_t &tot_cap,
-                      unsigned long long *stats) {
+static int trx_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, GenArgs &A, Plan &pl) {
     const size_t n = (size_t)prm->n_reads;
+    unsigned long long *stats = pl.stats;
     hipStream_t st = ctx->stream;
     const dim3 blk(256);
     const uint64_t W = NS_TRX_BLOCK, g0 = prm->first_read, b0 = g0 / W, nb = (g0 + n - 1) / W - b0 + 1;
     int rc;
-    float ms = 0;
     if (ctx->tx.n_expr >= (1u << 22)) return fail(ctx, NS_EINVAL, "transcriptome: more than 2^22 expressed transcripts");
     HIPCHK(hipEventRecord(ctx->evt[1], st));
     A.key_first = b0 * W;                                   // the keys of the candidate table count from the first block
@@ -3363,10 +3397,8 @@ static int trx_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, Ge
         const uint32_t M = (uint32_t)M64;
         const uint64_t n_picks = nb * M, np = nb * C;
         if (np > 0x7ffffff0ull || n_picks > 0x7ffffff0ull) return fail(ctx, NS_EINVAL, "transcriptome batch too large (split into several calls)");
-        if ((rc = ensure(ctx, ctx->trx_pick_e, n_picks * 4 + 64)) || (rc = ensure(ctx, ctx->trx_pick_y, n_picks * 4 + 64)) ||
-            (rc = ensure(ctx, ctx->trx_keys, n_picks * 8 + 64)) || (rc = ensure(ctx, ctx->trx_keys2, n_picks * 8 + 64)) ||
-            (rc = ensure(ctx, ctx->trx_prev, n_picks * 4 + 64)) || (rc = ensure(ctx, ctx->trx_cand, np * 4 + 64)) ||
-            (rc = ensure(ctx, ctx->meta_num, 64)))
+        if ((rc = ensure_all(ctx, {{ctx->trx_pick_e, n_picks * 4 + 64}, {ctx->trx_pick_y, n_picks * 4 + 64}, {ctx->trx_keys, n_picks * 8 + 64},
+                                   {ctx->trx_keys2, n_picks * 8 + 64}, {ctx->trx_prev, n_picks * 4 + 64}, {ctx->trx_cand, np * 4 + 64}, {ctx->meta_num, 64}})))
             return rc;
         unsigned long long *d_short = (unsigned long long *)ctx->meta_num.p;
         HIPCHK(hipMemsetAsync(d_short, 0, 16, st));
@@ -3393,32 +3425,21 @@ static int trx_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, Ge
             continue;
         }
         // ---- the candidate table: one try per position
-        if ((rc = ensure(ctx, ctx->pieces, np * sizeof(ns_piece) + 64)) || (rc = ensure(ctx, ctx->t_pieces, np * sizeof(ns_piece) + 64)) ||
-            (rc = ensure(ctx, ctx->t_reads, np * sizeof(ns_read))) || (rc = ensure(ctx, ctx->t_name_len, (np + 1) * 2)) ||
-            (rc = ensure(ctx, ctx->t_rec_len, (np + 1) * 8)) || (rc = ensure(ctx, ctx->t_err_len, (np + 1) * 8)) ||
-            (rc = ensure(ctx, ctx->accept, (np + 1) * 8)) || (rc = ensure(ctx, ctx->accept_scan, (np + 1) * 8)) ||
-            (rc = ensure(ctx, ctx->key_pos, (n + 1) * 4)) || (rc = ensure(ctx, ctx->t_polya, (np + 1) * 2)) ||
-            (rc = ensure(ctx, ctx->ev_cap, (np + 1) * 8)) || (rc = ensure(ctx, ctx->ev_off, (np + 1) * 8)) ||
-            (rc = ensure(ctx, ctx->sort_key, (np + 1) * 4)) || (rc = ensure(ctx, ctx->sort_idx, (np + 1) * 4)) ||
-            (rc = ensure(ctx, ctx->sort_key_out, (np + 1) * 4)) || (rc = ensure(ctx, ctx->list_b, (np + 1) * 4)) ||
+        if ((rc = ensure_all(ctx, {{ctx->pieces, np * sizeof(ns_piece) + 64}, {ctx->t_pieces, np * sizeof(ns_piece) + 64}, {ctx->t_reads, np * sizeof(ns_read)},
+                                   {ctx->t_name_len, (np + 1) * 2}, {ctx->t_rec_len, (np + 1) * 8}, {ctx->t_err_len, (np + 1) * 8}, {ctx->accept, (np + 1) * 8},
+                                   {ctx->accept_scan, (np + 1) * 8}, {ctx->key_pos, (n + 1) * 4}, {ctx->t_polya, (np + 1) * 2}, {ctx->ev_cap, (np + 1) * 8},
+                                   {ctx->ev_off, (np + 1) * 8}, {ctx->sort_key, (np + 1) * 4}, {ctx->sort_idx, (np + 1) * 4}, {ctx->sort_key_out, (np + 1) * 4},
+                                   {ctx->list_b, (np + 1) * 4}})) ||
             (A.ir_need && (rc = ensure(ctx, ctx->t_ir_need, (np + 1) * 8))))
             return rc;
         A.ev_cap = (uint64_t *)ctx->ev_cap.p; A.ev_off = (uint64_t *)ctx->ev_off.p;
         A.sort_key = (uint32_t *)ctx->sort_key.p; A.sort_idx = (uint32_t *)ctx->sort_idx.p;
-        A.f_reads = (ns_read *)ctx->reads.p; A.f_pieces = (ns_piece *)ctx->pieces.p; A.f_name_len = (uint16_t *)ctx->name_len.p;
-        A.f_rec_len = (uint64_t *)ctx->rec_len.p; A.f_err_len = (uint64_t *)ctx->err_len.p;
-        A.key_pos_w = (uint32_t *)ctx->key_pos.p;
-        GenArgs P = A;
-        P.reads = (ns_read *)ctx->t_reads.p; P.pieces = (ns_piece *)ctx->t_pieces.p; P.name_len = (uint16_t *)ctx->t_name_len.p;
-        P.rec_len = (uint64_t *)ctx->t_rec_len.p; P.err_len = (uint64_t *)ctx->t_err_len.p;
-        P.accept = (uint64_t *)ctx->accept.p; P.accept_scan = (uint64_t *)ctx->accept_scan.p;
+        GenArgs P = pass_views(ctx, A);
         P.polya = (uint16_t *)ctx->t_polya.p;
         if (A.ir_need) P.ir_need = (uint64_t *)ctx->t_ir_need.p;
         P.trx_C = C; P.trx_M = M; P.trx_cand = (const uint32_t *)ctx->trx_cand.p;
         P.trx_pick_e = (const uint32_t *)ctx->trx_pick_e.p; P.trx_pick_y = (const int32_t *)ctx->trx_pick_y.p;
-        P.list = nullptr; P.list_n = (uint32_t)np; P.list_base = 0; P.attempt = 0; P.l_off = nullptr; P.ev_base = 0;
-        P.cap_rate = ctx->cap_rate;
-        const bool lds = ctx->lds_tables && prm->kind != NS_KIND_PERFECT;
+        P.list_n = (uint32_t)np; P.list_base = 0; P.attempt = 0; P.l_off = nullptr; P.ev_base = 0;
         const dim3 grid_p((unsigned)((np + 255) / 256));
         uint64_t cap = 0;
         for (int retry = 0;; ++retry) {
@@ -3438,19 +3459,11 @@ static int trx_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, Ge
             A.events = P.events = (ns_event *)ctx->events.p;
             P.list = (const uint32_t *)ctx->list_b.p;
             HIPCHK(hipEventRecord(ctx->evt[3], st));
-            const uint32_t cb = lds ? ctx->chain_block : NS_CHAIN_BLOCK;
-            const dim3 grid_c((unsigned)((np + cb - 1) / cb)), blk_c(cb);
-            if (lds) k_chain<true, false><<<grid_c, blk_c, ctx->lds_bytes + (P.ev_stage ? cb * 32u : 0u), st>>>(P);
-            else k_chain<false, false><<<grid_c, blk_c, 0, st>>>(P);
-            HIPCHK(hipGetLastError());
+            if ((rc = launch_chain(ctx, P, st))) return rc;
             HIPCHK(hipEventRecord(ctx->evt[4], st));
-            fold_stats(ctx, st);
-            if ((rc = read_small(ctx, st, stats, ctx->stats.p, 8 * sizeof(unsigned long long)))) return rc;
-            HIPCHK(hipEventElapsedTime(&ms, ctx->evt[3], ctx->evt[4])); ms_chain += ms;
-            if (!(stats[0] & NS_OVER_MASK)) break;
-            info->n_overflow += stats[0] & NS_OVER_MASK;         // a read outgrew its event capacity (rare): again with twice the capacity
-            if (retry >= 6) return fail(ctx, NS_ENOMEM, "event capacity overflow persists after 6 retries");
-            P.cap_rate *= 2.0; P.cap_gap_mul *= 2;
+            bool again = false;
+            if ((rc = end_pass(ctx, P, retry, stats, ms_chain, info, again))) return rc;
+            if (!again) break;
         }
         if ((rc = scan_u64(ctx, P.accept, P.accept_scan, np + 1))) return rc;
         if (A.ir_need) HIPCHK(hipMemsetAsync(A.ir_need, 0, (n + 1) * 8, st));
@@ -3467,23 +3480,190 @@ static int trx_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, Ge
             ctx->trx_margin = (uint32_t)std::min<uint64_t>(W, 2ull * ctx->trx_margin);
             continue;
         }
-        tot_cap = cap;
+        pl.tot_cap = cap;
         break;
     }
     A.pieces = (ns_piece *)ctx->pieces.p;
     A.key_pos = (const uint32_t *)ctx->key_pos.p;
-    tot_pieces = n;
+    pl.tot_pieces = n;
     info->ms_kernel[NS_K_EVENTS] = ms_chain;
+    if (A.ir_need && (rc = ir_splice(ctx, A, n))) return rc;
+    if (A.hp && (rc = hp_stage1(ctx, prm, A, n, pl.tot_pieces, stats, &pl.ms_hp))) return rc;   // (no length limits on these reads: nothing fails S:1429)
     return NS_OK;
 }
 
-static void lend_tables(const ns_ctx *ctx, ns_ctx *c);
-int ns_generate(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info) {
-    if (!ctx) return NS_EINVAL;
-    if (!prm || !info) return fail(ctx, NS_EINVAL, "null params/info");
-    // a step companion called directly (include/nanosim_amd.h allows it): the owner may have loaded another model or reference since the
-    // tables were lent — the pointers the companion holds by value would be freed memory
-    if (ctx->borrowed && ctx->owner) lend_tables(ctx->owner, ctx);
+// The passes of a genome batch (aligned, unaligned, --perfect; the unaligned workers of the other modes too): plan the pieces, the
+// lengths of attempt 0 and the event capacity, then pass a generates attempt a of every read still without an accepted one.  A read that
+// outgrows its event capacity re-plans the batch with twice the rates (retry); -k: reads that fail the final length check re-run the
+// batch (hp_round)
+static int genome_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, GenArgs &A, Plan &pl) {
+    const size_t n = (size_t)prm->n_reads;
+    const Knobs &kn = ctx->knob;
+    hipStream_t st = ctx->stream;
+    unsigned long long *stats = pl.stats;
+    uint32_t *list_a = (uint32_t *)ctx->order.p, *list_b = (uint32_t *)ctx->list_b.p, *list_c = (uint32_t *)ctx->list_c.p;
+    const dim3 blk(256), grid_t((unsigned)((n + 1 + 255) / 256));        // thread-per-read kernels (n+1 for the scan sentinel)
+    const bool lds = ctx->lds_tables && prm->kind != NS_KIND_PERFECT;
+    const bool chim_al = prm->kind == NS_KIND_ALIGNED && prm->chimeric;
+    int rc;
+    A.cap_rate = ctx->cap_rate;
+    for (int hp_round = 0;; ++hp_round) {
+        for (int retry = 0;; ++retry) {
+            HIPCHK(hipMemsetAsync(ctx->stats.p, 0, NS_STATS_BYTES, st));
+            // ---- plan: pieces, lengths of attempt 0, event capacity, visiting order ----
+            HIPCHK(hipEventRecord(ctx->evt[1], st));
+            k_nseg<<<grid_t, blk, 0, st>>>(A);
+            HIPCHK(hipGetLastError());
+            if ((rc = scan_u32(ctx, A.n_pieces, A.piece_off, n + 1))) return rc;
+            // one piece per read unless the batch is chimeric (k_nseg): the total is n then, without a read-back (one stream round trip less
+            // per worker call)
+            if (chim_al) {
+                uint32_t tp32 = 0;
+                if ((rc = read_small(ctx, st, &tp32, A.piece_off + n, 4))) return rc;
+                pl.tot_pieces = tp32;
+            } else pl.tot_pieces = n;
+            if ((rc = ensure(ctx, ctx->pieces, (size_t)pl.tot_pieces * sizeof(ns_piece) + 64))) return rc;
+            A.pieces = (ns_piece *)ctx->pieces.p;
+            A.list = nullptr; A.list_n = (uint32_t)n; A.attempt = 0;
+            k_lengths<false><<<grid_t, blk, 0, st>>>(A);
+            HIPCHK(hipGetLastError());
+            if ((rc = scan_u64(ctx, A.ev_cap, A.ev_off, n + 1))) return rc;
+            if ((rc = visiting_order(ctx, A.sort_key, A.sort_idx, n, list_a))) return rc;
+            HIPCHK(hipEventRecord(ctx->evt[2], st));
+            uint32_t n_multi = 0;                 // reads of several pieces: the head of the visiting order (visiting_order; 0 with NS_EXACT_ORDER)
+            if (prm->chimeric && prm->kind == NS_KIND_ALIGNED && ctx->ord_bins.p && !kn.exact_order) {
+                if ((rc = read_small(ctx, st, &pl.tot_cap, A.ev_off + n, 8, &n_multi, (uint32_t *)ctx->ord_bins.p + 2 * NS_ORD_BINS, 4))) return rc;
+            } else if ((rc = read_small(ctx, st, &pl.tot_cap, A.ev_off + n, 8))) return rc;
+            if ((rc = ensure(ctx, ctx->events, (size_t)pl.tot_cap * sizeof(ns_event) + 64))) return rc;
+            A.events = (ns_event *)ctx->events.p;
+            // ---- passes: pass a generates attempt a of every read still without an accepted attempt ----
+            uint32_t *cur = list_a, *nxt = list_b;
+            uint32_t cur_n = (uint32_t)n;
+            bool overflow = false;
+            double ms_chain = 0;
+            uint64_t used = pl.tot_cap;               // event slots handed out so far
+            for (uint32_t a = 0;; ++a) {
+                A.list = cur; A.list_n = cur_n; A.attempt = a; A.next_list = nxt; A.hole_at = 0; A.hole_len = 0; A.prio_thr = nullptr;
+                A.l_off = nullptr; A.l_base = 0;
+                if (a > 0) HIPCHK(hipMemsetAsync(A.next_n, 0, 4, st));      // (pass 0: the counters were zeroed as a whole at the top of the retry loop)
+                const dim3 grid_p((cur_n + 255) / 256);
+                A.p_need = nullptr; A.p_off = nullptr; A.p_base = 0;
+                if (a > 0) {          // new lengths for the reads still open; their events go to a fresh region behind the earlier passes
+                    if (chim_al) {    // ... and a new segment count with a new epoch (read_nseg)
+                        if ((rc = ensure_all(ctx, {{ctx->p_need, ((size_t)cur_n + 1) * 4}, {ctx->p_off, ((size_t)cur_n + 1) * 4}}))) return rc;
+                        k_replan<<<dim3((cur_n + 1 + 255) / 256), blk, 0, st>>>(A, (uint32_t *)ctx->p_need.p);
+                        HIPCHK(hipGetLastError());
+                        if ((rc = scan_u32(ctx, (const uint32_t *)ctx->p_need.p, (uint32_t *)ctx->p_off.p, (size_t)cur_n + 1))) return rc;
+                        uint32_t extra = 0;
+                        if ((rc = read_small(ctx, st, &extra, (uint32_t *)ctx->p_off.p + cur_n, 4))) return rc;
+                        if (extra) {
+                            if ((rc = ensure_keep(ctx, ctx->pieces, (size_t)(pl.tot_pieces + extra) * sizeof(ns_piece) + 64,
+                                                  (size_t)pl.tot_pieces * sizeof(ns_piece)))) return rc;
+                            A.pieces = (ns_piece *)ctx->pieces.p;
+                            A.p_need = (const uint32_t *)ctx->p_need.p; A.p_off = (const uint32_t *)ctx->p_off.p; A.p_base = (uint32_t)pl.tot_pieces;
+                            pl.tot_pieces += extra;
+                        }
+                    }
+                    if (cur_n <= 4096u) k_lengths<true><<<dim3((cur_n + 63) / 64), dim3(64), 0, st>>>(A);
+                    else k_lengths<false><<<grid_p, blk, 0, st>>>(A);
+                    HIPCHK(hipGetLastError());
+                    HIPCHK(hipMemsetAsync(A.l_cap + cur_n, 0, 8, st));
+                    if ((rc = scan_u64(ctx, A.l_cap, (uint64_t *)ctx->l_off.p, (size_t)cur_n + 1))) return rc;
+                    uint64_t pass_cap = 0;
+                    if ((rc = read_small(ctx, st, &pass_cap, (uint64_t *)ctx->l_off.p + cur_n, 8))) return rc;
+                    if ((rc = ensure_keep(ctx, ctx->events, (size_t)(used + pass_cap) * sizeof(ns_event) + 64, (size_t)used * sizeof(ns_event)))) return rc;
+                    A.events = (ns_event *)ctx->events.p;
+                    A.l_off = (const uint64_t *)ctx->l_off.p; A.l_base = used;
+                    used += pass_cap;
+                }
+                if (a == 0 && ctx->gate_wait) {                                // (bounded: the owner opens the gate on every way out of its call; an owner
+                    const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(3);   // that blocks in front of its chain — a first-use
+                    while (!ctx->gate_wait->load(std::memory_order_acquire) && std::chrono::steady_clock::now() < t_end)   // hipMalloc, a result slot
+                        std::this_thread::yield();                                                         // still crossing PCIe — is not waited for: 3 ms)
+                }
+                HIPCHK(hipEventRecord(ctx->evt[3], st));
+                uint32_t n_coop = 0;
+                if (prm->kind == NS_KIND_UNALIGNED)                           // its loop is a prefix sum (coop_unaligned_error_list); pass 0 visits the reads longest first
+                    n_coop = (a == 0 && lds && cur_n >= kn.coop_min) ? std::max(cur_n >> kn.ucoop_shift, 1u) : cur_n;
+                else if (a == 0 && ctx->coop_ok && prm->kind == NS_KIND_ALIGNED && cur_n >= kn.coop_min)    // longest 0.1 % (of the single-segment reads)
+                    n_coop = (cur_n - std::min(cur_n, n_multi)) >> kn.coop_shift;
+                const uint32_t coop_at = (a == 0 && prm->kind == NS_KIND_ALIGNED) ? std::min(cur_n, n_multi) : 0u;     // where that list starts in the visiting order
+                // ... and the longest of the reads of several pieces (the head of the order): their chains are the sum of their pieces', so more of them
+                // lie beyond the length at which a thread-per-read chain becomes the tail of the launch (same-box sweeps in profiles/r06/ab_chimeric_order.log)
+                uint32_t m_coop = 0;
+                if (coop_at && n_coop) {
+                    // (a thread per piece for the rest — below — leaves few of them too long for that side: 1/512; one thread per read: 1/32)
+                    const bool piece_threads = lds && !kn.no_piece_threads;
+                    const uint32_t sh = piece_threads ? (kn.coop_shift > 1u ? kn.coop_shift - 1u : 0u) : (kn.coop_shift > 5u ? kn.coop_shift - 5u : 0u);
+                    m_coop = std::min(coop_at, std::max(coop_at >> sh, 64u));
+                }
+                if (n_coop) {      // wave-per-read for the head of the (length-sorted) list, thread-per-read for the rest
+                    GenArgs B = A; B.list_n = n_coop + m_coop; B.list = cur + (m_coop ? 0u : coop_at);
+                    if (m_coop) { B.hole_at = m_coop; B.hole_len = coop_at - m_coop; }      // [0, m_coop) and [coop_at, coop_at + n_coop) of the order
+                    B.coop_k1 = kn.ucoop_k1 ? 1u : 0u;
+                    if ((rc = launch_chain_coop(ctx, B, st))) return rc;
+                    if (coop_at) { A.list = cur + m_coop; A.hole_at = coop_at - m_coop; A.hole_len = n_coop; } else A.list = cur + n_coop;
+                    A.list_n = cur_n - n_coop - m_coop;
+                }
+                // The reads of several pieces that stay on the thread-per-read side: a thread per PIECE (k_chain's piece mode 1: the error lists, each into
+                // its piece's own share of the read's event slots), then a thread per read for what follows the lists (mode 2) — on a third stream, next
+                // to the launch of the single-segment reads.  A thread that walks all pieces of its read has 2-4 times the trip count of any other, and
+                // the slowest wavefront is what a chain launch waits for (profiles/r06/ab_chimeric_order.log).  NS_NO_PIECE_THREADS=1: one thread per read.
+                uint32_t n_pt = 0;
+                if (a == 0 && lds && n_coop && coop_at > m_coop && !kn.no_piece_threads) {
+                    if (!ctx->stream3) {
+                        HIPCHK(hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking));
+                        HIPCHK(hipEventCreateWithFlags(&ctx->ev_join3, hipEventDisableTiming));
+                    }
+                    n_pt = coop_at - m_coop;
+                    const uint32_t cb = ctx->chain_block;
+                    GenArgs P = A; P.list = cur + m_coop; P.list_n = n_pt; P.hole_at = 0; P.hole_len = 0; P.prio_thr = nullptr;
+                    const size_t lds_p = ctx->lds_bytes + (P.ev_stage ? cb * 32u : 0u);
+                    HIPCHK(hipStreamWaitEvent(ctx->stream3, ctx->ev_fork, 0));
+                    P.piece_mode = 1;
+                    k_chain<true, false, true><<<dim3((unsigned)(((uint64_t)n_pt * NS_PIECE_SLOTS + cb - 1) / cb)), dim3(cb), lds_p, ctx->stream3>>>(P);
+                    P.piece_mode = 2;
+                    k_chain<true, false, true><<<dim3((n_pt + cb - 1) / cb), dim3(cb), lds_p, ctx->stream3>>>(P);
+                    HIPCHK(hipGetLastError());
+                    HIPCHK(hipEventRecord(ctx->ev_join3, ctx->stream3));
+                    A.list = cur + coop_at + n_coop; A.hole_at = 0; A.hole_len = 0; A.list_n = cur_n - coop_at - n_coop;
+                }
+                if (a == 0 && n_multi && !n_pt && prm->kind == NS_KIND_ALIGNED) A.prio_thr = (const uint32_t *)ctx->ord_bins.p + 2 * NS_ORD_BINS;
+                if ((rc = launch_chain(ctx, A, st))) return rc;
+                if (n_coop) HIPCHK(hipStreamWaitEvent(st, ctx->ev_join, 0));
+                if (n_pt) HIPCHK(hipStreamWaitEvent(st, ctx->ev_join3, 0));
+                HIPCHK(hipEventRecord(ctx->evt[4], st));
+                if (ctx->gate_signal) ctx->gate_signal->store(1, std::memory_order_release);
+                if ((rc = end_pass(ctx, A, retry, stats, ms_chain, info, overflow))) return rc;
+                if (overflow) break;
+                cur_n = (uint32_t)(stats[6] & 0xffffffffull);
+                if (!cur_n) { pl.tot_cap = used; break; }
+                if (a + 1 >= NS_MAX_ATTEMPT) return attempt_limit(ctx);
+                cur = nxt; nxt = cur == list_b ? list_c : list_b;      // (list_a keeps the length-sorted order of the batch for the record kernels)
+            }
+            info->ms_kernel[NS_K_EVENTS] = ms_chain;
+#ifdef NS_CHAIN_CLOCK
+            if (prm->kind == NS_KIND_ALIGNED) { unsigned long long c[16], z[16] = {0}; HIPCHK(hipMemcpyFromSymbol(c, HIP_SYMBOL(g_chain_clock), sizeof c)); HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_chain_clock), z, sizeof z));
+              fprintf(stderr, "chain clock: lane 0 of the multi waves: aligned pieces %.3f ms, gaps %.3f ms, behind the lists %.3f ms (means) | ", c[6] ? c[8] * 1e-5 / c[6] : 0.0, c[6] ? c[9] * 1e-5 / c[6] : 0.0, c[6] ? c[10] * 1e-5 / c[6] : 0.0);
+              fprintf(stderr, "chain clock: single waves %llu max %.3f ms mean %.3f ms (the group's last block: %llu) | multi waves %llu max %.3f ms mean %.3f ms (the group's last block: %llu) | ms_chain %.3f\n",
+                  c[2], c[0] * 1e-5, c[2] ? c[1] * 1e-5 / c[2] : 0.0, c[3] >> 32, c[6], c[4] * 1e-5, c[6] ? c[5] * 1e-5 / c[6] : 0.0, c[7] >> 32, ms_chain); }
+#endif
+            if (!overflow) break;                     // (else again, with the rates end_pass doubled)
+        }
+        if (A.ir_need && (rc = ir_splice(ctx, A, n))) return rc;
+        if (!A.hp) break;
+        if ((rc = hp_stage1(ctx, prm, A, n, pl.tot_pieces, stats, &pl.ms_hp))) return rc;
+        if (!stats[5]) break;
+        // some reads failed the final length check (S:1429): they advanced their attempt state; every other read restarts at
+        // its accepted attempt, so re-running the batch reproduces them bit for bit
+        if (hp_round >= (int)NS_MAX_ATTEMPT) return fail(ctx, NS_EINVAL, "reads keep failing the final length check in -k mode");
+        A.keep_state = 1;
+    }
+    return NS_OK;
+}
+
+// the parameters of a worker call against each other and against what the context holds
+static int check_params(ns_ctx *ctx, const ns_params *prm) {
     if (!ctx->has_model || !ctx->has_ref) return fail(ctx, NS_ESTATE, "ns_generate before ns_load_model/ns_set_reference");
     if (prm->kind > NS_KIND_PERFECT) return fail(ctx, NS_EINVAL, "bad kind");
     if (prm->emit_records > NS_EMIT_SIZES) return fail(ctx, NS_EINVAL, "bad emit_records");
@@ -3492,8 +3672,8 @@ int ns_generate(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info) {
         return fail(ctx, NS_EINVAL, "model has no unaligned-length KDE");
     if (prm->fastq && !(ctx->m.flags & NS_MODEL_HAS_QUALS)) return fail(ctx, NS_EINVAL, "model has no quality tables");
     if (prm->chimeric && !(ctx->m.flags & NS_MODEL_HAS_CHIMERIC)) return fail(ctx, NS_EINVAL, "model has no chimeric tables");
-    const bool hp_on = prm->kmer_bias && prm->kind == NS_KIND_ALIGNED;      // S:1413: only aligned segments; --perfect never
-    if (hp_on && !(ctx->m.flags & NS_MODEL_HAS_HP)) return fail(ctx, NS_EINVAL, "-k needs the homopolymer model (-hp)");
+    if (prm->kmer_bias && prm->kind == NS_KIND_ALIGNED && !(ctx->m.flags & NS_MODEL_HAS_HP))
+        return fail(ctx, NS_EINVAL, "-k needs the homopolymer model (-hp)");
     const bool meta_al = prm->meta && prm->kind != NS_KIND_UNALIGNED;       // aligned or --perfect worker of simulation_aligned_metagenome
     if (prm->meta) {
         if (!ctx->nspecies) return fail(ctx, NS_ESTATE, "metagenome batch before ns_set_species");
@@ -3510,35 +3690,27 @@ int ns_generate(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info) {
         if (!prm->trx) return fail(ctx, NS_EINVAL, "model_ir is a transcriptome option");
         if (!ctx->has_ir) return fail(ctx, NS_ESTATE, "model_ir batch before ns_set_intron_retention");
     }
-    const bool ir_on = prm->model_ir && prm->kind == NS_KIND_ALIGNED;       // S:1156: not for --perfect, not for unaligned reads
     if (prm->n_reads > 0x7ffffff0ull) return fail(ctx, NS_EINVAL, "batch too large (split into several calls)");
     if (prm->first_read + prm->n_reads >= (1ull << 40)) return fail(ctx, NS_EINVAL, "read index exceeds 2^40");
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)prm->n_reads;
-    memset(info, 0, sizeof *info);
-    ctx->has_batch = false;
-    if (!n) { ctx->last = *info; ctx->has_batch = true; return NS_OK; }
-    int rc;
-    if ((rc = ensure(ctx, ctx->n_pieces, (n + 1) * 4)) || (rc = ensure(ctx, ctx->piece_off, (n + 1) * 4)) ||
-        (rc = ensure(ctx, ctx->ev_cap, (n + 1) * 8)) || (rc = ensure(ctx, ctx->ev_off, (n + 1) * 8)) || (rc = ensure(ctx, ctx->l_cap, (n + 1) * 8)) || (rc = ensure(ctx, ctx->l_off, (n + 1) * 8)) ||
-        (rc = ensure(ctx, ctx->rec_len, (n + 1) * 8)) || (rc = ensure(ctx, ctx->rec_off, (n + 1) * 8)) ||
-        (rc = ensure(ctx, ctx->err_len, (n + 1) * 8)) || (rc = ensure(ctx, ctx->err_off, (n + 1) * 8)) ||
-        (rc = ensure(ctx, ctx->name_len, (n + 1) * 2)) || (rc = ensure(ctx, ctx->reads, n * sizeof(ns_read))) ||
-        (rc = ensure(ctx, ctx->stats, NS_STATS_BYTES)) ||
-        (rc = ensure(ctx, ctx->sort_key, (n + 1) * 4)) || (rc = ensure(ctx, ctx->sort_idx, (n + 1) * 4)) ||
-        (rc = ensure(ctx, ctx->sort_key_out, (n + 1) * 4)) || (rc = ensure(ctx, ctx->order, (n + 1) * 4)) ||
-        (rc = ensure(ctx, ctx->list_b, (n + 1) * 4)) || (rc = ensure(ctx, ctx->list_c, (n + 1) * 4)) || (rc = ensure(ctx, ctx->rstate, (n + 1) * 4)) ||
-        (rc = ensure(ctx, ctx->att_base, (n + 1) * 4)) || (rc = ensure(ctx, ctx->scr_len, (n + 1) * 8)) ||
-        (rc = ensure(ctx, ctx->scr_off, (n + 1) * 8)))
-        return rc;
+    return NS_OK;
+}
 
-    GenArgs A;
+// the per-read buffers of a batch of n reads, and the arguments every kernel of the call starts from
+static int batch_args(ns_ctx *ctx, const ns_params *prm, size_t n, GenArgs &A) {
+    int rc;
+    if ((rc = ensure_all(ctx, {{ctx->n_pieces, (n + 1) * 4}, {ctx->piece_off, (n + 1) * 4}, {ctx->ev_cap, (n + 1) * 8}, {ctx->ev_off, (n + 1) * 8},
+                               {ctx->l_cap, (n + 1) * 8}, {ctx->l_off, (n + 1) * 8}, {ctx->rec_len, (n + 1) * 8}, {ctx->rec_off, (n + 1) * 8},
+                               {ctx->err_len, (n + 1) * 8}, {ctx->err_off, (n + 1) * 8}, {ctx->name_len, (n + 1) * 2}, {ctx->reads, n * sizeof(ns_read)},
+                               {ctx->stats, NS_STATS_BYTES}, {ctx->sort_key, (n + 1) * 4}, {ctx->sort_idx, (n + 1) * 4}, {ctx->sort_key_out, (n + 1) * 4},
+                               {ctx->order, (n + 1) * 4}, {ctx->list_b, (n + 1) * 4}, {ctx->list_c, (n + 1) * 4}, {ctx->rstate, (n + 1) * 4},
+                               {ctx->att_base, (n + 1) * 4}, {ctx->scr_len, (n + 1) * 8}, {ctx->scr_off, (n + 1) * 8}})))
+        return rc;
     memset(&A, 0, sizeof A);
     A.prm = *prm; A.m = ctx->m; A.ref = ctx->ref;
     A.key_first = A.name_first = prm->first_read;
     A.cap_gap_mul = 2;
     // events of the thread-per-read chain staged four at a time in LDS, when the tables leave room for it next to four workgroups per CU
-    A.ev_stage = (ctx->lds_tables && ctx->lds_bytes + ctx->chain_block * 32u <= 64u * 1024u && !getenv("NS_NO_EV_STAGE")) ? (uint32_t)ctx->lds_bytes : 0u;
+    A.ev_stage = (ctx->lds_tables && ctx->lds_bytes + ctx->chain_block * 32u <= 64u * 1024u) ? (uint32_t)ctx->lds_bytes : 0u;
     A.n_pieces = (uint32_t *)ctx->n_pieces.p; A.piece_off = (uint32_t *)ctx->piece_off.p;
     A.ev_cap = (uint64_t *)ctx->ev_cap.p; A.ev_off = (uint64_t *)ctx->ev_off.p; A.l_cap = (uint64_t *)ctx->l_cap.p;
     A.rec_len = (uint64_t *)ctx->rec_len.p; A.rec_off = (uint64_t *)ctx->rec_off.p;
@@ -3548,233 +3720,30 @@ int ns_generate(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info) {
     A.sort_key = (uint32_t *)ctx->sort_key.p; A.sort_idx = (uint32_t *)ctx->sort_idx.p;
     A.rstate = (uint32_t *)ctx->rstate.p; A.att_base = (uint32_t *)ctx->att_base.p;
     A.scr_len = (uint64_t *)ctx->scr_len.p; A.scr_off = (uint64_t *)ctx->scr_off.p;
-    A.hp = hp_on ? 1u : 0u; A.keep_state = 0;
+    A.hp = (prm->kmer_bias && prm->kind == NS_KIND_ALIGNED) ? 1u : 0u;     // S:1413: only aligned segments; --perfect never
     A.errlen_later = prm->emit_errlog ? 1u : 0u;
-    A.dbg = ctx->dbg;
+    A.dbg = ctx->knob.dbg;
     if (prm->trx) {
         if ((rc = ensure(ctx, ctx->polya, (n + 1) * 2))) return rc;
         A.tx = ctx->tx; A.polya = (uint16_t *)ctx->polya.p;
         HIPCHK(hipMemsetAsync(ctx->polya.p, 0, (n + 1) * 2, ctx->stream));
     }
     ctx->spliced_bytes = 0;
-    if (ir_on) {
-        if ((rc = ensure(ctx, ctx->ir_need, (n + 1) * 8)) || (rc = ensure(ctx, ctx->ir_off, (n + 1) * 8))) return rc;
-        A.ir = ctx->ir; A.ir_need = (uint64_t *)ctx->ir_need.p;
+    if (prm->model_ir && prm->kind == NS_KIND_ALIGNED) {                 // S:1156: not for --perfect, not for unaligned reads
+        if ((rc = ensure_all(ctx, {{ctx->ir_need, (n + 1) * 8}, {ctx->ir_off, (n + 1) * 8}}))) return rc;
+        A.ir = ctx->ir; A.ir_need = (uint64_t *)ctx->ir_need.p;        // (a non-null ir_need: intron retention is on)
     }
     A.meta = prm->meta ? 1u : 0u; A.nspecies = ctx->nspecies; A.species_chrom_off = (const uint32_t *)ctx->species_chrom_off.p;
     A.next_n = (uint32_t *)((unsigned long long *)ctx->stats.p + 6);
-    uint32_t *list_a = (uint32_t *)ctx->order.p, *list_b = (uint32_t *)ctx->list_b.p, *list_c = (uint32_t *)ctx->list_c.p;
-    const dim3 blk(256);
-    const dim3 grid_t((unsigned)((n + 1 + 255) / 256));        // thread-per-read kernels (n+1 for the scan sentinel)
-    const dim3 grid_w((unsigned)((n + NS_WPB - 1) / NS_WPB)), blk_w(64 * NS_WPB);     // wave-per-read kernels
+    return NS_OK;
+}
+
+// the record and error-profile images of the batch, in result slot *slot; `order`: the record kernels' visiting order (genome passes) or none
+static int write_images(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, GenArgs &A, const Plan &pl, bool meta_al,
+                        const uint32_t *order, int *slot) {
+    const size_t n = (size_t)prm->n_reads;
     hipStream_t st = ctx->stream;
-    unsigned long long stats[8];
-    uint64_t tot_pieces = 0, tot_cap = 0;
-    double cap_rate = ctx->cap_rate;
-    const bool lds = ctx->lds_tables && prm->kind != NS_KIND_PERFECT;
-    float ms = 0;
-    ctx->rec_timed = false;
-    HIPCHK(hipEventRecord(ctx->evt[0], st));
-    double ms_hp = 0;
-    const bool trx_tab = prm->trx && prm->kind != NS_KIND_UNALIGNED;        // transcript + aligned length per block walk (trx_passes)
-    if (meta_al && (rc = meta_passes(ctx, prm, info, A, tot_pieces, tot_cap, stats))) return rc;
-    if (meta_al && A.hp) {         // the passes validated the final lengths; the stage runs once more on the reads in their final order
-        ms_hp = info->ms_kernel[NS_K_HP];
-        if ((rc = hp_stage1(ctx, prm, A, n, tot_pieces, tot_cap, stats, &ms_hp))) return rc;
-    }
-    auto ir_splice = [&]() -> int {          // splice arena: slot offsets, then the copy from the genome (before anything reads the pieces' bases)
-        if ((rc = scan_u64(ctx, A.ir_need, (uint64_t *)ctx->ir_off.p, n + 1))) return rc;
-        uint64_t arena_bytes = 0;
-        if ((rc = read_small(ctx, st, &arena_bytes, (uint64_t *)ctx->ir_off.p + n, 8))) return rc;
-        if ((rc = ensure(ctx, ctx->spliced, (size_t)arena_bytes + 64))) return rc;
-        A.ir.arena = (uint8_t *)ctx->spliced.p; A.ir.arena_off = (const uint64_t *)ctx->ir_off.p;
-        A.ref.spliced = (const uint8_t *)ctx->spliced.p;
-        ctx->spliced_bytes = arena_bytes;
-        if (arena_bytes) {
-            k_ir_splice<<<grid_w, blk_w, 0, st>>>(A);
-            HIPCHK(hipGetLastError());
-        }
-        return NS_OK;
-    };
-    if (trx_tab) {
-        if ((rc = trx_passes(ctx, prm, info, A, tot_pieces, tot_cap, stats))) return rc;
-        if (ir_on && (rc = ir_splice())) return rc;
-        if (A.hp && (rc = hp_stage1(ctx, prm, A, n, tot_pieces, tot_cap, stats, &ms_hp))) return rc;    // (no length limits on these reads: nothing fails S:1429)
-    }
-    for (int hp_round = 0; !meta_al && !trx_tab; ++hp_round) {
-    for (int retry = 0;; ++retry) {
-        A.cap_rate = cap_rate;
-        HIPCHK(hipMemsetAsync(ctx->stats.p, 0, NS_STATS_BYTES, st));
-        // ---- plan: pieces, lengths of attempt 0, event capacity, visiting order ----
-        HIPCHK(hipEventRecord(ctx->evt[1], st));
-        k_nseg<<<grid_t, blk, 0, st>>>(A);
-        HIPCHK(hipGetLastError());
-        if ((rc = scan_u32(ctx, A.n_pieces, A.piece_off, n + 1))) return rc;
-        // one piece per read unless the batch is chimeric (k_nseg): the total is n then, without a read-back (one stream round trip less
-        // per worker call)
-        if (prm->kind == NS_KIND_ALIGNED && prm->chimeric) {
-            uint32_t tp32 = 0;
-            if ((rc = read_small(ctx, st, &tp32, A.piece_off + n, 4))) return rc;
-            tot_pieces = tp32;
-        } else tot_pieces = n;
-        if ((rc = ensure(ctx, ctx->pieces, (size_t)tot_pieces * sizeof(ns_piece) + 64))) return rc;
-        A.pieces = (ns_piece *)ctx->pieces.p;
-        A.list = nullptr; A.list_n = (uint32_t)n; A.attempt = 0;
-        k_lengths<false><<<grid_t, blk, 0, st>>>(A);
-        HIPCHK(hipGetLastError());
-        if ((rc = scan_u64(ctx, A.ev_cap, A.ev_off, n + 1))) return rc;
-        if ((rc = visiting_order(ctx, A.sort_key, A.sort_idx, n, list_a))) return rc;
-        HIPCHK(hipEventRecord(ctx->evt[2], st));
-        uint32_t n_multi = 0;                 // reads of several pieces: the head of the visiting order (visiting_order; 0 with NS_EXACT_ORDER)
-        if (prm->chimeric && prm->kind == NS_KIND_ALIGNED && ctx->ord_bins.p && !getenv("NS_EXACT_ORDER")) {
-            if ((rc = read_small(ctx, st, &tot_cap, A.ev_off + n, 8, &n_multi, (uint32_t *)ctx->ord_bins.p + 2 * NS_ORD_BINS, 4))) return rc;
-        } else if ((rc = read_small(ctx, st, &tot_cap, A.ev_off + n, 8))) return rc;
-        if ((rc = ensure(ctx, ctx->events, (size_t)tot_cap * sizeof(ns_event) + 64))) return rc;
-        A.events = (ns_event *)ctx->events.p;
-        // ---- passes: pass a generates attempt a of every read still without an accepted attempt ----
-        uint32_t *cur = list_a, *nxt = list_b;
-        uint32_t cur_n = (uint32_t)n;
-        bool overflow = false;
-        double ms_chain = 0;
-        uint64_t used = tot_cap;                  // event slots handed out so far
-        for (uint32_t a = 0;; ++a) {
-            A.list = cur; A.list_n = cur_n; A.attempt = a; A.next_list = nxt; A.hole_at = 0; A.hole_len = 0; A.prio_thr = nullptr;
-            A.l_off = nullptr; A.l_base = 0;
-            if (a > 0) HIPCHK(hipMemsetAsync(A.next_n, 0, 4, st));      // (pass 0: the counters were zeroed as a whole at the top of the retry loop)
-            const dim3 grid_p((cur_n + 255) / 256);
-            A.p_need = nullptr; A.p_off = nullptr; A.p_base = 0;
-            if (a > 0) {          // new lengths for the reads still open; their events go to a fresh region behind the earlier passes
-                if (prm->kind == NS_KIND_ALIGNED && prm->chimeric) {     // ... and a new segment count with a new epoch (read_nseg)
-                    if ((rc = ensure(ctx, ctx->p_need, ((size_t)cur_n + 1) * 4)) || (rc = ensure(ctx, ctx->p_off, ((size_t)cur_n + 1) * 4))) return rc;
-                    k_replan<<<dim3((cur_n + 1 + 255) / 256), blk, 0, st>>>(A, (uint32_t *)ctx->p_need.p);
-                    HIPCHK(hipGetLastError());
-                    if ((rc = scan_u32(ctx, (const uint32_t *)ctx->p_need.p, (uint32_t *)ctx->p_off.p, (size_t)cur_n + 1))) return rc;
-                    uint32_t extra = 0;
-                    if ((rc = read_small(ctx, st, &extra, (uint32_t *)ctx->p_off.p + cur_n, 4))) return rc;
-                    if (extra) {
-                        if ((rc = ensure_keep(ctx, ctx->pieces, (size_t)(tot_pieces + extra) * sizeof(ns_piece) + 64, (size_t)tot_pieces * sizeof(ns_piece)))) return rc;
-                        A.pieces = (ns_piece *)ctx->pieces.p;
-                        A.p_need = (const uint32_t *)ctx->p_need.p; A.p_off = (const uint32_t *)ctx->p_off.p; A.p_base = (uint32_t)tot_pieces;
-                        tot_pieces += extra;
-                    }
-                }
-                if (cur_n <= 4096u) k_lengths<true><<<dim3((cur_n + 63) / 64), dim3(64), 0, st>>>(A);
-                else k_lengths<false><<<grid_p, blk, 0, st>>>(A);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipMemsetAsync(A.l_cap + cur_n, 0, 8, st));
-                if ((rc = scan_u64(ctx, A.l_cap, (uint64_t *)ctx->l_off.p, (size_t)cur_n + 1))) return rc;
-                uint64_t pass_cap = 0;
-                if ((rc = read_small(ctx, st, &pass_cap, (uint64_t *)ctx->l_off.p + cur_n, 8))) return rc;
-                if ((rc = ensure_keep(ctx, ctx->events, (size_t)(used + pass_cap) * sizeof(ns_event) + 64, (size_t)used * sizeof(ns_event)))) return rc;
-                A.events = (ns_event *)ctx->events.p;
-                A.l_off = (const uint64_t *)ctx->l_off.p; A.l_base = used;
-                used += pass_cap;
-            }
-            if (a == 0 && ctx->gate_wait) {                                // (bounded: the owner opens the gate on every way out of its call; an owner
-                const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(3);   // that blocks in front of its chain — a first-use
-                while (!ctx->gate_wait->load(std::memory_order_acquire) && std::chrono::steady_clock::now() < t_end)   // hipMalloc, a result slot still
-                    std::this_thread::yield();                                                         // crossing PCIe — is not waited for: 3 ms)
-            }
-            HIPCHK(hipEventRecord(ctx->evt[3], st));
-            uint32_t n_coop = 0;
-            if (prm->kind == NS_KIND_UNALIGNED)                           // its loop is a prefix sum (coop_unaligned_error_list); pass 0 visits the reads longest first
-                n_coop = (a == 0 && lds && cur_n >= ctx->coop_min) ? std::max(cur_n >> ctx->ucoop_shift, 1u) : cur_n;
-            else if (a == 0 && ctx->coop_ok && prm->kind == NS_KIND_ALIGNED && cur_n >= ctx->coop_min)    // longest 0.1 % (of the single-segment reads)
-                n_coop = (cur_n - std::min(cur_n, n_multi)) >> ctx->coop_shift;
-            const uint32_t coop_at = (a == 0 && prm->kind == NS_KIND_ALIGNED) ? std::min(cur_n, n_multi) : 0u;     // where that list starts in the visiting order
-            // ... and the longest of the reads of several pieces (the head of the order): their chains are the sum of their pieces', so more of them
-            // lie beyond the length at which a thread-per-read chain becomes the tail of the launch (NS_COOP_MULTI_SHIFT; same-box sweeps in profiles/r06/ab_chimeric_order.log)
-            uint32_t m_coop = 0;
-            if (coop_at && n_coop) {
-                // (a thread per piece for the rest — below — leaves few of them too long for that side: 1/512; one thread per read: 1/32)
-                const bool piece_threads = lds && !getenv("NS_NO_PIECE_THREADS");
-                uint32_t sh = piece_threads ? (ctx->coop_shift > 1u ? ctx->coop_shift - 1u : 0u) : (ctx->coop_shift > 5u ? ctx->coop_shift - 5u : 0u);
-                if (const char *d = getenv("NS_COOP_MULTI_SHIFT")) sh = (uint32_t)atoi(d) & 31u;
-                m_coop = std::min(coop_at, std::max(coop_at >> sh, 64u));
-            }
-            if (n_coop) {      // wave-per-read for the head of the (length-sorted) list, thread-per-read for the rest
-                GenArgs B = A; B.list_n = n_coop + m_coop; B.list = cur + (m_coop ? 0u : coop_at);
-                if (m_coop) { B.hole_at = m_coop; B.hole_len = coop_at - m_coop; }      // [0, m_coop) and [coop_at, coop_at + n_coop) of the order
-                { const char *d = getenv("NS_UCOOP_K"); B.coop_k1 = d && atoi(d) == 1 ? 1u : 0u; }
-                HIPCHK(hipEventRecord(ctx->ev_fork, st));
-                HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-                // unaligned reads: the run-length tables in LDS (k_chain<true, true>; the image must fit next to nothing else: 64 KB)
-                if (prm->kind == NS_KIND_UNALIGNED && ctx->lds_tables && ctx->ucoop_lds && (size_t)A.m.ct.n_words_mix * 8 <= 64u * 1024u)
-                    k_chain<true, true><<<dim3(B.list_n), dim3(64), (size_t)A.m.ct.n_words_mix * 8, ctx->stream2>>>(B);
-                else { B.coop_mix = (size_t)B.m.ct.n_words_mix * 8 <= 32u * 1024u ? 1u : 0u;
-                       k_chain<false, true><<<dim3(B.list_n), dim3(64), B.coop_mix ? (size_t)B.m.ct.n_words_mix * 8 : 0, ctx->stream2>>>(B); }
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
-                if (coop_at) { A.list = cur + m_coop; A.hole_at = coop_at - m_coop; A.hole_len = n_coop; } else A.list = cur + n_coop;
-                A.list_n = cur_n - n_coop - m_coop;
-            }
-            const uint32_t cb = lds ? ctx->chain_block : NS_CHAIN_BLOCK;
-            // The reads of several pieces that stay on the thread-per-read side: a thread per PIECE (k_chain's piece mode 1: the error lists, each into
-            // its piece's own share of the read's event slots), then a thread per read for what follows the lists (mode 2) — on a third stream, next
-            // to the launch of the single-segment reads.  A thread that walks all pieces of its read has 2-4 times the trip count of any other, and
-            // the slowest wavefront is what a chain launch waits for (profiles/r06/ab_chimeric_order.log).  NS_NO_PIECE_THREADS=1: one thread per read.
-            uint32_t n_pt = 0;
-            if (a == 0 && lds && n_coop && coop_at > m_coop && !getenv("NS_NO_PIECE_THREADS")) {
-                if (!ctx->stream3) {
-                    HIPCHK(hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking));
-                    HIPCHK(hipEventCreateWithFlags(&ctx->ev_join3, hipEventDisableTiming));
-                }
-                n_pt = coop_at - m_coop;
-                GenArgs P = A; P.list = cur + m_coop; P.list_n = n_pt; P.hole_at = 0; P.hole_len = 0; P.prio_thr = nullptr;
-                const size_t lds_p = ctx->lds_bytes + (P.ev_stage ? cb * 32u : 0u);
-                HIPCHK(hipStreamWaitEvent(ctx->stream3, ctx->ev_fork, 0));
-                P.piece_mode = 1;
-                k_chain<true, false, true><<<dim3((unsigned)(((uint64_t)n_pt * NS_PIECE_SLOTS + cb - 1) / cb)), dim3(cb), lds_p, ctx->stream3>>>(P);
-                P.piece_mode = 2;
-                k_chain<true, false, true><<<dim3((n_pt + cb - 1) / cb), dim3(cb), lds_p, ctx->stream3>>>(P);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipEventRecord(ctx->ev_join3, ctx->stream3));
-                A.list = cur + coop_at + n_coop; A.hole_at = 0; A.hole_len = 0; A.list_n = cur_n - coop_at - n_coop;
-            }
-            if (a == 0 && n_multi && !n_pt && prm->kind == NS_KIND_ALIGNED && !getenv("NS_PRIO_BY_POSITION")) A.prio_thr = (const uint32_t *)ctx->ord_bins.p + 2 * NS_ORD_BINS;
-            const dim3 grid_c((A.list_n + cb - 1) / cb), blk_c(cb);
-            if (!A.list_n) {}
-            else if (lds) k_chain<true, false><<<grid_c, blk_c, ctx->lds_bytes + (A.ev_stage ? cb * 32u : 0u), st>>>(A);
-            else k_chain<false, false><<<grid_c, blk_c, 0, st>>>(A);
-            HIPCHK(hipGetLastError());
-            if (n_coop) HIPCHK(hipStreamWaitEvent(st, ctx->ev_join, 0));
-            if (n_pt) HIPCHK(hipStreamWaitEvent(st, ctx->ev_join3, 0));
-            HIPCHK(hipEventRecord(ctx->evt[4], st));
-            if (ctx->gate_signal) ctx->gate_signal->store(1, std::memory_order_release);
-            fold_stats(ctx, st);
-            if ((rc = read_small(ctx, st, stats, ctx->stats.p, sizeof stats))) return rc;
-            HIPCHK(hipEventElapsedTime(&ms, ctx->evt[3], ctx->evt[4]));
-            ms_chain += ms;
-            if (stats[0] & NS_OVER_MASK) { overflow = true; break; }
-            cur_n = (uint32_t)(stats[6] & 0xffffffffull);
-            if (!cur_n) { tot_cap = used; break; }
-            if (a + 1 >= NS_MAX_ATTEMPT)
-                return fail(ctx, NS_EINVAL, "some reads found no acceptable length within the attempt limit "
-                                            "(min_len/max_len too narrow for this model, or its reads do not fit the event record: runs <= 4095 bases, "
-                                            "insertion / deletion balance within +-131071 bases per segment)");
-            cur = nxt; nxt = cur == list_b ? list_c : list_b;      // (list_a keeps the length-sorted order of the batch for the record kernels)
-        }
-        info->ms_kernel[NS_K_EVENTS] = ms_chain;
-#ifdef NS_CHAIN_CLOCK
-        if (prm->kind == NS_KIND_ALIGNED) { unsigned long long c[16], z[16] = {0}; HIPCHK(hipMemcpyFromSymbol(c, HIP_SYMBOL(g_chain_clock), sizeof c)); HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_chain_clock), z, sizeof z));
-          fprintf(stderr, "chain clock: lane 0 of the multi waves: aligned pieces %.3f ms, gaps %.3f ms, behind the lists %.3f ms (means) | ", c[6] ? c[8] * 1e-5 / c[6] : 0.0, c[6] ? c[9] * 1e-5 / c[6] : 0.0, c[6] ? c[10] * 1e-5 / c[6] : 0.0);
-          fprintf(stderr, "chain clock: single waves %llu max %.3f ms mean %.3f ms (the group's last block: %llu) | multi waves %llu max %.3f ms mean %.3f ms (the group's last block: %llu) | ms_chain %.3f\n",
-              c[2], c[0] * 1e-5, c[2] ? c[1] * 1e-5 / c[2] : 0.0, c[3] >> 32, c[6], c[4] * 1e-5, c[6] ? c[5] * 1e-5 / c[6] : 0.0, c[7] >> 32, ms_chain); }
-#endif
-        if (!overflow) break;
-        info->n_overflow += stats[0] & NS_OVER_MASK;
-        if (retry >= 6) return fail(ctx, NS_ENOMEM, "event capacity overflow persists after 6 retries");
-        cap_rate *= 2.0; A.cap_gap_mul *= 2;          // rare: more events per base than planned -> re-plan the batch with twice the rates
-    }
-    if (ir_on && (rc = ir_splice())) return rc;
-    if (!A.hp) break;
-    if ((rc = hp_stage1(ctx, prm, A, n, tot_pieces, tot_cap, stats, &ms_hp))) return rc;
-    if (!stats[5]) break;
-    // some reads failed the final length check (S:1429): they advanced their attempt state; every other read restarts at
-    // its accepted attempt, so re-running the batch reproduces them bit for bit
-    if (hp_round >= (int)NS_MAX_ATTEMPT) return fail(ctx, NS_EINVAL, "reads keep failing the final length check in -k mode");
-    A.keep_state = 1;
-    }
+    int rc;
     if (A.errlen_later && !A.hp && !meta_al) {   // (-k: k_hp_filter_w has computed the sizes of the rows that survive the filter; metagenome: per pass)
         k_errlen<<<dim3((unsigned)((n + NS_WPB - 1) / NS_WPB)), dim3(64 * NS_WPB), 0, st>>>(A);
         HIPCHK(hipGetLastError());
@@ -3785,76 +3754,78 @@ int ns_generate(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info) {
                                : read_small(ctx, st, &info->record_bytes, A.rec_off + n, 8))) return rc;
     // result slot of this batch: the other one while the last batch is still being copied out (ns_sink_write); a slot is reused
     // once its copies have left the device
-    int slot = ctx->slot;
-    if (prm->emit_records == 1u && ctx->io) {
-        if (ctx->io->slot_busy(slot)) slot ^= 1;
-        ctx->io->wait_slot(slot);
+    *slot = ctx->slot;
+    const bool write_rec = prm->emit_records == 1u;            // (2 = NS_EMIT_SIZES: the sizes of the images only)
+    if (write_rec && ctx->io) {
+        if (ctx->io->slot_busy(*slot)) *slot ^= 1;
+        ctx->io->wait_slot(*slot);
     }
-    if (prm->emit_records == 1u && ((rc = ensure(ctx, ctx->rec_slot[slot], (size_t)info->record_bytes + 64)) ||
-                                    (rc = ensure(ctx, ctx->err_slot[slot], (size_t)info->errlog_bytes + 64))))
+    if (write_rec && (rc = ensure_all(ctx, {{ctx->rec_slot[*slot], (size_t)info->record_bytes + 64}, {ctx->err_slot[*slot], (size_t)info->errlog_bytes + 64}})))
         return rc;
     if (prm->emit_records == 0) info->errlog_bytes = 0;       // (no records: no error-profile image either; NS_EMIT_SIZES keeps the size)
-    A.records = (uint8_t *)ctx->rec_slot[slot].p; A.errlog = (uint8_t *)ctx->err_slot[slot].p;
+    A.records = (uint8_t *)ctx->rec_slot[*slot].p; A.errlog = (uint8_t *)ctx->err_slot[*slot].p;
     A.cls = nullptr;
-    if (prm->emit_records == 1u && prm->fastq && prm->kind != NS_KIND_UNALIGNED) {      // class words: k_materialise -> k_qualities (cls_word0)
+    if (write_rec && prm->fastq && prm->kind != NS_KIND_UNALIGNED) {      // class words: k_materialise -> k_qualities (cls_word0)
         const size_t per_read = prm->chimeric ? 2u * (2u * NS_MAX_SEG - 1u) : 2u;          // cls_per_read
         if ((rc = ensure(ctx, ctx->cls, (((size_t)info->record_bytes >> 4) + per_read * (n + 1) + 64) * 4))) return rc;
         A.cls = (uint32_t *)ctx->cls.p;
     }
-    const uint64_t max_unaligned = prm->kind == NS_KIND_UNALIGNED ? stats[1] : 0;      // emitted bases of the batch (k_chain): bounds the dense kernel's grid
+    const uint64_t max_unaligned = prm->kind == NS_KIND_UNALIGNED ? pl.stats[1] : 0;      // emitted bases of the batch (k_chain): bounds the dense kernel's grid
     HIPCHK(hipEventRecord(ctx->evt[5], st));
-    const bool write_rec = prm->emit_records == 1u;            // (2 = NS_EMIT_SIZES: the sizes of the images only)
-    const bool side_names = write_rec;                        // names + framing on the second stream, next to the record kernel (round 5: also
-                                                              // next to the second record pass of -k: 0.37 ms per 950 000 reads on the main stream)
-    if (side_names) {
+    // names + framing on the second stream, next to the record kernel (round 5: also next to the second record pass of -k: 0.37 ms per
+    // 950 000 reads on the main stream)
+    if (write_rec) {
         HIPCHK(hipEventRecord(ctx->ev_fork, st));
         HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
     }
-    k_names<<<grid_t, blk, 0, side_names ? ctx->stream2 : st>>>(A);
+    k_names<<<dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, write_rec ? ctx->stream2 : st>>>(A);
     HIPCHK(hipGetLastError());
-    if (side_names) HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
+    if (write_rec) HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
     HIPCHK(hipEventRecord(ctx->evt[6], st));
     if (A.hp) {          // second record pass of -k: the scratch read + its homopolymer edits -> the record
-        if (write_rec && (rc = launch_materialise(ctx, A, n, prm->fastq != 0, tot_cap, nullptr, (meta_al || trx_tab) ? nullptr : list_a, MAT_HP_FINAL))) return rc;
-        k_hp_report<<<dim3((unsigned)((tot_pieces + 255) / 256)), blk, 0, st>>>(A, tot_pieces);      // the pieces report their emitted length,
-        HIPCHK(hipGetLastError());                                                                    // like the path without -k
+        if (write_rec && (rc = launch_materialise(ctx, A, n, prm->fastq != 0, order, MAT_HP_FINAL))) return rc;
+        k_hp_report<<<dim3((unsigned)((pl.tot_pieces + 255) / 256)), dim3(256), 0, st>>>(A, pl.tot_pieces);      // the pieces report their emitted
+        HIPCHK(hipGetLastError());                                                                               // length, like the path without -k
     } else if (write_rec) {
         // (k_names runs NEXT to the record kernels on the second stream: they write different bytes of the image)
-        if ((rc = launch_materialise(ctx, A, n, prm->fastq != 0, tot_cap, nullptr, (meta_al || trx_tab) ? nullptr : list_a, MAT_REF, max_unaligned))) return rc;
+        if ((rc = launch_materialise(ctx, A, n, prm->fastq != 0, order, MAT_REF, max_unaligned))) return rc;
     }
-    if (side_names) HIPCHK(hipStreamWaitEvent(st, ctx->ev_join, 0));
+    if (write_rec) HIPCHK(hipStreamWaitEvent(st, ctx->ev_join, 0));
     HIPCHK(hipEventRecord(ctx->evt[7], st));
     if (prm->emit_errlog && write_rec) {
         // the block buffer of the kernel: the small one (six wavefronts per SIMD instead of four) when 64 average rows of this batch fit it
-        const uint64_t rows = stats[3] ? stats[3] : 1;
-        const bool small_buf = !getenv("NS_ERRLOG_BUF_LARGE") && (info->errlog_bytes / rows + 5) * 64 <= NS_ERR_BUF_SMALL;
-        if (small_buf) k_errlog<NS_ERR_BUF_SMALL><<<dim3((unsigned)n), dim3(64), 0, st>>>(A);
+        const uint64_t rows = pl.stats[3] ? pl.stats[3] : 1;
+        if ((info->errlog_bytes / rows + 5) * 64 <= NS_ERR_BUF_SMALL) k_errlog<NS_ERR_BUF_SMALL><<<dim3((unsigned)n), dim3(64), 0, st>>>(A);
         else k_errlog<NS_ERR_BUF_LARGE><<<dim3((unsigned)n), dim3(64), 0, st>>>(A);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(ctx->evt[8], st));
-    HIPCHK(hipStreamSynchronize(st));
+    return NS_OK;
+}
+
+// the timings and totals of the finished call (ns_batch_info), and the context's record of its batch
+static int finish_call(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, const Plan &pl, int slot) {
+    float ms = 0;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipEventElapsedTime(&ms, ctx->evt[0], ctx->evt[8])); info->ms_total = ms;
     HIPCHK(hipEventElapsedTime(&ms, ctx->evt[1], ctx->evt[2])); info->ms_kernel[NS_K_LENGTHS] = ms;   // nseg + lengths + scans + sort
     HIPCHK(hipEventElapsedTime(&ms, ctx->evt[5], ctx->evt[6])); info->ms_kernel[NS_K_SCAN] = ms;      // names/framing
     HIPCHK(hipEventElapsedTime(&ms, ctx->evt[6], ctx->evt[7])); info->ms_kernel[NS_K_MATERIALISE] = ms;
     HIPCHK(hipEventElapsedTime(&ms, ctx->evt[7], ctx->evt[8])); info->ms_kernel[NS_K_ERRLOG] = ms;
     if (ctx->rec_timed) { HIPCHK(hipEventElapsedTime(&ms, ctx->evt[12], ctx->evt[13])); info->ms_kernel[NS_K_RECORD_KERNEL] = ms; }
-    info->ms_kernel[NS_K_HP] = ms_hp;
-    info->n_reads = n; info->n_pieces = tot_pieces; info->n_events = tot_cap;
-    info->total_bases = stats[1]; info->total_ref_bases = stats[2]; info->events_used = stats[3];
-    info->n_range_redraws = stats[0] >> 40;
+    info->ms_kernel[NS_K_HP] = pl.ms_hp;
+    info->n_reads = prm->n_reads; info->n_pieces = pl.tot_pieces; info->n_events = pl.tot_cap;
+    info->total_bases = pl.stats[1]; info->total_ref_bases = pl.stats[2]; info->events_used = pl.stats[3];
+    info->n_range_redraws = pl.stats[0] >> 40;
     info->spliced_bytes = ctx->spliced_bytes;
     ctx->last = *info;
-    ctx->last.n_events = tot_cap;
     if (prm->emit_records != 1u) { ctx->last.record_bytes = 0; ctx->last.errlog_bytes = 0; }      // nothing to copy out
     ctx->slot = slot;
     ctx->has_batch = true;
     return NS_OK;
 }
 
-// ---- ns_generate_step: the aligned and the unaligned worker call of one step side by side (include/nanosim_amd.h) ----
-// what the companion borrows from its owner: everything ns_generate reads that ns_set_* / ns_load_model fill (device pointers by value)
+// what the step companion (ns_generate_step) borrows from its owner: everything ns_generate reads that ns_set_* / ns_load_model fill (device pointers by value)
 static void lend_tables(const ns_ctx *ctx, ns_ctx *c) {
     c->m = ctx->m; c->ref = ctx->ref; c->has_model = ctx->has_model; c->has_ref = ctx->has_ref;
     c->cap_rate = ctx->cap_rate; c->ref_nbases = ctx->ref_nbases;
@@ -3863,6 +3834,37 @@ static void lend_tables(const ns_ctx *ctx, ns_ctx *c) {
     c->tx = ctx->tx; c->has_trx = ctx->has_trx;
     c->has_abun = false; c->has_inflated = false; c->has_ir = false;                   // (aligned workers only: S:814-1040, 1156-1192)
 }
+int ns_generate(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info) {
+    if (!ctx) return NS_EINVAL;
+    if (!prm || !info) return fail(ctx, NS_EINVAL, "null params/info");
+    // a step companion called directly (include/nanosim_amd.h allows it): the owner may have loaded another model or reference since the
+    // tables were lent — the pointers the companion holds by value would be freed memory
+    if (ctx->borrowed && ctx->owner) lend_tables(ctx->owner, ctx);
+    int rc;
+    if ((rc = check_params(ctx, prm))) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)prm->n_reads;
+    memset(info, 0, sizeof *info);
+    ctx->has_batch = false;
+    if (!n) { ctx->last = *info; ctx->has_batch = true; return NS_OK; }
+    GenArgs A;
+    if ((rc = batch_args(ctx, prm, n, A))) return rc;
+    ctx->rec_timed = false;
+    HIPCHK(hipEventRecord(ctx->evt[0], ctx->stream));
+    // the planner of the mode; each runs the -k stage and the intron-retention splice in its own order: the metagenome passes run -k per
+    // pass and once more at the end, transcriptome batches splice and then run -k, genome batches run both in every hp_round
+    const bool meta_al = prm->meta && prm->kind != NS_KIND_UNALIGNED;       // aligned or --perfect worker of simulation_aligned_metagenome
+    const bool trx_tab = prm->trx && prm->kind != NS_KIND_UNALIGNED;        // transcript + aligned length per block walk
+    Plan pl;
+    rc = meta_al ? meta_passes(ctx, prm, info, A, pl) : trx_tab ? trx_passes(ctx, prm, info, A, pl) : genome_passes(ctx, prm, info, A, pl);
+    if (rc) return rc;
+    int slot = 0;
+    const uint32_t *order = (meta_al || trx_tab) ? nullptr : (const uint32_t *)ctx->order.p;
+    if ((rc = write_images(ctx, prm, info, A, pl, meta_al, order, &slot))) return rc;
+    return finish_call(ctx, prm, info, pl, slot);
+}
+
+// ---- ns_generate_step: the aligned and the unaligned worker call of one step side by side (include/nanosim_amd.h) ----
 static void step_worker_main(ns_ctx *owner) {
     ns_ctx::StepWorker *w = owner->step;
     std::unique_lock<std::mutex> lk(w->mu);
@@ -3884,11 +3886,9 @@ int ns_step_context(ns_ctx *ctx, ns_ctx **out) {
     if (ctx->borrowed) return fail(ctx, NS_EINVAL, "a step companion has no companion of its own");
     if (!ctx->companion) {
         ns_ctx *c = nullptr;
-        const char *pe = getenv("NS_STEP_PRIO");
-        const int rc = create_ctx(ctx->device, &c, pe ? atoi(pe) : 0);
+        const int rc = ns_create(ctx->device, &c);
         if (rc) return fail(ctx, rc, "ns_generate_step: the companion context could not be created");
         c->borrowed = true; c->owner = ctx;
-        ns_set_background(c, 1);
         ctx->companion = c;
     }
     lend_tables(ctx, ctx->companion);
@@ -3916,8 +3916,7 @@ int ns_generate_step(ns_ctx *ctx, const ns_params *aligned, const ns_params *una
         ctx->step->th = std::thread(step_worker_main, ctx);
     }
     ns_ctx::StepWorker *w = ctx->step;
-    const char *gate_env = getenv("NS_STEP_GATE");
-    const bool gated = !(gate_env && gate_env[0] == '0') && !aligned->meta && !aligned->trx;
+    const bool gated = !aligned->meta && !aligned->trx;               // the step gate (ns_ctx::gate): genome-mode steps
     ctx->gate.store(0); ctx->gate_signal = gated ? &ctx->gate : nullptr; c->gate_wait = gated ? &ctx->gate : nullptr;
     { std::lock_guard<std::mutex> lk(w->mu); w->prm = unaligned; w->info = &info[1]; w->done = false; w->rc = 0; }
     w->cv.notify_all();
@@ -4126,9 +4125,9 @@ static int histograms(ns_ctx *ctx, const uint8_t *cs, const uint8_t *qry, bool m
     if (e == hipSuccess && d_m2) e = hipMemsetAsync(d_m2, 0, (size_t)cap * cap * 8, st);
     if (e == hipSuccess) e = hipEventRecord(ctx->evt[14], st);
     // Alignments of 1 kb .. 100 kb on neighbouring lanes diverge like the thread-per-read chain did before its length sort: the walks are
-    // visited by descending length of their cs strings (the counts are sums: any order gives the same tables).  NS_CS_NO_SORT=1: file order.
+    // visited by descending length of their cs strings (the counts are sums: any order gives the same tables).
     uint32_t *d_order = nullptr;
-    if (e == hipSuccess && n_aln > 64 && !getenv("NS_CS_NO_SORT")) {
+    if (e == hipSuccess && n_aln > 64) {
         size_t tmp = 0;
         e = hipMalloc(&d_key, (size_t)n_aln * 16);                 // key, index, sorted key, sorted index
         if (e == hipSuccess) {
