@@ -106,7 +106,10 @@ typedef struct ns_model_tables {
     const double *nseg_cdf;
 
     /* base qualities (src/model_base_qualities.py:9-20,120-130): per class, thr[j] = round(65536*P(q<=j));
-     * q = #{j in [0,126] : h >= thr[j]} for a 16-bit draw h. */
+     * q = #{j in [0,126] : h >= thr[j]} for a 16-bit draw h.
+     * Contract: each class's thr[0..126] is non-decreasing (ns_load_model returns NS_EINVAL otherwise, naming the class and the
+     * level); thr[127] is never read.  Any such table is exact as given: no snapping of thresholds to 64-value buckets is needed.
+     * Entries of 65536 or more are never reached by h (<= 65535). */
     uint32_t qual_thr[NS_Q_COUNT][NS_QUAL_LEVELS];
 
     /* homopolymers (S:504-529; src/model_homopolymer_lengths.py:246-260) */

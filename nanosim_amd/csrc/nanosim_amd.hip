@@ -2591,17 +2591,13 @@ int ns_load_model(ns_ctx *ctx, const ns_model_tables *t) {
         if ((rc = upload(ctx, pool, t->nseg_cdf, t->nseg_n, &m.nseg_cdf))) return rc;
     }
     if (t->flags & NS_MODEL_HAS_QUALS) {
+        for (int c = 0; c < NS_Q_COUNT; ++c)
+            if (const uint32_t j = ns_qual_thr_decrease(t->qual_thr[c]))
+                return fail(ctx, NS_EINVAL, "qual_thr: class " + std::to_string(c) + " decreases at level " + std::to_string(j) +
+                                            " (each class must be non-decreasing over levels 0..126)");
         if ((rc = upload(ctx, pool, &t->qual_thr[0][0], (size_t)NS_Q_COUNT * NS_QUAL_LEVELS, &m.qual_thr))) return rc;
         std::vector<uint16_t> lut((size_t)NS_Q_COUNT * 1024);
-        for (int c = 0; c < NS_Q_COUNT; ++c)
-            for (uint32_t b = 0; b < 1024; ++b) {
-                uint32_t q = 0;
-                while (q < NS_QUAL_LEVELS - 1 && t->qual_thr[c][q] <= 64u * b) ++q;      // thresholds at or below the bucket start
-                uint32_t inside = 0, sub = 64;                                             // thresholds in (64 b, 64 b + 63]
-                for (uint32_t j = q; j < NS_QUAL_LEVELS - 1 && t->qual_thr[c][j] <= 64u * b + 63u; ++j) { if (!inside) sub = t->qual_thr[c][j] - 64u * b; ++inside; }
-                // q << 7 | (128 - sub): adding h & 63 carries into the count exactly when h & 63 >= sub (see qual_value_lut)
-                lut[(size_t)c * 1024 + b] = (uint16_t)(q << 7 | (128u - sub) | (inside > 1 ? 0x8000u : 0u));
-            }
+        for (int c = 0; c < NS_Q_COUNT; ++c) ns_build_qual_lut(t->qual_thr[c], lut.data() + (size_t)c * 1024);      // ns_pack.h
         if ((rc = upload(ctx, pool, lut.data(), lut.size(), &m.qual_lut))) return rc;
     }
     memcpy(m.hp, t->hp, sizeof m.hp);

@@ -365,17 +365,18 @@ __device__ __forceinline__ uint8_t ht_letter(const ns_key &key, uint32_t stream,
     u32x4 w = ns_draw(key, stream, 0, attempt, i >> 6, 0);
     return bases_atcg((ns_word(w, (i >> 4) & 3) >> (2 * (i & 15))) & 3u);
 }
-// the same count through a 1024-bucket look-up table: the count at the start of the bucket in bits 7.., and below it 128 minus the
-// offset of the only threshold inside the bucket — adding h & 63 carries into the count exactly when h is at or above that
-// threshold (buckets are 64 wide; a bucket with several thresholds is walked: the loader's tables have none, model.py)
-__device__ __forceinline__ uint8_t qual_value_lut(const uint32_t *__restrict__ thr, const uint16_t *__restrict__ lut, uint32_t h) {
+// the same count through a 1024-bucket look-up table (ns_build_qual_lut, ns_pack.h): the count at the start of the bucket in bits 7..,
+// and below it 128 minus the offset of the only threshold inside the bucket — adding h & 63 carries into the count exactly when h is at
+// or above that threshold (buckets are 64 wide; a bucket with several thresholds is walked: the Python loader's snapped tables have
+// none, model.py, but the ABI takes unsnapped ones)
+NS_DEV uint8_t qual_value_lut(const uint32_t *__restrict__ thr, const uint16_t *__restrict__ lut, uint32_t h) {
     const uint32_t e = lut[h >> 6];
     if (!(e & 0x8000u)) return (uint8_t)(((e & 0x7fffu) + (h & 63u)) >> 7);
     uint32_t q = (e >> 7) & 0x7fu;
     while (q < NS_QUAL_LEVELS - 1 && h >= thr[q]) ++q;
     return (uint8_t)q;
 }
-__device__ __forceinline__ uint8_t qual_value(const uint32_t *__restrict__ thr, uint32_t h) {
+NS_DEV uint8_t qual_value(const uint32_t *__restrict__ thr, uint32_t h) {
     // q = #{j in [0,126] : h >= thr[j]}; thr is non-decreasing -> binary search for the first thr[j] > h
     uint32_t lo = 0, hi = NS_QUAL_LEVELS - 1;
     while (lo < hi) {

@@ -565,7 +565,7 @@ struct QualState {
 };
 
 // 16 qualities from the 16 draws D and the class slot of every byte (cs[k]: slot << 3 in each byte of dword k of the chunk)
-__device__ __forceinline__ void qual_lookup16(const QualState &Q, const DevModel &m, const uint32_t D[8], const uint32_t cs[4], bool skip_lut,
+__device__ __forceinline__ void qual_lookup16(const QualState &Q, const DevModel &m, const uint32_t D[8], const uint32_t cs[4],
                                               uint64_t &qlo, uint64_t &qhi) {
     const uint8_t *lut = reinterpret_cast<const uint8_t *>(Q.lut);
     uint32_t Q2[8], flags = 0;
@@ -576,20 +576,16 @@ __device__ __forceinline__ void qual_lookup16(const QualState &Q, const DevModel
         const uint32_t o0 = __builtin_amdgcn_perm(0u, cw, (k & 1u) ? 0x0c0c020cu : 0x0c0c000cu);
         const uint32_t o1 = __builtin_amdgcn_perm(0u, cw, (k & 1u) ? 0x0c0c030cu : 0x0c0c010cu);
         const uint32_t a0 = and_or(d >> 5, 0x7feu, o0), a1 = and_or(d >> 21, 0x7feu, o1);        // byte address of entry [slot][h >> 6]
-        uint32_t E;
-        if (skip_lut) E = (a0 & 0x3f80u) | (a1 & 0x3f80u) << 16 | 0x00400040u;
-        else {                               // (built as a two-halfword vector: one v_perm_b32 instead of shift + or)
-            ns_v2u16 e2;
-            e2.x = *reinterpret_cast<const uint16_t *>(lut + a0); e2.y = *reinterpret_cast<const uint16_t *>(lut + a1);
-            E = __builtin_bit_cast(uint32_t, e2);
-        }
+        ns_v2u16 e2;                         // (built as a two-halfword vector: one v_perm_b32 instead of shift + or)
+        e2.x = *reinterpret_cast<const uint16_t *>(lut + a0); e2.y = *reinterpret_cast<const uint16_t *>(lut + a1);
+        const uint32_t E = __builtin_bit_cast(uint32_t, e2);
         flags |= E;
         // see qual_value_lut — on both halfwords at once (packed 16-bit add and shift: no carry between the halves, nothing to mask; an
         // entry with bit 15 set gives garbage here and is redone by the exact walk below)
         const ns_v2u16 s2 = (__builtin_bit_cast(ns_v2u16, E) + __builtin_bit_cast(ns_v2u16, d & 0x003f003fu)) >> (uint16_t)7;
         Q2[k] = __builtin_bit_cast(uint32_t, s2);
     }
-    if (__ballot((flags & 0x80008000u) != 0)) {                        // a bucket with several thresholds (never with the loader's tables)
+    if (__ballot((flags & 0x80008000u) != 0)) {                        // a bucket with several thresholds (not with model.py's snapped tables)
 #pragma unroll
         for (uint32_t k = 0; k < 8; ++k) {
             const uint32_t c0 = (cs[k >> 1] >> (16 * (k & 1) + 3)) & 7u, c1 = (cs[k >> 1] >> (16 * (k & 1) + 11)) & 7u;      // slot = class
@@ -996,7 +992,7 @@ __device__ __forceinline__ void quals16(const QualState &Q, const DevModel &m, c
                                         uint32_t j, const uint32_t cs[4], uint64_t &qlo, uint64_t &qhi) {
     const u32x4 k1 = ns_draw(key, stream, sid, a, 2u * j, 0), k2 = ns_draw(key, stream, sid, a, 2u * j + 1u, 0);
     const uint32_t D[8] = {k1.x, k1.y, k1.z, k1.w, k2.x, k2.y, k2.z, k2.w};
-    qual_lookup16(Q, m, D, cs, false, qlo, qhi);
+    qual_lookup16(Q, m, D, cs, qlo, qhi);
 }
 // A piece: the class words lie on the record kernel's chunk grid, g positions ahead of the piece's positions — two neighbouring words,
 // funnel-shifted; the next iteration's words are in flight during this one's draws.  kind != 0 (the gap of a chimeric read): every base

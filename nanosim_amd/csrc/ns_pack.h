@@ -218,3 +218,26 @@ static inline void ns_pack_chain_tables(const ns_model_tables *t, uint32_t nseg,
     ct.int_image = whole ? 1u : 0u;
     ct.n_words = (uint32_t)blob.size();
 }
+
+// ---- base qualities (ns_model_tables.qual_thr, include/nanosim_amd.h) ------------------------------------------------------------------
+// The first level j in [1, NS_QUAL_LEVELS - 1) of one class's thresholds with thr[j] < thr[j - 1], or 0 when the table is non-decreasing
+// over j = 0..126 (thr[127] is never compared).  The count q = #{j : h >= thr[j]} only has one value for the bucket table, the binary search
+// (qual_value) and the oracle's linear count when the table is monotone; ns_load_model refuses one that is not.
+static inline uint32_t ns_qual_thr_decrease(const uint32_t *thr) {
+    for (uint32_t j = 1; j < NS_QUAL_LEVELS - 1; ++j)
+        if (thr[j] < thr[j - 1]) return j;
+    return 0;
+}
+// The 1024-bucket table of one class (qual_value_lut, ns_device.h), for a non-decreasing thr: entry b (h in [64 b, 64 b + 63]) holds the
+// count of thresholds at or below the bucket start in bits 7-13, 128 minus the offset in the bucket of the first threshold strictly inside
+// it in bits 0-6 (64 if none lies inside), and bit 15 when two or more thresholds lie strictly inside (the look-up then walks them).
+static inline void ns_build_qual_lut(const uint32_t *thr, uint16_t *lut) {
+    for (uint32_t b = 0; b < 1024; ++b) {
+        uint32_t q = 0;
+        while (q < NS_QUAL_LEVELS - 1 && thr[q] <= 64u * b) ++q;                  // thresholds at or below the bucket start
+        uint32_t inside = 0, sub = 64;                                             // thresholds in (64 b, 64 b + 63]
+        for (uint32_t j = q; j < NS_QUAL_LEVELS - 1 && thr[j] <= 64u * b + 63u; ++j) { if (!inside) sub = thr[j] - 64u * b; ++inside; }
+        // q << 7 | (128 - sub): adding h & 63 carries into the count exactly when h & 63 >= sub (see qual_value_lut)
+        lut[b] = (uint16_t)(q << 7 | (128u - sub) | (inside > 1 ? 0x8000u : 0u));
+    }
+}

@@ -1,5 +1,7 @@
 """GPU parity: the HIP path (through the C-ABI) must equal the CPU oracle bit-for-bit — same reads,
 same per-read error CIGAR (events), same FASTA/FASTQ bytes, same error-profile rows."""
+import copy
+
 import numpy as np
 import pytest
 
@@ -200,6 +202,38 @@ def test_error_paths(eng, small_ref):
     p = E.make_params(seed=1, first_read=0, n_reads=10, min_len=10 ** 7, max_len=10 ** 8)
     with pytest.raises(E.EngineError):
         eng.generate(p)
+
+
+def test_decreasing_quality_table_is_refused(small_model, small_ref):
+    """ns_load_model refuses a quality table that decreases (NS_EINVAL, naming the class and the level); the same engine then loads a good
+    model and generates as before"""
+    e = E.Engine(0)
+    try:
+        e.set_reference(small_ref)
+        p = E.make_params(seed=3, first_read=0, n_reads=50, fastq=True, max_len=small_ref.max_chrom)
+        for c, j in ((2, 40), (0, 1), (4, 126)):          # (classes ins, match, unmapped)
+            bad = copy.copy(small_model)
+            bad._keep = []
+            bad.qual_thr = small_model.qual_thr.copy()
+            bad.qual_thr[c, j - 1] = bad.qual_thr[c, j] + 1         # the first decrease is at level j
+            with pytest.raises(E.EngineError) as err:
+                e.load_model(bad)
+            assert err.value.code == E.NS_EINVAL
+            msg = str(err.value)
+            assert ("class %d" % c) in msg and ("level %d" % j) in msg, msg
+            with pytest.raises(E.EngineError):
+                e.generate(p)                                 # (no model after a refused load)
+        # thr[127] is never compared: a table that only "decreases" there is accepted
+        ok = copy.copy(small_model)
+        ok._keep = []
+        ok.qual_thr = small_model.qual_thr.copy()
+        ok.qual_thr[:, 127] = 0
+        e.load_model(ok)
+        e.load_model(small_model)
+        b = e.generate(p)
+        compare(b, O.generate(small_model, small_ref, p), p)
+    finally:
+        e.close()
 
 
 def test_cooperative_chain_equals_oracle(small_model, small_ref, monkeypatch):
