@@ -28,6 +28,7 @@
 #include <functional>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <string>
 #include <vector>
 
@@ -140,8 +141,7 @@ struct GenArgs {
     uint8_t *errlog;
     const uint8_t *hp_bm;       // -k: two bits per reference base (k_hp_bitmap), nullptr: none
     uint32_t *cls;              // FASTQ: the class of every base of the aligned pieces, 2 bits each (k_materialise -> k_qualities; cls_word0)
-    unsigned long long *stats;  // [0] overflow reads [1] total bases [2] total ref bases [3] events [4] longest accepted read (unaligned batches)
-                                // [5] reads that failed the final length check of -k [6] reads queued for the next pass [7] -k event capacity overflow
+    unsigned long long *stats;  // the counters, by NsStat (ns_device.h), and their NS_STATS_WAYS copies
 };
 
 __device__ __forceinline__ ns_key make_key(const GenArgs &A, uint64_t r) {
@@ -334,8 +334,6 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
 #ifndef NS_UCOOP_MINW
 #define NS_UCOOP_MINW 4      // wavefronts per SIMD that kernel is compiled for
 #endif
-#define NS_STATS_WAYS 64u    // copies of the chain counters (k_chain -> k_stats_fold); == the threads of k_stats_fold
-#define NS_STATS_BYTES ((8u + 8u * NS_STATS_WAYS) * sizeof(unsigned long long))
 #ifndef NS_CHAIN_BLOCK
 #define NS_CHAIN_BLOCK 256     // threads per block of the thread-per-read chain (320 was measured slower: 4.56 vs 4.09 ms)
 #endif
@@ -512,10 +510,10 @@ __global__ void __launch_bounds__(COOP ? 64 : NS_CHAIN_BLOCK_BIG, COOP ? (LDS_TA
             }
             // An event that does not fit the 8-byte record (a run of more than NS_EV_LEN_MAX bases, a net insertion / deletion balance
             // beyond the 18-bit shift field: multi-megabase reads only): this ATTEMPT is dropped like one that fails the final length
-            // check (S:1429-1430) and the read draws new lengths; counted in stats[0] >> 40 (ns_batch_info.n_range_redraws).  The
+            // check (S:1429-1430) and the read draws new lengths; counted in NS_STAT_OVER >> NS_RANGE_SHIFT (ns_batch_info.n_range_redraws).  The
             // reference keeps Python integers (S:1875-1882) and would emit the read: a documented limit of the record format.
             if (piece_only) break;
-            if (sink.range) { if (lead) st_over = 1ull << 40; if (!meta_al) { ++epoch; fails = 0; } break; }
+            if (sink.range) { if (lead) st_over = 1ull << NS_RANGE_SHIFT; if (!meta_al) { ++epoch; fails = 0; } break; }
             if (sink.overflow) { overflow = true; break; }
             int64_t trx_len = 0;
             if (trx_al) {                                    // S:1143-1144: middle_ref > ref_trx_len -> start over (no length limits)
@@ -658,31 +656,32 @@ __global__ void __launch_bounds__(COOP ? 64 : NS_CHAIN_BLOCK_BIG, COOP ? (LDS_TA
     // 200 000 atomics of a wave-per-read launch over 50 000 unaligned reads were executed one after the other at the memory side, ~12 ns
     // each: they, not the error lists, were the 2.6 ms of that kernel (round 6: the kernel without its lists took 2.44 ms)
     if ((threadIdx.x & 63) == 0) {
-        unsigned long long *S = A.stats + 8u + 8u * (blockIdx.x & (NS_STATS_WAYS - 1u));
-        if (st_over) atomicAdd(&S[0], st_over);
-        if (st_bases) atomicAdd(&S[1], st_bases);
-        if (st_ref) atomicAdd(&S[2], st_ref);
-        if (st_ev) atomicAdd(&S[3], st_ev);
-        if (A.prm.kind == NS_KIND_UNALIGNED && st_max) atomicMax(&S[4], (unsigned long long)st_max);
+        unsigned long long *S = ns_stats_way(A.stats, blockIdx.x & (NS_STATS_WAYS - 1u));
+        if (st_over) atomicAdd(&S[NS_STAT_OVER], st_over);
+        if (st_bases) atomicAdd(&S[NS_STAT_BASES], st_bases);
+        if (st_ref) atomicAdd(&S[NS_STAT_REF_BASES], st_ref);
+        if (st_ev) atomicAdd(&S[NS_STAT_EVENTS], st_ev);
+        if (A.prm.kind == NS_KIND_UNALIGNED && st_max) atomicMax(&S[NS_STAT_MAX_READ], (unsigned long long)st_max);
     }
 }
 
-// the NS_STATS_WAYS copies of the chain counters -> stats[0..4]; the copies are left zeroed for the next launch
+// the NS_STATS_WAYS copies of the chain counters -> NS_STAT_OVER .. NS_STAT_MAX_READ; the copies are left zeroed for the next launch
 // zero_me: the counter of the record kernel's slow-tile queue (a 4-byte hipMemsetAsync in front of that kernel is a launch of its own that waits
 // for room next to the other call's kernels: 0.1 ms in the timeline of a step)
 __global__ void __launch_bounds__(64) k_stats_fold(unsigned long long *stats, uint32_t *zero_me) {
     if (threadIdx.x == 0 && zero_me) *zero_me = 0;
-    unsigned long long *S = stats + 8u + 8u * threadIdx.x;
-    unsigned long long v[5];
+    unsigned long long *S = ns_stats_way(stats, threadIdx.x);
+    constexpr int MAX = NS_STAT_MAX_READ;          // the sums lie below it
+    unsigned long long v[MAX + 1];
     #pragma unroll
-    for (int k = 0; k < 5; ++k) { v[k] = S[k]; S[k] = 0; }
+    for (int k = 0; k <= MAX; ++k) { v[k] = S[k]; S[k] = 0; }
     #pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = wave_sum(v[k]);
-    for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(v[4], off); v[4] = o > v[4] ? o : v[4]; }
+    for (int k = 0; k < MAX; ++k) v[k] = wave_sum(v[k]);
+    for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(v[MAX], off); v[MAX] = o > v[MAX] ? o : v[MAX]; }
     if (threadIdx.x == 0) {
         #pragma unroll
-        for (int k = 0; k < 4; ++k) if (v[k]) atomicAdd(&stats[k], v[k]);
-        if (v[4]) atomicMax(&stats[4], v[4]);
+        for (int k = 0; k < MAX; ++k) if (v[k]) atomicAdd(&stats[k], v[k]);
+        if (v[MAX]) atomicMax(&stats[MAX], v[MAX]);
     }
 }
 
@@ -820,8 +819,8 @@ __global__ void __launch_bounds__(256) k_meta_tail(GenArgs A) {
     }
     st_bases = wave_sum(st_bases); st_ref = wave_sum(st_ref); st_ev = wave_sum(st_ev);
     if ((threadIdx.x & 63) == 0 && (st_bases | st_ref | st_ev)) {
-        unsigned long long *S = A.stats + 8u + 8u * (blockIdx.x & (NS_STATS_WAYS - 1u));
-        atomicAdd(&S[1], st_bases); atomicAdd(&S[2], st_ref); atomicAdd(&S[3], st_ev);
+        unsigned long long *S = ns_stats_way(A.stats, blockIdx.x & (NS_STATS_WAYS - 1u));
+        atomicAdd(&S[NS_STAT_BASES], st_bases); atomicAdd(&S[NS_STAT_REF_BASES], st_ref); atomicAdd(&S[NS_STAT_EVENTS], st_ev);
     }
 }
 
@@ -1022,8 +1021,8 @@ __global__ void __launch_bounds__(256) k_trx_commit(GenArgs A, uint64_t n_pos, u
     }
     st_bases = wave_sum(st_bases); st_ref = wave_sum(st_ref); st_ev = wave_sum(st_ev);
     if ((threadIdx.x & 63) == 0 && (st_bases | st_ref | st_ev)) {         // (one of the copies of the counters: k_stats_fold — on one set these
-        unsigned long long *S = A.stats + 8u + 8u * (blockIdx.x & (NS_STATS_WAYS - 1u));      // 94 000 atomics were 1.1 of the kernel's 1.2 ms)
-        atomicAdd(&S[1], st_bases); atomicAdd(&S[2], st_ref); atomicAdd(&S[3], st_ev);
+        unsigned long long *S = ns_stats_way(A.stats, blockIdx.x & (NS_STATS_WAYS - 1u));      // 94 000 atomics were 1.1 of the kernel's 1.2 ms)
+        atomicAdd(&S[NS_STAT_BASES], st_bases); atomicAdd(&S[NS_STAT_REF_BASES], st_ref); atomicAdd(&S[NS_STAT_EVENTS], st_ev);
     }
 }
 
@@ -1546,8 +1545,8 @@ __device__ inline void hp_final_length(const GenArgs &A, uint64_t r, ns_read &rd
             A.accept[r] = 0; st_fail = 1;
             unsigned long long rb = 0;               // k_chain had counted it as accepted
             for (uint32_t pi = 0; pi < rd.n_pieces; ++pi) rb += A.pieces[rd.piece_off + pi].ref_len;
-            atomicAdd(&A.stats[2], 0ull - rb);
-            atomicAdd(&A.stats[3], 0ull - (unsigned long long)A.sort_key[r]);
+            atomicAdd(&A.stats[NS_STAT_REF_BASES], 0ull - rb);
+            atomicAdd(&A.stats[NS_STAT_EVENTS], 0ull - (unsigned long long)A.sort_key[r]);
         } else {
             rd.seq_len = (uint32_t)final_len;
             A.reads[r] = rd;
@@ -1696,7 +1695,7 @@ __global__ void __launch_bounds__(64 * NS_WPB) k_hp_scan(GenArgs A, uint2 *__res
         }
         q += n;
     }
-    if (lane == 0 && over) atomicAdd(&A.stats[7], 1ull);                        // a piece outgrew its capacity: the stage is repeated with more
+    if (lane == 0 && over) atomicAdd(&A.stats[NS_STAT_HP_OVER], 1ull);                        // a piece outgrew its capacity: the stage is repeated with more
 }
 
 #ifndef NS_HPD_WAVES
@@ -1783,7 +1782,7 @@ __global__ void __launch_bounds__(64 * NS_WPB, NS_HPD_WAVES) k_hp_drain(GenArgs 
     }
     if (lane == 0) {
         hp_final[r] = final_len;                                                // (checked by k_hp_finalize, S:1429-1430)
-        if (over) atomicAdd(&A.stats[7], 1ull);                                 // a piece outgrew its event capacity: the stage is repeated with more
+        if (over) atomicAdd(&A.stats[NS_STAT_HP_OVER], 1ull);                                 // a piece outgrew its event capacity: the stage is repeated with more
     }
 }
 
@@ -1791,13 +1790,13 @@ __global__ void __launch_bounds__(64 * NS_WPB, NS_HPD_WAVES) k_hp_drain(GenArgs 
 __global__ void __launch_bounds__(256) k_hp_finalize(GenArgs A, const uint64_t *__restrict__ final_len) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long st_bases = 0, st_fail = 0;
-    if (r < A.prm.n_reads && !A.stats[7]) {
+    if (r < A.prm.n_reads && !A.stats[NS_STAT_HP_OVER]) {
         ns_read rd = A.reads[r];
         if (!rd.flags) hp_final_length(A, r, rd, rd.attempts, final_len[r], st_bases, st_fail);
         A.scr_len[r] = st_bases;                    // emitted bases of the read: summed by k_sum_u64 afterwards
     }
     st_fail = wave_sum(st_fail);
-    if ((threadIdx.x & 63) == 0 && st_fail) atomicAdd(&A.stats[5], st_fail);
+    if ((threadIdx.x & 63) == 0 && st_fail) atomicAdd(&A.stats[NS_STAT_HP_FAILED], st_fail);
 }
 // batches without records: the pieces report their emitted length, like the path without -k
 __global__ void __launch_bounds__(256) k_hp_report(GenArgs A, uint64_t n_pieces) {
@@ -2127,10 +2126,39 @@ __global__ void __launch_bounds__(256) k_normalise(uint8_t *bases, uint64_t n) {
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
-struct DevBuf {
+// A grow-only buffer of T on the device (or, `pinned`, in page-locked host memory); ensure() sizes it in elements, `cap` is in bytes.
+// The few buffers that are read under several views are DevBuf<uint8_t>, and view<U>(byte offset) is the one place such a view is taken.
+struct RawBuf {
     void *p = nullptr;
     size_t cap = 0;
+    bool pinned = false;
 };
+template <typename T> struct DevBuf : RawBuf {
+    T *data() const { return static_cast<T *>(p); }
+    template <typename U> U *view(size_t byte_off = 0) const {
+        static_assert(sizeof(T) == 1, "views are taken of byte buffers only");
+        return reinterpret_cast<U *>(data() + byte_off);
+    }
+};
+using ByteBuf = DevBuf<uint8_t>;
+struct PinBuf : ByteBuf { PinBuf() { pinned = true; } };
+
+// the sixteen events of a context (ns_ctx::evt).  A timing pair brackets a stretch of the main stream; finish_call, end_pass and hp_stage1
+// turn the pairs into ns_batch_info.ms_total / ms_kernel[] as noted (EVT_TIMED is finish_call's table)
+enum Evt {
+    EV_CALL_BEGIN,                      // .. EV_CALL_END: ms_total
+    EV_PLAN_BEGIN, EV_PLAN_END,         // NS_K_LENGTHS: nseg + lengths + scans + visiting order
+    EV_CHAIN_BEGIN, EV_CHAIN_END,       // NS_K_EVENTS: the chain launches of one pass, summed over the passes (end_pass)
+    EV_NAMES_BEGIN, EV_RECORD_BEGIN, EV_ERRLOG_BEGIN, EV_CALL_END,   // each up to the next: NS_K_SCAN (names / framing), NS_K_MATERIALISE, NS_K_ERRLOG
+    EV_HP_BEGIN, EV_HP_END,             // NS_K_HP: one -k stage, summed over the stages of the call (hp_stage1)
+    EV_DRAWS_ON_HOST,                   // no timing pair: the filtered draws of a metagenome pass have reached the host
+    EV_RECKERNEL_BEGIN, EV_RECKERNEL_END,   // NS_K_RECORD_KERNEL: the record kernel itself (when ns_ctx::rec_timed)
+    EV_HIST_BEGIN, EV_HIST_END,         // ns_cs_hist.ms_kernel (histograms)
+    EV_COUNT
+};
+static const struct { Evt from, to; int slot; } EVT_TIMED[] = {
+    {EV_PLAN_BEGIN, EV_PLAN_END, NS_K_LENGTHS}, {EV_NAMES_BEGIN, EV_RECORD_BEGIN, NS_K_SCAN},
+    {EV_RECORD_BEGIN, EV_ERRLOG_BEGIN, NS_K_MATERIALISE}, {EV_ERRLOG_BEGIN, EV_CALL_END, NS_K_ERRLOG}};
 
 // the environment knobs of the library, read once when the context is created (read_knobs)
 struct Knobs {
@@ -2169,47 +2197,54 @@ struct ns_ctx {
     std::vector<void *> model_allocs;
     void *ref_bases_owned = nullptr;
     std::vector<void *> ref_allocs;
+    std::vector<void *> owned[2];      // what ensure / ensure_keep allocated for this context's buffers ([1]: page-locked); ns_destroy frees these
     double cap_rate = 0.1;
     uint64_t ref_nbases = 0;
     Knobs knob;
     // planning + result buffers
-    DevBuf l_cap, l_off, p_need, p_off;
-    DevBuf n_pieces, piece_off, ev_cap, ev_off, rec_len, rec_off, err_len, err_off, name_len;
-    DevBuf reads, pieces, events, stats, scan_tmp;
-    DevBuf rec_slot[2], err_slot[2];   // two result slots: the record / error-profile images of the last batch and of the one before (ns_io.h)
+    DevBuf<uint64_t> l_cap, l_off, ev_cap, ev_off, rec_len, rec_off, err_len, err_off;
+    DevBuf<uint32_t> p_need, p_off, n_pieces, piece_off;
+    DevBuf<uint16_t> name_len; DevBuf<ns_read> reads; DevBuf<ns_piece> pieces; DevBuf<ns_event> events;
+    ByteBuf stats;                     // the counters (NsStat, ns_device.h): 64-bit words, and the 32-bit next_n inside NS_STAT_NEXT_N
+    ByteBuf scan_tmp;                  // temporary storage of the hipcub calls (with_tmp)
+    ByteBuf rec_slot[2], err_slot[2];  // two result slots: the record / error-profile images of the last batch and of the one before (ns_io.h)
     int slot = 0;                      // slot of the last batch
     IoEngine *io = nullptr;            // copy stream, staging slices, writer threads (created by the first ns_sink_open)
     std::vector<ns_sink *> sinks;
-    DevBuf ord_bins;                 // k_order_*: histogram + cursors of the visiting-order bins
-    DevBuf sort_key, sort_idx, sort_key_out, order, list_b, list_c, rstate, att_base, scr, scr_len, scr_off, hp_len, hp_nev, hp_ev, hp_wd, hp_runs, hp_nrun, slow_q, cls, hp_bm, hp_pcnt, hp_pord;
+    ByteBuf ord_bins;                // k_order_*: histogram + cursors of the visiting-order bins, then n_multi and k_chain's priority thresholds
+    DevBuf<uint32_t> sort_key, sort_idx, sort_key_out, order, rstate, att_base, hp_len, hp_nev, hp_wd, hp_nrun, cls, hp_pcnt, hp_pord;
+    ByteBuf list_b, list_c;          // the pass lists of uint32_t; once the passes are done, the dense kernel's cnt / seg_off
+    ByteBuf slow_q;                  // SlowQueue: a 16-byte header (the counter), then the SlowTile items
+    DevBuf<uint8_t> scr, hp_bm; DevBuf<uint64_t> scr_len, scr_off; DevBuf<ns_event> hp_ev; DevBuf<uint2> hp_runs;
     uint32_t hp_shift = 5, hp_pad = 64, hp_cap_k = 0;       // -k: event capacity of a piece (hp_ev_slot), planned for kmer_bias hp_cap_k
     // metagenome: species view of the reference, abundances of the sample, per-pass scratch
-    DevBuf species_chrom_off, t_reads, t_pieces, t_name_len, t_rec_len, t_err_len, accept, accept_scan, key_pos, draw_x, m_segptr,
-        m_len, m_species, species_bases;
-    DevBuf draw_sel, draw_sorted, meta_words, meta_num;
-    DevBuf trx_chrom, trx_cum, trx_polya, polya;            // transcriptome: expression view of the reference, polyA length per read
-    DevBuf trx_pick_e, trx_pick_y, trx_keys, trx_keys2, trx_prev, trx_cand, t_polya, t_ir_need;   // ... the pick walk of its aligned batches (trx_passes)
+    DevBuf<uint32_t> species_chrom_off, key_pos, m_segptr; DevBuf<ns_read> t_reads; DevBuf<ns_piece> t_pieces;
+    DevBuf<uint16_t> t_name_len, m_species; DevBuf<uint64_t> t_rec_len, t_err_len, accept, accept_scan;
+    DevBuf<double> draw_x, draw_sel, draw_sorted; DevBuf<int32_t> m_len; DevBuf<unsigned long long> species_bases; DevBuf<uint2> meta_words;
+    ByteBuf meta_num;                // DeviceSelect's count (int) | at +16 the 64-bit segment-count histogram; transcriptome: d_short
+    DevBuf<uint32_t> trx_chrom; DevBuf<double> trx_cum; DevBuf<uint8_t> trx_polya; DevBuf<uint16_t> polya;   // transcriptome: expression view of the reference, polyA length per read
+    DevBuf<uint32_t> trx_pick_e, trx_cand; DevBuf<int32_t> trx_pick_y, trx_prev; DevBuf<uint64_t> trx_keys, trx_keys2, t_ir_need; DevBuf<uint16_t> t_polya;   // ... the pick walk of its aligned batches (trx_passes)
     uint32_t trx_margin = 128, trx_pick_pct = 125;          // candidates per block beyond NS_TRX_BLOCK / picks per candidate in percent: grown on demand, kept
     DevTrx tx{};
     bool has_trx = false;
     DevIr ir{};                                             // intron retention: genome, transcript structures, Markov chain
     bool has_ir = false;
     std::vector<void *> ir_allocs;
-    DevBuf ir_need, ir_off, spliced;
+    DevBuf<uint64_t> ir_need, ir_off; DevBuf<uint8_t> spliced;
     uint64_t spliced_bytes = 0;
     uint8_t *pin_small = nullptr;    // page-locked slots for the scalar read-backs of a call (read_small)
-    struct PinBuf { void *p = nullptr; size_t cap = 0; } pin_a, pin_b, pin_c, pin_d;     // pinned host staging of the metagenome passes
+    PinBuf pin_a, pin_b, pin_c;      // pinned host staging of the metagenome passes: draws (then species ids), sorted lengths, words
     uint32_t nspecies = 0;
     bool has_abun = false, has_inflated = false, has_key_pos = false;
     std::vector<double> abun, abun_inflated, last_species_bases;
     bool lds_tables = false, coop_ok = false;
-    uint32_t chain_block = NS_CHAIN_BLOCK;     // threads per workgroup of k_chain<LDS> (ns_load_model: 256, or 640 for a large image)
+    uint32_t chain_block = NS_CHAIN_BLOCK;     // threads per workgroup of k_chain<LDS> (ns_load_model: NS_CHAIN_BLOCK, or NS_CHAIN_BLOCK_BIG for a large image)
     size_t lds_bytes = 0;
     uint32_t hp_bm_k = 0;                // -k: the k the bitmap hp_bm was built for (0: none)
     ns_batch_info last{};
-    hipEvent_t evt[16]{};
+    hipEvent_t evt[EV_COUNT]{};
     bool sq_zeroed = false;                      // k_stats_fold has zeroed the slow-tile queue's counter and nothing has used the queue since
-    bool rec_timed = false;                      // evt[12] / evt[13] bracket the record kernel of this call
+    bool rec_timed = false;                      // EV_RECKERNEL_BEGIN / _END bracket the record kernel of this call
     bool evt_ok = false;
     // ns_generate_step: the companion context the unaligned worker call of a step runs on (it borrows this context's reference, model and
     // mode tables) and the worker thread that makes that call
@@ -2247,54 +2282,76 @@ static int fail(ns_ctx *c, int code, const std::string &msg) {
         if (e_ != hipSuccess) return fail(ctx, NS_EHIP, std::string(#call ": ") + hipGetErrorString(e_)); \
     } while (0)
 
-static int ensure(ns_ctx *ctx, DevBuf &b, size_t bytes) {
+// grows `b` to `bytes` and an eighth more; the old contents are gone.  `keeping`: and a half more, into a new allocation made before the
+// old one is freed, with the first `keep` bytes copied over.  The context records what it allocates here (ns_ctx::owned), a regrow drops
+// the pointer it frees from that record, and ns_destroy frees what the record holds
+static int grow(ns_ctx *ctx, RawBuf &b, size_t bytes, bool keeping = false, size_t keep = 0) {
     if (bytes <= b.cap) return NS_OK;
-    size_t want = bytes + bytes / 8 + 4096;
-    if (b.p) { hipError_t e = hipFree(b.p); (void)e; b.p = nullptr; b.cap = 0; }
-    hipError_t e = hipMalloc(&b.p, want);
+    const size_t want = bytes + bytes / (keeping ? 2 : 8) + 4096;
+    std::vector<void *> &own = ctx->owned[b.pinned];
+    auto release = [&](void *p) {
+        hipError_t e = b.pinned ? hipHostFree(p) : hipFree(p); (void)e;
+        own.erase(std::remove(own.begin(), own.end(), p), own.end());
+    };
+    if (b.p && !keeping) { release(b.p); b.p = nullptr; b.cap = 0; }
+    void *np = nullptr;
+    hipError_t e = b.pinned ? hipHostMalloc(&np, want, hipHostMallocDefault) : hipMalloc(&np, want);
     if (e != hipSuccess) {
-        b.p = nullptr; b.cap = 0;
         size_t fr = 0, tot = 0;
         hipError_t e2 = hipMemGetInfo(&fr, &tot); (void)e2;
         (void)hipGetLastError();             // the failed allocation must not poison the next call
-        return fail(ctx, NS_ENOMEM, std::string("hipMalloc(") + std::to_string(want) + " bytes): " + hipGetErrorString(e) + " (" +
-                                        std::to_string(fr >> 20) + " MiB free of " + std::to_string(tot >> 20) + ")");
+        return fail(ctx, NS_ENOMEM, std::string(b.pinned ? "hipHostMalloc(" : "hipMalloc(") + std::to_string(want) + " bytes): " + hipGetErrorString(e) +
+                                        " (" + std::to_string(fr >> 20) + " MiB free of " + std::to_string(tot >> 20) + ")");
     }
-    b.cap = want;
-    return NS_OK;
-}
-
-struct Need { DevBuf &b; size_t bytes; };
-static int ensure_all(ns_ctx *ctx, std::initializer_list<Need> need) {      // ensure() for each (buffer, bytes), in order, up to the first failure
-    for (const Need &x : need) if (int rc = ensure(ctx, x.b, x.bytes)) return rc;
-    return NS_OK;
-}
-
-static int ensure_pin(ns_ctx *ctx, ns_ctx::PinBuf &b, size_t bytes) {
-    if (bytes <= b.cap) return NS_OK;
-    size_t want = bytes + bytes / 8 + 4096;
-    if (b.p) { hipError_t e = hipHostFree(b.p); (void)e; b.p = nullptr; b.cap = 0; }
-    hipError_t e = hipHostMalloc(&b.p, want, hipHostMallocDefault);
-    if (e != hipSuccess) { b.p = nullptr; return fail(ctx, NS_ENOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e)); }
-    b.cap = want;
-    return NS_OK;
-}
-
-// grows a buffer whose first `keep` bytes must survive
-static int ensure_keep(ns_ctx *ctx, DevBuf &b, size_t bytes, size_t keep) {
-    if (bytes <= b.cap) return NS_OK;
-    size_t want = bytes + bytes / 2 + 4096;
-    void *np = nullptr;
-    hipError_t e = hipMalloc(&np, want);
-    if (e != hipSuccess) return fail(ctx, NS_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    own.push_back(np);
     if (b.p && keep) {
         e = hipMemcpyAsync(np, b.p, keep, hipMemcpyDeviceToDevice, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { hipError_t e2 = hipFree(np); (void)e2; return fail(ctx, NS_EHIP, std::string("hipMemcpy: ") + hipGetErrorString(e)); }
+        if (e != hipSuccess) { release(np); return fail(ctx, NS_EHIP, std::string("hipMemcpy: ") + hipGetErrorString(e)); }
     }
-    if (b.p) { e = hipFree(b.p); (void)e; }
+    if (b.p) release(b.p);
     b.p = np; b.cap = want;
     return NS_OK;
+}
+
+// room for n elements (+ pad bytes); ensure_keep: in a buffer whose first `keep` elements must survive
+template <typename T> static int ensure(ns_ctx *ctx, DevBuf<T> &b, size_t n, size_t pad = 0) { return grow(ctx, b, n * sizeof(T) + pad); }
+template <typename T> static int ensure_keep(ns_ctx *ctx, DevBuf<T> &b, size_t n, size_t pad, size_t keep) {
+    return grow(ctx, b, n * sizeof(T) + pad, true, keep * sizeof(T));
+}
+struct Need {
+    RawBuf &b; size_t bytes;
+    template <typename T> Need(DevBuf<T> &buf, size_t n, size_t pad = 0) : b(buf), bytes(n * sizeof(T) + pad) {}
+};
+static int ensure_all(ns_ctx *ctx, std::initializer_list<Need> need) {      // ensure() for each (buffer, elements[, pad]), in order, up to the first failure
+    for (const Need &x : need) if (int rc = grow(ctx, x.b, x.bytes)) return rc;
+    return NS_OK;
+}
+
+// a hipcub algorithm works in temporary storage whose size it reports itself when called without any: `call(tmp, bytes)` runs once for the
+// size and once, with scan_tmp grown to it, for the work
+template <typename F> static int with_tmp(ns_ctx *ctx, const char *what, F &&call) {
+    size_t bytes = 0;
+    hipError_t e = call(nullptr, bytes);
+    if (e == hipSuccess) {
+        if (int rc = ensure(ctx, ctx->scan_tmp, bytes)) return rc;
+        e = call(ctx->scan_tmp.data(), bytes);
+    }
+    return e == hipSuccess ? NS_OK : fail(ctx, NS_EHIP, std::string("hipcub::") + what + ": " + hipGetErrorString(e));
+}
+template <typename T> static int scan_sum(ns_ctx *ctx, const T *in, T *out, size_t n) {      // exclusive prefix sum on the main stream
+    return with_tmp(ctx, "DeviceScan::ExclusiveSum", [&](void *tmp, size_t &bytes) {
+        return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, in, out, (int)n, ctx->stream); });
+}
+
+// f(fastq, mode) with both as compile-time constants (std::integral_constant): the record kernels are templates over them
+template <typename F> static void by_fastq_mode(bool fastq, int mode, F &&f) {
+    auto by_mode = [&](auto fq) {
+        if (mode == MAT_REF) f(fq, std::integral_constant<int, MAT_REF>{});
+        else if (mode == MAT_HP_SCRATCH) f(fq, std::integral_constant<int, MAT_HP_SCRATCH>{});
+        else f(fq, std::integral_constant<int, MAT_HP_FINAL>{});
+    };
+    if (fastq) by_mode(std::true_type{}); else by_mode(std::false_type{});
 }
 
 template <typename T>
@@ -2347,25 +2404,19 @@ int ns_create(int device, ns_ctx **out) {
     return NS_OK;
 }
 
-// Scalar read-backs of a call (totals of the scans, the counters): device -> page-locked slot -> destination, with the stream
-// synchronised in between.  (hipMemcpyAsync into pageable memory goes through a staging blit kernel; next to another context's
-// kernels on the same GPU that costs hundreds of microseconds per read-back.)
 // the visiting order of a batch: reads by descending key (planned work) — bins of the key, 3 % wide (k_order_*); NS_EXACT_ORDER=1: a full sort (A/B)
 static int visiting_order(ns_ctx *ctx, const uint32_t *keys, const uint32_t *idx, size_t n, uint32_t *list) {
     hipStream_t st = ctx->stream;
     int rc;
     if (ctx->knob.exact_order) {
-        size_t tmp = 0;
-        HIPCHK(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tmp, keys, (uint32_t *)ctx->sort_key_out.p, idx, list, (int)n, 0, 32, st));
-        if ((rc = ensure(ctx, ctx->scan_tmp, tmp))) return rc;
-        HIPCHK(hipcub::DeviceRadixSort::SortPairsDescending(ctx->scan_tmp.p, tmp, keys, (uint32_t *)ctx->sort_key_out.p, idx, list, (int)n, 0, 32, st));
-        return NS_OK;
+        return with_tmp(ctx, "DeviceRadixSort::SortPairsDescending", [&](void *tmp, size_t &bytes) {
+            return hipcub::DeviceRadixSort::SortPairsDescending(tmp, bytes, keys, ctx->sort_key_out.data(), idx, list, (int)n, 0, 32, st); });
     }
-    if (!ctx->ord_bins.p) {
+    if (!ctx->ord_bins.data()) {
         if ((rc = ensure(ctx, ctx->ord_bins, (2 * NS_ORD_BINS + 16) * 4))) return rc;
-        HIPCHK(hipMemsetAsync(ctx->ord_bins.p, 0, (2 * NS_ORD_BINS + 16) * 4, st));
+        HIPCHK(hipMemsetAsync(ctx->ord_bins.data(), 0, (2 * NS_ORD_BINS + 16) * 4, st));
     }
-    uint32_t *hist = (uint32_t *)ctx->ord_bins.p, *cursor = hist + NS_ORD_BINS;
+    uint32_t *hist = ctx->ord_bins.view<uint32_t>(), *cursor = ctx->ord_bins.view<uint32_t>(NS_ORD_BINS * 4);
     const unsigned tiles = (unsigned)((n + 1023) / 1024);
     if (!tiles) return NS_OK;
     // k_order_scan leaves the bins zeroed, but a call that failed between k_order_hist and k_order_scan would not: the cursors of the
@@ -2377,11 +2428,15 @@ static int visiting_order(ns_ctx *ctx, const uint32_t *keys, const uint32_t *idx
     HIPCHK(hipGetLastError());
     return NS_OK;
 }
+static unsigned long long *stat_at(const ns_ctx *ctx, NsStat k) { return ctx->stats.view<unsigned long long>(k * sizeof(unsigned long long)); }
 static void fold_stats(ns_ctx *ctx, hipStream_t st) {
-    uint32_t *z = ctx->slow_q.cap >= 16 ? (uint32_t *)ctx->slow_q.p : nullptr;
-    k_stats_fold<<<dim3(1), dim3(64), 0, st>>>((unsigned long long *)ctx->stats.p, z);
+    uint32_t *z = ctx->slow_q.cap >= 16 ? ctx->slow_q.view<uint32_t>() : nullptr;
+    k_stats_fold<<<dim3(1), dim3(NS_STATS_WAYS), 0, st>>>(stat_at(ctx, NS_STAT_OVER), z);
     ctx->sq_zeroed = z != nullptr;
 }
+// Scalar read-backs of a call (totals of the scans, the counters): device -> page-locked slot -> destination, with the stream
+// synchronised in between.  (hipMemcpyAsync into pageable memory goes through a staging blit kernel; next to another context's
+// kernels on the same GPU that costs hundreds of microseconds per read-back.)
 static int read_small(ns_ctx *ctx, hipStream_t st, void *dst, const void *src, size_t n, void *dst2 = nullptr, const void *src2 = nullptr, size_t n2 = 0) {
     if (n > (dst2 ? 512u : 1024u) || n2 > 512) return fail(ctx, NS_EINVAL, "read_small: too large");
     HIPCHK(hipMemcpyAsync(ctx->pin_small, src, n, hipMemcpyDeviceToHost, st));
@@ -2406,10 +2461,7 @@ void ns_destroy(ns_ctx *ctx) {
         delete ctx->step; ctx->step = nullptr;
     }
     if (ctx->companion) { ns_destroy(ctx->companion); ctx->companion = nullptr; }
-    if (ctx->borrowed) {                             // a companion frees its own batch buffers only
-        ctx->model_allocs.clear(); ctx->ref_allocs.clear(); ctx->ir_allocs.clear(); ctx->ref_bases_owned = nullptr;
-        ctx->species_chrom_off = DevBuf{}; ctx->trx_chrom = DevBuf{}; ctx->trx_cum = DevBuf{}; ctx->trx_polya = DevBuf{};
-    }
+    // (a companion frees its own batch buffers only: what it was lent is in none of its records of allocations)
     hipError_t e = hipSetDevice(ctx->device); (void)e;
     if (ctx->io) { ctx->io->wait_all(); ctx->io->shutdown(); delete ctx->io; ctx->io = nullptr; }
     for (ns_sink *s : ctx->sinks) delete s;
@@ -2424,21 +2476,9 @@ void ns_destroy(ns_ctx *ctx) {
     free_pool(ctx->ref_allocs);
     free_pool(ctx->ir_allocs);
     if (ctx->ref_bases_owned) e = hipFree(ctx->ref_bases_owned);
-    DevBuf *bufs[] = {&ctx->n_pieces, &ctx->piece_off, &ctx->ev_cap, &ctx->ev_off, &ctx->rec_len, &ctx->rec_off,
-                      &ctx->err_len, &ctx->err_off, &ctx->name_len, &ctx->reads, &ctx->pieces, &ctx->events,
-                      &ctx->rec_slot[0], &ctx->rec_slot[1], &ctx->err_slot[0], &ctx->err_slot[1], &ctx->stats, &ctx->scan_tmp, &ctx->sort_key, &ctx->sort_idx, &ctx->ord_bins,
-                      &ctx->sort_key_out, &ctx->order, &ctx->list_b, &ctx->list_c, &ctx->rstate, &ctx->att_base, &ctx->scr, &ctx->hp_nev, &ctx->hp_ev, &ctx->hp_wd, &ctx->hp_runs, &ctx->hp_nrun,
-                      &ctx->scr_len, &ctx->scr_off, &ctx->hp_len, &ctx->slow_q, &ctx->l_cap, &ctx->l_off, &ctx->species_chrom_off, &ctx->t_reads, &ctx->t_pieces,
-                      &ctx->t_name_len, &ctx->t_rec_len, &ctx->t_err_len, &ctx->accept, &ctx->accept_scan, &ctx->key_pos,
-                      &ctx->draw_x, &ctx->m_segptr, &ctx->m_len, &ctx->m_species, &ctx->species_bases, &ctx->draw_sel,
-                      &ctx->draw_sorted, &ctx->meta_words, &ctx->meta_num, &ctx->trx_chrom, &ctx->trx_cum, &ctx->trx_polya, &ctx->polya,
-                      &ctx->ir_need, &ctx->ir_off, &ctx->spliced, &ctx->p_need, &ctx->p_off, &ctx->cls, &ctx->hp_bm, &ctx->hp_pcnt, &ctx->hp_pord,
-                      &ctx->trx_pick_e, &ctx->trx_pick_y, &ctx->trx_keys, &ctx->trx_keys2, &ctx->trx_prev, &ctx->trx_cand, &ctx->t_polya, &ctx->t_ir_need};
-    for (auto *pb : {&ctx->pin_a, &ctx->pin_b, &ctx->pin_c, &ctx->pin_d})
-        if (pb->p) e = hipHostFree(pb->p);
+    for (void *p : ctx->owned[1]) e = hipHostFree(p);
     if (ctx->pin_small) e = hipHostFree(ctx->pin_small);
-    for (DevBuf *b : bufs)
-        if (b->p) e = hipFree(b->p);
+    for (void *p : ctx->owned[0]) e = hipFree(p);
     if (ctx->evt_ok)
         for (auto &ev : ctx->evt) if (ev) e = hipEventDestroy(ev);
     delete ctx;
@@ -2613,25 +2653,6 @@ int ns_load_model(ns_ctx *ctx, const ns_model_tables *t) {
     return NS_OK;
 }
 
-#define NS_OVER_MASK ((1ull << 40) - 1)          // stats[0]: capacity overflows in the low bits, attempts dropped for the event-record range above
-static int scan_u64(ns_ctx *ctx, const uint64_t *in, uint64_t *out, size_t n) {
-    size_t tmp = 0;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, in, out, (int)n, ctx->stream));
-    int rc = ensure(ctx, ctx->scan_tmp, tmp);
-    if (rc) return rc;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(ctx->scan_tmp.p, tmp, in, out, (int)n, ctx->stream));
-    return NS_OK;
-}
-static int scan_u32(ns_ctx *ctx, const uint32_t *in, uint32_t *out, size_t n) {
-    size_t tmp = 0;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, in, out, (int)n, ctx->stream));
-    int rc = ensure(ctx, ctx->scan_tmp, tmp);
-    if (rc) return rc;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(ctx->scan_tmp.p, tmp, in, out, (int)n, ctx->stream));
-    return NS_OK;
-}
-
-
 // ---------------------------------------------------------------------------------------------------------
 // the steps of a worker call (ns_generate)
 // ---------------------------------------------------------------------------------------------------------
@@ -2646,10 +2667,10 @@ static int launch_materialise(ns_ctx *ctx, const GenArgs &A, size_t n, bool fast
         // workgroups to start.  Neither fewer launches in this tail — plan + both scans as ONE single-workgroup kernel: 10.0-10.2 against
         // 9.7 ms per step — nor the aligned record kernel as two launches on two streams (80 % + 20 %: 9.75-9.82 against 9.81-10.1, noise)
         // nor stream priorities moved it: profiles/r05/ab_step_gate.log.)
-        uint32_t *cnt = (uint32_t *)ctx->list_b.p, *seg_off = (uint32_t *)ctx->list_c.p;
+        uint32_t *cnt = ctx->list_b.view<uint32_t>(), *seg_off = ctx->list_c.view<uint32_t>();
         k_dense_plan<<<dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st>>>(A, cnt);
         HIPCHK(hipGetLastError());
-        if (int rc = scan_u32(ctx, cnt, seg_off, n + 1)) return rc;
+        if (int rc = scan_sum(ctx, cnt, seg_off, n + 1)) return rc;
         const uint64_t bound = total_bases / NS_DENSE_SEG + n + 1;
         if (bound > 0x7fffffffull) return fail(ctx, NS_EINVAL, "unaligned batch too large for one launch of the record kernel (split it)");
         // FASTQ: the bases here, the quality lines in k_qualities (one class for the whole read, S:1521: no class words) — drawn inside the
@@ -2665,33 +2686,27 @@ static int launch_materialise(ns_ctx *ctx, const GenArgs &A, size_t n, bool fast
     for (int round = 0;; ++round) {
         size_t cap = ctx->slow_q.cap >= 16 + sizeof(SlowTile) ? (ctx->slow_q.cap - 16) / sizeof(SlowTile) : 0;
         if (cap < n / 4 + 4096) {
-            int rc = ensure(ctx, ctx->slow_q, 16 + (n / 4 + 4096) * sizeof(SlowTile));
+            int rc = ensure(ctx, ctx->slow_q, 16 + (n / 4 + 4096) * sizeof(SlowTile));      // (bytes: header + items)
             if (rc) return rc;
             cap = (ctx->slow_q.cap - 16) / sizeof(SlowTile);
             ctx->sq_zeroed = false;                 // a NEW buffer: k_stats_fold zeroed the counter of the one just freed.  (Until the last day of round 6 the
         }                                           // launch went ahead on whatever the new allocation held — a batch larger than all before it, on recycled device
                                                     // memory, queued `garbage` tiles: a memory fault in the generic kernel; scripts/parity_chimeric_big.py found it)
         SlowQueue sq;
-        sq.count = (uint32_t *)ctx->slow_q.p; sq.items = (SlowTile *)((uint8_t *)ctx->slow_q.p + 16);
+        sq.count = ctx->slow_q.view<uint32_t>(); sq.items = ctx->slow_q.view<SlowTile>(16);
         sq.cap = (uint32_t)(cap > 0xffffffffull ? 0xffffffffull : cap);
         if (!(ctx->sq_zeroed && round == 0)) HIPCHK(hipMemsetAsync(sq.count, 0, 4, st));
         ctx->sq_zeroed = false;
         if (ctx->knob.dbg & 1024u) order = nullptr;     // (profiling: reads in index order)
         const dim3 grid_q((unsigned)((n + NS_MATQ_WAVES - 1) / NS_MATQ_WAVES)), blk_q(64 * NS_MATQ_WAVES), grid_1((unsigned)n), blk_1(64);
         const uint32_t *order_b = (ctx->knob.dbg & 2048u) ? order : nullptr; // (the record kernel: reads in index order)
-        if (round == 0) HIPCHK(hipEventRecord(ctx->evt[12], st));            // the record kernel itself (ns_batch_info.ms_kernel[NS_K_RECORD_KERNEL])
-        if (mode == MAT_REF) {
-            if (fastq) k_materialise<true, MAT_REF><<<grid_1, blk_1, 0, st>>>(A, nullptr, ctx->knob.dbg, sq, order_b);
-            else k_materialise<false, MAT_REF><<<grid_1, blk_1, 0, st>>>(A, nullptr, ctx->knob.dbg, sq, order_b);
-        } else if (mode == MAT_HP_SCRATCH) {
-            if (fastq) k_materialise<true, MAT_HP_SCRATCH><<<grid_1, blk_1, 0, st>>>(A, nullptr, ctx->knob.dbg, sq, nullptr);
-            else k_materialise<false, MAT_HP_SCRATCH><<<grid_1, blk_1, 0, st>>>(A, nullptr, ctx->knob.dbg, sq, nullptr);
-        } else {
-            if (fastq) k_materialise<true, MAT_HP_FINAL><<<grid_1, blk_1, 0, st>>>(A, nullptr, ctx->knob.dbg, sq, order_b);
-            else k_materialise<false, MAT_HP_FINAL><<<grid_1, blk_1, 0, st>>>(A, nullptr, ctx->knob.dbg, sq, nullptr);
-        }
+        if (round == 0) HIPCHK(hipEventRecord(ctx->evt[EV_RECKERNEL_BEGIN], st));            // the record kernel itself (ns_batch_info.ms_kernel[NS_K_RECORD_KERNEL])
+        by_fastq_mode(fastq, mode, [&](auto fq, auto md) {      // (reads in order_b's order: from the reference, and the FASTQ second pass of -k)
+            constexpr bool FQ = decltype(fq)::value; constexpr int MD = decltype(md)::value;
+            k_materialise<FQ, MD><<<grid_1, blk_1, 0, st>>>(A, nullptr, ctx->knob.dbg, sq, (MD == MAT_REF || (FQ && MD == MAT_HP_FINAL)) ? order_b : nullptr);
+        });
         HIPCHK(hipGetLastError());
-        if (round == 0) { HIPCHK(hipEventRecord(ctx->evt[13], st)); ctx->rec_timed = true; }
+        if (round == 0) { HIPCHK(hipEventRecord(ctx->evt[EV_RECKERNEL_END], st)); ctx->rec_timed = true; }
         // FASTQ: the quality lines, from the class words the record kernel left (before the generic kernel below: a tile queued for it
         // has no class words, and its qualities are that kernel's)
         if (fastq && mode != MAT_HP_SCRATCH && round == 0) {
@@ -2709,15 +2724,12 @@ static int launch_materialise(ns_ctx *ctx, const GenArgs &A, size_t n, bool fast
         }
         if (queued) {
             const unsigned grid = queued < 16384u ? queued : 16384u;
-            if (mode == MAT_HP_FINAL) {          // >= 64 homopolymer edits at one output offset (adjacent runs all re-sampled to nothing)
-                if (fastq) k_materialise_slow_hpf<true><<<dim3(grid), dim3(64), 0, st>>>(A, sq);
-                else k_materialise_slow_hpf<false><<<dim3(grid), dim3(64), 0, st>>>(A, sq);
-            } else
-            if (mode == MAT_HP_SCRATCH) {
-                if (fastq) k_materialise_slow<true, true><<<dim3(grid), dim3(64), 0, st>>>(A, sq);
-                else k_materialise_slow<false, true><<<dim3(grid), dim3(64), 0, st>>>(A, sq);
-            } else if (fastq) k_materialise_slow<true, false><<<dim3(grid), dim3(64), 0, st>>>(A, sq);
-            else k_materialise_slow<false, false><<<dim3(grid), dim3(64), 0, st>>>(A, sq);
+            by_fastq_mode(fastq, mode, [&](auto fq, auto md) {
+                constexpr bool FQ = decltype(fq)::value; constexpr int MD = decltype(md)::value;
+                // MAT_HP_FINAL: >= 64 homopolymer edits at one output offset (adjacent runs all re-sampled to nothing)
+                if constexpr (MD == MAT_HP_FINAL) k_materialise_slow_hpf<FQ><<<dim3(grid), dim3(64), 0, st>>>(A, sq);
+                else k_materialise_slow<FQ, MD == MAT_HP_SCRATCH><<<dim3(grid), dim3(64), 0, st>>>(A, sq);
+            });
             HIPCHK(hipGetLastError());
         }
         return NS_OK;
@@ -2726,38 +2738,38 @@ static int launch_materialise(ns_ctx *ctx, const GenArgs &A, size_t n, bool fast
 
 // -k stage 1 on the reads of `A` (A.prm.n_reads of them): filter the events inside homopolymers (S:1920-1947), write the pieces before
 // mutate_homo to the scratch buffer, turn mutate_homo (S:618-706) into an edit list per piece + final lengths, and apply the final
-// length check (stats[5] = reads that failed it)
+// length check (NS_STAT_HP_FAILED = reads that failed it)
 static int hp_stage1(ns_ctx *ctx, const ns_params *prm, GenArgs &A, size_t n, uint64_t tot_pieces, unsigned long long *stats, double *ms_hp) {
     hipStream_t st = ctx->stream;
     const dim3 blk(256), grid_t((unsigned)((n + 1 + 255) / 256));
     int rc;
     float ms = 0;
-    HIPCHK(hipEventRecord(ctx->evt[9], st));
-    if ((rc = ensure_all(ctx, {{ctx->hp_len, (size_t)tot_pieces * 4 + 64}, {ctx->hp_nev, (size_t)tot_pieces * 4 + 64},
-                               {ctx->hp_nrun, (size_t)tot_pieces * 4 + 64}, {ctx->hp_pcnt, (n + 1) * 4}, {ctx->hp_pord, (n + 1) * 4}})))
+    HIPCHK(hipEventRecord(ctx->evt[EV_HP_BEGIN], st));
+    if ((rc = ensure_all(ctx, {{ctx->hp_len, (size_t)tot_pieces, 64}, {ctx->hp_nev, (size_t)tot_pieces, 64},
+                               {ctx->hp_nrun, (size_t)tot_pieces, 64}, {ctx->hp_pcnt, n + 1}, {ctx->hp_pord, n + 1}})))
         return rc;
-    A.hp_len = (uint32_t *)ctx->hp_len.p; A.hp_nev = (uint32_t *)ctx->hp_nev.p;
-    A.hp_pcnt = (uint32_t *)ctx->hp_pcnt.p; A.hp_pord = (const uint32_t *)ctx->hp_pord.p;
+    A.hp_len = ctx->hp_len.data(); A.hp_nev = ctx->hp_nev.data();
+    A.hp_pcnt = ctx->hp_pcnt.data(); A.hp_pord = ctx->hp_pord.data();
     A.hp_bm = nullptr;
     if (prm->kmer_bias >= 2 && prm->kmer_bias <= 16) {               // (k > 16: the windowed walk over the reference)
         if (ctx->hp_bm_k != prm->kmer_bias) {           // once per (reference, k)
             const uint64_t nb = ctx->ref_nbases, nthreads = (nb + 3) / 4;
-            if ((rc = ensure(ctx, ctx->hp_bm, (size_t)nthreads + 64))) return rc;
-            HIPCHK(hipMemsetAsync((uint8_t *)ctx->hp_bm.p + nthreads, 0, 64, st));       // (8-byte loads may run past the last base)
-            k_hp_bitmap<<<dim3((unsigned)((nthreads + 255) / 256)), blk, 0, st>>>(ctx->ref.bases, nb, prm->kmer_bias, (uint8_t *)ctx->hp_bm.p);
+            if ((rc = ensure(ctx, ctx->hp_bm, (size_t)nthreads, 64))) return rc;
+            HIPCHK(hipMemsetAsync(ctx->hp_bm.data() + nthreads, 0, 64, st));       // (8-byte loads may run past the last base)
+            k_hp_bitmap<<<dim3((unsigned)((nthreads + 255) / 256)), blk, 0, st>>>(ctx->ref.bases, nb, prm->kmer_bias, ctx->hp_bm.data());
             HIPCHK(hipGetLastError());
             ctx->hp_bm_k = prm->kmer_bias;
         }
-        A.hp_bm = (const uint8_t *)ctx->hp_bm.p;
+        A.hp_bm = ctx->hp_bm.data();
     }
     k_hp_filter_w<<<dim3((unsigned)((n + NS_WPB) / NS_WPB)), dim3(64 * NS_WPB), 0, st>>>(A);
     HIPCHK(hipGetLastError());
-    if ((rc = scan_u64(ctx, A.scr_len, A.scr_off, n + 1)) || (rc = scan_u32(ctx, A.hp_pcnt, (uint32_t *)ctx->hp_pord.p, n + 1))) return rc;
+    if ((rc = scan_sum(ctx, A.scr_len, A.scr_off, n + 1)) || (rc = scan_sum(ctx, A.hp_pcnt, ctx->hp_pord.data(), n + 1))) return rc;
     uint64_t scr_bytes = 0;
     if ((rc = read_small(ctx, st, &scr_bytes, A.scr_off + n, 8))) return rc;
     // (the second record pass reads the scratch pieces with unaligned 16-byte loads that may start before / end behind a piece)
-    if ((rc = ensure(ctx, ctx->scr, (size_t)scr_bytes + 2 * NS_REF_PAD + 64))) return rc;
-    A.scr = (uint8_t *)ctx->scr.p + NS_REF_PAD;
+    if ((rc = ensure(ctx, ctx->scr, (size_t)scr_bytes, 2 * NS_REF_PAD + 64))) return rc;
+    A.scr = ctx->scr.data() + NS_REF_PAD;
     if ((rc = launch_materialise(ctx, A, n, prm->fastq != 0, nullptr, MAT_HP_SCRATCH))) return rc;
     if (ctx->hp_cap_k != prm->kmer_bias) {      // event capacity per scratch byte: 8x the density of runs >= k in a random sequence
         double rate = 6.0;
@@ -2771,26 +2783,26 @@ static int hp_stage1(ns_ctx *ctx, const ns_params *prm, GenArgs &A, size_t n, ui
     for (int retry = 0;; ++retry) {
         A.hp_shift = ctx->hp_shift; A.hp_pad = ctx->hp_pad;
         const size_t slots = (size_t)(scr_bytes >> A.hp_shift) + (size_t)A.hp_pad * (tot_pieces + 1) + 64;
-        if ((rc = ensure_all(ctx, {{ctx->hp_ev, slots * sizeof(ns_event)}, {ctx->hp_wd, slots * 4}, {ctx->hp_runs, slots * 8}}))) return rc;
-        A.hp_ev = (ns_event *)ctx->hp_ev.p; A.hp_wd = (uint32_t *)ctx->hp_wd.p;
-        if (!A.meta || A.key_pos) HIPCHK(hipMemsetAsync((unsigned long long *)ctx->stats.p + 1, 0, sizeof(unsigned long long), st));   // (kept across metagenome passes)
-        HIPCHK(hipMemsetAsync((unsigned long long *)ctx->stats.p + 5, 0, sizeof(unsigned long long), st));
-        HIPCHK(hipMemsetAsync((unsigned long long *)ctx->stats.p + 7, 0, sizeof(unsigned long long), st));
-        k_hp_scan<<<dim3((unsigned)((n + NS_WPB - 1) / NS_WPB)), dim3(64 * NS_WPB), 0, st>>>(A, (uint2 *)ctx->hp_runs.p, (uint32_t *)ctx->hp_nrun.p);
-        k_hp_drain<<<dim3((unsigned)((n + NS_WPB - 1) / NS_WPB)), dim3(64 * NS_WPB), 0, st>>>(A, (const uint2 *)ctx->hp_runs.p, (const uint32_t *)ctx->hp_nrun.p, A.l_cap);
+        if ((rc = ensure_all(ctx, {{ctx->hp_ev, slots}, {ctx->hp_wd, slots}, {ctx->hp_runs, slots}}))) return rc;
+        A.hp_ev = ctx->hp_ev.data(); A.hp_wd = ctx->hp_wd.data();
+        if (!A.meta || A.key_pos) HIPCHK(hipMemsetAsync(stat_at(ctx, NS_STAT_BASES), 0, sizeof(unsigned long long), st));   // (kept across metagenome passes)
+        HIPCHK(hipMemsetAsync(stat_at(ctx, NS_STAT_HP_FAILED), 0, sizeof(unsigned long long), st));
+        HIPCHK(hipMemsetAsync(stat_at(ctx, NS_STAT_HP_OVER), 0, sizeof(unsigned long long), st));
+        k_hp_scan<<<dim3((unsigned)((n + NS_WPB - 1) / NS_WPB)), dim3(64 * NS_WPB), 0, st>>>(A, ctx->hp_runs.data(), ctx->hp_nrun.data());
+        k_hp_drain<<<dim3((unsigned)((n + NS_WPB - 1) / NS_WPB)), dim3(64 * NS_WPB), 0, st>>>(A, ctx->hp_runs.data(), ctx->hp_nrun.data(), A.l_cap);
         k_hp_finalize<<<grid_t, blk, 0, st>>>(A, A.l_cap);
-        k_sum_u64<<<dim3((unsigned)std::min<size_t>(512, (n + 255) / 256)), blk, 0, st>>>(A.scr_len, n, (unsigned long long *)ctx->stats.p + 1);
+        k_sum_u64<<<dim3((unsigned)std::min<size_t>(512, (n + 255) / 256)), blk, 0, st>>>(A.scr_len, n, stat_at(ctx, NS_STAT_BASES));
         HIPCHK(hipGetLastError());
-        if ((rc = read_small(ctx, st, stats, ctx->stats.p, 8 * sizeof(unsigned long long)))) return rc;
-        if (!stats[7]) break;
+        if ((rc = read_small(ctx, st, stats, ctx->stats.data(), NS_STAT_COUNT * sizeof(unsigned long long)))) return rc;
+        if (!stats[NS_STAT_HP_OVER]) break;
         // more homopolymer edits per base than planned (low-complexity reference): nothing was finalised; again with twice the capacity
         if (retry >= 12) return fail(ctx, NS_ENOMEM, "-k: event capacity overflow persists");
         if (ctx->hp_shift) --ctx->hp_shift;
         ctx->hp_pad *= 2;
     }
-    HIPCHK(hipEventRecord(ctx->evt[10], st));
+    HIPCHK(hipEventRecord(ctx->evt[EV_HP_END], st));
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipEventElapsedTime(&ms, ctx->evt[9], ctx->evt[10]));
+    HIPCHK(hipEventElapsedTime(&ms, ctx->evt[EV_HP_BEGIN], ctx->evt[EV_HP_END]));
     *ms_hp += ms;
     return NS_OK;
 }
@@ -2798,7 +2810,7 @@ static int hp_stage1(ns_ctx *ctx, const ns_params *prm, GenArgs &A, size_t n, ui
 // what a planner (genome_passes, meta_passes, trx_passes) leaves for the record stage
 struct Plan {
     uint64_t tot_pieces = 0, tot_cap = 0;     // pieces of the batch, event slots handed out
-    unsigned long long stats[8] = {};         // the counters after the last pass (k_stats_fold)
+    unsigned long long stats[NS_STAT_COUNT] = {};         // the counters after the last pass (k_stats_fold)
     double ms_hp = 0;                         // time of the -k stage
 };
 
@@ -2828,16 +2840,16 @@ static int launch_chain_coop(ns_ctx *ctx, GenArgs B, hipStream_t st) {
     return NS_OK;
 }
 
-// the end of a chain pass (evt[3] .. evt[4]): fold the counters, read them back, add the chain's time.  A read that outgrew its event
+// the end of a chain pass (EV_CHAIN_BEGIN .. EV_CHAIN_END): fold the counters, read them back, add the chain's time.  A read that outgrew its event
 // capacity (rare): counted, and `again` with twice the planned rates — the caller restores what the pass changed and repeats it
 static int end_pass(ns_ctx *ctx, GenArgs &A, int retry, unsigned long long *stats, double &ms_chain, ns_batch_info *info, bool &again) {
     fold_stats(ctx, ctx->stream);
-    if (int rc = read_small(ctx, ctx->stream, stats, ctx->stats.p, 8 * sizeof(unsigned long long))) return rc;
+    if (int rc = read_small(ctx, ctx->stream, stats, ctx->stats.data(), NS_STAT_COUNT * sizeof(unsigned long long))) return rc;
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, ctx->evt[3], ctx->evt[4])); ms_chain += ms;
-    again = (stats[0] & NS_OVER_MASK) != 0;
+    HIPCHK(hipEventElapsedTime(&ms, ctx->evt[EV_CHAIN_BEGIN], ctx->evt[EV_CHAIN_END])); ms_chain += ms;
+    again = (stats[NS_STAT_OVER] & NS_OVER_MASK) != 0;
     if (!again) return NS_OK;
-    info->n_overflow += stats[0] & NS_OVER_MASK;
+    info->n_overflow += stats[NS_STAT_OVER] & NS_OVER_MASK;
     if (retry >= 6) return fail(ctx, NS_ENOMEM, "event capacity overflow persists after 6 retries");
     A.cap_rate *= 2.0; A.cap_gap_mul *= 2;
     return NS_OK;
@@ -2852,13 +2864,13 @@ static int attempt_limit(ns_ctx *ctx) {
 // metagenome / transcriptome: A writes the final arrays (what the record kernels read); the view returned writes the per-pass arrays of
 // the same kernels
 static GenArgs pass_views(ns_ctx *ctx, GenArgs &A) {
-    A.f_reads = (ns_read *)ctx->reads.p; A.f_pieces = (ns_piece *)ctx->pieces.p; A.f_name_len = (uint16_t *)ctx->name_len.p;
-    A.f_rec_len = (uint64_t *)ctx->rec_len.p; A.f_err_len = (uint64_t *)ctx->err_len.p;
-    A.key_pos_w = (uint32_t *)ctx->key_pos.p;
+    A.f_reads = ctx->reads.data(); A.f_pieces = ctx->pieces.data(); A.f_name_len = ctx->name_len.data();
+    A.f_rec_len = ctx->rec_len.data(); A.f_err_len = ctx->err_len.data();
+    A.key_pos_w = ctx->key_pos.data();
     GenArgs P = A;
-    P.reads = (ns_read *)ctx->t_reads.p; P.pieces = (ns_piece *)ctx->t_pieces.p; P.name_len = (uint16_t *)ctx->t_name_len.p;
-    P.rec_len = (uint64_t *)ctx->t_rec_len.p; P.err_len = (uint64_t *)ctx->t_err_len.p;
-    P.accept = (uint64_t *)ctx->accept.p; P.accept_scan = (uint64_t *)ctx->accept_scan.p;
+    P.reads = ctx->t_reads.data(); P.pieces = ctx->t_pieces.data(); P.name_len = ctx->t_name_len.data();
+    P.rec_len = ctx->t_rec_len.data(); P.err_len = ctx->t_err_len.data();
+    P.accept = ctx->accept.data(); P.accept_scan = ctx->accept_scan.data();
     P.list = nullptr;
     P.cap_rate = ctx->cap_rate;
     return P;
@@ -2867,12 +2879,12 @@ static GenArgs pass_views(ns_ctx *ctx, GenArgs &A) {
 // intron retention: the splice arena — slot offsets, then the copy from the genome (before anything reads the pieces' bases)
 static int ir_splice(ns_ctx *ctx, GenArgs &A, size_t n) {
     int rc;
-    if ((rc = scan_u64(ctx, A.ir_need, (uint64_t *)ctx->ir_off.p, n + 1))) return rc;
+    if ((rc = scan_sum(ctx, A.ir_need, ctx->ir_off.data(), n + 1))) return rc;
     uint64_t arena_bytes = 0;
-    if ((rc = read_small(ctx, ctx->stream, &arena_bytes, (uint64_t *)ctx->ir_off.p + n, 8))) return rc;
-    if ((rc = ensure(ctx, ctx->spliced, (size_t)arena_bytes + 64))) return rc;
-    A.ir.arena = (uint8_t *)ctx->spliced.p; A.ir.arena_off = (const uint64_t *)ctx->ir_off.p;
-    A.ref.spliced = (const uint8_t *)ctx->spliced.p;
+    if ((rc = read_small(ctx, ctx->stream, &arena_bytes, ctx->ir_off.data() + n, 8))) return rc;
+    if ((rc = ensure(ctx, ctx->spliced, (size_t)arena_bytes, 64))) return rc;
+    A.ir.arena = ctx->spliced.data(); A.ir.arena_off = ctx->ir_off.data();
+    A.ref.spliced = ctx->spliced.data();
     ctx->spliced_bytes = arena_bytes;
     if (arena_bytes) {
         k_ir_splice<<<dim3((unsigned)((n + NS_WPB - 1) / NS_WPB)), dim3(64 * NS_WPB), 0, ctx->stream>>>(A);
@@ -2894,15 +2906,15 @@ int ns_set_transcriptome(ns_ctx *ctx, uint32_t n_expr, const uint32_t *expr_chro
     if (!(expr_cum[n_expr - 1] > 0)) return fail(ctx, NS_EINVAL, "no expression weight");
     HIPCHK(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = ensure(ctx, ctx->trx_chrom, (size_t)n_expr * 4)) || (rc = ensure(ctx, ctx->trx_cum, (size_t)n_expr * 8))) return rc;
-    HIPCHK(hipMemcpy(ctx->trx_chrom.p, expr_chrom, (size_t)n_expr * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ctx->trx_cum.p, expr_cum, (size_t)n_expr * 8, hipMemcpyHostToDevice));
-    ctx->tx.n_expr = n_expr; ctx->tx.expr_chrom = (const uint32_t *)ctx->trx_chrom.p; ctx->tx.expr_cum = (const double *)ctx->trx_cum.p;
+    if ((rc = ensure(ctx, ctx->trx_chrom, n_expr)) || (rc = ensure(ctx, ctx->trx_cum, n_expr))) return rc;
+    HIPCHK(hipMemcpy(ctx->trx_chrom.data(), expr_chrom, (size_t)n_expr * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ctx->trx_cum.data(), expr_cum, (size_t)n_expr * 8, hipMemcpyHostToDevice));
+    ctx->tx.n_expr = n_expr; ctx->tx.expr_chrom = ctx->trx_chrom.data(); ctx->tx.expr_cum = ctx->trx_cum.data();
     ctx->tx.polya = nullptr; ctx->tx.polya_scale = polya_scale;
     if (polya) {
         if ((rc = ensure(ctx, ctx->trx_polya, (size_t)ctx->ref.nchrom))) return rc;
-        HIPCHK(hipMemcpy(ctx->trx_polya.p, polya, (size_t)ctx->ref.nchrom, hipMemcpyHostToDevice));
-        ctx->tx.polya = (const uint8_t *)ctx->trx_polya.p;
+        HIPCHK(hipMemcpy(ctx->trx_polya.data(), polya, (size_t)ctx->ref.nchrom, hipMemcpyHostToDevice));
+        ctx->tx.polya = ctx->trx_polya.data();
     }
     ctx->has_trx = true;
     return NS_OK;
@@ -2962,9 +2974,9 @@ int ns_set_species(ns_ctx *ctx, uint32_t nspecies, const uint32_t *species_chrom
     for (uint32_t s = 0; s < nspecies; ++s)
         if (species_chrom_off[s + 1] <= species_chrom_off[s]) return fail(ctx, NS_EINVAL, "species without chromosomes");
     HIPCHK(hipSetDevice(ctx->device));
-    int rc = ensure(ctx, ctx->species_chrom_off, ((size_t)nspecies + 1) * 4);
+    int rc = ensure(ctx, ctx->species_chrom_off, (size_t)nspecies + 1);
     if (rc) return rc;
-    HIPCHK(hipMemcpy(ctx->species_chrom_off.p, species_chrom_off, ((size_t)nspecies + 1) * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ctx->species_chrom_off.data(), species_chrom_off, ((size_t)nspecies + 1) * 4, hipMemcpyHostToDevice));
     ctx->nspecies = nspecies;
     ctx->has_abun = ctx->has_inflated = false;
     return NS_OK;
@@ -3137,13 +3149,13 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
     hipStream_t st = ctx->stream;
     const dim3 blk(256);
     int rc;
-    HIPCHK(hipMemsetAsync(ctx->stats.p, 0, NS_STATS_BYTES, st));
-    HIPCHK(hipEventRecord(ctx->evt[1], st));
+    HIPCHK(hipMemsetAsync(ctx->stats.data(), 0, NS_STATS_BYTES, st));
+    HIPCHK(hipEventRecord(ctx->evt[EV_PLAN_BEGIN], st));
     k_nseg<<<dim3((unsigned)((n + 1 + 255) / 256)), blk, 0, st>>>(A);       // num_segment (S:825-828); zeroes the scan sentinels
     HIPCHK(hipGetLastError());
     // num_segment (k_nseg) stays on the device: the passes need its histogram over the reads still missing, 65 counters per pass
     if ((rc = ensure(ctx, ctx->meta_num, 16 + (NS_MAX_SEG + 1) * 8))) return rc;
-    unsigned long long *d_hist = (unsigned long long *)((uint8_t *)ctx->meta_num.p + 16);
+    unsigned long long *d_hist = ctx->meta_num.view<unsigned long long>(16);
     uint64_t hist[NS_MAX_SEG + 1];
     auto seg_hist = [&](uint64_t lo) -> int {
         HIPCHK(hipMemsetAsync(d_hist, 0, (NS_MAX_SEG + 1) * 8, st));
@@ -3154,24 +3166,24 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
     if ((rc = seg_hist(0))) return rc;
     uint64_t tot_pieces = 0, tot_seg = 0;
     for (uint32_t v = 1; v <= NS_MAX_SEG; ++v) { tot_pieces += (2ull * v - 1ull) * hist[v]; tot_seg += (uint64_t)v * hist[v]; }
-    if ((rc = ensure_all(ctx, {{ctx->pieces, tot_pieces * sizeof(ns_piece) + 64}, {ctx->t_pieces, tot_pieces * sizeof(ns_piece) + 64},
-                               {ctx->t_reads, n * sizeof(ns_read)}, {ctx->t_name_len, (n + 1) * 2}, {ctx->t_rec_len, (n + 1) * 8}, {ctx->t_err_len, (n + 1) * 8},
-                               {ctx->accept, (n + 1) * 8}, {ctx->accept_scan, (n + 1) * 8}, {ctx->key_pos, (n + 1) * 4}, {ctx->draw_x, (tot_seg + 1) * 8},
-                               {ctx->m_segptr, (n + 1) * 4}, {ctx->m_len, (tot_seg + 1) * 4}, {ctx->m_species, (tot_seg + 1) * 2},
-                               {ctx->species_bases, (size_t)ns * 8 * NS_STATS_WAYS}})))
+    if ((rc = ensure_all(ctx, {{ctx->pieces, tot_pieces, 64}, {ctx->t_pieces, tot_pieces, 64},
+                               {ctx->t_reads, n}, {ctx->t_name_len, n + 1}, {ctx->t_rec_len, n + 1}, {ctx->t_err_len, n + 1},
+                               {ctx->accept, n + 1}, {ctx->accept_scan, n + 1}, {ctx->key_pos, n + 1}, {ctx->draw_x, tot_seg + 1},
+                               {ctx->m_segptr, n + 1}, {ctx->m_len, tot_seg + 1}, {ctx->m_species, tot_seg + 1},
+                               {ctx->species_bases, (size_t)ns * NS_STATS_WAYS}})))
         return rc;
-    HIPCHK(hipMemsetAsync(ctx->species_bases.p, 0, (size_t)ns * 8 * NS_STATS_WAYS, st));
-    A.species_bases = (unsigned long long *)ctx->species_bases.p;
+    HIPCHK(hipMemsetAsync(ctx->species_bases.data(), 0, (size_t)ns * 8 * NS_STATS_WAYS, st));
+    A.species_bases = ctx->species_bases.data();
     GenArgs P = pass_views(ctx, A);
-    P.draw_x = (double *)ctx->draw_x.p;
-    P.m_segptr = (const uint32_t *)ctx->m_segptr.p; P.m_len = (const int32_t *)ctx->m_len.p; P.m_species = (const uint16_t *)ctx->m_species.p;
+    P.draw_x = ctx->draw_x.data();
+    P.m_segptr = ctx->m_segptr.data(); P.m_len = ctx->m_len.data(); P.m_species = ctx->m_species.data();
     const bool perfect = prm->kind == NS_KIND_PERFECT;      // S:838-842, 879-910: no errors, no head/tail, the quotas are never updated
     const ns_key bkey{(uint32_t)prm->seed, (uint32_t)(prm->seed >> 32), (uint32_t)prm->first_read, (uint32_t)(prm->first_read >> 32)};
     std::vector<double> cur_bases(ns, 0.0);
     std::vector<unsigned long long> sb((size_t)ns * NS_STATS_WAYS);
     uint64_t passed = 0, pieces_passed = 0, ev_base = 0;
     double ms_chain = 0;
-    unsigned long long good_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // counters after the last complete pass
+    unsigned long long good_stats[NS_STAT_COUNT] = {};       // counters after the last complete pass
     bool first_pass = true;
     for (uint32_t p = 0; passed < n; ++p) {
         if (p >= NS_MAX_ATTEMPT) return attempt_limit(ctx);
@@ -3183,43 +3195,35 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
         P.attempt = p; P.draw_n = D;
         k_meta_draw<<<dim3((unsigned)((D + 255) / 256)), blk, 0, st>>>(P);         // S:852
         HIPCHK(hipGetLastError());
-        if ((rc = ensure_pin(ctx, ctx->pin_a, (D + 1) * 8)) || (rc = ensure_pin(ctx, ctx->pin_b, (D + 1) * 8)) || (rc = ensure_pin(ctx, ctx->pin_c, (D + 1) * 8)) ||
-            (rc = ensure_all(ctx, {{ctx->draw_sel, (D + 1) * 8}, {ctx->draw_sorted, (D + 1) * 8}, {ctx->meta_words, (D + 1) * 8}})))
+        if ((rc = ensure_all(ctx, {{ctx->pin_a, (D + 1) * 8}, {ctx->pin_b, (D + 1) * 8}, {ctx->pin_c, (D + 1) * 8},
+                                   {ctx->draw_sel, D + 1}, {ctx->draw_sorted, D + 1}, {ctx->meta_words, D + 1}})))
             return rc;
-        double *h_draw = (double *)ctx->pin_a.p;
+        double *h_draw = ctx->pin_a.view<double>();
         // the filter (S:857; --perfect: S:841) on the device, order kept; sum(length_list) (S:767) is taken left to right, as Python
         // does, by the host — over the filtered values, while the device sorts them
         const MetaLenFilter flt{perfect ? (double)prm->min_len : 0.0, (double)prm->max_len, perfect};
-        double *d_sel = (double *)ctx->draw_sel.p, *d_sorted = (double *)ctx->draw_sorted.p;
-        {
-            size_t tmp = 0;
-            HIPCHK(hipcub::DeviceSelect::If(nullptr, tmp, P.draw_x, d_sel, (int *)ctx->meta_num.p, (int)D, flt, st));
-            if ((rc = ensure(ctx, ctx->scan_tmp, tmp))) return rc;
-            HIPCHK(hipcub::DeviceSelect::If(ctx->scan_tmp.p, tmp, P.draw_x, d_sel, (int *)ctx->meta_num.p, (int)D, flt, st));
-        }
+        double *d_sel = ctx->draw_sel.data(), *d_sorted = ctx->draw_sorted.data();
+        if ((rc = with_tmp(ctx, "DeviceSelect::If", [&](void *tmp, size_t &bytes) {
+                return hipcub::DeviceSelect::If(tmp, bytes, P.draw_x, d_sel, ctx->meta_num.view<int>(), (int)D, flt, st); }))) return rc;
         int v_sel = 0;
-        if ((rc = read_small(ctx, st, &v_sel, ctx->meta_num.p, 4))) return rc;
+        if ((rc = read_small(ctx, st, &v_sel, ctx->meta_num.data(), 4))) return rc;
         const uint64_t V = (uint64_t)v_sel;
         if (!V) continue;                                                          // S:858-859
         uint64_t chim = 0;
         for (uint32_t v = 2; v <= NS_MAX_SEG; ++v) chim += (uint64_t)v * hist[v];  // S:761: the first `chim` lengths keep their order
         if (chim > V) chim = V;
         HIPCHK(hipMemcpyAsync(h_draw, d_sel, V * 8, hipMemcpyDeviceToHost, st));
-        hipEvent_t ev_draws = ctx->evt[11];                                        // (the filtered draws have reached the host)
-        HIPCHK(hipEventRecord(ev_draws, st));
+        HIPCHK(hipEventRecord(ctx->evt[EV_DRAWS_ON_HOST], st));
         if (chim) HIPCHK(hipMemcpyAsync(d_sorted, d_sel, chim * 8, hipMemcpyDeviceToDevice, st));
-        if (V > chim) {                                                            // S:764-765
-            size_t tmp = 0;
-            HIPCHK(hipcub::DeviceRadixSort::SortKeysDescending(nullptr, tmp, d_sel + chim, d_sorted + chim, (int)(V - chim), 0, 64, st));
-            if ((rc = ensure(ctx, ctx->scan_tmp, tmp))) return rc;
-            HIPCHK(hipcub::DeviceRadixSort::SortKeysDescending(ctx->scan_tmp.p, tmp, d_sel + chim, d_sorted + chim, (int)(V - chim), 0, 64, st));
-        }
-        k_meta_words<<<dim3((unsigned)((V + 255) / 256)), blk, 0, st>>>(P, (uint2 *)ctx->meta_words.p, V);
+        if (V > chim &&                                                            // S:764-765
+            (rc = with_tmp(ctx, "DeviceRadixSort::SortKeysDescending", [&](void *tmp, size_t &bytes) {
+                return hipcub::DeviceRadixSort::SortKeysDescending(tmp, bytes, d_sel + chim, d_sorted + chim, (int)(V - chim), 0, 64, st); }))) return rc;
+        k_meta_words<<<dim3((unsigned)((V + 255) / 256)), blk, 0, st>>>(P, ctx->meta_words.data(), V);
         HIPCHK(hipGetLastError());
-        double *h_sorted = (double *)ctx->pin_b.p;
-        uint2 *h_words = (uint2 *)ctx->pin_c.p;
+        double *h_sorted = ctx->pin_b.view<double>();
+        uint2 *h_words = ctx->pin_c.view<uint2>();
         HIPCHK(hipMemcpyAsync(h_sorted, d_sorted, V * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(h_words, ctx->meta_words.p, V * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_words, ctx->meta_words.data(), V * 8, hipMemcpyDeviceToHost, st));
         P.m_reversed = u32_to_p(ns_draw(bkey, ST_STRAND, 0, p, 0, 0).x) > ctx->m.strandness_rate ? 1u : 0u;   // S:860
         // S:862-865: the reads that get their lengths are the first np of the descending segment-count order; their first segment / first
         // piece are closed forms of the histogram (k_meta_layout).  The error lists of a read do not depend on its species, so the pass
@@ -3246,7 +3250,7 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
         double to_add = 0;
         size_t np = 0;
         bool walked = false;
-        uint16_t *h_species = (uint16_t *)h_draw;                                  // (once the sum is taken the draws are no longer needed: reuse the staging)
+        uint16_t *h_species = ctx->pin_a.view<uint16_t>();                                 // (once the sum is taken the draws are no longer needed: reuse the staging)
         for (int retry = 0;; ++retry) {
             const size_t np_l = walked ? np : (size_t)np_spec;                     // the reads of this launch
             // np_spec == 0 (no read's segments fit the V lengths): the walk would assign no read either; it has no effect a later pass
@@ -3255,9 +3259,9 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
             MetaHist H;
             uint64_t sp_l, po_l;
             layout(np_l, H, sp_l, po_l);
-            k_meta_layout<<<dim3((unsigned)((np_l + 1 + 255) / 256)), blk, 0, st>>>(H, (uint32_t)np_l, (uint32_t *)ctx->m_segptr.p, (uint32_t *)ctx->piece_off.p);
+            k_meta_layout<<<dim3((unsigned)((np_l + 1 + 255) / 256)), blk, 0, st>>>(H, (uint32_t)np_l, ctx->m_segptr.data(), ctx->piece_off.data());
             HIPCHK(hipGetLastError());
-            k_meta_round<<<dim3((unsigned)((sp_l + 255) / 256)), blk, 0, st>>>(d_sorted, (int32_t *)ctx->m_len.p, sp_l);   // S:871: int(round(length))
+            k_meta_round<<<dim3((unsigned)((sp_l + 255) / 256)), blk, 0, st>>>(d_sorted, ctx->m_len.data(), sp_l);   // S:871: int(round(length))
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemsetAsync(P.accept, 0, (np_l + 1) * 8, st));
             HIPCHK(hipMemsetAsync(P.ev_cap + np_l, 0, 8, st));
@@ -3266,17 +3270,17 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
             const dim3 grid_l((unsigned)((np_l + 255) / 256));
             k_lengths<false><<<grid_l, blk, 0, st>>>(P);                           // gaps, head/tail, planned pieces (S:872, 898-903)
             HIPCHK(hipGetLastError());
-            if ((rc = scan_u64(ctx, P.ev_cap, P.ev_off, np_l + 1))) return rc;
+            if ((rc = scan_sum(ctx, P.ev_cap, P.ev_off, np_l + 1))) return rc;
             if (!walked) {               // S:767: sum(length_list), left to right as Python adds (~1 ms per 10^6 values) — while the device sorts and plans
-                HIPCHK(hipEventSynchronize(ev_draws));
+                HIPCHK(hipEventSynchronize(ctx->evt[EV_DRAWS_ON_HOST]));
                 for (uint64_t j = 0; j < V; ++j) to_add += h_draw[j];
             }
             if ((rc = read_small(ctx, st, &pass_cap, P.ev_off + np_l, 8))) return rc;   // also: the sorted lengths and the words have reached the host
-            if ((rc = ensure_keep(ctx, ctx->events, (size_t)(ev_base + pass_cap) * sizeof(ns_event) + 64, (size_t)ev_base * sizeof(ns_event)))) return rc;
-            P.events = (ns_event *)ctx->events.p; P.ev_base = ev_base;
+            if ((rc = ensure_keep(ctx, ctx->events, (size_t)(ev_base + pass_cap), 64, (size_t)ev_base))) return rc;
+            P.events = ctx->events.data(); P.ev_base = ev_base;
             P.m_passed = (uint32_t)passed; P.m_pieces_passed = (uint32_t)pieces_passed;
-            HIPCHK(hipEventRecord(ctx->evt[3], st));
-            if (first_pass && retry == 0) { HIPCHK(hipEventRecord(ctx->evt[2], st)); first_pass = false; }
+            HIPCHK(hipEventRecord(ctx->evt[EV_CHAIN_BEGIN], st));
+            if (first_pass && retry == 0) { HIPCHK(hipEventRecord(ctx->evt[EV_PLAN_END], st)); first_pass = false; }
             // the pass positions are (nearly) sorted by descending length: the head of the list goes to the cooperative chain
             uint32_t n_coop = 0;
             if (ctx->coop_ok && !perfect && np_l >= ctx->knob.coop_min) n_coop = (uint32_t)(np_l >> ctx->knob.coop_shift);
@@ -3288,7 +3292,7 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
             }
             if ((rc = launch_chain(ctx, Q, st))) return rc;
             if (n_coop) HIPCHK(hipStreamWaitEvent(st, ctx->ev_join, 0));
-            HIPCHK(hipEventRecord(ctx->evt[4], st));
+            HIPCHK(hipEventRecord(ctx->evt[EV_CHAIN_END], st));
             if (!walked) {               // ---- the host's walk over the quotas, next to the chain kernels
                 assign_species_host(ctx, h_sorted, V, to_add, h_words, hist, cur_bases, h_species, &np64);   // S:866-867
                 np = (size_t)std::min<uint64_t>(np64, m);
@@ -3300,12 +3304,12 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
             }
             if (!np) {                   // every quota is used up: nothing of this launch counts
                 fold_stats(ctx, st);
-                HIPCHK(hipMemcpyAsync(ctx->stats.p, good_stats, 8 * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+                HIPCHK(hipMemcpyAsync(ctx->stats.data(), good_stats, NS_STAT_COUNT * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
                 break;
             }
             MetaHist Hn;
             layout(np, Hn, sp, po);                          // (the first np reads of the launch: the layout of a prefix is a prefix of the layout)
-            HIPCHK(hipMemcpyAsync(ctx->m_species.p, h_species, sp * 2, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(ctx->m_species.data(), h_species, sp * 2, hipMemcpyHostToDevice, st));
             HIPCHK(hipMemsetAsync(P.accept + np, 0, 8, st)); // (a read beyond np that the launch left pending is not a read of this pass)
             P.list_n = (uint32_t)np;
             k_meta_tail<<<dim3((unsigned)((np + 255) / 256)), blk, 0, st>>>(P);
@@ -3314,7 +3318,7 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
             if ((rc = end_pass(ctx, P, retry, stats, ms_chain, info, again))) return rc;
             if (!again) break;
             // (the lists of the pass are repeated with twice the capacity, on the counters of the last complete pass)
-            HIPCHK(hipMemcpyAsync(ctx->stats.p, good_stats, 8 * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(ctx->stats.data(), good_stats, NS_STAT_COUNT * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
         }
         if (!np) continue;
         const dim3 grid_p((unsigned)((np + 255) / 256));
@@ -3324,7 +3328,7 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
             double ms_hp = 0;
             if ((rc = hp_stage1(ctx, prm, H, np, tot_pieces, stats, &ms_hp))) return rc;
             info->ms_kernel[NS_K_HP] += ms_hp;
-            stats[5] = 0;
+            stats[NS_STAT_HP_FAILED] = 0;
         } else if (prm->emit_errlog) {     // sizes of the error-profile rows of the reads this pass accepted (k_meta_commit adds the read numbers)
             GenArgs H = P;
             H.prm.n_reads = np;
@@ -3334,14 +3338,14 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
         memcpy(good_stats, stats, sizeof good_stats);
         // the pieces of the reads this pass accepts go behind those of the earlier passes: a pass re-sorts the remaining segment counts, so
         // the total over all passes can exceed the first plan (sum over the reads in their original order)
-        if ((rc = ensure_keep(ctx, ctx->pieces, (size_t)(pieces_passed + po) * sizeof(ns_piece) + 64, (size_t)pieces_passed * sizeof(ns_piece)))) return rc;
-        A.f_pieces = P.f_pieces = (ns_piece *)ctx->pieces.p;
-        if ((rc = scan_u64(ctx, P.accept, P.accept_scan, np + 1))) return rc;
+        if ((rc = ensure_keep(ctx, ctx->pieces, (size_t)(pieces_passed + po), 64, (size_t)pieces_passed))) return rc;
+        A.f_pieces = P.f_pieces = ctx->pieces.data();
+        if ((rc = scan_sum(ctx, P.accept, P.accept_scan, np + 1))) return rc;
         k_meta_commit<<<grid_p, blk, 0, st>>>(P);
         HIPCHK(hipGetLastError());
         uint64_t acc = 0;
         HIPCHK(hipMemcpyAsync(&acc, P.accept_scan + np, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(sb.data(), ctx->species_bases.p, (size_t)ns * 8 * NS_STATS_WAYS, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(sb.data(), ctx->species_bases.data(), (size_t)ns * 8 * NS_STATS_WAYS, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         for (uint32_t s = 0; s < ns && !perfect; ++s) {
             unsigned long long tot = 0;
@@ -3351,10 +3355,10 @@ static int meta_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, G
         passed += acc & 0xffffffffull; pieces_passed += acc >> 32;
         ev_base += pass_cap;
     }
-    if (first_pass) HIPCHK(hipEventRecord(ctx->evt[2], st));
-    A.events = (ns_event *)ctx->events.p;
-    A.pieces = (ns_piece *)ctx->pieces.p;
-    A.key_pos = (const uint32_t *)ctx->key_pos.p;
+    if (first_pass) HIPCHK(hipEventRecord(ctx->evt[EV_PLAN_END], st));
+    A.events = ctx->events.data();
+    A.pieces = ctx->pieces.data();
+    A.key_pos = ctx->key_pos.data();
     A.m_species = P.m_species; A.m_segptr = P.m_segptr;
     pl.tot_pieces = pieces_passed;
     pl.tot_cap = ev_base;
@@ -3380,7 +3384,7 @@ static int trx_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, Ge
     const uint64_t W = NS_TRX_BLOCK, g0 = prm->first_read, b0 = g0 / W, nb = (g0 + n - 1) / W - b0 + 1;
     int rc;
     if (ctx->tx.n_expr >= (1u << 22)) return fail(ctx, NS_EINVAL, "transcriptome: more than 2^22 expressed transcripts");
-    HIPCHK(hipEventRecord(ctx->evt[1], st));
+    HIPCHK(hipEventRecord(ctx->evt[EV_PLAN_BEGIN], st));
     A.key_first = b0 * W;                                   // the keys of the candidate table count from the first block
     double ms_chain = 0;
     bool planned = false;
@@ -3393,25 +3397,21 @@ static int trx_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, Ge
         const uint32_t M = (uint32_t)M64;
         const uint64_t n_picks = nb * M, np = nb * C;
         if (np > 0x7ffffff0ull || n_picks > 0x7ffffff0ull) return fail(ctx, NS_EINVAL, "transcriptome batch too large (split into several calls)");
-        if ((rc = ensure_all(ctx, {{ctx->trx_pick_e, n_picks * 4 + 64}, {ctx->trx_pick_y, n_picks * 4 + 64}, {ctx->trx_keys, n_picks * 8 + 64},
-                                   {ctx->trx_keys2, n_picks * 8 + 64}, {ctx->trx_prev, n_picks * 4 + 64}, {ctx->trx_cand, np * 4 + 64}, {ctx->meta_num, 64}})))
+        if ((rc = ensure_all(ctx, {{ctx->trx_pick_e, n_picks, 64}, {ctx->trx_pick_y, n_picks, 64}, {ctx->trx_keys, n_picks, 64},
+                                   {ctx->trx_keys2, n_picks, 64}, {ctx->trx_prev, n_picks, 64}, {ctx->trx_cand, np, 64}, {ctx->meta_num, 64}})))
             return rc;
-        unsigned long long *d_short = (unsigned long long *)ctx->meta_num.p;
+        unsigned long long *d_short = ctx->meta_num.view<unsigned long long>();
         HIPCHK(hipMemsetAsync(d_short, 0, 16, st));
-        k_trx_picks<<<dim3((unsigned)((n_picks + 255) / 256)), blk, 0, st>>>(A, n_picks, M, b0, (uint32_t *)ctx->trx_pick_e.p, (int32_t *)ctx->trx_pick_y.p,
-                                                                              (uint64_t *)ctx->trx_keys.p);
+        k_trx_picks<<<dim3((unsigned)((n_picks + 255) / 256)), blk, 0, st>>>(A, n_picks, M, b0, ctx->trx_pick_e.data(), ctx->trx_pick_y.data(),
+                                                                              ctx->trx_keys.data());
         HIPCHK(hipGetLastError());
-        {
-            int end_bit = 22 + (int)NS_TRX_PICK_BITS;
-            for (uint64_t v = nb - 1; v; v >>= 1) ++end_bit;
-            size_t tmp = 0;
-            HIPCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp, (const uint64_t *)ctx->trx_keys.p, (uint64_t *)ctx->trx_keys2.p, (int)n_picks, 0, end_bit, st));
-            if ((rc = ensure(ctx, ctx->scan_tmp, tmp))) return rc;
-            HIPCHK(hipcub::DeviceRadixSort::SortKeys(ctx->scan_tmp.p, tmp, (const uint64_t *)ctx->trx_keys.p, (uint64_t *)ctx->trx_keys2.p, (int)n_picks, 0, end_bit, st));
-        }
-        k_trx_prev<<<dim3((unsigned)((n_picks + 255) / 256)), blk, 0, st>>>((const uint64_t *)ctx->trx_keys2.p, n_picks, M, (int32_t *)ctx->trx_prev.p);
-        k_trx_walk<<<dim3((unsigned)nb), dim3(64), M, st>>>(M, C, (const int32_t *)ctx->trx_prev.p, (const int32_t *)ctx->trx_pick_y.p,
-                                                            (uint32_t *)ctx->trx_cand.p, d_short);
+        int end_bit = 22 + (int)NS_TRX_PICK_BITS;
+        for (uint64_t v = nb - 1; v; v >>= 1) ++end_bit;
+        if ((rc = with_tmp(ctx, "DeviceRadixSort::SortKeys", [&](void *tmp, size_t &bytes) {
+                return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, ctx->trx_keys.data(), ctx->trx_keys2.data(), (int)n_picks, 0, end_bit, st); }))) return rc;
+        k_trx_prev<<<dim3((unsigned)((n_picks + 255) / 256)), blk, 0, st>>>(ctx->trx_keys2.data(), n_picks, M, ctx->trx_prev.data());
+        k_trx_walk<<<dim3((unsigned)nb), dim3(64), M, st>>>(M, C, ctx->trx_prev.data(), ctx->trx_pick_y.data(),
+                                                            ctx->trx_cand.data(), d_short);
         HIPCHK(hipGetLastError());
         unsigned long long n_short = 0;
         if ((rc = read_small(ctx, st, &n_short, d_short, 8))) return rc;
@@ -3421,25 +3421,25 @@ static int trx_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, Ge
             continue;
         }
         // ---- the candidate table: one try per position
-        if ((rc = ensure_all(ctx, {{ctx->pieces, np * sizeof(ns_piece) + 64}, {ctx->t_pieces, np * sizeof(ns_piece) + 64}, {ctx->t_reads, np * sizeof(ns_read)},
-                                   {ctx->t_name_len, (np + 1) * 2}, {ctx->t_rec_len, (np + 1) * 8}, {ctx->t_err_len, (np + 1) * 8}, {ctx->accept, (np + 1) * 8},
-                                   {ctx->accept_scan, (np + 1) * 8}, {ctx->key_pos, (n + 1) * 4}, {ctx->t_polya, (np + 1) * 2}, {ctx->ev_cap, (np + 1) * 8},
-                                   {ctx->ev_off, (np + 1) * 8}, {ctx->sort_key, (np + 1) * 4}, {ctx->sort_idx, (np + 1) * 4}, {ctx->sort_key_out, (np + 1) * 4},
+        if ((rc = ensure_all(ctx, {{ctx->pieces, np, 64}, {ctx->t_pieces, np, 64}, {ctx->t_reads, np},
+                                   {ctx->t_name_len, np + 1}, {ctx->t_rec_len, np + 1}, {ctx->t_err_len, np + 1}, {ctx->accept, np + 1},
+                                   {ctx->accept_scan, np + 1}, {ctx->key_pos, n + 1}, {ctx->t_polya, np + 1}, {ctx->ev_cap, np + 1},
+                                   {ctx->ev_off, np + 1}, {ctx->sort_key, np + 1}, {ctx->sort_idx, np + 1}, {ctx->sort_key_out, np + 1},
                                    {ctx->list_b, (np + 1) * 4}})) ||
-            (A.ir_need && (rc = ensure(ctx, ctx->t_ir_need, (np + 1) * 8))))
+            (A.ir_need && (rc = ensure(ctx, ctx->t_ir_need, np + 1))))
             return rc;
-        A.ev_cap = (uint64_t *)ctx->ev_cap.p; A.ev_off = (uint64_t *)ctx->ev_off.p;
-        A.sort_key = (uint32_t *)ctx->sort_key.p; A.sort_idx = (uint32_t *)ctx->sort_idx.p;
+        A.ev_cap = ctx->ev_cap.data(); A.ev_off = ctx->ev_off.data();
+        A.sort_key = ctx->sort_key.data(); A.sort_idx = ctx->sort_idx.data();
         GenArgs P = pass_views(ctx, A);
-        P.polya = (uint16_t *)ctx->t_polya.p;
-        if (A.ir_need) P.ir_need = (uint64_t *)ctx->t_ir_need.p;
-        P.trx_C = C; P.trx_M = M; P.trx_cand = (const uint32_t *)ctx->trx_cand.p;
-        P.trx_pick_e = (const uint32_t *)ctx->trx_pick_e.p; P.trx_pick_y = (const int32_t *)ctx->trx_pick_y.p;
+        P.polya = ctx->t_polya.data();
+        if (A.ir_need) P.ir_need = ctx->t_ir_need.data();
+        P.trx_C = C; P.trx_M = M; P.trx_cand = ctx->trx_cand.data();
+        P.trx_pick_e = ctx->trx_pick_e.data(); P.trx_pick_y = ctx->trx_pick_y.data();
         P.list_n = (uint32_t)np; P.list_base = 0; P.attempt = 0; P.l_off = nullptr; P.ev_base = 0;
         const dim3 grid_p((unsigned)((np + 255) / 256));
         uint64_t cap = 0;
         for (int retry = 0;; ++retry) {
-            HIPCHK(hipMemsetAsync(ctx->stats.p, 0, NS_STATS_BYTES, st));
+            HIPCHK(hipMemsetAsync(ctx->stats.data(), 0, NS_STATS_BYTES, st));
             HIPCHK(hipMemsetAsync(P.accept, 0, (np + 1) * 8, st));
             HIPCHK(hipMemsetAsync(P.polya, 0, (np + 1) * 2, st));
             if (P.ir_need) HIPCHK(hipMemsetAsync(P.ir_need, 0, (np + 1) * 8, st));
@@ -3447,30 +3447,30 @@ static int trx_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, Ge
             P.list = nullptr;
             k_lengths<false><<<grid_p, blk, 0, st>>>(P);
             HIPCHK(hipGetLastError());
-            if ((rc = scan_u64(ctx, P.ev_cap, P.ev_off, np + 1))) return rc;
-            if ((rc = visiting_order(ctx, P.sort_key, P.sort_idx, np, (uint32_t *)ctx->list_b.p))) return rc;      // candidates by descending length
-            if (!planned) { HIPCHK(hipEventRecord(ctx->evt[2], st)); planned = true; }
+            if ((rc = scan_sum(ctx, P.ev_cap, P.ev_off, np + 1))) return rc;
+            if ((rc = visiting_order(ctx, P.sort_key, P.sort_idx, np, ctx->list_b.view<uint32_t>()))) return rc;      // candidates by descending length
+            if (!planned) { HIPCHK(hipEventRecord(ctx->evt[EV_PLAN_END], st)); planned = true; }
             if ((rc = read_small(ctx, st, &cap, P.ev_off + np, 8))) return rc;
-            if ((rc = ensure(ctx, ctx->events, (size_t)cap * sizeof(ns_event) + 64))) return rc;
-            A.events = P.events = (ns_event *)ctx->events.p;
-            P.list = (const uint32_t *)ctx->list_b.p;
-            HIPCHK(hipEventRecord(ctx->evt[3], st));
+            if ((rc = ensure(ctx, ctx->events, (size_t)cap, 64))) return rc;
+            A.events = P.events = ctx->events.data();
+            P.list = ctx->list_b.view<const uint32_t>();
+            HIPCHK(hipEventRecord(ctx->evt[EV_CHAIN_BEGIN], st));
             if ((rc = launch_chain(ctx, P, st))) return rc;
-            HIPCHK(hipEventRecord(ctx->evt[4], st));
+            HIPCHK(hipEventRecord(ctx->evt[EV_CHAIN_END], st));
             bool again = false;
             if ((rc = end_pass(ctx, P, retry, stats, ms_chain, info, again))) return rc;
             if (!again) break;
         }
-        if ((rc = scan_u64(ctx, P.accept, P.accept_scan, np + 1))) return rc;
+        if ((rc = scan_sum(ctx, P.accept, P.accept_scan, np + 1))) return rc;
         if (A.ir_need) HIPCHK(hipMemsetAsync(A.ir_need, 0, (n + 1) * 8, st));
         HIPCHK(hipMemsetAsync(A.rec_len + n, 0, 8, st));     // the sentinels of the scans over the final reads
         HIPCHK(hipMemsetAsync(A.err_len + n, 0, 8, st));
         HIPCHK(hipMemsetAsync(d_short, 0, 16, st));
-        HIPCHK(hipMemsetAsync((unsigned long long *)ctx->stats.p + 1, 0, 3 * sizeof(unsigned long long), st));
-        k_trx_commit<<<grid_p, blk, 0, st>>>(P, np, b0, g0, (uint64_t)n, (uint16_t *)ctx->polya.p, A.ir_need, d_short);
+        HIPCHK(hipMemsetAsync(stat_at(ctx, NS_STAT_BASES), 0, 3 * sizeof(unsigned long long), st));     // bases, reference bases, events
+        k_trx_commit<<<grid_p, blk, 0, st>>>(P, np, b0, g0, (uint64_t)n, ctx->polya.data(), A.ir_need, d_short);
         HIPCHK(hipGetLastError());
         fold_stats(ctx, st);
-        if ((rc = read_small(ctx, st, &n_short, d_short, 8, stats, ctx->stats.p, 8 * sizeof(unsigned long long)))) return rc;
+        if ((rc = read_small(ctx, st, &n_short, d_short, 8, stats, ctx->stats.data(), NS_STAT_COUNT * sizeof(unsigned long long)))) return rc;
         if (n_short) {                                       // a block lost more candidates than the table has to spare: a longer table
             if (C >= 2 * W) return fail(ctx, NS_EINVAL, "transcriptome: more than half of the candidates of a block overshoot their transcript");
             ctx->trx_margin = (uint32_t)std::min<uint64_t>(W, 2ull * ctx->trx_margin);
@@ -3479,8 +3479,8 @@ static int trx_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, Ge
         pl.tot_cap = cap;
         break;
     }
-    A.pieces = (ns_piece *)ctx->pieces.p;
-    A.key_pos = (const uint32_t *)ctx->key_pos.p;
+    A.pieces = ctx->pieces.data();
+    A.key_pos = ctx->key_pos.data();
     pl.tot_pieces = n;
     info->ms_kernel[NS_K_EVENTS] = ms_chain;
     if (A.ir_need && (rc = ir_splice(ctx, A, n))) return rc;
@@ -3497,7 +3497,7 @@ static int genome_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info,
     const Knobs &kn = ctx->knob;
     hipStream_t st = ctx->stream;
     unsigned long long *stats = pl.stats;
-    uint32_t *list_a = (uint32_t *)ctx->order.p, *list_b = (uint32_t *)ctx->list_b.p, *list_c = (uint32_t *)ctx->list_c.p;
+    uint32_t *list_a = ctx->order.data(), *list_b = ctx->list_b.view<uint32_t>(), *list_c = ctx->list_c.view<uint32_t>();
     const dim3 blk(256), grid_t((unsigned)((n + 1 + 255) / 256));        // thread-per-read kernels (n+1 for the scan sentinel)
     const bool lds = ctx->lds_tables && prm->kind != NS_KIND_PERFECT;
     const bool chim_al = prm->kind == NS_KIND_ALIGNED && prm->chimeric;
@@ -3505,12 +3505,12 @@ static int genome_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info,
     A.cap_rate = ctx->cap_rate;
     for (int hp_round = 0;; ++hp_round) {
         for (int retry = 0;; ++retry) {
-            HIPCHK(hipMemsetAsync(ctx->stats.p, 0, NS_STATS_BYTES, st));
+            HIPCHK(hipMemsetAsync(ctx->stats.data(), 0, NS_STATS_BYTES, st));
             // ---- plan: pieces, lengths of attempt 0, event capacity, visiting order ----
-            HIPCHK(hipEventRecord(ctx->evt[1], st));
+            HIPCHK(hipEventRecord(ctx->evt[EV_PLAN_BEGIN], st));
             k_nseg<<<grid_t, blk, 0, st>>>(A);
             HIPCHK(hipGetLastError());
-            if ((rc = scan_u32(ctx, A.n_pieces, A.piece_off, n + 1))) return rc;
+            if ((rc = scan_sum(ctx, A.n_pieces, A.piece_off, n + 1))) return rc;
             // one piece per read unless the batch is chimeric (k_nseg): the total is n then, without a read-back (one stream round trip less
             // per worker call)
             if (chim_al) {
@@ -3518,20 +3518,20 @@ static int genome_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info,
                 if ((rc = read_small(ctx, st, &tp32, A.piece_off + n, 4))) return rc;
                 pl.tot_pieces = tp32;
             } else pl.tot_pieces = n;
-            if ((rc = ensure(ctx, ctx->pieces, (size_t)pl.tot_pieces * sizeof(ns_piece) + 64))) return rc;
-            A.pieces = (ns_piece *)ctx->pieces.p;
+            if ((rc = ensure(ctx, ctx->pieces, (size_t)pl.tot_pieces, 64))) return rc;
+            A.pieces = ctx->pieces.data();
             A.list = nullptr; A.list_n = (uint32_t)n; A.attempt = 0;
             k_lengths<false><<<grid_t, blk, 0, st>>>(A);
             HIPCHK(hipGetLastError());
-            if ((rc = scan_u64(ctx, A.ev_cap, A.ev_off, n + 1))) return rc;
+            if ((rc = scan_sum(ctx, A.ev_cap, A.ev_off, n + 1))) return rc;
             if ((rc = visiting_order(ctx, A.sort_key, A.sort_idx, n, list_a))) return rc;
-            HIPCHK(hipEventRecord(ctx->evt[2], st));
+            HIPCHK(hipEventRecord(ctx->evt[EV_PLAN_END], st));
             uint32_t n_multi = 0;                 // reads of several pieces: the head of the visiting order (visiting_order; 0 with NS_EXACT_ORDER)
-            if (prm->chimeric && prm->kind == NS_KIND_ALIGNED && ctx->ord_bins.p && !kn.exact_order) {
-                if ((rc = read_small(ctx, st, &pl.tot_cap, A.ev_off + n, 8, &n_multi, (uint32_t *)ctx->ord_bins.p + 2 * NS_ORD_BINS, 4))) return rc;
+            if (prm->chimeric && prm->kind == NS_KIND_ALIGNED && ctx->ord_bins.data() && !kn.exact_order) {
+                if ((rc = read_small(ctx, st, &pl.tot_cap, A.ev_off + n, 8, &n_multi, ctx->ord_bins.view<uint32_t>() + 2 * NS_ORD_BINS, 4))) return rc;
             } else if ((rc = read_small(ctx, st, &pl.tot_cap, A.ev_off + n, 8))) return rc;
-            if ((rc = ensure(ctx, ctx->events, (size_t)pl.tot_cap * sizeof(ns_event) + 64))) return rc;
-            A.events = (ns_event *)ctx->events.p;
+            if ((rc = ensure(ctx, ctx->events, (size_t)pl.tot_cap, 64))) return rc;
+            A.events = ctx->events.data();
             // ---- passes: pass a generates attempt a of every read still without an accepted attempt ----
             uint32_t *cur = list_a, *nxt = list_b;
             uint32_t cur_n = (uint32_t)n;
@@ -3546,17 +3546,16 @@ static int genome_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info,
                 A.p_need = nullptr; A.p_off = nullptr; A.p_base = 0;
                 if (a > 0) {          // new lengths for the reads still open; their events go to a fresh region behind the earlier passes
                     if (chim_al) {    // ... and a new segment count with a new epoch (read_nseg)
-                        if ((rc = ensure_all(ctx, {{ctx->p_need, ((size_t)cur_n + 1) * 4}, {ctx->p_off, ((size_t)cur_n + 1) * 4}}))) return rc;
-                        k_replan<<<dim3((cur_n + 1 + 255) / 256), blk, 0, st>>>(A, (uint32_t *)ctx->p_need.p);
+                        if ((rc = ensure_all(ctx, {{ctx->p_need, (size_t)cur_n + 1}, {ctx->p_off, (size_t)cur_n + 1}}))) return rc;
+                        k_replan<<<dim3((cur_n + 1 + 255) / 256), blk, 0, st>>>(A, ctx->p_need.data());
                         HIPCHK(hipGetLastError());
-                        if ((rc = scan_u32(ctx, (const uint32_t *)ctx->p_need.p, (uint32_t *)ctx->p_off.p, (size_t)cur_n + 1))) return rc;
+                        if ((rc = scan_sum(ctx, ctx->p_need.data(), ctx->p_off.data(), (size_t)cur_n + 1))) return rc;
                         uint32_t extra = 0;
-                        if ((rc = read_small(ctx, st, &extra, (uint32_t *)ctx->p_off.p + cur_n, 4))) return rc;
+                        if ((rc = read_small(ctx, st, &extra, ctx->p_off.data() + cur_n, 4))) return rc;
                         if (extra) {
-                            if ((rc = ensure_keep(ctx, ctx->pieces, (size_t)(pl.tot_pieces + extra) * sizeof(ns_piece) + 64,
-                                                  (size_t)pl.tot_pieces * sizeof(ns_piece)))) return rc;
-                            A.pieces = (ns_piece *)ctx->pieces.p;
-                            A.p_need = (const uint32_t *)ctx->p_need.p; A.p_off = (const uint32_t *)ctx->p_off.p; A.p_base = (uint32_t)pl.tot_pieces;
+                            if ((rc = ensure_keep(ctx, ctx->pieces, (size_t)(pl.tot_pieces + extra), 64, (size_t)pl.tot_pieces))) return rc;
+                            A.pieces = ctx->pieces.data();
+                            A.p_need = ctx->p_need.data(); A.p_off = ctx->p_off.data(); A.p_base = (uint32_t)pl.tot_pieces;
                             pl.tot_pieces += extra;
                         }
                     }
@@ -3564,12 +3563,12 @@ static int genome_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info,
                     else k_lengths<false><<<grid_p, blk, 0, st>>>(A);
                     HIPCHK(hipGetLastError());
                     HIPCHK(hipMemsetAsync(A.l_cap + cur_n, 0, 8, st));
-                    if ((rc = scan_u64(ctx, A.l_cap, (uint64_t *)ctx->l_off.p, (size_t)cur_n + 1))) return rc;
+                    if ((rc = scan_sum(ctx, A.l_cap, ctx->l_off.data(), (size_t)cur_n + 1))) return rc;
                     uint64_t pass_cap = 0;
-                    if ((rc = read_small(ctx, st, &pass_cap, (uint64_t *)ctx->l_off.p + cur_n, 8))) return rc;
-                    if ((rc = ensure_keep(ctx, ctx->events, (size_t)(used + pass_cap) * sizeof(ns_event) + 64, (size_t)used * sizeof(ns_event)))) return rc;
-                    A.events = (ns_event *)ctx->events.p;
-                    A.l_off = (const uint64_t *)ctx->l_off.p; A.l_base = used;
+                    if ((rc = read_small(ctx, st, &pass_cap, ctx->l_off.data() + cur_n, 8))) return rc;
+                    if ((rc = ensure_keep(ctx, ctx->events, (size_t)(used + pass_cap), 64, (size_t)used))) return rc;
+                    A.events = ctx->events.data();
+                    A.l_off = ctx->l_off.data(); A.l_base = used;
                     used += pass_cap;
                 }
                 if (a == 0 && ctx->gate_wait) {                                // (bounded: the owner opens the gate on every way out of its call; an owner
@@ -3577,7 +3576,7 @@ static int genome_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info,
                     while (!ctx->gate_wait->load(std::memory_order_acquire) && std::chrono::steady_clock::now() < t_end)   // hipMalloc, a result slot
                         std::this_thread::yield();                                                         // still crossing PCIe — is not waited for: 3 ms)
                 }
-                HIPCHK(hipEventRecord(ctx->evt[3], st));
+                HIPCHK(hipEventRecord(ctx->evt[EV_CHAIN_BEGIN], st));
                 uint32_t n_coop = 0;
                 if (prm->kind == NS_KIND_UNALIGNED)                           // its loop is a prefix sum (coop_unaligned_error_list); pass 0 visits the reads longest first
                     n_coop = (a == 0 && lds && cur_n >= kn.coop_min) ? std::max(cur_n >> kn.ucoop_shift, 1u) : cur_n;
@@ -3624,15 +3623,15 @@ static int genome_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info,
                     HIPCHK(hipEventRecord(ctx->ev_join3, ctx->stream3));
                     A.list = cur + coop_at + n_coop; A.hole_at = 0; A.hole_len = 0; A.list_n = cur_n - coop_at - n_coop;
                 }
-                if (a == 0 && n_multi && !n_pt && prm->kind == NS_KIND_ALIGNED) A.prio_thr = (const uint32_t *)ctx->ord_bins.p + 2 * NS_ORD_BINS;
+                if (a == 0 && n_multi && !n_pt && prm->kind == NS_KIND_ALIGNED) A.prio_thr = ctx->ord_bins.view<const uint32_t>() + 2 * NS_ORD_BINS;
                 if ((rc = launch_chain(ctx, A, st))) return rc;
                 if (n_coop) HIPCHK(hipStreamWaitEvent(st, ctx->ev_join, 0));
                 if (n_pt) HIPCHK(hipStreamWaitEvent(st, ctx->ev_join3, 0));
-                HIPCHK(hipEventRecord(ctx->evt[4], st));
+                HIPCHK(hipEventRecord(ctx->evt[EV_CHAIN_END], st));
                 if (ctx->gate_signal) ctx->gate_signal->store(1, std::memory_order_release);
                 if ((rc = end_pass(ctx, A, retry, stats, ms_chain, info, overflow))) return rc;
                 if (overflow) break;
-                cur_n = (uint32_t)(stats[6] & 0xffffffffull);
+                cur_n = (uint32_t)(stats[NS_STAT_NEXT_N] & 0xffffffffull);     // (GenArgs::next_n)
                 if (!cur_n) { pl.tot_cap = used; break; }
                 if (a + 1 >= NS_MAX_ATTEMPT) return attempt_limit(ctx);
                 cur = nxt; nxt = cur == list_b ? list_c : list_b;      // (list_a keeps the length-sorted order of the batch for the record kernels)
@@ -3649,7 +3648,7 @@ static int genome_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info,
         if (A.ir_need && (rc = ir_splice(ctx, A, n))) return rc;
         if (!A.hp) break;
         if ((rc = hp_stage1(ctx, prm, A, n, pl.tot_pieces, stats, &pl.ms_hp))) return rc;
-        if (!stats[5]) break;
+        if (!stats[NS_STAT_HP_FAILED]) break;
         // some reads failed the final length check (S:1429): they advanced their attempt state; every other read restarts at
         // its accepted attempt, so re-running the batch reproduces them bit for bit
         if (hp_round >= (int)NS_MAX_ATTEMPT) return fail(ctx, NS_EINVAL, "reads keep failing the final length check in -k mode");
@@ -3694,12 +3693,12 @@ static int check_params(ns_ctx *ctx, const ns_params *prm) {
 // the per-read buffers of a batch of n reads, and the arguments every kernel of the call starts from
 static int batch_args(ns_ctx *ctx, const ns_params *prm, size_t n, GenArgs &A) {
     int rc;
-    if ((rc = ensure_all(ctx, {{ctx->n_pieces, (n + 1) * 4}, {ctx->piece_off, (n + 1) * 4}, {ctx->ev_cap, (n + 1) * 8}, {ctx->ev_off, (n + 1) * 8},
-                               {ctx->l_cap, (n + 1) * 8}, {ctx->l_off, (n + 1) * 8}, {ctx->rec_len, (n + 1) * 8}, {ctx->rec_off, (n + 1) * 8},
-                               {ctx->err_len, (n + 1) * 8}, {ctx->err_off, (n + 1) * 8}, {ctx->name_len, (n + 1) * 2}, {ctx->reads, n * sizeof(ns_read)},
-                               {ctx->stats, NS_STATS_BYTES}, {ctx->sort_key, (n + 1) * 4}, {ctx->sort_idx, (n + 1) * 4}, {ctx->sort_key_out, (n + 1) * 4},
-                               {ctx->order, (n + 1) * 4}, {ctx->list_b, (n + 1) * 4}, {ctx->list_c, (n + 1) * 4}, {ctx->rstate, (n + 1) * 4},
-                               {ctx->att_base, (n + 1) * 4}, {ctx->scr_len, (n + 1) * 8}, {ctx->scr_off, (n + 1) * 8}})))
+    if ((rc = ensure_all(ctx, {{ctx->n_pieces, n + 1}, {ctx->piece_off, n + 1}, {ctx->ev_cap, n + 1}, {ctx->ev_off, n + 1},
+                               {ctx->l_cap, n + 1}, {ctx->l_off, n + 1}, {ctx->rec_len, n + 1}, {ctx->rec_off, n + 1},
+                               {ctx->err_len, n + 1}, {ctx->err_off, n + 1}, {ctx->name_len, n + 1}, {ctx->reads, n},
+                               {ctx->stats, NS_STATS_BYTES}, {ctx->sort_key, n + 1}, {ctx->sort_idx, n + 1}, {ctx->sort_key_out, n + 1},
+                               {ctx->order, n + 1}, {ctx->list_b, (n + 1) * 4}, {ctx->list_c, (n + 1) * 4}, {ctx->rstate, n + 1},
+                               {ctx->att_base, n + 1}, {ctx->scr_len, n + 1}, {ctx->scr_off, n + 1}})))
         return rc;
     memset(&A, 0, sizeof A);
     A.prm = *prm; A.m = ctx->m; A.ref = ctx->ref;
@@ -3707,30 +3706,30 @@ static int batch_args(ns_ctx *ctx, const ns_params *prm, size_t n, GenArgs &A) {
     A.cap_gap_mul = 2;
     // events of the thread-per-read chain staged four at a time in LDS, when the tables leave room for it next to four workgroups per CU
     A.ev_stage = (ctx->lds_tables && ctx->lds_bytes + ctx->chain_block * 32u <= 64u * 1024u) ? (uint32_t)ctx->lds_bytes : 0u;
-    A.n_pieces = (uint32_t *)ctx->n_pieces.p; A.piece_off = (uint32_t *)ctx->piece_off.p;
-    A.ev_cap = (uint64_t *)ctx->ev_cap.p; A.ev_off = (uint64_t *)ctx->ev_off.p; A.l_cap = (uint64_t *)ctx->l_cap.p;
-    A.rec_len = (uint64_t *)ctx->rec_len.p; A.rec_off = (uint64_t *)ctx->rec_off.p;
-    A.err_len = (uint64_t *)ctx->err_len.p; A.err_off = (uint64_t *)ctx->err_off.p;
-    A.name_len = (uint16_t *)ctx->name_len.p; A.reads = (ns_read *)ctx->reads.p;
-    A.stats = (unsigned long long *)ctx->stats.p;
-    A.sort_key = (uint32_t *)ctx->sort_key.p; A.sort_idx = (uint32_t *)ctx->sort_idx.p;
-    A.rstate = (uint32_t *)ctx->rstate.p; A.att_base = (uint32_t *)ctx->att_base.p;
-    A.scr_len = (uint64_t *)ctx->scr_len.p; A.scr_off = (uint64_t *)ctx->scr_off.p;
+    A.n_pieces = ctx->n_pieces.data(); A.piece_off = ctx->piece_off.data();
+    A.ev_cap = ctx->ev_cap.data(); A.ev_off = ctx->ev_off.data(); A.l_cap = ctx->l_cap.data();
+    A.rec_len = ctx->rec_len.data(); A.rec_off = ctx->rec_off.data();
+    A.err_len = ctx->err_len.data(); A.err_off = ctx->err_off.data();
+    A.name_len = ctx->name_len.data(); A.reads = ctx->reads.data();
+    A.stats = stat_at(ctx, NS_STAT_OVER);
+    A.sort_key = ctx->sort_key.data(); A.sort_idx = ctx->sort_idx.data();
+    A.rstate = ctx->rstate.data(); A.att_base = ctx->att_base.data();
+    A.scr_len = ctx->scr_len.data(); A.scr_off = ctx->scr_off.data();
     A.hp = (prm->kmer_bias && prm->kind == NS_KIND_ALIGNED) ? 1u : 0u;     // S:1413: only aligned segments; --perfect never
     A.errlen_later = prm->emit_errlog ? 1u : 0u;
     A.dbg = ctx->knob.dbg;
     if (prm->trx) {
-        if ((rc = ensure(ctx, ctx->polya, (n + 1) * 2))) return rc;
-        A.tx = ctx->tx; A.polya = (uint16_t *)ctx->polya.p;
-        HIPCHK(hipMemsetAsync(ctx->polya.p, 0, (n + 1) * 2, ctx->stream));
+        if ((rc = ensure(ctx, ctx->polya, n + 1))) return rc;
+        A.tx = ctx->tx; A.polya = ctx->polya.data();
+        HIPCHK(hipMemsetAsync(ctx->polya.data(), 0, (n + 1) * 2, ctx->stream));
     }
     ctx->spliced_bytes = 0;
     if (prm->model_ir && prm->kind == NS_KIND_ALIGNED) {                 // S:1156: not for --perfect, not for unaligned reads
-        if ((rc = ensure_all(ctx, {{ctx->ir_need, (n + 1) * 8}, {ctx->ir_off, (n + 1) * 8}}))) return rc;
-        A.ir = ctx->ir; A.ir_need = (uint64_t *)ctx->ir_need.p;        // (a non-null ir_need: intron retention is on)
+        if ((rc = ensure_all(ctx, {{ctx->ir_need, n + 1}, {ctx->ir_off, n + 1}}))) return rc;
+        A.ir = ctx->ir; A.ir_need = ctx->ir_need.data();        // (a non-null ir_need: intron retention is on)
     }
-    A.meta = prm->meta ? 1u : 0u; A.nspecies = ctx->nspecies; A.species_chrom_off = (const uint32_t *)ctx->species_chrom_off.p;
-    A.next_n = (uint32_t *)((unsigned long long *)ctx->stats.p + 6);
+    A.meta = prm->meta ? 1u : 0u; A.nspecies = ctx->nspecies; A.species_chrom_off = ctx->species_chrom_off.data();
+    A.next_n = ctx->stats.view<uint32_t>(NS_STAT_NEXT_N * sizeof(unsigned long long));
     return NS_OK;
 }
 
@@ -3744,8 +3743,8 @@ static int write_images(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, 
         k_errlen<<<dim3((unsigned)((n + NS_WPB - 1) / NS_WPB)), dim3(64 * NS_WPB), 0, st>>>(A);
         HIPCHK(hipGetLastError());
     }
-    if ((rc = scan_u64(ctx, A.rec_len, A.rec_off, n + 1))) return rc;
-    if (prm->emit_errlog && (rc = scan_u64(ctx, A.err_len, A.err_off, n + 1))) return rc;
+    if ((rc = scan_sum(ctx, A.rec_len, A.rec_off, n + 1))) return rc;
+    if (prm->emit_errlog && (rc = scan_sum(ctx, A.err_len, A.err_off, n + 1))) return rc;
     if ((rc = prm->emit_errlog ? read_small(ctx, st, &info->record_bytes, A.rec_off + n, 8, &info->errlog_bytes, A.err_off + n, 8)
                                : read_small(ctx, st, &info->record_bytes, A.rec_off + n, 8))) return rc;
     // result slot of this batch: the other one while the last batch is still being copied out (ns_sink_write); a slot is reused
@@ -3756,18 +3755,18 @@ static int write_images(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, 
         if (ctx->io->slot_busy(*slot)) *slot ^= 1;
         ctx->io->wait_slot(*slot);
     }
-    if (write_rec && (rc = ensure_all(ctx, {{ctx->rec_slot[*slot], (size_t)info->record_bytes + 64}, {ctx->err_slot[*slot], (size_t)info->errlog_bytes + 64}})))
+    if (write_rec && (rc = ensure_all(ctx, {{ctx->rec_slot[*slot], (size_t)info->record_bytes, 64}, {ctx->err_slot[*slot], (size_t)info->errlog_bytes, 64}})))
         return rc;
     if (prm->emit_records == 0) info->errlog_bytes = 0;       // (no records: no error-profile image either; NS_EMIT_SIZES keeps the size)
-    A.records = (uint8_t *)ctx->rec_slot[*slot].p; A.errlog = (uint8_t *)ctx->err_slot[*slot].p;
+    A.records = ctx->rec_slot[*slot].data(); A.errlog = ctx->err_slot[*slot].data();
     A.cls = nullptr;
     if (write_rec && prm->fastq && prm->kind != NS_KIND_UNALIGNED) {      // class words: k_materialise -> k_qualities (cls_word0)
         const size_t per_read = prm->chimeric ? 2u * (2u * NS_MAX_SEG - 1u) : 2u;          // cls_per_read
-        if ((rc = ensure(ctx, ctx->cls, (((size_t)info->record_bytes >> 4) + per_read * (n + 1) + 64) * 4))) return rc;
-        A.cls = (uint32_t *)ctx->cls.p;
+        if ((rc = ensure(ctx, ctx->cls, ((size_t)info->record_bytes >> 4) + per_read * (n + 1) + 64))) return rc;
+        A.cls = ctx->cls.data();
     }
-    const uint64_t max_unaligned = prm->kind == NS_KIND_UNALIGNED ? pl.stats[1] : 0;      // emitted bases of the batch (k_chain): bounds the dense kernel's grid
-    HIPCHK(hipEventRecord(ctx->evt[5], st));
+    const uint64_t max_unaligned = prm->kind == NS_KIND_UNALIGNED ? pl.stats[NS_STAT_BASES] : 0;      // emitted bases of the batch (k_chain): bounds the dense kernel's grid
+    HIPCHK(hipEventRecord(ctx->evt[EV_NAMES_BEGIN], st));
     // names + framing on the second stream, next to the record kernel (round 5: also next to the second record pass of -k: 0.37 ms per
     // 950 000 reads on the main stream)
     if (write_rec) {
@@ -3777,7 +3776,7 @@ static int write_images(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, 
     k_names<<<dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, write_rec ? ctx->stream2 : st>>>(A);
     HIPCHK(hipGetLastError());
     if (write_rec) HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
-    HIPCHK(hipEventRecord(ctx->evt[6], st));
+    HIPCHK(hipEventRecord(ctx->evt[EV_RECORD_BEGIN], st));
     if (A.hp) {          // second record pass of -k: the scratch read + its homopolymer edits -> the record
         if (write_rec && (rc = launch_materialise(ctx, A, n, prm->fastq != 0, order, MAT_HP_FINAL))) return rc;
         k_hp_report<<<dim3((unsigned)((pl.tot_pieces + 255) / 256)), dim3(256), 0, st>>>(A, pl.tot_pieces);      // the pieces report their emitted
@@ -3787,15 +3786,15 @@ static int write_images(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, 
         if ((rc = launch_materialise(ctx, A, n, prm->fastq != 0, order, MAT_REF, max_unaligned))) return rc;
     }
     if (write_rec) HIPCHK(hipStreamWaitEvent(st, ctx->ev_join, 0));
-    HIPCHK(hipEventRecord(ctx->evt[7], st));
+    HIPCHK(hipEventRecord(ctx->evt[EV_ERRLOG_BEGIN], st));
     if (prm->emit_errlog && write_rec) {
         // the block buffer of the kernel: the small one (six wavefronts per SIMD instead of four) when 64 average rows of this batch fit it
-        const uint64_t rows = pl.stats[3] ? pl.stats[3] : 1;
+        const uint64_t rows = pl.stats[NS_STAT_EVENTS] ? pl.stats[NS_STAT_EVENTS] : 1;
         if ((info->errlog_bytes / rows + 5) * 64 <= NS_ERR_BUF_SMALL) k_errlog<NS_ERR_BUF_SMALL><<<dim3((unsigned)n), dim3(64), 0, st>>>(A);
         else k_errlog<NS_ERR_BUF_LARGE><<<dim3((unsigned)n), dim3(64), 0, st>>>(A);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(ctx->evt[8], st));
+    HIPCHK(hipEventRecord(ctx->evt[EV_CALL_END], st));
     return NS_OK;
 }
 
@@ -3803,16 +3802,13 @@ static int write_images(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, 
 static int finish_call(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, const Plan &pl, int slot) {
     float ms = 0;
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipEventElapsedTime(&ms, ctx->evt[0], ctx->evt[8])); info->ms_total = ms;
-    HIPCHK(hipEventElapsedTime(&ms, ctx->evt[1], ctx->evt[2])); info->ms_kernel[NS_K_LENGTHS] = ms;   // nseg + lengths + scans + sort
-    HIPCHK(hipEventElapsedTime(&ms, ctx->evt[5], ctx->evt[6])); info->ms_kernel[NS_K_SCAN] = ms;      // names/framing
-    HIPCHK(hipEventElapsedTime(&ms, ctx->evt[6], ctx->evt[7])); info->ms_kernel[NS_K_MATERIALISE] = ms;
-    HIPCHK(hipEventElapsedTime(&ms, ctx->evt[7], ctx->evt[8])); info->ms_kernel[NS_K_ERRLOG] = ms;
-    if (ctx->rec_timed) { HIPCHK(hipEventElapsedTime(&ms, ctx->evt[12], ctx->evt[13])); info->ms_kernel[NS_K_RECORD_KERNEL] = ms; }
+    HIPCHK(hipEventElapsedTime(&ms, ctx->evt[EV_CALL_BEGIN], ctx->evt[EV_CALL_END])); info->ms_total = ms;
+    for (const auto &t : EVT_TIMED) { HIPCHK(hipEventElapsedTime(&ms, ctx->evt[t.from], ctx->evt[t.to])); info->ms_kernel[t.slot] = ms; }
+    if (ctx->rec_timed) { HIPCHK(hipEventElapsedTime(&ms, ctx->evt[EV_RECKERNEL_BEGIN], ctx->evt[EV_RECKERNEL_END])); info->ms_kernel[NS_K_RECORD_KERNEL] = ms; }
     info->ms_kernel[NS_K_HP] = pl.ms_hp;
     info->n_reads = prm->n_reads; info->n_pieces = pl.tot_pieces; info->n_events = pl.tot_cap;
-    info->total_bases = pl.stats[1]; info->total_ref_bases = pl.stats[2]; info->events_used = pl.stats[3];
-    info->n_range_redraws = pl.stats[0] >> 40;
+    info->total_bases = pl.stats[NS_STAT_BASES]; info->total_ref_bases = pl.stats[NS_STAT_REF_BASES]; info->events_used = pl.stats[NS_STAT_EVENTS];
+    info->n_range_redraws = pl.stats[NS_STAT_OVER] >> NS_RANGE_SHIFT;
     info->spliced_bytes = ctx->spliced_bytes;
     ctx->last = *info;
     if (prm->emit_records != 1u) { ctx->last.record_bytes = 0; ctx->last.errlog_bytes = 0; }      // nothing to copy out
@@ -3826,7 +3822,7 @@ static void lend_tables(const ns_ctx *ctx, ns_ctx *c) {
     c->m = ctx->m; c->ref = ctx->ref; c->has_model = ctx->has_model; c->has_ref = ctx->has_ref;
     c->cap_rate = ctx->cap_rate; c->ref_nbases = ctx->ref_nbases;
     c->lds_tables = ctx->lds_tables; c->lds_bytes = ctx->lds_bytes; c->coop_ok = ctx->coop_ok; c->chain_block = ctx->chain_block;
-    c->nspecies = ctx->nspecies; c->species_chrom_off = ctx->species_chrom_off;      // (DevBuf by value: not freed by the companion)
+    c->nspecies = ctx->nspecies; c->species_chrom_off = ctx->species_chrom_off;      // (DevBuf by value: the companion never allocated it, so never frees it)
     c->tx = ctx->tx; c->has_trx = ctx->has_trx;
     c->has_abun = false; c->has_inflated = false; c->has_ir = false;                   // (aligned workers only: S:814-1040, 1156-1192)
 }
@@ -3846,7 +3842,7 @@ int ns_generate(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info) {
     GenArgs A;
     if ((rc = batch_args(ctx, prm, n, A))) return rc;
     ctx->rec_timed = false;
-    HIPCHK(hipEventRecord(ctx->evt[0], ctx->stream));
+    HIPCHK(hipEventRecord(ctx->evt[EV_CALL_BEGIN], ctx->stream));
     // the planner of the mode; each runs the -k stage and the intron-retention splice in its own order: the metagenome passes run -k per
     // pass and once more at the end, transcriptome batches splice and then run -k, genome batches run both in every hp_round
     const bool meta_al = prm->meta && prm->kind != NS_KIND_UNALIGNED;       // aligned or --perfect worker of simulation_aligned_metagenome
@@ -3855,7 +3851,7 @@ int ns_generate(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info) {
     rc = meta_al ? meta_passes(ctx, prm, info, A, pl) : trx_tab ? trx_passes(ctx, prm, info, A, pl) : genome_passes(ctx, prm, info, A, pl);
     if (rc) return rc;
     int slot = 0;
-    const uint32_t *order = (meta_al || trx_tab) ? nullptr : (const uint32_t *)ctx->order.p;
+    const uint32_t *order = (meta_al || trx_tab) ? nullptr : ctx->order.data();
     if ((rc = write_images(ctx, prm, info, A, pl, meta_al, order, &slot))) return rc;
     return finish_call(ctx, prm, info, pl, slot);
 }
@@ -3929,13 +3925,13 @@ int ns_generate_step(ns_ctx *ctx, const ns_params *aligned, const ns_params *una
 static int result_buf(ns_ctx *ctx, int which, const void **p, uint64_t *size) {
     const ns_batch_info &b = ctx->last;
     switch (which) {
-        case NS_BUF_RECORDS: *p = ctx->rec_slot[ctx->slot].p; *size = b.record_bytes; return NS_OK;
-        case NS_BUF_READS: *p = ctx->reads.p; *size = b.n_reads * sizeof(ns_read); return NS_OK;
-        case NS_BUF_PIECES: *p = ctx->pieces.p; *size = b.n_pieces * sizeof(ns_piece); return NS_OK;
-        case NS_BUF_EVENTS: *p = ctx->events.p; *size = b.n_events * sizeof(ns_event); return NS_OK;
-        case NS_BUF_ERRLOG: *p = ctx->err_slot[ctx->slot].p; *size = b.errlog_bytes; return NS_OK;
-        case NS_BUF_POLYA: *p = ctx->polya.p; *size = ctx->polya.p ? b.n_reads * 2 : 0; return NS_OK;
-        case NS_BUF_SPLICED: *p = ctx->spliced.p; *size = ctx->spliced_bytes; return NS_OK;
+        case NS_BUF_RECORDS: *p = ctx->rec_slot[ctx->slot].data(); *size = b.record_bytes; return NS_OK;
+        case NS_BUF_READS: *p = ctx->reads.data(); *size = b.n_reads * sizeof(ns_read); return NS_OK;
+        case NS_BUF_PIECES: *p = ctx->pieces.data(); *size = b.n_pieces * sizeof(ns_piece); return NS_OK;
+        case NS_BUF_EVENTS: *p = ctx->events.data(); *size = b.n_events * sizeof(ns_event); return NS_OK;
+        case NS_BUF_ERRLOG: *p = ctx->err_slot[ctx->slot].data(); *size = b.errlog_bytes; return NS_OK;
+        case NS_BUF_POLYA: *p = ctx->polya.data(); *size = ctx->polya.data() ? b.n_reads * 2 : 0; return NS_OK;
+        case NS_BUF_SPLICED: *p = ctx->spliced.data(); *size = ctx->spliced_bytes; return NS_OK;
         default: return NS_EINVAL;
     }
 }
@@ -4042,8 +4038,8 @@ int ns_record_offsets(ns_ctx *ctx, const uint64_t *read_index, uint32_t n, uint6
     for (uint32_t i0 = 0; i0 < n; i0 += 64) {
         const uint32_t m = std::min<uint32_t>(64u, n - i0);
         for (uint32_t i = 0; i < m; ++i) {
-            HIPCHK(hipMemcpyAsync(slots + i, (const uint64_t *)ctx->rec_off.p + read_index[i0 + i], 8, hipMemcpyDeviceToHost, ctx->stream));
-            if (with_err) HIPCHK(hipMemcpyAsync(slots + 64 + i, (const uint64_t *)ctx->err_off.p + read_index[i0 + i], 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipMemcpyAsync(slots + i, ctx->rec_off.data() + read_index[i0 + i], 8, hipMemcpyDeviceToHost, ctx->stream));
+            if (with_err) HIPCHK(hipMemcpyAsync(slots + 64 + i, ctx->err_off.data() + read_index[i0 + i], 8, hipMemcpyDeviceToHost, ctx->stream));
         }
         HIPCHK(hipStreamSynchronize(ctx->stream));
         for (uint32_t i = 0; i < m; ++i) { rec_off[i0 + i] = slots[i]; if (err_off) err_off[i0 + i] = with_err ? slots[64 + i] : 0; }
@@ -4119,7 +4115,7 @@ static int histograms(ns_ctx *ctx, const uint8_t *cs, const uint8_t *qry, bool m
     if (e == hipSuccess) e = hipMemcpyAsync(d_off, aln_off, ((size_t)n_aln + 1) * 8, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_small, 0, n_small * 8, st);
     if (e == hipSuccess && d_m2) e = hipMemsetAsync(d_m2, 0, (size_t)cap * cap * 8, st);
-    if (e == hipSuccess) e = hipEventRecord(ctx->evt[14], st);
+    if (e == hipSuccess) e = hipEventRecord(ctx->evt[EV_HIST_BEGIN], st);
     // Alignments of 1 kb .. 100 kb on neighbouring lanes diverge like the thread-per-read chain did before its length sort: the walks are
     // visited by descending length of their cs strings (the counts are sums: any order gives the same tables).
     uint32_t *d_order = nullptr;
@@ -4130,9 +4126,10 @@ static int histograms(ns_ctx *ctx, const uint8_t *cs, const uint8_t *qry, bool m
             uint32_t *key = (uint32_t *)d_key, *idx = key + n_aln, *key2 = idx + n_aln, *idx2 = key2 + n_aln;
             k_cs_len<<<dim3((n_aln + 255u) / 256u), dim3(256), 0, st>>>((const uint64_t *)d_off, n_aln, key, idx);
             e = hipGetLastError();
-            if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tmp, key, key2, idx, idx2, (int)n_aln, 0, 32, st);
+            auto sort = [&](void *t) { return hipcub::DeviceRadixSort::SortPairsDescending(t, tmp, key, key2, idx, idx2, (int)n_aln, 0, 32, st); };
+            if (e == hipSuccess) e = sort(nullptr);               // (the size of its temporary storage)
             if (e == hipSuccess) e = hipMalloc(&d_tmp, tmp + 16);
-            if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairsDescending(d_tmp, tmp, key, key2, idx, idx2, (int)n_aln, 0, 32, st);
+            if (e == hipSuccess) e = sort(d_tmp);
             d_order = idx2;
         }
     }
@@ -4143,13 +4140,13 @@ static int histograms(ns_ctx *ctx, const uint8_t *cs, const uint8_t *qry, bool m
         k_cs_hist<<<dim3((n_aln + 255u) / 256u), dim3(256), 0, st>>>((const uint8_t *)d_cs, (const uint64_t *)d_off, n_aln, H, d_order, (const uint8_t *)d_qry);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipEventRecord(ctx->evt[15], st);
+    if (e == hipSuccess) e = hipEventRecord(ctx->evt[EV_HIST_END], st);
     std::vector<unsigned long long> small(n_small);
     if (e == hipSuccess) e = hipMemcpyAsync(small.data(), d_small, n_small * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && d_m2) e = hipMemcpyAsync(m2_host, d_m2, (size_t)cap * cap * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ctx->evt[14], ctx->evt[15]);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ctx->evt[EV_HIST_BEGIN], ctx->evt[EV_HIST_END]);
     release();
     if (e != hipSuccess) return fail(ctx, NS_EHIP, std::string("ns_cs_histograms: ") + hipGetErrorString(e));
     for (int w = 0; w < 5; ++w) for (int v = 0; v <= 1000; ++v) h->dic[w][v] = small[(size_t)w * 1001 + v];

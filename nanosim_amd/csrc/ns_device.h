@@ -5,6 +5,27 @@
 #include "ns_rng.h"
 #include "../../include/nanosim_amd.h"
 
+// The counters of a worker call (GenArgs::stats, ns_ctx::stats): NS_STAT_COUNT 64-bit words, then NS_STATS_WAYS copies of them that the chain
+// kernels add to (one set of counters serialises their atomics) and k_stats_fold sums into the first NS_STAT_MAX_READ + 1 words
+enum NsStat : uint32_t {
+    NS_STAT_OVER,         // reads that outgrew their event capacity (low NS_RANGE_SHIFT bits: NS_OVER_MASK) | attempts dropped for the
+                          // event-record range << NS_RANGE_SHIFT (ns_batch_info.n_range_redraws)
+    NS_STAT_BASES,        // emitted bases
+    NS_STAT_REF_BASES,    // reference bases
+    NS_STAT_EVENTS,       // events used
+    NS_STAT_MAX_READ,     // longest accepted read (unaligned batches): a maximum, not a sum
+    NS_STAT_HP_FAILED,    // -k: reads that failed the final length check
+    NS_STAT_NEXT_N,       // length of the next pass list: its low 32 bits are GenArgs::next_n
+    NS_STAT_HP_OVER,      // -k: pieces that outgrew their event capacity
+    NS_STAT_COUNT
+};
+#define NS_RANGE_SHIFT 40
+#define NS_OVER_MASK ((1ull << NS_RANGE_SHIFT) - 1)
+#define NS_STATS_WAYS 64u    // copies of the chain counters (k_chain -> k_stats_fold); == the threads of k_stats_fold
+#define NS_STATS_BYTES ((NS_STAT_COUNT + NS_STAT_COUNT * NS_STATS_WAYS) * sizeof(unsigned long long))
+// copy `way` of the counters
+__host__ __device__ inline unsigned long long *ns_stats_way(unsigned long long *stats, uint32_t way) { return stats + NS_STAT_COUNT + NS_STAT_COUNT * way; }
+
 struct ChainTab {                 // offsets are in 8-byte words from the start of the blob (ns_pack.h describes the image)
     uint32_t n_words;
     uint32_t trans;               // 21 thresholds: rows start,mis,ins,del,mis0,ins0,del0 x (a, a+b, -)
