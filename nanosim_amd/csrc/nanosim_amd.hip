@@ -1203,10 +1203,10 @@ __device__ __forceinline__ uint64_t hp_ev_slot(const GenArgs &A, uint64_t pos, u
 #endif
 template <bool FASTQ, int MODE>
 __global__ void __launch_bounds__(64, MODE == MAT_HP_FINAL ? NS_MAT_WAVES_FINAL : NS_MAT_WAVES)
-k_materialise(GenArgs A, const uint32_t *ev_word, uint32_t dbg, SlowQueue sq, const uint32_t *order) {
+k_materialise(GenArgs A, uint32_t dbg, SlowQueue sq, const uint32_t *order) {
     constexpr bool CLSOUT = FASTQ && MODE != MAT_HP_SCRATCH;           // FASTQ: the bases here, the quality line in k_qualities
     constexpr uint32_t TC = MODE == MAT_HP_FINAL ? NS_TILE_CHUNKS_FINAL : NS_TILE_CHUNKS;
-    __shared__ TileLds7<TC> T;
+    __shared__ TileLds<TC> T;
     const uint32_t lane = threadIdx.x;
     const uint64_t slot = blockIdx.x;
     if (slot >= A.prm.n_reads) return;
@@ -1223,8 +1223,8 @@ k_materialise(GenArgs A, const uint32_t *ev_word, uint32_t dbg, SlowQueue sq, co
         ro.seq = A.scr + uni64(A.scr_off[r]); ro.qual = nullptr; ro.reversed = false; ro.uracil = false;
         uint32_t q = 0;
         for (uint32_t pi = 0; pi < rd.n_pieces; ++pi) {
-            const PieceCtx pc = load_piece_uniform(A.events, A.ref, A.pieces[rd.piece_off + pi], pi, ev_word);
-            materialise_piece7<FASTQ, MODE, TC>(A.m, A.ref, T, ro, key, a, pc, q, lane, dbg, sq, (uint32_t)r, pi, nullptr);
+            const PieceCtx pc = load_piece_uniform(A.events, A.ref, A.pieces[rd.piece_off + pi], pi);
+            materialise_piece<FASTQ, MODE, TC>(A.m, A.ref, T, ro, key, a, pc, q, lane, dbg, sq, (uint32_t)r, pi, nullptr);
             q += pc.out_len;
         }
         return;
@@ -1232,7 +1232,7 @@ k_materialise(GenArgs A, const uint32_t *ev_word, uint32_t dbg, SlowQueue sq, co
 #ifdef NS_ABLATE
     if (!(dbg & 8))
 #endif
-    emit_head_tail(A.m, ro, key, a, rd.head, rd.tail, lane);                                                              // S:1426-1427
+    emit_head_tail(ro, key, a, rd.head, rd.tail, lane);                                                                   // S:1426-1427
     uint32_t q = rd.head;
     uint64_t q_in = MODE == MAT_HP_FINAL ? uni64(A.scr_off[r]) : 0;
     for (uint32_t pi = 0; pi < rd.n_pieces; ++pi) {
@@ -1248,13 +1248,13 @@ k_materialise(GenArgs A, const uint32_t *ev_word, uint32_t dbg, SlowQueue sq, co
             pc.chrom_base = (uint64_t)((uintptr_t)A.scr - (uintptr_t)A.ref.bases) + q_in; pc.chrom_len = ~0ull; pc.pos = 0;
             pc.sid = pc.kind ? NS_GAP_SEG + (pi >> 1) : (pi >> 1);
             q_in += pc.ref_len;
-        } else pc = load_piece_uniform(A.events, A.ref, A.pieces[rd.piece_off + pi], pi, ev_word);
-        materialise_piece7<FASTQ, MODE, TC>(A.m, A.ref, T, ro, key, a, pc, q, lane, dbg, sq, (uint32_t)r, pi, CLSOUT ? cls + (q >> 4) + 2u * pi : nullptr);
+        } else pc = load_piece_uniform(A.events, A.ref, A.pieces[rd.piece_off + pi], pi);
+        materialise_piece<FASTQ, MODE, TC>(A.m, A.ref, T, ro, key, a, pc, q, lane, dbg, sq, (uint32_t)r, pi, CLSOUT ? cls + (q >> 4) + 2u * pi : nullptr);
         q += pc.out_len;                                 // (-k: k_hp_report files the emitted length in the piece once the record kernels are done)
     }
     if (A.polya) {                                                                          // transcriptome: polyA tail (S:1224-1225)
         const uint32_t pl = uni(A.polya[r]);
-        if (pl) emit_polya(A.m, ro, key, a, q, pl, rd.head, rd.tail, lane);
+        if (pl) emit_polya(ro, q, pl, lane);
     }
 }
 
@@ -1303,8 +1303,6 @@ __global__ void __launch_bounds__(256) k_dense_plan(GenArgs A, uint32_t *cnt) {
     if (r < A.prm.n_reads) { const ns_read rd = A.reads[r]; c = rd.flags ? 0u : max(1u, (rd.seq_len + NS_DENSE_SEG - 1u) / NS_DENSE_SEG); }
     cnt[r] = c;
 }
-// (FASTQ = true draws the qualities in place through the per-value look-up; launch_materialise uses <false> + k_qualities since round 3)
-template <bool FASTQ>
 __global__ void __launch_bounds__(64) k_materialise_dense(GenArgs A, const uint32_t *__restrict__ seg_off) {
     __shared__ DenseLds S;
     const uint32_t lane = threadIdx.x;
@@ -1315,9 +1313,9 @@ __global__ void __launch_bounds__(64) k_materialise_dense(GenArgs A, const uint3
     const uint64_t r = uni(lo);
     const uint32_t seg = uni(w - seg_off[lo]);
     ns_read rd; ns_key key; ReadOut ro;
-    if (!load_read_uniform(A, r, FASTQ, rd, key, ro)) return;
+    if (!load_read_uniform(A, r, false, rd, key, ro)) return;
     const uint32_t a = rd.attempts;
-    if (seg == 0) emit_head_tail(A.m, ro, key, a, rd.head, rd.tail, lane);
+    if (seg == 0) emit_head_tail(ro, key, a, rd.head, rd.tail, lane);
     uint32_t q = rd.head;
     for (uint32_t pi = 0; pi < rd.n_pieces; ++pi) {
         const PieceCtx pc = load_piece_uniform(A.events, A.ref, A.pieces[rd.piece_off + pi], pi);
@@ -1326,7 +1324,7 @@ __global__ void __launch_bounds__(64) k_materialise_dense(GenArgs A, const uint3
         if (p_hi > s_lo && p_lo < s_hi) {
             const uint32_t m_lo = (uint32_t)(max(s_lo, p_lo) - p_lo), m_hi = (uint32_t)(min(s_hi, p_hi) - p_lo);
             if (A.dbg & 16384u) slow_piece_range(A.m, A.ref, ro, key, a, pc, q, m_lo, m_hi, lane);      // (profiling: the per-byte path)
-            else dense_piece<FASTQ>(A.m, A.ref, S, ro, key, a, pc, q, m_lo, m_hi, lane);
+            else dense_piece(A.m, A.ref, S, ro, key, a, pc, q, m_lo, m_hi, lane);
         }
         q += pc.out_len;
     }
@@ -1391,7 +1389,7 @@ __global__ void __launch_bounds__(64) k_materialise_slow_hpf(GenArgs A, SlowQueu
                 else {
                     const ns_event e = ev[j - 1];
                     const uint32_t len = ns_ev_len(e.info), ty = ns_ev_type(e.info), os = ev_out_start(e), d = m - os, w = wd[j - 1];
-                    const uint32_t pl = ty == NS_DEL ? 0u : len;
+                    const uint32_t pl = ev_letters(ty, len);
                     if (d < pl) {
                         if (ty == NS_INS) {                      // inserted letters: 2-bit fields of the edit's word; letter 0 may be the run's first mismatch
                             b = bases_atcg((w >> (2 * (d & 15))) & 3u);
@@ -1403,7 +1401,7 @@ __global__ void __launch_bounds__(64) k_materialise_slow_hpf(GenArgs A, SlowQueu
                             cls_bits = (w & 1u) ? NS_CLS_MIS_BIT : (c & (NS_CLS_MIS_BIT | NS_CLS_INS_BIT));
                         }
                     } else {
-                        const uint32_t c = src[e.pos + (ty == NS_INS ? 0u : len) + (d - pl)];
+                        const uint32_t c = src[ev_resume(e.pos, ty, len) + (d - pl)];
                         b = c & ~(NS_CLS_MIS_BIT | NS_CLS_INS_BIT); cls_bits = c & (NS_CLS_MIS_BIT | NS_CLS_INS_BIT);
                     }
                 }
@@ -2675,7 +2673,7 @@ static int launch_materialise(ns_ctx *ctx, const GenArgs &A, size_t n, bool fast
         if (bound > 0x7fffffffull) return fail(ctx, NS_EINVAL, "unaligned batch too large for one launch of the record kernel (split it)");
         // FASTQ: the bases here, the quality lines in k_qualities (one class for the whole read, S:1521: no class words) — drawn inside the
         // dense kernel they came through the per-value look-up in global memory: 1.25 against 0.7 ms per 50 000 reads
-        k_materialise_dense<false><<<dim3((unsigned)bound), dim3(64), 0, st>>>(A, seg_off);
+        k_materialise_dense<<<dim3((unsigned)bound), dim3(64), 0, st>>>(A, seg_off);
         HIPCHK(hipGetLastError());
         if (fastq) {
             k_qualities<false><<<dim3((unsigned)((n + NS_MATQ_WAVES - 1) / NS_MATQ_WAVES)), dim3(64 * NS_MATQ_WAVES), 0, st>>>(A, nullptr);
@@ -2703,7 +2701,7 @@ static int launch_materialise(ns_ctx *ctx, const GenArgs &A, size_t n, bool fast
         if (round == 0) HIPCHK(hipEventRecord(ctx->evt[EV_RECKERNEL_BEGIN], st));            // the record kernel itself (ns_batch_info.ms_kernel[NS_K_RECORD_KERNEL])
         by_fastq_mode(fastq, mode, [&](auto fq, auto md) {      // (reads in order_b's order: from the reference, and the FASTQ second pass of -k)
             constexpr bool FQ = decltype(fq)::value; constexpr int MD = decltype(md)::value;
-            k_materialise<FQ, MD><<<grid_1, blk_1, 0, st>>>(A, nullptr, ctx->knob.dbg, sq, (MD == MAT_REF || (FQ && MD == MAT_HP_FINAL)) ? order_b : nullptr);
+            k_materialise<FQ, MD><<<grid_1, blk_1, 0, st>>>(A, ctx->knob.dbg, sq, (MD == MAT_REF || (FQ && MD == MAT_HP_FINAL)) ? order_b : nullptr);
         });
         HIPCHK(hipGetLastError());
         if (round == 0) { HIPCHK(hipEventRecord(ctx->evt[EV_RECKERNEL_END], st)); ctx->rec_timed = true; }

@@ -1,5 +1,5 @@
 // ns_materialise.h — the record kernels' device code: one read per wavefront, tiles of <= 2 KB of output whose 16-byte chunks are
-// aligned in the destination.  Per tile (materialise_piece7 below has the details):
+// aligned in the destination.  Per tile (materialise_piece below has the details):
 //   1. the events that start inside the tile (<= 63; lane = event, prefetched with their letter words) are staged in LDS;
 //   2. lane per 16-byte chunk: histogram + wavefront prefix maximum -> the event in force at the chunk's first byte; the bytes copied
 //      under it come with ONE unaligned 16-byte global load straight from the source (no source tile in LDS: neighbouring lanes hit the
@@ -18,9 +18,7 @@
 #ifndef NS_TILE_CHUNKS
 #define NS_TILE_CHUNKS 2u                                  // 16-byte chunks per lane and tile
 #endif
-#define T_OUT (1024u * NS_TILE_CHUNKS)
 #define T_EV 64u            // events staged per tile: slot 0 = the event in force at the tile start, slots 1..63 = lanes 0..62
-#define T_DUMP (T_OUT + 16u)
 // quality class of an emitted base travels in two spare bits of its ASCII code (A 41, C 43, G 47, T 54: bits 3 and 5 are free)
 // until the qualities are drawn: bit 3 = substituted ('mis'), bit 5 = inserted ('ins', the base is in lower case)
 #define NS_CLS_MIS_BIT 0x08u
@@ -106,9 +104,11 @@ __device__ __forceinline__ void reverse_bytes(uint64_t &lo, uint64_t &hi, uint32
 __device__ __forceinline__ uint64_t complement8(uint64_t x) {              // A<->T, C<->G on 8 packed ASCII bases
     return x ^ 0x1515151515151515ull ^ (((x >> 1) & 0x0101010101010101ull) * 0x11ull);
 }
-// `count` bytes whose pre-revcomp coordinates are [q0, q0+count), byte i in bits 8i of (lo,hi)
+// `count` bytes whose pre-revcomp coordinates are [q0, q0+count), byte i in bits 8i of (lo,hi).  The quality half (ro.qual, with qual_draw
+// below) runs on the per-byte paths only — slow_piece_range and k_materialise_slow_hpf; every other caller writes bases, and k_qualities
+// writes their quality line from the class words
 __device__ __forceinline__ void store_chunk(const ReadOut &ro, uint32_t q0, uint32_t count, uint64_t lo, uint64_t hi,
-                                            uint64_t qlo, uint64_t qhi, bool ascii_quals = false) {
+                                            uint64_t qlo, uint64_t qhi) {
     uint32_t o0 = q0;
     if (ro.reversed) {
         lo = complement8(lo); hi = complement8(hi);
@@ -118,13 +118,16 @@ __device__ __forceinline__ void store_chunk(const ReadOut &ro, uint32_t q0, uint
     if (ro.uracil) { lo = t_to_u8(lo); hi = t_to_u8(hi); }
     store16(ro.seq + o0, count, lo, hi);
     if (ro.qual) {
-        if (!ascii_quals) { qlo += 0x2121212121212121ull; qhi += 0x2121212121212121ull; }        // chr(q + 33), S:1441
+        qlo += 0x2121212121212121ull; qhi += 0x2121212121212121ull;         // chr(q + 33), S:1441
         if (ro.reversed) reverse_bytes(qlo, qhi, count);
         store16(ro.qual + o0, count, qlo, qhi);
     }
 }
-// the same in two steps: final bytes / record offset now, the store later (k_materialise keeps one chunk per lane pending so
-// that the store is issued behind the next tile's loads and never sits in front of a load the wave waits for)
+// The chunks of the tiled kernel (materialise_piece, step 4: prep_chunk and flush_chunk back to back).  ro.qual is null there, so the
+// quality halves never run — but they are alive while the compiler optimises materialise_piece on its own, before it is inlined into
+// k_materialise, and without them (or with the two folded into one function) the vectoriser pairs other values of the two chunks of a lane
+// and the instruction streams of k_materialise<., MAT_REF> and <., MAT_HP_SCRATCH> change.  They go with the next change of that kernel
+// that is timed on a GPU.
 struct PendingChunk { uint64_t lo, hi, qlo, qhi; uint32_t o0, count; };
 __device__ __forceinline__ PendingChunk prep_chunk(const ReadOut &ro, uint32_t q0, uint32_t count, uint64_t lo, uint64_t hi,
                                                    uint64_t qlo, uint64_t qhi) {
@@ -173,45 +176,35 @@ __device__ __forceinline__ uint32_t qual_draw(QualDraw &qd, const DevModel &m, i
     return qual_value_lut(m.qual_thr + cls * NS_QUAL_LEVELS, m.qual_lut + cls * 1024, h);
 }
 
-// head / tail: uniform bases (S:1426-1427) + 'ht' qualities (S:1421-1423).  One Philox block per 64 letters.  Both regions in
+// four inserted (or head / tail) letters from byte k of a letter word: 2-bit fields -> byte selectors -> "ATCG" (S:1990)
+__device__ __forceinline__ uint32_t ins_letters4(uint32_t word, uint32_t k) {
+    const uint32_t x = (word >> (8u * k)) & 0xffu, t = (x | x << 12) & 0x000f000fu;
+    return __builtin_amdgcn_perm(0u, 0x47435441u, (t | t << 6) & 0x03030303u);
+}
+
+// head / tail: uniform bases (S:1426-1427; their qualities: qualities_head_tail).  One Philox block per 64 letters.  Both regions in
 // one pass: lanes 0..31 take 16-letter groups of the head, lanes 32..63 of the tail (one Philox evaluation for the wavefront).
-__device__ inline void emit_head_tail(const DevModel &m, const ReadOut &ro, const ns_key &key, uint32_t a, uint32_t head, uint32_t tail,
-                                      uint32_t lane) {
+__device__ inline void emit_head_tail(const ReadOut &ro, const ns_key &key, uint32_t a, uint32_t head, uint32_t tail, uint32_t lane) {
     const bool is_tail = lane >= 32;
     const uint32_t len = is_tail ? tail : head, stream = is_tail ? ST_TAIL : ST_HEAD;
-    const uint32_t q_start = is_tail ? ro.seq_len - tail : 0u, hq_off = is_tail ? head : 0u;
+    const uint32_t q_start = is_tail ? ro.seq_len - tail : 0u;
     for (uint32_t i0 = (lane & 31u) * 16; i0 < len; i0 += 32 * 16) {
         const uint32_t count = min(16u, len - i0);
         u32x4 w = ns_draw(key, stream, 0, a, i0 >> 6, 0);
         const uint32_t word = ns_word(w, (i0 >> 4) & 3);
         uint32_t l4[4];
 #pragma unroll
-        for (uint32_t k = 0; k < 4; ++k) {                       // letters 4k..4k+3: 2-bit fields -> byte selectors -> "ATCG"
-            const uint32_t x = (word >> (8 * k)) & 0xffu;
-            const uint32_t t = (x | x << 12) & 0x000f000fu;
-            l4[k] = __builtin_amdgcn_perm(0u, 0x47435441u, (t | t << 6) & 0x03030303u);
-        }
-        uint64_t lo = (uint64_t)l4[0] | (uint64_t)l4[1] << 32, hi = (uint64_t)l4[2] | (uint64_t)l4[3] << 32, qlo = 0, qhi = 0;
-        if (ro.qual) {
-            QualDraw qd; qd.blk = 0xffffffffu;
-            for (uint32_t i = 0; i < count; ++i) put_byte(qlo, qhi, i, qual_draw(qd, m, NS_Q_HT, key, ST_HTQ, 0, a, hq_off + i0 + i));
-        }
-        store_chunk(ro, q_start + i0, count, lo, hi, qlo, qhi);
+        for (uint32_t k = 0; k < 4; ++k) l4[k] = ins_letters4(word, k);      // letters 4k..4k+3
+        const uint64_t lo = (uint64_t)l4[0] | (uint64_t)l4[1] << 32, hi = (uint64_t)l4[2] | (uint64_t)l4[3] << 32;
+        store_chunk(ro, q_start + i0, count, lo, hi, 0, 0);
     }
 }
 
-// polyA tail of a transcriptome read (S:1224-1225): `len` A's after the last piece; their qualities are the LAST `len` values of the
-// head/tail quality draw, in reverse order (S:1229-1231: popped from the end and appended)
-__device__ inline void emit_polya(const DevModel &m, const ReadOut &ro, const ns_key &key, uint32_t a, uint32_t q_start, uint32_t len,
-                                  uint32_t head, uint32_t tail, uint32_t lane) {
+// polyA tail of a transcriptome read (S:1224-1225): `len` A's after the last piece
+__device__ inline void emit_polya(const ReadOut &ro, uint32_t q_start, uint32_t len, uint32_t lane) {
     for (uint32_t i0 = lane * 16; i0 < len; i0 += 64 * 16) {
         const uint32_t count = min(16u, len - i0);
-        uint64_t qlo = 0, qhi = 0;
-        if (ro.qual) {
-            QualDraw qd; qd.blk = 0xffffffffu;
-            for (uint32_t i = 0; i < count; ++i) put_byte(qlo, qhi, i, qual_draw(qd, m, NS_Q_HT, key, ST_HTQ, 0, a, head + tail + len - 1 - (i0 + i)));
-        }
-        store_chunk(ro, q_start + i0, count, 0x4141414141414141ull, 0x4141414141414141ull, qlo, qhi);
+        store_chunk(ro, q_start + i0, count, 0x4141414141414141ull, 0x4141414141414141ull, 0, 0);
     }
 }
 
@@ -226,7 +219,8 @@ __device__ __forceinline__ void store_qual_chunk(const ReadOut &ro, uint32_t q0,
     }
     store16(ro.qual + o0, count, qlo, qhi);
 }
-// the quality half of emit_polya (k_qualities: the record kernel of a FASTQ batch writes the bases only)
+// the qualities of the polyA tail (k_qualities): the LAST `len` values of the head/tail quality draw, in reverse order (S:1229-1231: popped
+// from the end and appended)
 __device__ inline void emit_polya_quals(const DevModel &m, const ReadOut &ro, const ns_key &key, uint32_t a, uint32_t q_start, uint32_t len,
                                         uint32_t head, uint32_t tail, uint32_t lane) {
     for (uint32_t i0 = lane * 16; i0 < len; i0 += 64 * 16) {
@@ -256,24 +250,28 @@ struct Cursor {
     uint32_t next_out;
 };
 __device__ __forceinline__ uint32_t ev_out_start(const ns_event &e) { return (uint32_t)((int32_t)e.pos + ns_ev_shift(e.info)); }
+// what an event of type ty and length len does: the letters it emits (a deletion: none), and the segment position the copy resumes at
+// behind them (an insertion consumes nothing)
+__device__ __forceinline__ uint32_t ev_letters(uint32_t ty, uint32_t len) { return ty == NS_DEL ? 0u : len; }
+__device__ __forceinline__ uint32_t ev_resume(uint32_t pos, uint32_t ty, uint32_t len) { return pos + (ty == NS_INS ? 0u : len); }
+// number of events whose first output offset is <= m (= the event in force at m, plus one)
+__device__ __forceinline__ uint32_t events_up_to(const ns_event *ev, uint32_t n_ev, uint32_t m) {
+    uint32_t lo = 0, hi = n_ev;
+    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (ev_out_start(ev[mid]) <= m) lo = mid + 1; else hi = mid; }
+    return lo;
+}
 __device__ __forceinline__ void cursor_load(Cursor &c, const PieceCtx &pc) {
     if (c.j == 0) { c.cur_out = 0; c.cur_pl = 0; c.cur_type = 3; c.cur_pos = 0; c.cur_rp = 0; }
     else {
         ns_event e = pc.ev[c.j - 1];
         uint32_t len = ns_ev_len(e.info), ty = ns_ev_type(e.info);
         c.cur_out = ev_out_start(e); c.cur_type = ty; c.cur_pos = e.pos;
-        c.cur_pl = (ty == NS_DEL) ? 0 : len;
-        c.cur_rp = e.pos + ((ty == NS_INS) ? 0 : len);
+        c.cur_pl = ev_letters(ty, len); c.cur_rp = ev_resume(e.pos, ty, len);
     }
     c.next_out = (c.j < pc.n_ev) ? ev_out_start(pc.ev[c.j]) : 0xffffffffu;
 }
 __device__ __forceinline__ void cursor_seek(Cursor &c, const PieceCtx &pc, uint32_t m) {
-    uint32_t lo = 0, hi = pc.n_ev;
-    while (lo < hi) {
-        uint32_t mid = (lo + hi) >> 1;
-        if (ev_out_start(pc.ev[mid]) <= m) lo = mid + 1; else hi = mid;
-    }
-    c.j = lo;
+    c.j = events_up_to(pc.ev, pc.n_ev, m);
     cursor_load(c, pc);
 }
 NS_DEV uint8_t ref_base_at(const DevRef &ref, const PieceCtx &pc, uint32_t x) {
@@ -313,11 +311,10 @@ NS_DEV PieceCtx load_piece(const ns_event *events, const DevRef &ref, const ns_p
     return pc;
 }
 // the same for kernels in which the whole wavefront works on one piece: everything wave-uniform, held in SGPRs
-__device__ __forceinline__ PieceCtx load_piece_uniform(const ns_event *events, const DevRef &ref, const ns_piece &p, uint32_t pi,
-                                                       const uint32_t *ev_word = nullptr) {
+__device__ __forceinline__ PieceCtx load_piece_uniform(const ns_event *events, const DevRef &ref, const ns_piece &p, uint32_t pi) {
     PieceCtx pc;
     const uint64_t eo = uni64(p.ev_off);
-    pc.ev = events + eo; pc.wd = ev_word + eo; pc.n_ev = uni(p.n_ev); pc.out_len = uni(p.out_len); pc.ref_len = uni(p.ref_len);
+    pc.ev = events + eo; pc.wd = nullptr; pc.n_ev = uni(p.n_ev); pc.out_len = uni(p.out_len); pc.ref_len = uni(p.ref_len);
     const uint32_t chrom = uni(p.chrom);
     pc.chrom_base = uni64(ref.chrom_off[chrom]);
     pc.chrom_len = uni64(ref.chrom_off[chrom + 1]) - pc.chrom_base;
@@ -396,7 +393,6 @@ __device__ __forceinline__ void lds_put_bytes(LdsBytes d, uint32_t x0, uint32_t 
 #define NS_DENSE_TILE 1024u
 struct __align__(16) DenseLds { uint8_t out[NS_DENSE_TILE + 64]; };      // + a dump slot per lane for predicated-off letter stores
 
-template <bool FASTQ>
 __device__ inline void dense_piece(const DevModel &m, const DevRef &ref, DenseLds &S, const ReadOut &ro, const ns_key &key, uint32_t a,
                                    const PieceCtx &pc, uint32_t pq, uint32_t m_lo, uint32_t m_hi, uint32_t lane) {
     if (m_lo & 15u) { slow_piece_range(m, ref, ro, key, a, pc, pq, m_lo, m_hi, lane); return; }   // (the tiles below start on a multiple of 16)
@@ -404,11 +400,7 @@ __device__ inline void dense_piece(const DevModel &m, const DevRef &ref, DenseLd
     const uint8_t *seg0 = ref.bases + pc.chrom_base + pc.pos;
     const uint64_t lin = pc.chrom_len - pc.pos;               // segment positions below this lie before the origin of a circular chromosome
     uint32_t jb = 0;                                          // item in force at the tile start: the last one that starts at or before it
-    if (m_lo) {
-        uint32_t lo = 0, hi = pc.n_ev;                        // events with out_start <= m_lo
-        while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (ev_out_start(pc.ev[mid]) <= m_lo) lo = mid + 1; else hi = mid; }
-        jb = uni(lo);
-    }
+    if (m_lo) jb = uni(events_up_to(pc.ev, pc.n_ev, m_lo));
     for (uint32_t M0 = m_lo; M0 < m_hi; M0 += NS_DENSE_TILE) {
         const uint32_t M1 = min(M0 + NS_DENSE_TILE, m_hi);
         uint32_t seen = 0;                                    // items with out_start <= M1 met in this tile
@@ -421,7 +413,7 @@ __device__ inline void dense_piece(const DevModel &m, const DevRef &ref, DenseLd
                     const ns_event e = pc.ev[jj - 1];
                     const uint32_t len = ns_ev_len(e.info);
                     ty = ns_ev_type(e.info); os = ev_out_start(e); pos = e.pos;
-                    pl = ty == NS_DEL ? 0u : len; rp = e.pos + (ty == NS_INS ? 0u : len);
+                    pl = ev_letters(ty, len); rp = ev_resume(e.pos, ty, len);
                 }
                 if (jj < pc.n_ev) nxt = ev_out_start(pc.ev[jj]);
             }
@@ -463,9 +455,7 @@ __device__ inline void dense_piece(const DevModel &m, const DevRef &ref, DenseLd
                             cur4 = rs;
                         }
                     }
-                    // insertion: 2-bit fields -> "ATCG" (S:1990)
-                    const uint32_t x8 = (frac >> (8u * (g & 3u))) & 0xffu, t8 = (x8 | x8 << 12) & 0x000f000fu;
-                    const uint32_t ins4 = __builtin_amdgcn_perm(0u, 0x47435441u, (t8 | t8 << 6) & 0x03030303u);
+                    const uint32_t ins4 = ins_letters4(frac, g & 3u);
                     // substitution: the next four base-3 digits pick among the three other bases (S:1968-1972)
                     uint32_t f3 = frac;
                     const uint32_t d0 = next_digit3(f3), d1 = next_digit3(f3), d2 = next_digit3(f3), d3 = next_digit3(f3);
@@ -510,24 +500,12 @@ __device__ inline void dense_piece(const DevModel &m, const DevRef &ref, DenseLd
         }
         jb = jb + seen - 1u;                                  // the last item that starts at or before M1 is in force there
         wave_sync();
-        // ---- the tile leaves: 16 bytes per lane (+ their qualities: class 'unmapped', S:1521, 1564)
+        // ---- the tile leaves: 16 bytes per lane
         const uint32_t m0 = M0 + 16u * lane;
         if (m0 < M1) {
             const uint32_t count = min(16u, M1 - m0);
             const uint4 v = *reinterpret_cast<const uint4 *>(&S.out[16u * lane]);
-            uint64_t qlo = 0, qhi = 0;
-            if constexpr (FASTQ) {
-                const u32x4 w0 = ns_draw(key, ST_QUAL, pc.sid, a, m0 >> 3, 0), w1 = ns_draw(key, ST_QUAL, pc.sid, a, (m0 >> 3) + 1u, 0);
-                const uint32_t cls = pc.kind ? (uint32_t)NS_Q_UNMAPPED : (uint32_t)NS_Q_MATCH;
-                const uint32_t *thr = m.qual_thr + cls * NS_QUAL_LEVELS;
-                const uint16_t *lut = m.qual_lut + cls * 1024u;
-#pragma unroll
-                for (uint32_t i = 0; i < 8; ++i) {
-                    qlo |= (uint64_t)qual_value_lut(thr, lut, (ns_word(w0, i >> 1) >> (16u * (i & 1u))) & 0xffffu) << (8u * i);
-                    qhi |= (uint64_t)qual_value_lut(thr, lut, (ns_word(w1, i >> 1) >> (16u * (i & 1u))) & 0xffffu) << (8u * i);
-                }
-            }
-            store_chunk(ro, pq + m0, count, (uint64_t)v.x | (uint64_t)v.y << 32, (uint64_t)v.z | (uint64_t)v.w << 32, qlo, qhi);
+            store_chunk(ro, pq + m0, count, (uint64_t)v.x | (uint64_t)v.y << 32, (uint64_t)v.z | (uint64_t)v.w << 32, 0, 0);
         }
         wave_sync();
     }
@@ -539,6 +517,12 @@ __device__ inline void dense_piece(const DevModel &m, const DevRef &ref, DenseLd
 // k_materialise_slow
 struct SlowTile { uint32_t read, piece, m0, m1; };
 struct SlowQueue { SlowTile *items; uint32_t *count; uint32_t cap; };
+__device__ __forceinline__ void slow_queue_push(const SlowQueue &sq, uint32_t lane, const SlowTile &t) {     // (a full queue: counted, not stored)
+    if (lane == 0) {
+        const uint32_t slot = atomicAdd(sq.count, 1u);
+        if (slot < sq.cap) sq.items[slot] = t;
+    }
+}
 
 #define NS_REF_PAD 64u       // bytes allocated before and after the reference bases: any 16-byte load that overlaps a segment is in bounds
 
@@ -662,7 +646,7 @@ __device__ __forceinline__ uint32_t event_word(const PieceCtx &pc, const ns_key 
 // two at 8 waves with 64 VGPRs — spills — 6.0 ms).
 // ================================================================================================================================
 template <uint32_t TC>
-struct __align__(16) TileLds7 {
+struct __align__(16) TileLds {
     static constexpr uint32_t T_OUT_ = 1024u * TC;          // output bytes of a tile: TC 16-byte chunks per lane
     uint32_t mlut[17][4];                       // mlut[i]: 16-byte mask with bytes >= i set; [16] empty
     uint2 ent[T_EV + 1];                        // per staged event (0: the event in force at the tile start): x = first output offset copied
@@ -672,7 +656,7 @@ struct __align__(16) TileLds7 {
     __align__(16) uint8_t out[1024u * TC + 16 + 64]; // letters and event sub-runs of the tile (zero where nothing has been written) + dump slots
 };
 template <uint32_t TC>
-__device__ __forceinline__ void tile_lds_init(TileLds7<TC> &T, uint32_t lane) {
+__device__ __forceinline__ void tile_lds_init(TileLds<TC> &T, uint32_t lane) {
     for (uint32_t c = lane * 16; c < 1024u * TC + 16 + 64; c += 64 * 16) *reinterpret_cast<uint4 *>(&T.out[c]) = make_uint4(0, 0, 0, 0);
     if (lane < 17) {
 #pragma unroll
@@ -703,9 +687,9 @@ __device__ __forceinline__ void resolve16(uint32_t &a0, uint32_t &a1, uint32_t &
 // a & b & ~c in one instruction (v_bitop3_b32, truth table 0x40 for inputs 0xF0, 0xCC, 0xAA; the compiler emits not + and + and)
 __device__ __forceinline__ uint32_t and_andn(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x40); }
 template <bool FASTQ, int MODE, uint32_t TC>
-__device__ inline void materialise_piece7(const DevModel &m, const DevRef &ref, TileLds7<TC> &T, const ReadOut &ro, const ns_key &key,
-                                          uint32_t a, const PieceCtx &pc, uint32_t pq, uint32_t lane, uint32_t dbg, const SlowQueue &sq,
-                                          uint32_t read_idx, uint32_t piece_idx, uint32_t *__restrict__ cls) {
+__device__ inline void materialise_piece(const DevModel &m, const DevRef &ref, TileLds<TC> &T, const ReadOut &ro, const ns_key &key,
+                                         uint32_t a, const PieceCtx &pc, uint32_t pq, uint32_t lane, uint32_t dbg, const SlowQueue &sq,
+                                         uint32_t read_idx, uint32_t piece_idx, uint32_t *__restrict__ cls) {
     constexpr bool CLSOUT = FASTQ && MODE != MAT_HP_SCRATCH;           // the class of every base leaves as 2 bits for k_qualities (cls: the piece's words)
     constexpr bool HPF = MODE == MAT_HP_FINAL;
     constexpr uint32_t T_OUT_ = 1024u * TC;
@@ -729,7 +713,7 @@ __device__ inline void materialise_piece7(const DevModel &m, const DevRef &ref, 
         const uint32_t e_wd = w_pre;
         const bool valid = jb + lane < pc.n_ev;
         const uint32_t os = ev_out_start(e), len = ns_ev_len(e.info), ty = ns_ev_type(e.info);
-        const uint32_t e_pt = (ty == NS_DEL ? 0u : len) | ty << 12, e_rp = e.pos + (ty == NS_INS ? 0u : len);
+        const uint32_t e_pt = ev_letters(ty, len) | ty << 12, e_rp = ev_resume(e.pos, ty, len);
         if (jb + 63 < pc.n_ev) {           // more events than lanes: the tile ends early — on a CHUNK boundary, so that the next tile starts on one
             const uint32_t os63 = (uint32_t)__builtin_amdgcn_readlane((int)os, 63);
             if (os63 < M1) {
@@ -744,14 +728,11 @@ __device__ inline void materialise_piece7(const DevModel &m, const DevRef &ref, 
             M1 = min(M0 + T_OUT_, pc.out_len);
             uint32_t j2 = jb;
             while (j2 < pc.n_ev && ev_out_start(pc.ev[j2]) < M1) ++j2;
-            if (lane == 0) {
-                const uint32_t slot = atomicAdd(sq.count, 1u);
-                if (slot < sq.cap) sq.items[slot] = SlowTile{read_idx, piece_idx, M0, M1};
-            }
+            slow_queue_push(sq, lane, SlowTile{read_idx, piece_idx, M0, M1});
             if (j2 > jb) {
                 const ns_event le = pc.ev[j2 - 1];
                 const uint32_t ll = ns_ev_len(le.info), lt = ns_ev_type(le.info);
-                L0_out = uni(ev_out_start(le)); L0_pt = uni((lt == NS_DEL ? 0u : ll) | lt << 12); L0_rp = uni(le.pos + (lt == NS_INS ? 0u : ll));
+                L0_out = uni(ev_out_start(le)); L0_pt = uni(ev_letters(lt, ll) | lt << 12); L0_rp = uni(ev_resume(le.pos, lt, ll));
                 L0_wd = uni(event_word<MODE>(pc, key, a, j2 - 1)); L0_j = uni(j2 - 1);
             }
             jb = uni(j2); M0 = M1;
@@ -807,10 +788,7 @@ __device__ inline void materialise_piece7(const DevModel &m, const DevRef &ref, 
         }
         if (!fast) {
             cls_carry = 0;
-            if (lane == 0) {
-                const uint32_t slot = atomicAdd(sq.count, 1u);
-                if (slot < sq.cap) sq.items[slot] = SlowTile{read_idx, piece_idx, M0, M1};
-            }
+            slow_queue_push(sq, lane, SlowTile{read_idx, piece_idx, M0, M1});
             L0_out = osl; L0_rp = rpl; L0_pt = ptl; L0_wd = wdl; L0_j = jl;
             jb = jb_next; M0 = M1;
             wave_sync();
@@ -871,8 +849,7 @@ __device__ inline void materialise_piece7(const DevModel &m, const DevRef &ref, 
 #pragma unroll
                 for (uint32_t g = 0; g < 2; ++g) {
                     const uint32_t cur4 = g ? cur8.y : cur8.x;
-                    const uint32_t x8 = (frac >> (8u * g)) & 0xffu, t8 = (x8 | x8 << 12) & 0x000f000fu;
-                    const uint32_t ins4 = __builtin_amdgcn_perm(0u, 0x47435441u, (t8 | t8 << 6) & 0x03030303u);          // S:1990
+                    const uint32_t ins4 = ins_letters4(frac, g);
                     const uint32_t d0 = next_digit3(f3), d1 = next_digit3(f3), d2 = next_digit3(f3), d3 = next_digit3(f3);
                     const uint32_t d4 = d0 | d1 << 8 | d2 << 16 | d3 << 24;
                     const uint32_t vv = (cur4 >> 1) & 0x03030303u;                           // A 0, C 1, T 2, G 3
@@ -957,7 +934,6 @@ __device__ inline void materialise_piece7(const DevModel &m, const DevRef &ref, 
                 }
                 if (NS_DBG(512u)) { a0 = a1 = a2 = a3 = 0x41414141u; }
                 uint32_t r0 = v.x | a0, r1 = v.y | a1, r2 = v.z | a2, r3 = v.w | a3;
-                uint64_t qlo = 0, qhi = 0;
                 uint32_t s0 = lo_m - c0, count = hi_m - lo_m;          // bytes [s0, s0 + count) of the chunk are this tile's
                 if constexpr (CLSOUT) {                                // chunk k of the piece covers its positions [16 k - g, 16 k - g + 16), g = -phi mod 16
                     cw = cls_pack16(r0, r1, r2, r3);
@@ -971,7 +947,7 @@ __device__ inline void materialise_piece7(const DevModel &m, const DevRef &ref, 
                     if (sh < 64) { lo = (lo >> sh) | (hi << (64 - sh)); hi >>= sh; }
                     else { lo = hi >> (sh - 64); hi = 0; }
                 }
-                if (!NS_DBG(16u)) { PendingChunk pd = prep_chunk(ro, pq + lo_m, count, lo, hi, qlo, qhi); flush_chunk(ro, pd); }
+                if (!NS_DBG(16u)) { PendingChunk pd = prep_chunk(ro, pq + lo_m, count, lo, hi, 0, 0); flush_chunk(ro, pd); }
             }
             if constexpr (CLSOUT) {                                    // the tile ends inside a chunk: its word goes on in the next tile's chunk 0
                 const uint32_t cl = (M1 - 1u - A0) >> 4;

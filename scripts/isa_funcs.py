@@ -14,7 +14,7 @@ def read(path):
     for ln in open(path):
         if "__hip_cuid_" in ln:
             continue
-        ln = NUMBERED.sub(r"\2", ln)
+        ln = re.sub(r"[ \t]+;", " ;", NUMBERED.sub(r"\2", ln))      # (the comment column moves with the width of the label's number)
         m = re.search(r"; -- Begin function (\S+)", ln)
         if m and cur is None:
             name, cur = m.group(1), []
