@@ -385,6 +385,26 @@ int ns_cs_histograms(ns_ctx *ctx, const uint8_t *cs, uint64_t nbytes, const uint
 int ns_maf_histograms(ns_ctx *ctx, const uint8_t *ref_lines, const uint8_t *query_lines, uint64_t nbytes, const uint64_t *aln_off,
                       uint32_t n_aln, ns_cs_hist *h);
 
+/* ---- training side: the base-quality model ---------------------------------------------------------------------------------------------
+ * replaces the collecting loops of src/model_base_qualities.py (M:23-79): for every query base of every primary alignment its class —
+ * mismatch, insertion, match (from the cs string), head / tail (the soft clips), unmapped (every base of an unmapped read) — and its
+ * quality, as a histogram per class.  The log-normal fit the reference runs on the collected values (M:82-96) is a closed form of the
+ * histogram and is done on the host (nanosim_amd/characterize.py: fit_qualities).
+ * cs / qual: the cs strings and the QUAL strings (SAM text, Phred + 33; soft clips included, hard clips are not in QUAL) of the
+ * alignments back to back in host memory, alignment a at cs_off[a] .. cs_off[a + 1] and qual_off[a] .. qual_off[a + 1]; aln[a]: its soft
+ * clips.  head + tail must not exceed the alignment's quality length.  Added without an ABI change (a new function breaks no caller). */
+typedef struct ns_qual_aln { uint32_t head, tail, unmapped, reserved; } ns_qual_aln;   /* soft-clip lengths in bases; unmapped != 0: whole string is class 4, cs ignored */
+typedef struct ns_qual_hist {
+    uint64_t hist[5][128];      /* [mis, ins, match, ht, unmapped][quality 0..93]; the rest stays 0 */
+    uint64_t n_short;           /* alignments whose cs covers fewer bases than qual_len - head - tail */
+    uint64_t n_bad_qual;        /* bytes outside '!'..'~' (not counted anywhere else) */
+    double   ms_kernel;
+} ns_qual_hist;
+enum { NS_QH_MIS = 0, NS_QH_INS = 1, NS_QH_MATCH = 2, NS_QH_HT = 3, NS_QH_UNMAPPED = 4 };
+int ns_qual_histograms(ns_ctx *ctx, const uint8_t *cs, uint64_t cs_bytes, const uint64_t *cs_off,
+                       const uint8_t *qual, uint64_t qual_bytes, const uint64_t *qual_off,
+                       const ns_qual_aln *aln, uint32_t n_aln, ns_qual_hist *out);
+
 /* device address of a result buffer (for zero-copy consumers such as torch / RCCL); NULL if absent */
 const void *ns_device_ptr(ns_ctx *ctx, int which);
 

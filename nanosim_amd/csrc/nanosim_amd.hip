@@ -40,6 +40,7 @@
 #include "ns_io.h"
 #include "ns_pack.h"
 #include "ns_cs_hist.h"
+#include "ns_qual_hist.h"
 
 // Reads per workgroup of the wave-per-read kernels.  One: read lengths vary by an order of magnitude inside a batch, and a wavefront
 // that is done cannot leave before the longest read of its workgroup is.
@@ -2100,6 +2101,108 @@ __global__ void __launch_bounds__(256) k_cs_hist(const uint8_t *__restrict__ cs,
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// k_qual_mark, k_qual_count: the base-quality histograms of the training side (ns_qual_hist.h; src/model_base_qualities.py:23-79).
+// MARK, one alignment per thread: the cs walk records a 2-bit mark per mismatched / inserted base (16 bases per word of `marks`, zeroed
+// by the caller).  A thread meets its bases in ascending order, so it gathers a word's marks in a register and writes the word once:
+// with a plain store when the word lies inside its own quality string, with an atomic OR for the string's first and last word, which
+// a neighbouring alignment may share.
+// COUNT streams the quality bytes and the marks once: a thread takes 16 bytes + one mark word per load, four loads in flight, wherever
+// the alignments begin; the alignment of a position comes from a binary search of the offsets, then from a walk forward.  Counters:
+// 32 copies of the 5 x 94 (+ 1) table per workgroup in LDS, copy = lane mod 32 = the LDS bank — `match` at the modal quality takes
+// most bases, and one counter per workgroup would serialise every wavefront's 64 adds on it; a copy per bank leaves two lanes of a
+// wavefront (one per 32-lane half) and the four wavefronts on an address.  A workgroup counts a contiguous span of at most 2^31 bytes
+// (the caller's grid), so no 32-bit counter can wrap; the copies are summed and flushed once with 64-bit atomics.
+// ---------------------------------------------------------------------------------------------------------
+#define NS_QH_BINS (QH_CLASSES * NS_QUAL_VALUES + 1u)      // the last one: bytes that are no quality value
+#define NS_QH_COPIES 32u
+#define NS_QH_LOADS 4u
+#define NS_QH_SUBTILE 4096u                                // 256 threads x 16 bytes
+#define NS_QH_TILE (NS_QH_LOADS * NS_QH_SUBTILE)
+#define NS_QH_OUT_SHORT (QH_CLASSES * 128u)                // the device image of ns_qual_hist: hist[5][128], n_short, n_bad_qual
+#define NS_QH_OUT_BAD (QH_CLASSES * 128u + 1u)
+#define NS_QH_OUT_WORDS (QH_CLASSES * 128u + 2u)
+struct QualMarkDev {
+    uint32_t *marks;
+    uint64_t base;                    // where the aligned part begins in the quality bytes
+    uint64_t w_first, w_last;         // the words a neighbouring alignment may write too
+    uint64_t cur; uint32_t bits;
+    __device__ __forceinline__ void flush() {
+        if (!bits) return;
+        if (cur == w_first || cur == w_last) atomicOr(&marks[cur], bits); else marks[cur] = bits;
+    }
+    __device__ __forceinline__ void mark(uint64_t i, uint32_t m) {
+        const uint64_t pos = base + i, w = pos >> 4;
+        if (w != cur) { flush(); cur = w; bits = 0; }
+        bits |= m << (2u * (uint32_t)(pos & 15u));
+    }
+};
+__global__ void __launch_bounds__(256) k_qual_mark(const uint8_t *__restrict__ cs, const uint64_t *__restrict__ cs_off, const uint64_t *__restrict__ qual_off,
+                                                   const ns_qual_aln *__restrict__ aln, uint32_t n_aln, const uint32_t *__restrict__ order,
+                                                   uint32_t *__restrict__ marks, unsigned long long *__restrict__ out) {
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= n_aln) return;
+    const uint64_t a = order ? order[tid] : tid;              // by descending length of the cs strings, as k_cs_hist
+    const ns_qual_aln A = aln[a];
+    const uint64_t lo = qual_off[a], hi = qual_off[a + 1];
+    const uint64_t aligned = hi - lo - A.head - A.tail;
+    if (A.unmapped || !aligned) return;
+    QualMarkDev sink{marks, lo + A.head, lo >> 4, (hi - 1u) >> 4, ~0ull, 0u};
+    CsBytes sb(cs + cs_off[a]);
+    const bool covered = qual_mark_alignment(sb, cs_off[a + 1] - cs_off[a], aligned, sink);
+    sink.flush();
+    if (!covered) atomicAdd(&out[NS_QH_OUT_SHORT], 1ull);
+}
+__global__ void __launch_bounds__(256) k_qual_count(const uint8_t *__restrict__ qual, const uint32_t *__restrict__ marks, const uint64_t *__restrict__ off,
+                                                    const ns_qual_aln *__restrict__ aln, uint32_t n_aln, uint64_t tiles_per_wg, uint64_t n_tiles,
+                                                    unsigned long long *__restrict__ out) {
+    __shared__ uint32_t cnt[NS_QH_BINS * NS_QH_COPIES];
+    for (uint32_t i = threadIdx.x; i < NS_QH_BINS * NS_QH_COPIES; i += blockDim.x) cnt[i] = 0;
+    __syncthreads();
+    uint32_t *mine = cnt + (threadIdx.x & (NS_QH_COPIES - 1u));
+    const uint64_t begin = off[0], end = off[n_aln];
+    const uint64_t t0 = (uint64_t)blockIdx.x * tiles_per_wg, t1 = t0 + tiles_per_wg < n_tiles ? t0 + tiles_per_wg : n_tiles;
+    uint32_t a = 0, next = 0;                                 // the alignment of the last byte looked at; where the search for the next goes on
+    uint64_t lo = 0, hi = 0;                                  // its bytes (hi = 0: none yet)
+    ns_qual_aln A{0u, 0u, 0u, 0u};
+    for (uint64_t t = t0; t < t1; ++t) {
+        const uint64_t p0 = t * NS_QH_TILE + (uint64_t)threadIdx.x * 16u;
+        uint4 v[NS_QH_LOADS]; uint32_t m[NS_QH_LOADS];
+#pragma unroll
+        for (uint32_t j = 0; j < NS_QH_LOADS; ++j) {
+            const uint64_t p = p0 + (uint64_t)j * NS_QH_SUBTILE;
+            v[j] = make_uint4(0u, 0u, 0u, 0u); m[j] = 0u;
+            if (p < end) { v[j] = *reinterpret_cast<const uint4 *>(qual + p); m[j] = marks[p >> 4]; }     // (both buffers are padded to whole words)
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < NS_QH_LOADS; ++j) {
+            const uint64_t p = p0 + (uint64_t)j * NS_QH_SUBTILE;
+            const uint32_t w[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+#pragma unroll
+            for (uint32_t k = 0; k < 16u; ++k) {
+                const uint64_t pos = p + k;
+                if (pos < begin || pos >= end) continue;
+                if (pos >= hi) {                              // the next alignment that holds a byte: a few steps forward, else a search
+                    for (uint32_t s = 0; s < 4u && off[next + 1u] <= pos; ++s) ++next;
+                    if (off[next + 1u] <= pos) next = qual_locate(off, next + 1u, n_aln, pos);
+                    a = next; next = a + 1u;
+                    lo = off[a]; hi = off[a + 1u]; A = aln[a];
+                }
+                const uint32_t q = ((w[k >> 2] >> (8u * (k & 3u))) & 0xffu) - NS_QUAL_FIRST;
+                const uint32_t bin = q < NS_QUAL_VALUES ? qual_class(pos - lo, hi - lo, A.head, A.tail, A.unmapped, (m[j] >> (2u * k)) & 3u) * NS_QUAL_VALUES + q
+                                                        : NS_QH_BINS - 1u;
+                atomicAdd(&mine[bin * NS_QH_COPIES], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t bin = threadIdx.x; bin < NS_QH_BINS; bin += blockDim.x) {
+        unsigned long long sum = 0;
+        for (uint32_t c = 0; c < NS_QH_COPIES; ++c) sum += cnt[bin * NS_QH_COPIES + ((c + bin) & (NS_QH_COPIES - 1u))];   // (rotated: the lanes read 32 banks)
+        if (sum) atomicAdd(&out[bin < NS_QH_BINS - 1u ? (bin / NS_QUAL_VALUES) * 128u + bin % NS_QUAL_VALUES : NS_QH_OUT_BAD], sum);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // reference normalisation (once per ns_set_reference): upper-case, non-IUPAC -> N
 // ---------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_normalise(uint8_t *bases, uint64_t n) {
@@ -2151,7 +2254,7 @@ enum Evt {
     EV_HP_BEGIN, EV_HP_END,             // NS_K_HP: one -k stage, summed over the stages of the call (hp_stage1)
     EV_DRAWS_ON_HOST,                   // no timing pair: the filtered draws of a metagenome pass have reached the host
     EV_RECKERNEL_BEGIN, EV_RECKERNEL_END,   // NS_K_RECORD_KERNEL: the record kernel itself (when ns_ctx::rec_timed)
-    EV_HIST_BEGIN, EV_HIST_END,         // ns_cs_hist.ms_kernel (histograms)
+    EV_HIST_BEGIN, EV_HIST_END,         // ns_cs_hist.ms_kernel (histograms), ns_qual_hist.ms_kernel (ns_qual_histograms)
     EV_COUNT
 };
 static const struct { Evt from, to; int slot; } EVT_TIMED[] = {
@@ -4086,6 +4189,25 @@ int ns_maf_histograms(ns_ctx *ctx, const uint8_t *ref_lines, const uint8_t *quer
     if (ctx && n_aln && nbytes && !query_lines) return fail(ctx, NS_EINVAL, "ns_maf_histograms: null argument");
     return histograms(ctx, ref_lines, query_lines, true, nbytes, aln_off, n_aln, h);
 }
+// Alignments of 1 kb .. 100 kb on neighbouring lanes diverge like the thread-per-read chain did before its length sort: the walks are
+// visited by descending length of their cs strings (the counts are sums: any order gives the same tables).  *order: the visiting order
+// (nullptr for 64 alignments or fewer: index order); *key and *tmp are the caller's to free.
+static hipError_t order_by_length(hipStream_t st, const uint64_t *d_off, uint32_t n_aln, void **d_key, void **d_tmp, uint32_t **order) {
+    *order = nullptr;
+    if (n_aln <= 64) return hipSuccess;
+    size_t tmp = 0;
+    hipError_t e = hipMalloc(d_key, (size_t)n_aln * 16);                 // key, index, sorted key, sorted index
+    if (e != hipSuccess) return e;
+    uint32_t *key = (uint32_t *)*d_key, *idx = key + n_aln, *key2 = idx + n_aln, *idx2 = key2 + n_aln;
+    k_cs_len<<<dim3((n_aln + 255u) / 256u), dim3(256), 0, st>>>(d_off, n_aln, key, idx);
+    e = hipGetLastError();
+    auto sort = [&](void *t) { return hipcub::DeviceRadixSort::SortPairsDescending(t, tmp, key, key2, idx, idx2, (int)n_aln, 0, 32, st); };
+    if (e == hipSuccess) e = sort(nullptr);                               // (the size of its temporary storage)
+    if (e == hipSuccess) e = hipMalloc(d_tmp, tmp + 16);
+    if (e == hipSuccess) e = sort(*d_tmp);
+    *order = idx2;
+    return e;
+}
 static int histograms(ns_ctx *ctx, const uint8_t *cs, const uint8_t *qry, bool maf, uint64_t nbytes, const uint64_t *aln_off, uint32_t n_aln, ns_cs_hist *h) {
     if (!ctx) return NS_EINVAL;
     if (!h || (n_aln && (!aln_off || (!cs && nbytes)))) return fail(ctx, NS_EINVAL, "ns_cs_histograms: null argument");
@@ -4114,23 +4236,8 @@ static int histograms(ns_ctx *ctx, const uint8_t *cs, const uint8_t *qry, bool m
     if (e == hipSuccess) e = hipMemsetAsync(d_small, 0, n_small * 8, st);
     if (e == hipSuccess && d_m2) e = hipMemsetAsync(d_m2, 0, (size_t)cap * cap * 8, st);
     if (e == hipSuccess) e = hipEventRecord(ctx->evt[EV_HIST_BEGIN], st);
-    // Alignments of 1 kb .. 100 kb on neighbouring lanes diverge like the thread-per-read chain did before its length sort: the walks are
-    // visited by descending length of their cs strings (the counts are sums: any order gives the same tables).
     uint32_t *d_order = nullptr;
-    if (e == hipSuccess && n_aln > 64) {
-        size_t tmp = 0;
-        e = hipMalloc(&d_key, (size_t)n_aln * 16);                 // key, index, sorted key, sorted index
-        if (e == hipSuccess) {
-            uint32_t *key = (uint32_t *)d_key, *idx = key + n_aln, *key2 = idx + n_aln, *idx2 = key2 + n_aln;
-            k_cs_len<<<dim3((n_aln + 255u) / 256u), dim3(256), 0, st>>>((const uint64_t *)d_off, n_aln, key, idx);
-            e = hipGetLastError();
-            auto sort = [&](void *t) { return hipcub::DeviceRadixSort::SortPairsDescending(t, tmp, key, key2, idx, idx2, (int)n_aln, 0, 32, st); };
-            if (e == hipSuccess) e = sort(nullptr);               // (the size of its temporary storage)
-            if (e == hipSuccess) e = hipMalloc(&d_tmp, tmp + 16);
-            if (e == hipSuccess) e = sort(d_tmp);
-            d_order = idx2;
-        }
-    }
+    if (e == hipSuccess) e = order_by_length(st, (const uint64_t *)d_off, n_aln, &d_key, &d_tmp, &d_order);
     if (e == hipSuccess) {
         CsHistDev H;
         H.dic = (unsigned long long *)d_small; H.err = H.dic + 5 * 1001; H.misc = H.err + 24;
@@ -4152,6 +4259,72 @@ static int histograms(ns_ctx *ctx, const uint8_t *cs, const uint8_t *qry, bool m
     for (int i = 0; i < 3; ++i) h->first_error[i] = small[5 * 1001 + 18 + i];
     h->max_match = small[5 * 1001 + 24]; h->n_match2d_overflow = small[5 * 1001 + 25]; h->n_skip = small[5 * 1001 + 26];
     h->ms_kernel = ms;
+    return NS_OK;
+}
+
+// the base-quality histograms of the training side (include/nanosim_amd.h: ns_qual_hist; src/model_base_qualities.py:23-79)
+int ns_qual_histograms(ns_ctx *ctx, const uint8_t *cs, uint64_t cs_bytes, const uint64_t *cs_off, const uint8_t *qual, uint64_t qual_bytes,
+                       const uint64_t *qual_off, const ns_qual_aln *aln, uint32_t n_aln, ns_qual_hist *out) {
+    if (!ctx) return NS_EINVAL;
+    if (!out || (n_aln && (!cs_off || !qual_off || !aln || (!cs && cs_bytes) || (!qual && qual_bytes)))) return fail(ctx, NS_EINVAL, "ns_qual_histograms: null argument");
+    for (uint32_t a = 0; a < n_aln; ++a) {
+        if (cs_off[a] > cs_off[a + 1] || cs_off[a + 1] > cs_bytes || qual_off[a] > qual_off[a + 1] || qual_off[a + 1] > qual_bytes)
+            return fail(ctx, NS_EINVAL, "ns_qual_histograms: offsets not ascending / beyond the strings");
+        if ((uint64_t)aln[a].head + aln[a].tail > qual_off[a + 1] - qual_off[a])
+            return fail(ctx, NS_EINVAL, "ns_qual_histograms: soft clips longer than the quality string of alignment " + std::to_string(a));
+    }
+    memset(out, 0, sizeof *out);
+    if (!n_aln) return NS_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n_marks = (size_t)(qual_bytes / 16u) + 2u;               // 2 bits per quality byte, in whole words
+    void *d_cs = nullptr, *d_cs_off = nullptr, *d_qual = nullptr, *d_qual_off = nullptr, *d_aln = nullptr, *d_marks = nullptr, *d_out = nullptr,
+         *d_key = nullptr, *d_tmp = nullptr;
+    auto release = [&]() { for (void *p : {d_cs, d_cs_off, d_qual, d_qual_off, d_aln, d_marks, d_out, d_key, d_tmp}) if (p) { hipError_t e = hipFree(p); (void)e; } };
+    hipError_t e = hipMalloc(&d_cs, (size_t)cs_bytes + 16);               // (16 bytes to spare: the window loads of CsBytes and of k_qual_count)
+    if (e == hipSuccess) e = hipMalloc(&d_qual, (size_t)qual_bytes + 32);
+    if (e == hipSuccess) e = hipMalloc(&d_cs_off, ((size_t)n_aln + 1) * 8);
+    if (e == hipSuccess) e = hipMalloc(&d_qual_off, ((size_t)n_aln + 1) * 8);
+    if (e == hipSuccess) e = hipMalloc(&d_aln, (size_t)n_aln * sizeof(ns_qual_aln));
+    if (e == hipSuccess) e = hipMalloc(&d_marks, n_marks * 4);
+    if (e == hipSuccess) e = hipMalloc(&d_out, NS_QH_OUT_WORDS * 8);
+    if (e != hipSuccess) { release(); (void)hipGetLastError(); return fail(ctx, NS_ENOMEM, std::string("ns_qual_histograms: hipMalloc: ") + hipGetErrorString(e)); }
+    hipStream_t st = ctx->stream;
+    if (cs_bytes) e = hipMemcpyAsync(d_cs, cs, (size_t)cs_bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && qual_bytes) e = hipMemcpyAsync(d_qual, qual, (size_t)qual_bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_cs_off, cs_off, ((size_t)n_aln + 1) * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_qual_off, qual_off, ((size_t)n_aln + 1) * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_aln, aln, (size_t)n_aln * sizeof(ns_qual_aln), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, NS_QH_OUT_WORDS * 8, st);
+    if (e == hipSuccess) e = hipEventRecord(ctx->evt[EV_HIST_BEGIN], st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_marks, 0, n_marks * 4, st);
+    uint32_t *d_order = nullptr;
+    if (e == hipSuccess) e = order_by_length(st, (const uint64_t *)d_cs_off, n_aln, &d_key, &d_tmp, &d_order);
+    if (e == hipSuccess) {
+        k_qual_mark<<<dim3((n_aln + 255u) / 256u), dim3(256), 0, st>>>((const uint8_t *)d_cs, (const uint64_t *)d_cs_off, (const uint64_t *)d_qual_off,
+                                                                       (const ns_qual_aln *)d_aln, n_aln, d_order, (uint32_t *)d_marks, (unsigned long long *)d_out);
+        e = hipGetLastError();
+    }
+    // a workgroup counts a contiguous span of tiles: at most 512 workgroups (its 60 KB of counters let two of them share a compute unit:
+    // one resident set, one flush each), but never more than 2^31 bytes per workgroup (32-bit counters in LDS)
+    const uint64_t n_tiles = (qual_off[n_aln] + NS_QH_TILE - 1u) / NS_QH_TILE;
+    const uint64_t tiles_per_wg = std::min<uint64_t>(std::max<uint64_t>((n_tiles + 511u) / 512u, 1u), (1ull << 31) / NS_QH_TILE);
+    if (e == hipSuccess && n_tiles && !(ctx->knob.dbg & (1u << 20))) {    // (NS_DEBUG_SKIP 1 << 20, profiling only: the mark phase alone)
+        k_qual_count<<<dim3((uint32_t)((n_tiles + tiles_per_wg - 1u) / tiles_per_wg)), dim3(256), 0, st>>>(
+            (const uint8_t *)d_qual, (const uint32_t *)d_marks, (const uint64_t *)d_qual_off, (const ns_qual_aln *)d_aln, n_aln, tiles_per_wg, n_tiles,
+            (unsigned long long *)d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ctx->evt[EV_HIST_END], st);
+    std::vector<unsigned long long> res(NS_QH_OUT_WORDS);
+    if (e == hipSuccess) e = hipMemcpyAsync(res.data(), d_out, NS_QH_OUT_WORDS * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    float ms = 0;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ctx->evt[EV_HIST_BEGIN], ctx->evt[EV_HIST_END]);
+    release();
+    if (e != hipSuccess) return fail(ctx, NS_EHIP, std::string("ns_qual_histograms: ") + hipGetErrorString(e));
+    for (int c = 0; c < 5; ++c) for (int q = 0; q < 128; ++q) out->hist[c][q] = res[(size_t)c * 128 + q];
+    out->n_short = res[NS_QH_OUT_SHORT]; out->n_bad_qual = res[NS_QH_OUT_BAD];
+    out->ms_kernel = ms;
     return NS_OK;
 }
 

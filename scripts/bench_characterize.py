@@ -2,7 +2,11 @@
 """Training-side histogramming throughput on one GPU (not the headline bench): cs strings of N synthetic alignments (built from the event
 lists of reads the engine itself generates with the hg002-like model, ~1 KB of cs per 8 kb read) through ns_cs_histograms; prints
 alignments/s, the kernel's own time and its fraction of the HBM roofline (algorithmic bytes = the cs strings, read once).
-    python scripts/bench_characterize.py [--alignments 200000]"""
+    python scripts/bench_characterize.py [--alignments 200000]
+--qualities: the base-quality histograms instead (ns_qual_histograms: the same cs strings plus a QUAL string per alignment, ~8.4 KB per
+read): milliseconds of the two phases (the mark phase alone from a second context with NS_DEBUG_SKIP = 1 << 20, the count phase as the
+difference), the end-to-end time, GB/s over cs + quality bytes — as measured and scaled to 10^6 alignments.
+    python scripts/bench_characterize.py --qualities [--alignments 200000]"""
 import argparse
 import json
 import os
@@ -19,6 +23,7 @@ from nanosim_amd import characterize, engine as E, model as M, synth  # noqa: E4
 ap = argparse.ArgumentParser()
 ap.add_argument("--alignments", type=int, default=200_000)
 ap.add_argument("--steps", type=int, default=3)
+ap.add_argument("--qualities", action="store_true")
 a = ap.parse_args()
 SEED = 20260926
 tmp = tempfile.mkdtemp(prefix="nschar_")
@@ -35,23 +40,54 @@ b = eng.generate(E.make_params(seed=SEED, first_read=0, n_reads=n_src, max_len=r
 pieces, events = b.pieces(), b.events()
 rng = np.random.default_rng(SEED)
 letters = np.frombuffer(b"acgt", dtype=np.uint8)
-cs = []
+cs, cover = [], []
 for pc in pieces:
     ev = events[int(pc["ev_off"]):int(pc["ev_off"]) + int(pc["n_ev"])]
-    s, pos = [], 0
+    s, pos, qn = [], 0, 0
     for e in ev:
         epos, ln, ty = int(e["pos"]), int(e["info"]) & 0xfff, (int(e["info"]) >> 12) & 3
         if epos > pos:
-            s.append(":%d" % (epos - pos)); pos = epos
+            s.append(":%d" % (epos - pos)); qn += epos - pos; pos = epos
         if ty == 0:
-            s.append("*ac" * ln); pos += ln
+            s.append("*ac" * ln); pos += ln; qn += ln
         elif ty == 1:
-            s.append("+" + "a" * ln)
+            s.append("+" + "a" * ln); qn += ln
         else:
             s.append("-" + "a" * ln); pos += ln
     if int(pc["ref_len"]) > pos:
-        s.append(":%d" % (int(pc["ref_len"]) - pos))
-    cs.append("".join(s))
+        s.append(":%d" % (int(pc["ref_len"]) - pos)); qn += int(pc["ref_len"]) - pos
+    cs.append("".join(s)); cover.append(qn)
+if a.qualities:
+    # a QUAL string per alignment: a head and a tail clip of 0-40 bases around the bases the cs string covers, log-normal values
+    clips = rng.integers(0, 41, (len(cs), 2))
+    pool = (np.clip(np.rint(np.exp(rng.normal(3.0, 0.4, 1 << 24))), 1, 93).astype(np.uint8) + 33).tobytes()
+    src = []
+    for c, n, (hd, tl) in zip(cs, cover, clips):
+        at = int(rng.integers(0, len(pool) - (n + 81)))
+        src.append((c, pool[at:at + int(hd) + n + int(tl)], int(hd), int(tl)))
+    aligned = (src * (a.alignments // len(src) + 1))[:a.alignments]
+    nbytes = sum(len(x[0]) + len(x[1]) for x in aligned)
+    characterize.count_qualities(eng, aligned)             # warms up
+    t0 = time.perf_counter()
+    ms = [characterize.count_qualities(eng, aligned)["ms_kernel"] for _ in range(a.steps)]
+    dt = (time.perf_counter() - t0) / a.steps
+    eng.close()
+    os.environ["NS_DEBUG_SKIP"] = str(1 << 20)             # (read when a context is created) the count phase is left out: counts are not used
+    eng = E.Engine(0)
+    characterize._qual_call(eng, [x + (0,) for x in aligned])       # warms up
+    ms_mark = [characterize._qual_call(eng, [x + (0,) for x in aligned]).ms_kernel for _ in range(a.steps)]
+    eng.close()
+    per_m = 1e6 / a.alignments
+    both, mark = float(np.mean(ms)), float(np.mean(ms_mark))
+    qbytes = sum(len(x[1]) for x in aligned)
+    print(json.dumps({"metric": "base-quality histograms, alignments/s (ns_qual_histograms incl. packing + H2D)", "value": a.alignments / dt,
+                      "alignments": a.alignments, "cs_plus_qual_bytes": nbytes, "qual_bytes_per_alignment": qbytes / a.alignments,
+                      "kernels_ms": both, "mark_ms(memset+sort+k_qual_mark)": mark, "count_ms(k_qual_count, by difference)": both - mark,
+                      "end_to_end_s": dt, "kernels_gb_per_s": nbytes / (both * 1e-3) / 1e9,
+                      "count_gb_per_s(qual bytes + marks)": qbytes * 1.25 / ((both - mark) * 1e-3) / 1e9,
+                      "count_frac_of_hbm_8tbs": qbytes * 1.25 / ((both - mark) * 1e-3) / 1e9 / 8000.0,
+                      "per_1e6_alignments": {"kernels_ms": both * per_m, "mark_ms": mark * per_m, "count_ms": (both - mark) * per_m, "end_to_end_s": dt * per_m}}))
+    sys.exit(0)
 cs = (cs * (a.alignments // len(cs) + 1))[:a.alignments]
 nbytes = sum(len(x) for x in cs)
 t = characterize.count(eng, cs)                          # sizes the match matrix, warms up
