@@ -21,13 +21,13 @@ struct Tabs {
     NS_DEV const int32_t *i(uint32_t off) const { return reinterpret_cast<const int32_t *>(w + off); }
 };
 
-// first s with p <= hi[s] (guide[u>>24] is a lower bound of s), then the interpolation of S:1847 / S:1897.
+// first s with p <= hi[s] (guide[guide_cell(u)] is a lower bound of s: ns_device.h), then the interpolation of S:1847 / S:1897.
 // hi[s] and hi[s+1] are fetched together: the look-up sits on the chain's critical path.
 template <class V>       // V = double, or uint32_t for the integer copy of the value edges in LDS (same values, converted on the fly)
 NS_DEV int32_t ecdf_lookup_g(const double *__restrict__ hi, const V *__restrict__ vhi, uint32_t n,
                                                  double vlo0, const uint16_t *__restrict__ guide, uint32_t u) {
     double p = u32_to_p(u);
-    uint32_t s = guide[u >> 24];
+    uint32_t s = guide[guide_cell(u)];
     if (s < n) {
         const double h0 = hi[s], h1 = hi[min(s + 1, n - 1)];
         if (p > h0) {
@@ -110,7 +110,7 @@ NS_DEV void ev_push32(EvSink32 &s, int32_t pos, uint32_t type, int32_t len) {
 struct EList32 { int32_t l_new, middle_ref; };
 
 // error_list, S:1833-1916, on the fp64 tables (T = the whole blob in global memory): fp64 compares + the fp64 interpolation of the
-// reference, every search started from a 256-entry guide index instead of a full binary search
+// reference, every search started from a guide index (guide_cell) instead of a full binary search
 NS_DEV EList32 chain_error_list_g(const Tabs &T, const ChainTab &c, int32_t m_ref, const ns_key &key, uint32_t seg, uint32_t attempt, EvSink32 &s) {
     int32_t l_new = m_ref, pos = 0, middle_ref = m_ref;
     int state = NS_ST_START;
@@ -149,7 +149,7 @@ NS_DEV EList32 chain_error_list_g(const Tabs &T, const ChainTab &c, int32_t m_re
             if (b >= c.mm_nbins) b = c.mm_nbins - 1;
         }
         const uint32_t o = seg_off[b], ncol = seg_off[b + 1] - o;
-        step = ecdf_lookup_g(T.d(c.mm_hi) + o, T.d(c.mm_vhi) + o, ncol, T.d(c.mm_vlo0)[b], T.h(c.mm_guide) + 256 * b, w.w);
+        step = ecdf_lookup_g(T.d(c.mm_hi) + o, T.d(c.mm_vhi) + o, ncol, T.d(c.mm_vlo0)[b], T.h(c.mm_guide) + NS_GUIDE_CELLS * b, w.w);
         if (prev_match == 0 && step == 0) step = 1;                                                // S:1900-1901
         prev_match = step;
         if (pos + prev_match > middle_ref) { l_new += pos + prev_match - middle_ref; middle_ref = pos + prev_match; }
@@ -218,6 +218,13 @@ NS_DEV int32_t run_length_r(const Tabs &T, const ChainTab &c, uint32_t type, uin
 }
 
 #define NS_G_THR(g) ((g) & 0x1ffffffffull)
+// test instrumentation: tests/chain_guide_host.hip defines NS_CHAIN_COUNT to count how often chain_error_list leaves its straight-line
+// path (no other build defines it)
+#ifndef NS_CHAIN_COUNT
+#define NS_CHAIN_COUNT(what)
+#endif
+enum { NS_CNT_ITER, NS_CNT_FALLBACK, NS_CNT_NARROW, NS_CNT_K1, NS_CNT_N };      // iterations; calls of next_match_gv; narrow segments answered
+                                                                                // in place; draws three or more segments behind the guide's
 #define NS_GV_UNIT (1ull << 33)
 #define NS_GV_NARROW (1ull << 34)
 // the segment of draw u in a column of n one-word segments and the value it gives.  Straight-line for the common case — the guide's
@@ -225,7 +232,7 @@ NS_DEV int32_t run_length_r(const Tabs &T, const ChainTab &c, uint32_t type, uin
 // table's first word: read, never used), the compares are arithmetic, nothing the compiler could sink a load into
 NS_DEV int32_t ecdf_lookup_gv(const uint64_t *__restrict__ GV, uint32_t n, const uint16_t *__restrict__ guide, uint32_t u,
                               const uint64_t *__restrict__ sub2, const double *__restrict__ hi_g, const double *__restrict__ vhi_g, double vlo0) {
-    const uint32_t s0 = guide[u >> 24];
+    const uint32_t cell = guide_cell(u), s0 = guide[cell];
     const uint64_t uu = u;
     const uint32_t sc = min(s0, n - 1u);
     const uint64_t g0 = GV[sc], g1 = GV[sc + 1u];
@@ -233,8 +240,8 @@ NS_DEV int32_t ecdf_lookup_gv(const uint64_t *__restrict__ GV, uint32_t n, const
     uint64_t g = k0 ? g1 : g0;
     uint32_t s = s0 + k0 + k1;
     if (k1) {                                     // three or more segments inside one guide cell: bisection between the guide's bounds — the
-        const uint32_t cell = u >> 24;            // last cells of a trained model's column hold hundreds of segments (its tail rows), and in the
-        uint32_t hi2 = cell < 255u ? min((uint32_t)guide[cell + 1u], n) : n;      // full column every step of a walk is a global-memory read
+                                                  // last cell of a trained model's column holds its tail rows, and in the
+        uint32_t hi2 = cell + 1u < NS_GUIDE_CELLS ? min((uint32_t)guide[cell + 1u], n) : n;      // full column every step of a walk is a global-memory read
         while (s < hi2) { const uint32_t mid = (s + hi2) >> 1; if (uu >= NS_G_THR(GV[mid])) s = mid + 1u; else hi2 = mid; }
         if (s < n) g = GV[s];
     }
@@ -259,8 +266,8 @@ NS_DEV int32_t ecdf_lookup_gv(const uint64_t *__restrict__ GV, uint32_t n, const
 NS_DEV bool ecdf_lookup_pre(const uint64_t *__restrict__ GV, uint32_t n, const uint16_t *__restrict__ guide, uint32_t u,
                             const uint64_t *__restrict__ sub2, int32_t &out) {
     const uint64_t uu = u;
-    const uint32_t cell = u >> 24;
-    uint32_t s = guide[cell], hi2 = cell < 255u ? min((uint32_t)guide[cell + 1u], n) : n;       // first segment with u < threshold: bisection
+    const uint32_t cell = guide_cell(u);
+    uint32_t s = guide[cell], hi2 = cell + 1u < NS_GUIDE_CELLS ? min((uint32_t)guide[cell + 1u], n) : n;       // first segment with u < threshold: bisection
     while (s < hi2) { const uint32_t mid = (s + hi2) >> 1; if (uu >= NS_G_THR(GV[mid])) s = mid + 1u; else hi2 = mid; }   // between the guide's bounds
     if (s >= n) return false;
     const uint64_t g = GV[s];
@@ -277,14 +284,15 @@ NS_DEV bool ecdf_lookup_pre(const uint64_t *__restrict__ GV, uint32_t n, const u
     return false;
 }
 // the generic look-up of the next match length (any previous match, any segment class, any draw): the fall-back of chain_error_list's fast
-// path.  The prefix column in the LDS image first (a walk of more than two segments, a narrow segment: a few percent of the events); the
+// path.  The prefix column in the LDS image first (a walk of more than two segments: 0.13 % of the draws with the octave guide, 4 % with
+// equal cells — nearly every iteration of a wavefront ran this for two or three of its lanes; a narrow segment behind a previous match >= 256); the
 // FULL column in global memory for what the prefix cannot answer (a draw behind it: one in 2^tail_bits; a wide segment; a previous match >= 256)
 NS_DEV int32_t next_match_gv(const Tabs &T, const Tabs &TG, const ChainTab &c, int32_t prev_match, uint32_t u) {
     uint32_t b, o, ncol;
     if ((uint32_t)prev_match < 256u) {
         const uint64_t pp = T.q(c.pm_lut)[prev_match];
         int32_t r;
-        if (ecdf_lookup_pre(T.q(c.mm_gv) + (uint32_t)pp, (uint32_t)(pp >> 32) & 0xffffffu, T.h(c.mm_guide) + 256u * (uint32_t)(pp >> 56), u, T.q(c.sub2), r)) return r;
+        if (ecdf_lookup_pre(T.q(c.mm_gv) + (uint32_t)pp, (uint32_t)(pp >> 32) & 0xffffffu, T.h(c.mm_guide) + NS_GUIDE_CELLS * (uint32_t)(pp >> 56), u, T.q(c.sub2), r)) return r;
         const uint64_t pe = TG.q(c.pm_full)[prev_match];
         b = (uint32_t)(pe >> 56); o = (uint32_t)pe; ncol = (uint32_t)(pe >> 32) & 0xffffffu;
     } else {                                                                                       // S:1891-1893
@@ -297,10 +305,10 @@ NS_DEV int32_t next_match_gv(const Tabs &T, const Tabs &TG, const ChainTab &c, i
         // of a wavefront; its prefix column answers from LDS like any other)
         const uint64_t pp = T.q(c.pm_bin)[b];
         int32_t r;
-        if (ecdf_lookup_pre(T.q(c.mm_gv) + (uint32_t)pp, (uint32_t)(pp >> 32) & 0xffffffu, T.h(c.mm_guide) + 256u * b, u, T.q(c.sub2), r)) return r;
+        if (ecdf_lookup_pre(T.q(c.mm_gv) + (uint32_t)pp, (uint32_t)(pp >> 32) & 0xffffffu, T.h(c.mm_guide) + NS_GUIDE_CELLS * b, u, T.q(c.sub2), r)) return r;
         o = seg_off[b]; ncol = seg_off[b + 1] - o;
     }
-    return ecdf_lookup_gv(TG.q(c.mm_gv_full) + o, ncol, T.h(c.mm_guide) + 256u * b, u, TG.q(c.sub2_full), TG.d(c.mm_hi) + o, TG.d(c.mm_vhi) + o, T.d(c.mm_vlo0)[b]);
+    return ecdf_lookup_gv(TG.q(c.mm_gv_full) + o, ncol, T.h(c.mm_guide) + NS_GUIDE_CELLS * b, u, TG.q(c.sub2_full), TG.d(c.mm_hi) + o, TG.d(c.mm_vhi) + o, T.d(c.mm_vlo0)[b]);
 }
 
 // T: the LDS image (the first n_words_lds words of the blob); TG: the whole blob in global memory (fp64 tables of the wide segments)
@@ -330,8 +338,8 @@ NS_DEV EList32 chain_error_list(const Tabs &T, const Tabs &TG, const ChainTab &c
         // The iteration asks the tables two independent questions: the run length of this event (transition row -> record of (type,
         // component) -> guide byte -> two thresholds) and the next match length, which depends on the PREVIOUS match and the draw only
         // (column word -> guide -> two segment words).  Their reads are issued side by side, round by round, in one basic block; whatever
-        // does not fit the common case — a walk of more than two steps, a segment that is not one unit wide, a draw beyond the column, a
-        // previous match >= 256 — is recomputed by the generic functions behind it.
+        // does not fit the common case — a walk of more than two steps, a wide segment, a draw beyond the column, a previous match >= 256 —
+        // is recomputed by the generic functions behind it; a narrow segment is answered from its step list with the word in hand.
         // ---- round 1: transition row (S:1860-1864); column of the previous match (S:1891-1893)
         const uint64_t t0 = trans[3u * state], t1 = trans[3u * state + 1u];
         const uint32_t small = (uint32_t)prev_match < 256u ? 1u : 0u;
@@ -343,7 +351,7 @@ NS_DEV EList32 chain_error_list(const Tabs &T, const Tabs &TG, const ChainTab &c
         const uint64_t mw = error == NS_MIS ? mw0 : error == NS_INS ? mw1 : mw2;
         const uint32_t comp = uy >= mw ? 1u : 0u;                                                  // tmp_rand < weight, mm:44,54
         const uint64_t r0 = rec[2u * (2u * error + comp)], r1 = rec[2u * (2u * error + comp) + 1u];
-        const uint32_t s0 = guide[256u * b + (w.w >> 24)];
+        const uint32_t s0 = guide[NS_GUIDE_CELLS * b + guide_cell(w.w)];
         // ---- round 3: guide byte of the threshold walk; the guide's segment and the next
         const uint32_t go = (uint32_t)r0, rn = (uint32_t)(r0 >> 32);
         uint32_t rv = bytes[8u * (uint32_t)r1 + ns_clz32(~w.z)];
@@ -354,12 +362,27 @@ NS_DEV EList32 chain_error_list(const Tabs &T, const Tabs &TG, const ChainTab &c
         // ---- answers
         const uint32_t k0 = (s0 < ncol ? 1u : 0u) & (uw >= NS_G_THR(g0) ? 1u : 0u), k1 = k0 & (s0 + 1u < ncol ? 1u : 0u) & (uw >= NS_G_THR(g1) ? 1u : 0u);
         const uint64_t g = k0 ? g1 : g0;
-        const uint32_t fast = small & (s0 + k0 < ncol ? 1u : 0u) & (k1 ^ 1u) & ((g & NS_GV_UNIT) ? 1u : 0u);
+        const uint32_t found = small & (s0 + k0 < ncol ? 1u : 0u) & (k1 ^ 1u);                    // g is the draw's segment
+        const uint32_t fast = found & ((g & NS_GV_UNIT) ? 1u : 0u);
         int32_t next = (int32_t)(uint32_t)(g >> 35) - 1;
         const uint32_t c1 = (rv + 1u < rn ? 1u : 0u) & (uz >= ra ? 1u : 0u), c2 = c1 & (rv + 2u < rn ? 1u : 0u) & (uz >= rb ? 1u : 0u);
         rv += c1 + c2;
         if (c2) while (rv + 1u < rn && uz >= T.w[go + rv]) ++rv;                                   // (rare: a run longer than the guide's bound + 2)
-        if (!fast) next = next_match_gv(T, TG, c, prev_match, w.w);
+        NS_CHAIN_COUNT(NS_CNT_ITER);
+        if (k1) NS_CHAIN_COUNT(NS_CNT_K1);
+        if (!fast) {
+            if (found && (g & NS_GV_NARROW)) {                                                     // a narrow segment: its step list answers, with the
+                const uint64_t *t = T.q(c.sub2) + (g >> 35);                                       // segment word already here (ecdf_lookup_pre would walk
+                const uint64_t h = t[0];                                                           // column word, guide and segments again)
+                const uint32_t nt = (uint32_t)(h >> 32);
+                next = (int32_t)(uint32_t)h - (int32_t)nt;
+                for (uint32_t k = 1; k <= nt; ++k) next += uw >= t[k] ? 1 : 0;
+                NS_CHAIN_COUNT(NS_CNT_NARROW);
+            } else {
+                next = next_match_gv(T, TG, c, prev_match, w.w);
+                NS_CHAIN_COUNT(NS_CNT_FALLBACK);
+            }
+        }
         const int32_t step = (int32_t)rv + 1;                                                      // S:1866-1873
         if (prev_match == 0 && next == 0) next = 1;                                                // S:1900-1901
         // ---- the event (S:1875-1882), one store site
@@ -731,7 +754,7 @@ __device__ inline EList32 coop_error_list(const Tabs &TM, const Tabs &T, const C
                         const uint64_t g = k0 ? gb[k] : ga[k];
                         int32_t v = (int32_t)(uint32_t)(g >> 35) - 1;
                         if (!((s0[k] + k0 < nc[k]) && !k1 && (g & NS_GV_UNIT)))
-                            v = ecdf_lookup_gv(gvf + o[k], nc[k], T.h(c.mm_guide) + 256u * b, wi.w, T.q(c.sub2_full), T.d(c.mm_hi) + o[k], T.d(c.mm_vhi) + o[k], T.d(c.mm_vlo0)[b]);
+                            v = ecdf_lookup_gv(gvf + o[k], nc[k], T.h(c.mm_guide) + NS_GUIDE_CELLS * b, wi.w, T.q(c.sub2_full), T.d(c.mm_hi) + o[k], T.d(c.mm_vhi) + o[k], T.d(c.mm_vlo0)[b]);
                         // (the value as the walk will use it — "no two 0-matches", S:1900-1901, is decided there — and the bin of either outcome)
                         if (b0 + k < nb) S.match_tab[lane][b0 + k] = (uint32_t)(uint16_t)v | bin_of(v) << 16 | bin_of(v == 0 ? 1 : v) << 24;
                     }
@@ -739,7 +762,7 @@ __device__ inline EList32 coop_error_list(const Tabs &TM, const Tabs &T, const C
             } else
             for (uint32_t b = 0; b < c.mm_nbins; ++b) {
                 const uint32_t o = seg_off[b];
-                const int32_t v = ecdf_lookup_g(T.d(c.mm_hi) + o, T.d(c.mm_vhi) + o, seg_off[b + 1] - o, T.d(c.mm_vlo0)[b], T.h(c.mm_guide) + 256 * b, wi.w);
+                const int32_t v = ecdf_lookup_g(T.d(c.mm_hi) + o, T.d(c.mm_vhi) + o, seg_off[b + 1] - o, T.d(c.mm_vlo0)[b], T.h(c.mm_guide) + NS_GUIDE_CELLS * b, wi.w);
                 S.match_tab[lane][b] = (uint32_t)(uint16_t)v | bin_of(v) << 16 | bin_of(v == 0 ? 1 : v) << 24;
             }
         }

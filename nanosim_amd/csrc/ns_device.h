@@ -147,6 +147,30 @@ __host__ __device__ inline uint64_t ns_thr_gt(double t) {
     return y <= 0.0 ? 0ull : (uint64_t)y;
 }
 
+// ---- the guide of an ECDF column (fm_guide, mm_guide: built by ns_pack.h, read by ns_chain.h) -------------------------------------------
+// The tail of a match-length ECDF is geometric: a constant number of segments per halving of 1 - p.  A guide of 256 equal cells put dozens
+// of segments into its last cells (every draw that needed a bisection lay in cells >= 232: 4 % of the draws, an iteration of nearly every
+// wavefront), so the cells follow the draw's LEADING ONE BITS, like the guide of the run-length tables: octave = min(leading ones,
+// NS_GUIDE_OCTAVES - 1); inside an octave the five bits behind the ones and the zero that ends them (the last octave has no such zero)
+// select one of 32 cells.  The cell index is monotone in the draw; guide[cell] = segments that end below the cell's smallest draw.
+// 8 octaves are the 256 entries of the equal-cell guide (same LDS image) and leave 0.13 % of the bench model's draws three or more
+// segments behind their guide entry; 10 octaves leave 0.001 % but cost the bench image 1.1 KB and a trained model's prefixes a bit of
+// tail_bits, and measured no faster (profiles/r07/ab_chain_guide.log).  16 octaves x 16 cells are worse than equal cells.
+#ifndef NS_GUIDE_OCTAVES
+#define NS_GUIDE_OCTAVES 8u
+#endif
+#define NS_GUIDE_CELLS (32u * NS_GUIDE_OCTAVES)            // cells (uint16 entries) per column
+NS_HD uint32_t guide_cell(uint32_t u) {
+    const uint32_t ones = ns_clz32(~u);
+    const uint32_t last = ones >= NS_GUIDE_OCTAVES - 1u ? 1u : 0u, l = last ? NS_GUIDE_OCTAVES - 1u : ones;
+    return 32u * l + ((u >> (26u + last - l)) & 31u);
+}
+// the smallest draw of a cell
+NS_HD uint32_t guide_cell_start(uint32_t cell) {
+    const uint32_t l = cell >> 5, m = cell & 31u, last = l == NS_GUIDE_OCTAVES - 1u ? 1u : 0u;
+    return (uint32_t)(0xffffffff00000000ull >> l) | m << (26u + last - l);
+}
+
 // S:1860-1864 on the integer thresholds of a transition row (T0 = ns_thr_lt(a), T1 = ns_thr_lt(a + b)): the intervals are tested in
 // the order mis [0, a), ins [a, a + b), del [1 - c, 1); a draw that falls between a + b and 1 - c (rounding gap) takes del
 // (DESIGN.md section 5.5), so everything that is neither mis nor ins is del

@@ -9,7 +9,9 @@
 //              g[l] = thresholds at or below the smallest draw with l leading one bits (the walk of run_length_r starts there)
 //   mix_rec    6 records {table offset | thresholds << 32, guide offset}, index 2 * type + component — ONE LDS read instead of three
 //              per-lane indexed kernel-argument loads
-//   fm_guide, mm_guide   256-entry guides of the ECDF columns: g[i] = #{s : hi[s] < i/256}
+//   fm_guide, mm_guide   guides of the ECDF columns, NS_GUIDE_CELLS entries each: cells by the leading one bits of the draw (octaves x 32 cells,
+//              guide_cell of ns_device.h — an ECDF's tail is geometric like a run-length table's, equal cells leave dozens of segments in the
+//              last ones); g[cell] = #{s : hi[s] < the cell's smallest draw / 2^32}
 //   mm_bin, mm_bin_lut, mm_seg_off, mm_vlo0   bins of the previous match length (S:1891-1893), the bin of a length < 256, the columns' ranges
 //   mm_gv      (LDS: the hot prefix of every column, ns_device.h; the full columns mm_gv_full and the first-match column fm_gv lie in the global part)
 //              per ECDF segment ONE word: bits 0..32 the threshold ns_thr_gt(hi[s]) (p > hi[s] <=> u >= thr, exactly); bit 33: the
@@ -36,11 +38,11 @@ static inline void ns_pack_chain_tables(const ns_model_tables *t, uint32_t nseg,
     auto put_raw = [&](const void *src, size_t bytes) { uint32_t off = (uint32_t)blob.size(); blob.resize(off + (bytes + 7) / 8, 0);
                                                          memcpy(blob.data() + off, src, bytes); return off; };
     auto put_q = [&](const std::vector<uint64_t> &v) { uint32_t off = (uint32_t)blob.size(); blob.insert(blob.end(), v.begin(), v.end()); return off; };
-    auto guide = [&](const double *hi, uint32_t n) {          // g[i] = #{s : hi[s] < i/256}: lower bound of the segment of any p >= i/256
-        std::vector<uint16_t> g(256);
+    auto guide = [&](const double *hi, uint32_t n) {          // g[cell] = #{s : hi[s] < the smallest draw of the cell / 2^32}: lower bound of the
+        std::vector<uint16_t> g(NS_GUIDE_CELLS);              // segment of every draw of the cell (guide_cell, ns_device.h), and g[cell + 1] an upper one
         uint32_t sidx = 0;
-        for (uint32_t i = 0; i < 256; ++i) {
-            double edge = (double)i / 256.0;
+        for (uint32_t i = 0; i < NS_GUIDE_CELLS; ++i) {
+            double edge = (double)guide_cell_start(i) * 0x1p-32;
             while (sidx < n && hi[sidx] < edge) ++sidx;
             g[i] = (uint16_t)(sidx > 65535u ? 65535u : sidx);
         }
@@ -77,7 +79,7 @@ static inline void ns_pack_chain_tables(const ns_model_tables *t, uint32_t nseg,
     ct.mix_rec = put_raw(rec, sizeof rec);
     ct.n_words_mix = (uint32_t)blob.size();                   // everything unaligned_error_list reads lies in front of here
     ct.fm_n = t->fm_nseg; ct.fm_vlo0 = t->fm_vlo0;
-    { auto g = guide(t->fm_hi, t->fm_nseg); ct.fm_guide = put_raw(g.data(), 512); }
+    { auto g = guide(t->fm_hi, t->fm_nseg); ct.fm_guide = put_raw(g.data(), g.size() * 2); }
     ct.mm_nbins = t->mm_nbins;
     std::vector<int32_t> bins(2 * (size_t)t->mm_nbins);
     for (uint32_t b = 0; b < t->mm_nbins; ++b) {
