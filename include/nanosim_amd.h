@@ -405,6 +405,40 @@ int ns_qual_histograms(ns_ctx *ctx, const uint8_t *cs, uint64_t cs_bytes, const 
                        const uint8_t *qual, uint64_t qual_bytes, const uint64_t *qual_off,
                        const ns_qual_aln *aln, uint32_t n_aln, ns_qual_hist *out);
 
+/* ---- training side: the homopolymer-length model ---------------------------------------------------------------------------------------
+ * replaces the per-alignment loop of src/model_homopolymer_lengths.py (analyze_homopolymers H:64-119, calc_homopolymer_mis_rate H:9-33):
+ * for every homopolymer of the reference line with at least min_hp_len (>= 1) letters its length there and the length the read shows
+ * for it (the reference's fuzzy regular expression, restated in nanosim_amd/csrc/ns_hp_hist.h), counted per class — AT, CG — in
+ *   table[2][cap_ref][cap_read]   dense, in caller-owned host memory (row = reference length, column = read length); a homopolymer with
+ *                                 ref_len >= cap_ref or read_len >= cap_read counts in n_overflow, and max_ref / max_read (the largest
+ *                                 lengths met) say how large the table has to be;
+ *   columns[4]                    insertions, deletions, mismatches, matches over the columns of all homopolymer spans (H:15-31);
+ *   records                       optional (NULL: none): one ns_hp_record per homopolymer, alignment by alignment in the order of the
+ *                                 call and left to right inside an alignment.  n_hp is their number; when it exceeds cap_records none
+ *                                 is written: call again with a larger buffer.
+ * The fits the reference runs on these (H:142-201) are done on the host (nanosim_amd/characterize.py: fit_homopolymers).
+ * ref_lines / query_lines / aln_off: as ns_maf_histograms; an alignment may have at most 2^24 - 1 columns.  Added without an ABI change. */
+typedef struct ns_hp_record {
+    uint32_t aln;               /* index of the alignment in the call */
+    uint32_t start;             /* first letter of the homopolymer in the dash-less reference line */
+    uint32_t ref_len;
+    uint32_t read_base;         /* read_len << 2 | base (0 A, 1 C, 2 G, 3 T) */
+} ns_hp_record;
+typedef struct ns_hp_hist {
+    uint32_t cap_ref, cap_read;   /* in: 1 .. 65536 each, cap_ref * cap_read <= 2^26 */
+    uint64_t *table;              /* in: host buffer of 2 * cap_ref * cap_read counters */
+    ns_hp_record *records;        /* in: host buffer of cap_records records, or NULL */
+    uint64_t cap_records;         /* in */
+    uint64_t n_hp;                /* out: homopolymers (inside the table or not) */
+    uint64_t columns[4];          /* out: NS_HPC_INS, NS_HPC_DEL, NS_HPC_MIS, NS_HPC_MATCH */
+    uint64_t max_ref, max_read;
+    uint64_t n_overflow;
+    double ms_kernel;
+} ns_hp_hist;
+enum { NS_HPC_INS = 0, NS_HPC_DEL = 1, NS_HPC_MIS = 2, NS_HPC_MATCH = 3 };
+int ns_hp_histograms(ns_ctx *ctx, const uint8_t *ref_lines, const uint8_t *query_lines, uint64_t nbytes, const uint64_t *aln_off,
+                     uint32_t n_aln, uint32_t min_hp_len, ns_hp_hist *out);
+
 /* device address of a result buffer (for zero-copy consumers such as torch / RCCL); NULL if absent */
 const void *ns_device_ptr(ns_ctx *ctx, int which);
 

@@ -41,6 +41,7 @@
 #include "ns_pack.h"
 #include "ns_cs_hist.h"
 #include "ns_qual_hist.h"
+#include "ns_hp_hist.h"
 
 // Reads per workgroup of the wave-per-read kernels.  One: read lengths vary by an order of magnitude inside a batch, and a wavefront
 // that is done cannot leave before the longest read of its workgroup is.
@@ -2203,6 +2204,96 @@ __global__ void __launch_bounds__(256) k_qual_count(const uint8_t *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// k_hp_count, k_hp_records: the homopolymer-length model of the training side (ns_hp_hist.h; src/model_homopolymer_lengths.py:9-119 —
+// not the -k stage of the simulation above).  One alignment per thread, both lines through 8-byte CsBytes windows, visited by
+// descending length as k_cs_hist.  The [2][ref_len][read_len] counts: the corner below NS_HPT_CORNER in both lengths — where almost
+// every homopolymer falls — is privatised per workgroup in LDS and flushed once; 2 x 48 x 48 x 4 B = 18 KB leaves eight workgroups
+// (32 wavefronts, the limit) on a compute unit's 160 KB.  What lies outside goes to the caller's dense table by global atomics, or,
+// beyond its caps, to the overflow counter.  A workgroup counts 256 alignments of fewer than 2^24 columns each (the host checks), so
+// no 32-bit counter can wrap.  The column counters, the number of homopolymers and the overflow are summed over the wavefront first.
+// k_hp_records repeats the walk and writes the homopolymers of alignment a from slot[a] on (the exclusive scan of k_hp_count's
+// per-alignment numbers; slot[n_aln] is their total): nothing when the caller's buffer is too small for all of them.
+// ---------------------------------------------------------------------------------------------------------
+#define NS_HPT_CORNER 48u
+#define NS_HPT_LDS_WORDS (2u * NS_HPT_CORNER * NS_HPT_CORNER)
+enum { HPT_COLUMNS = 0, HPT_N_HP = 4, HPT_OVERFLOW = 5, HPT_MAX_REF = 6, HPT_MAX_READ = 7, HPT_WORDS = 8 };   // the device image of the small results
+struct HpTrainDev {
+    unsigned long long *table;        // [2][cap_ref][cap_read]
+    unsigned long long *small;        // [HPT_WORDS]
+    uint32_t cap_ref, cap_read;
+};
+struct HpTrainAcc {
+    uint32_t *l;                      // the workgroup's corner of the table
+    const HpTrainDev *H;
+    uint32_t mx_ref, mx_read, over, col[4];
+    __device__ __forceinline__ void hp(uint32_t cls, uint8_t, uint32_t ref_len, uint32_t read_len, uint32_t, uint32_t) {
+        mx_ref = mx_ref > ref_len ? mx_ref : ref_len;
+        mx_read = mx_read > read_len ? mx_read : read_len;
+        if (ref_len >= H->cap_ref || read_len >= H->cap_read) ++over;
+        else if (ref_len < NS_HPT_CORNER && read_len < NS_HPT_CORNER) atomicAdd(&l[(cls * NS_HPT_CORNER + ref_len) * NS_HPT_CORNER + read_len], 1u);
+        else atomicAdd(&H->table[((uint64_t)cls * H->cap_ref + ref_len) * H->cap_read + read_len], 1ull);
+    }
+    __device__ __forceinline__ void columns(uint32_t ins, uint32_t del, uint32_t mis, uint32_t match) {
+        col[HPC_INS] = ins; col[HPC_DEL] = del; col[HPC_MIS] = mis; col[HPC_MATCH] = match;
+    }
+};
+__global__ void __launch_bounds__(256) k_hp_count(const uint8_t *__restrict__ ref, const uint8_t *__restrict__ qry, const uint64_t *__restrict__ off,
+                                                  uint32_t n_aln, uint32_t min_hp_len, HpTrainDev H, const uint32_t *__restrict__ order,
+                                                  unsigned long long *__restrict__ n_per_aln) {
+    __shared__ uint32_t cnt[NS_HPT_LDS_WORDS];
+    for (uint32_t i = threadIdx.x; i < NS_HPT_LDS_WORDS; i += blockDim.x) cnt[i] = 0;
+    __syncthreads();
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    HpTrainAcc acc{cnt, &H, 0u, 0u, 0u, {0u, 0u, 0u, 0u}};
+    uint32_t n_hp = 0;
+    if (tid < n_aln) {
+        const uint64_t a = order ? order[tid] : tid;
+        CsBytes rb(ref + off[a]), qb(qry + off[a]);
+        n_hp = hp_hist_alignment(rb, qb, off[a + 1] - off[a], min_hp_len, acc);
+        n_per_aln[a] = n_hp;
+    }
+    // (every lane of the workgroup comes here: the wavefront sums need them all)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t sums[6] = {acc.col[0], acc.col[1], acc.col[2], acc.col[3], n_hp, acc.over};
+#pragma unroll
+    for (uint32_t j = 0; j < 6u; ++j) {
+        const unsigned long long s = wave_sum(sums[j]);
+        if (lane == 0 && s) atomicAdd(&H.small[j], s);          // HPT_COLUMNS .. HPT_OVERFLOW
+    }
+    uint32_t mr = acc.mx_ref, mq = acc.mx_read;
+    for (int o = 32; o > 0; o >>= 1) { mr = max(mr, (uint32_t)__shfl_xor((int)mr, o)); mq = max(mq, (uint32_t)__shfl_xor((int)mq, o)); }
+    if (lane == 0 && mr) atomicMax(&H.small[HPT_MAX_REF], (unsigned long long)mr);
+    if (lane == 0 && mq) atomicMax(&H.small[HPT_MAX_READ], (unsigned long long)mq);
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < NS_HPT_LDS_WORDS; i += blockDim.x) {
+        const uint32_t v = cnt[i];
+        if (!v) continue;                                           // (an entry counted here lies inside the caps: HpTrainAcc::hp)
+        const uint32_t cls = i / (NS_HPT_CORNER * NS_HPT_CORNER), r = i / NS_HPT_CORNER % NS_HPT_CORNER, q = i % NS_HPT_CORNER;
+        atomicAdd(&H.table[((uint64_t)cls * H.cap_ref + r) * H.cap_read + q], (unsigned long long)v);
+    }
+}
+struct HpRecordSink {
+    ns_hp_record *rec; uint64_t at, end; uint32_t aln;
+    __device__ __forceinline__ void hp(uint32_t, uint8_t base, uint32_t ref_len, uint32_t read_len, uint32_t start, uint32_t) {
+        const uint32_t code = base == 'A' ? 0u : base == 'C' ? 1u : base == 'G' ? 2u : 3u;
+        if (at < end) rec[at] = ns_hp_record{aln, start, ref_len, read_len << 2 | code};
+        ++at;
+    }
+    __device__ __forceinline__ void columns(uint32_t, uint32_t, uint32_t, uint32_t) {}
+};
+__global__ void __launch_bounds__(256) k_hp_records(const uint8_t *__restrict__ ref, const uint8_t *__restrict__ qry, const uint64_t *__restrict__ off,
+                                                    uint32_t n_aln, uint32_t min_hp_len, const uint32_t *__restrict__ order,
+                                                    const unsigned long long *__restrict__ slot, ns_hp_record *__restrict__ rec, uint64_t cap_records) {
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= n_aln || slot[n_aln] > cap_records) return;
+    const uint64_t a = order ? order[tid] : tid;
+    if (slot[a + 1] == slot[a]) return;
+    HpRecordSink sink{rec, slot[a], slot[a + 1], (uint32_t)a};
+    CsBytes rb(ref + off[a]), qb(qry + off[a]);
+    hp_hist_alignment(rb, qb, off[a + 1] - off[a], min_hp_len, sink);
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // reference normalisation (once per ns_set_reference): upper-case, non-IUPAC -> N
 // ---------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_normalise(uint8_t *bases, uint64_t n) {
@@ -2254,7 +2345,7 @@ enum Evt {
     EV_HP_BEGIN, EV_HP_END,             // NS_K_HP: one -k stage, summed over the stages of the call (hp_stage1)
     EV_DRAWS_ON_HOST,                   // no timing pair: the filtered draws of a metagenome pass have reached the host
     EV_RECKERNEL_BEGIN, EV_RECKERNEL_END,   // NS_K_RECORD_KERNEL: the record kernel itself (when ns_ctx::rec_timed)
-    EV_HIST_BEGIN, EV_HIST_END,         // ns_cs_hist.ms_kernel (histograms), ns_qual_hist.ms_kernel (ns_qual_histograms)
+    EV_HIST_BEGIN, EV_HIST_END,         // ns_cs_hist.ms_kernel (histograms), ns_qual_hist.ms_kernel (ns_qual_histograms), ns_hp_hist.ms_kernel (ns_hp_histograms)
     EV_COUNT
 };
 static const struct { Evt from, to; int slot; } EVT_TIMED[] = {
@@ -4324,6 +4415,82 @@ int ns_qual_histograms(ns_ctx *ctx, const uint8_t *cs, uint64_t cs_bytes, const 
     if (e != hipSuccess) return fail(ctx, NS_EHIP, std::string("ns_qual_histograms: ") + hipGetErrorString(e));
     for (int c = 0; c < 5; ++c) for (int q = 0; q < 128; ++q) out->hist[c][q] = res[(size_t)c * 128 + q];
     out->n_short = res[NS_QH_OUT_SHORT]; out->n_bad_qual = res[NS_QH_OUT_BAD];
+    out->ms_kernel = ms;
+    return NS_OK;
+}
+
+// the homopolymer-length model of the training side (include/nanosim_amd.h: ns_hp_hist; src/model_homopolymer_lengths.py:9-119)
+int ns_hp_histograms(ns_ctx *ctx, const uint8_t *ref_lines, const uint8_t *query_lines, uint64_t nbytes, const uint64_t *aln_off, uint32_t n_aln,
+                     uint32_t min_hp_len, ns_hp_hist *out) {
+    if (!ctx) return NS_EINVAL;
+    if (!out || !out->table || (n_aln && (!aln_off || ((!ref_lines || !query_lines) && nbytes)))) return fail(ctx, NS_EINVAL, "ns_hp_histograms: null argument");
+    for (uint32_t a = 0; a < n_aln; ++a) {
+        if (aln_off[a] > aln_off[a + 1] || aln_off[a + 1] > nbytes) return fail(ctx, NS_EINVAL, "ns_hp_histograms: offsets not ascending / beyond the lines");
+        if (aln_off[a + 1] - aln_off[a] >= (1ull << 24))        // (the 32-bit counters of a workgroup of k_hp_count, the 30 bits of a record's read_len)
+            return fail(ctx, NS_EINVAL, "ns_hp_histograms: alignment " + std::to_string(a) + " has 2^24 columns or more");
+    }
+    if (!min_hp_len) return fail(ctx, NS_EINVAL, "ns_hp_histograms: min_hp_len must be at least 1");
+    const uint32_t cap_ref = out->cap_ref, cap_read = out->cap_read;
+    if (!cap_ref || cap_ref > 65536u || !cap_read || cap_read > 65536u) return fail(ctx, NS_EINVAL, "ns_hp_histograms: cap_ref and cap_read must be 1 .. 65536");
+    if ((uint64_t)cap_ref * cap_read > (1ull << 26)) return fail(ctx, NS_EINVAL, "ns_hp_histograms: cap_ref * cap_read must not exceed 2^26");
+    const size_t table_bytes = (size_t)2 * cap_ref * cap_read * 8;
+    const uint64_t cap_records = out->records ? out->cap_records : 0;
+    out->n_hp = out->max_ref = out->max_read = out->n_overflow = 0; out->ms_kernel = 0;
+    memset(out->columns, 0, sizeof out->columns);
+    if (!n_aln) { memset(out->table, 0, table_bytes); return NS_OK; }
+    HIPCHK(hipSetDevice(ctx->device));
+    void *d_ref = nullptr, *d_qry = nullptr, *d_off = nullptr, *d_small = nullptr, *d_table = nullptr, *d_cnt = nullptr, *d_slot = nullptr, *d_rec = nullptr,
+         *d_key = nullptr, *d_tmp = nullptr;
+    auto release = [&]() { for (void *p : {d_ref, d_qry, d_off, d_small, d_table, d_cnt, d_slot, d_rec, d_key, d_tmp}) if (p) { hipError_t e = hipFree(p); (void)e; } };
+    hipError_t e = hipMalloc(&d_ref, (size_t)nbytes + 16);                // (16 bytes to spare: the window loads of CsBytes)
+    if (e == hipSuccess) e = hipMalloc(&d_qry, (size_t)nbytes + 16);
+    if (e == hipSuccess) e = hipMalloc(&d_off, ((size_t)n_aln + 1) * 8);
+    if (e == hipSuccess) e = hipMalloc(&d_small, HPT_WORDS * 8);
+    if (e == hipSuccess) e = hipMalloc(&d_table, table_bytes);
+    if (e == hipSuccess) e = hipMalloc(&d_cnt, ((size_t)n_aln + 1) * 8);
+    if (e == hipSuccess && out->records) e = hipMalloc(&d_slot, ((size_t)n_aln + 1) * 8);
+    if (e == hipSuccess && cap_records) e = hipMalloc(&d_rec, (size_t)cap_records * sizeof(ns_hp_record));
+    if (e != hipSuccess) { release(); (void)hipGetLastError(); return fail(ctx, NS_ENOMEM, std::string("ns_hp_histograms: hipMalloc: ") + hipGetErrorString(e)); }
+    hipStream_t st = ctx->stream;
+    if (nbytes) e = hipMemcpyAsync(d_ref, ref_lines, (size_t)nbytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && nbytes) e = hipMemcpyAsync(d_qry, query_lines, (size_t)nbytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_off, aln_off, ((size_t)n_aln + 1) * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_small, 0, HPT_WORDS * 8, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_table, 0, table_bytes, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, ((size_t)n_aln + 1) * 8, st);      // (entry n_aln stays 0: the scan leaves the total in slot[n_aln])
+    if (e == hipSuccess) e = hipEventRecord(ctx->evt[EV_HIST_BEGIN], st);
+    uint32_t *d_order = nullptr;
+    if (e == hipSuccess) e = order_by_length(st, (const uint64_t *)d_off, n_aln, &d_key, &d_tmp, &d_order);
+    const dim3 grid((n_aln + 255u) / 256u), block(256);
+    if (e == hipSuccess) {
+        HpTrainDev H{(unsigned long long *)d_table, (unsigned long long *)d_small, cap_ref, cap_read};
+        k_hp_count<<<grid, block, 0, st>>>((const uint8_t *)d_ref, (const uint8_t *)d_qry, (const uint64_t *)d_off, n_aln, min_hp_len, H, d_order,
+                                           (unsigned long long *)d_cnt);
+        e = hipGetLastError();
+    }
+    int rc = NS_OK;
+    if (e == hipSuccess && out->records) {
+        rc = scan_sum(ctx, (const unsigned long long *)d_cnt, (unsigned long long *)d_slot, (size_t)n_aln + 1);
+        if (rc == NS_OK && cap_records) {
+            k_hp_records<<<grid, block, 0, st>>>((const uint8_t *)d_ref, (const uint8_t *)d_qry, (const uint64_t *)d_off, n_aln, min_hp_len, d_order,
+                                                 (const unsigned long long *)d_slot, (ns_hp_record *)d_rec, cap_records);
+            e = hipGetLastError();
+        }
+    }
+    if (e == hipSuccess) e = hipEventRecord(ctx->evt[EV_HIST_END], st);
+    unsigned long long small[HPT_WORDS] = {0};
+    if (e == hipSuccess) e = hipMemcpyAsync(small, d_small, sizeof small, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(out->table, d_table, table_bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && rc == NS_OK && small[HPT_N_HP] && small[HPT_N_HP] <= cap_records)
+        e = hipMemcpy(out->records, d_rec, (size_t)small[HPT_N_HP] * sizeof(ns_hp_record), hipMemcpyDeviceToHost);
+    float ms = 0;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ctx->evt[EV_HIST_BEGIN], ctx->evt[EV_HIST_END]);
+    release();
+    if (rc != NS_OK) return rc;
+    if (e != hipSuccess) return fail(ctx, NS_EHIP, std::string("ns_hp_histograms: ") + hipGetErrorString(e));
+    for (int c = 0; c < 4; ++c) out->columns[c] = small[HPT_COLUMNS + c];
+    out->n_hp = small[HPT_N_HP]; out->n_overflow = small[HPT_OVERFLOW]; out->max_ref = small[HPT_MAX_REF]; out->max_read = small[HPT_MAX_READ];
     out->ms_kernel = ms;
     return NS_OK;
 }

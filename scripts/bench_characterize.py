@@ -6,8 +6,15 @@ alignments/s, the kernel's own time and its fraction of the HBM roofline (algori
 --qualities: the base-quality histograms instead (ns_qual_histograms: the same cs strings plus a QUAL string per alignment, ~8.4 KB per
 read): milliseconds of the two phases (the mark phase alone from a second context with NS_DEBUG_SKIP = 1 << 20, the count phase as the
 difference), the end-to-end time, GB/s over cs + quality bytes — as measured and scaled to 10^6 alignments.
-    python scripts/bench_characterize.py --qualities [--alignments 200000]"""
+    python scripts/bench_characterize.py --qualities [--alignments 200000]
+--homopolymers: the homopolymer-length model instead (ns_hp_histograms, min_hp_len 5): the same reads as aligned line pairs — the
+reference's letters along a piece, `-` for the gaps, the events as mismatched / inserted / deleted columns —, ~8.5 KB per line; prints
+alignments/s, the kernels' time (k_hp_count alone; with --records also the scan and k_hp_records) and GB/s over both lines.
+--host-walk times the same walk compiled for the host (tests/hp_train_host.cpp) on one core over the same input; --dump-maf PATH writes
+the first 2 000 pairs as `s` lines (what the reference's analyze_homopolymers reads).
+    python scripts/bench_characterize.py --homopolymers [--records] [--host-walk] [--dump-maf PATH] [--alignments 200000]"""
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -24,6 +31,10 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--alignments", type=int, default=200_000)
 ap.add_argument("--steps", type=int, default=3)
 ap.add_argument("--qualities", action="store_true")
+ap.add_argument("--homopolymers", action="store_true")
+ap.add_argument("--records", action="store_true")
+ap.add_argument("--host-walk", action="store_true")
+ap.add_argument("--dump-maf", default=None)
 a = ap.parse_args()
 SEED = 20260926
 tmp = tempfile.mkdtemp(prefix="nschar_")
@@ -40,6 +51,69 @@ b = eng.generate(E.make_params(seed=SEED, first_read=0, n_reads=n_src, max_len=r
 pieces, events = b.pieces(), b.events()
 rng = np.random.default_rng(SEED)
 letters = np.frombuffer(b"acgt", dtype=np.uint8)
+if a.homopolymers:
+    # the two lines of an alignment: the reference's letters from a random place of the genome (its homopolymer runs included), the
+    # events of the piece as columns
+    pairs = []
+    dash = ord("-")
+    other = np.full(256, ord("A"), dtype=np.uint8)            # the letter a mismatch column shows: another one than the reference's
+    other[np.frombuffer(b"ACGTacgt", dtype=np.uint8)] = np.frombuffer(b"CGTACGTA", dtype=np.uint8)
+    for pc in pieces:
+        ev = events[int(pc["ev_off"]):int(pc["ev_off"]) + int(pc["n_ev"])]
+        n = int(pc["ref_len"])
+        at = int(rng.integers(0, len(seq) - n - 1))
+        r = seq[at:at + n].copy()
+        q = r.copy()
+        ins_at, ins_n = [], []
+        for e in ev:
+            epos, ln, ty = int(e["pos"]), int(e["info"]) & 0xfff, (int(e["info"]) >> 12) & 3
+            if ty == 0:
+                q[epos:epos + ln] = other[r[epos:epos + ln]]
+            elif ty == 1:
+                ins_at.append(epos); ins_n.append(ln)
+            else:
+                q[epos:epos + ln] = dash
+        if ins_at:
+            where = np.repeat(np.minimum(ins_at, n), ins_n)
+            r, q = np.insert(r, where, dash), np.insert(q, where, letters[rng.integers(0, 4, len(where))] - 32)
+        pairs.append((r.tobytes(), q.tobytes()))
+    pairs = (pairs * (a.alignments // len(pairs) + 1))[:a.alignments]
+    nbytes = 2 * sum(len(x[0]) for x in pairs)
+    if a.dump_maf:
+        with open(a.dump_maf, "w") as f:
+            for r, q in pairs[:2000]:
+                f.write("s ref 0 %d + %d %s\ns read 0 %d + %d %s\n" % (len(r) - r.count(b"-"), len(seq), r.decode(), len(q) - q.count(b"-"),
+                                                                       len(q), q.decode()))
+    t = characterize.count_homopolymers(eng, pairs, 5, records=a.records)          # sizes the table and the record buffer, warms up
+    caps = dict(cap_ref=max(64, 1 << int(t["table"].shape[1] - 1).bit_length()), cap_read=max(64, 1 << int(t["table"].shape[2] - 1).bit_length()),
+                cap_records=max(t["n_hp"], 1))
+    t0 = time.perf_counter()
+    ms = [characterize.count_homopolymers(eng, pairs, 5, records=a.records, **caps)["ms_kernel"] for _ in range(a.steps)]
+    dt = (time.perf_counter() - t0) / a.steps
+    res = {"metric": "homopolymer-length model, alignments/s (ns_hp_histograms incl. packing + H2D)", "value": a.alignments / dt,
+           "alignments": a.alignments, "line_bytes": nbytes, "bytes_per_alignment": nbytes / a.alignments, "homopolymers": t["n_hp"],
+           "records": bool(a.records), "kernel_ms": float(np.mean(ms)), "kernel_alignments_per_s": a.alignments / (float(np.mean(ms)) * 1e-3),
+           "kernel_gb_per_s": nbytes / (float(np.mean(ms)) * 1e-3) / 1e9, "end_to_end_s": dt,
+           "max_ref_len": int(t["table"].shape[1] - 1), "max_read_len": int(t["table"].shape[2] - 1)}
+    if a.host_walk:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from test_hp_train import build_host_walk
+        host = build_host_walk()
+        th = characterize.count_homopolymers(host, pairs, 5, records=a.records, **caps)
+        assert np.array_equal(th["table"], t["table"]) and np.array_equal(th["columns"], t["columns"])
+        # the call alone (no packing): the shim is handed the packed buffers
+        rb, qb = b"".join(x[0] for x in pairs), b"".join(x[1] for x in pairs)
+        off = np.cumsum([0] + [len(x[0]) for x in pairs]).astype(np.uint64)
+        h = characterize.NsHpHist()
+        tab = np.zeros((2, caps["cap_ref"], caps["cap_read"]), dtype=np.uint64)
+        h.cap_ref, h.cap_read, h.table = caps["cap_ref"], caps["cap_read"], tab.ctypes.data
+        t0 = time.perf_counter()
+        host.L.ns_hp_histograms(None, rb, qb, len(rb), off.ctypes.data, len(pairs), 5, C.byref(h))
+        res["host_walk_one_core_s"] = time.perf_counter() - t0
+        res["host_walk_alignments_per_s"] = a.alignments / res["host_walk_one_core_s"]
+    print(json.dumps(res))
+    eng.close()
+    sys.exit(0)
 cs, cover = [], []
 for pc in pieces:
     ev = events[int(pc["ev_off"]):int(pc["ev_off"]) + int(pc["n_ev"])]
