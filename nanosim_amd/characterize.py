@@ -144,26 +144,47 @@ def cs_from_sam(path: str):
     return out
 
 
-def count(eng, cs_list, cap: int = 2048) -> dict:
-    """the counts of hist()'s loop for these alignments, from the GPU (ns_cs_histograms)"""
-    blobs = [c.encode() if isinstance(c, str) else bytes(c) for c in cs_list]
+def _pack(strings):
+    """(the bytes of these str / bytes one behind the other plus a NUL as a uint8 array, their len + 1 offsets as uint64)"""
+    blobs = [x.encode() if isinstance(x, str) else bytes(x) for x in strings]
     off = np.zeros(len(blobs) + 1, dtype=np.uint64)
     np.cumsum([len(b) for b in blobs], out=off[1:])
-    data = np.frombuffer(b"".join(blobs) + b"\0", dtype=np.uint8)
+    return np.frombuffer(b"".join(blobs) + b"\0", dtype=np.uint8), off
+
+
+def _pack_pairs(ref_lines, query_lines):
+    """_pack of the two lines of every alignment: (reference bytes, query bytes, the offsets of both)"""
+    ref, off = _pack(ref_lines)
+    qry, q_off = _pack(query_lines)
+    if not np.array_equal(off, q_off):
+        raise ValueError("the two lines of an alignment differ in length")
+    return ref, qry, off
+
+
+def _count(call, cap: int) -> dict:
+    """count and count_maf: `call(h)` makes the library's call on an NsCsHist; repeated with a larger match matrix while it overflows"""
     while True:
         h = NsCsHist()
         m2 = np.zeros((cap, cap), dtype=np.uint64)
         h.cap_match2d, h.match_list = cap, m2.ctypes.data
-        eng._check(eng.L.ns_cs_histograms(eng.ctx, data.ctypes.data, int(off[-1]), off.ctypes.data, len(blobs), C.byref(h)))
-        if h.n_skip:
-            raise ValueError("long-form cs strings (`=` items) are not supported: the reference's parse_cs loses the pairing of its two "
-                             "lists on them (src/besthit_to_histogram.py:49-65)")
+        call(h)
         if not h.n_match2d_overflow:
             break
         cap = 1 << int(h.max_match).bit_length()                       # the matrix has to hold index max_match
-    dic = np.ctypeslib.as_array(h.dic).copy()
-    return dict(dic=dic, match_list=m2, error_list=np.ctypeslib.as_array(h.error_list).copy().reshape(6, 3),
+    return dict(dic=np.ctypeslib.as_array(h.dic).copy(), match_list=m2, error_list=np.ctypeslib.as_array(h.error_list).copy().reshape(6, 3),
                 first_error=np.ctypeslib.as_array(h.first_error).copy(), max_match=int(h.max_match), ms_kernel=float(h.ms_kernel))
+
+
+def count(eng, cs_list, cap: int = 2048) -> dict:
+    """the counts of hist()'s loop for these alignments, from the GPU (ns_cs_histograms)"""
+    data, off = _pack(cs_list)
+
+    def call(h):
+        eng._check(eng.L.ns_cs_histograms(eng.ctx, data.ctypes.data, int(off[-1]), off.ctypes.data, len(off) - 1, C.byref(h)))
+        if h.n_skip:
+            raise ValueError("long-form cs strings (`=` items) are not supported: the reference's parse_cs loses the pairing of its two "
+                             "lists on them (src/besthit_to_histogram.py:49-65)")
+    return _count(call, cap)
 
 
 def maf_pairs(path: str):
@@ -191,24 +212,9 @@ def maf_pairs(path: str):
 
 def count_maf(eng, pairs, cap: int = 2048) -> dict:
     """the counts of hist()'s MAF loop for these alignments, from the GPU (ns_maf_histograms)"""
-    rb = [a.encode() if isinstance(a, str) else bytes(a) for a, _ in pairs]
-    qb = [b.encode() if isinstance(b, str) else bytes(b) for _, b in pairs]
-    if any(len(a) != len(b) for a, b in zip(rb, qb)):
-        raise ValueError("the two lines of an alignment differ in length")
-    off = np.zeros(len(rb) + 1, dtype=np.uint64)
-    np.cumsum([len(b) for b in rb], out=off[1:])
-    ref = np.frombuffer(b"".join(rb) + b"\0", dtype=np.uint8)
-    qry = np.frombuffer(b"".join(qb) + b"\0", dtype=np.uint8)
-    while True:
-        h = NsCsHist()
-        m2 = np.zeros((cap, cap), dtype=np.uint64)
-        h.cap_match2d, h.match_list = cap, m2.ctypes.data
-        eng._check(eng.L.ns_maf_histograms(eng.ctx, ref.ctypes.data, qry.ctypes.data, int(off[-1]), off.ctypes.data, len(rb), C.byref(h)))
-        if not h.n_match2d_overflow:
-            break
-        cap = 1 << int(h.max_match).bit_length()
-    return dict(dic=np.ctypeslib.as_array(h.dic).copy(), match_list=m2, error_list=np.ctypeslib.as_array(h.error_list).copy().reshape(6, 3),
-                first_error=np.ctypeslib.as_array(h.first_error).copy(), max_match=int(h.max_match), ms_kernel=float(h.ms_kernel))
+    ref, qry, off = _pack_pairs([a for a, _ in pairs], [b for _, b in pairs])
+    return _count(lambda h: eng._check(eng.L.ns_maf_histograms(eng.ctx, ref.ctypes.data, qry.ctypes.data, int(off[-1]), off.ctypes.data,
+                                                               len(off) - 1, C.byref(h))), cap)
 
 
 def _dict_len(cnt, initial):
@@ -353,14 +359,8 @@ def quals_from_sam(path: str, primary_only: bool = True):
 
 def _qual_call(eng, entries) -> NsQualHist:
     """ns_qual_histograms on [(cs, QUAL, head, tail, unmapped)], in this order"""
-    cs = [e[0].encode() if isinstance(e[0], str) else bytes(e[0]) for e in entries]
-    qs = [e[1].encode() if isinstance(e[1], str) else bytes(e[1]) for e in entries]
-    cs_off = np.zeros(len(entries) + 1, dtype=np.uint64)
-    q_off = np.zeros(len(entries) + 1, dtype=np.uint64)
-    np.cumsum([len(b) for b in cs], out=cs_off[1:])
-    np.cumsum([len(b) for b in qs], out=q_off[1:])
-    cs_data = np.frombuffer(b"".join(cs) + b"\0", dtype=np.uint8)
-    q_data = np.frombuffer(b"".join(qs) + b"\0", dtype=np.uint8)
+    cs_data, cs_off = _pack([e[0] for e in entries])
+    q_data, q_off = _pack([e[1] for e in entries])
     aln = np.zeros(len(entries), dtype=QUAL_ALN_DTYPE)
     for i, e in enumerate(entries):
         aln[i] = (e[2], e[3], 1 if e[4] else 0, 0)
@@ -462,14 +462,7 @@ def count_homopolymers(eng, pairs, min_hp_len: int = 5, records: bool = False, c
     The caps are first sizes only: a call that reports an overflow is repeated with what it asks for."""
     if min_hp_len < 1:
         raise ValueError("min_hp_len must be at least 1 (the reference's `A{0,}` matches empty strings)")
-    rb = [p[-2].encode() if isinstance(p[-2], str) else bytes(p[-2]) for p in pairs]
-    qb = [p[-1].encode() if isinstance(p[-1], str) else bytes(p[-1]) for p in pairs]
-    if any(len(a) != len(b) for a, b in zip(rb, qb)):
-        raise ValueError("the two lines of an alignment differ in length")
-    off = np.zeros(len(rb) + 1, dtype=np.uint64)
-    np.cumsum([len(b) for b in rb], out=off[1:])
-    ref = np.frombuffer(b"".join(rb) + b"\0", dtype=np.uint8)
-    qry = np.frombuffer(b"".join(qb) + b"\0", dtype=np.uint8)
+    ref, qry, off = _pack_pairs([p[-2] for p in pairs], [p[-1] for p in pairs])
     if cap_records is None:
         cap_records = int(off[-1]) // (4 * min_hp_len) + 16
     while True:
@@ -479,7 +472,7 @@ def count_homopolymers(eng, pairs, min_hp_len: int = 5, records: bool = False, c
         h.cap_ref, h.cap_read, h.table = cap_ref, cap_read, table.ctypes.data
         if records:
             h.records, h.cap_records = rec.ctypes.data, len(rec)
-        eng._check(eng.L.ns_hp_histograms(eng.ctx, ref.ctypes.data, qry.ctypes.data, int(off[-1]), off.ctypes.data, len(rb), int(min_hp_len), C.byref(h)))
+        eng._check(eng.L.ns_hp_histograms(eng.ctx, ref.ctypes.data, qry.ctypes.data, int(off[-1]), off.ctypes.data, len(off) - 1, int(min_hp_len), C.byref(h)))
         again = False
         if h.n_overflow:
             cap_ref = max(cap_ref, 1 << int(h.max_ref).bit_length())           # the table has to hold index max_ref

@@ -16,6 +16,7 @@
 //   k_errlog            wave/read     _aligned_error_profile rows                           (S:2006-2008)
 // Metagenome worker calls run k_lengths / k_chain per PASS of the reference's while loop (S:844-1040) with k_meta_* around them; the lists of a
 // pass are launched before the host has walked the species quotas (assign_species), k_meta_tail does positions + acceptance afterwards.
+// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms: at the end of the host part) has its kernels in ns_train.h.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdio.h>
@@ -42,6 +43,7 @@
 #include "ns_cs_hist.h"
 #include "ns_qual_hist.h"
 #include "ns_hp_hist.h"
+#include "ns_train.h"
 
 // Reads per workgroup of the wave-per-read kernels.  One: read lengths vary by an order of magnitude inside a batch, and a wavefront
 // that is done cannot leave before the longest read of its workgroup is.
@@ -324,11 +326,6 @@ __global__ void __launch_bounds__(SMALL ? 64 : 256, SMALL ? 7 : 1) k_lengths(Gen
 // descending length (A.list) so that the 64 chains of a wavefront have similar trip counts; the chain tables
 // live in LDS when they fit.  A rejected read is queued for the next pass (attempt a+1).
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // loop iterations per lane of the wave-per-read unaligned chain (coopk_unaligned_error_list): 4 = 116 VGPRs, 3 = 98, 2 = 82
 #ifndef NS_UCOOP_ITER
 #define NS_UCOOP_ITER 3
@@ -2035,265 +2032,6 @@ __global__ void __launch_bounds__(64) k_errlog(GenArgs A) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// k_cs_hist: the counting loop of the characterisation stage (ns_cs_hist.h; src/besthit_to_histogram.py:316-365), one alignment per
-// thread.  The 1-D histograms and the transition counters are privatised per workgroup in LDS (their hot bins — one-base mismatches,
-// short matches — would serialise millions of atomics on a few addresses) and flushed once; the (previous match, next match) matrix is
-// large and sparse: global atomics.
-// ---------------------------------------------------------------------------------------------------------
-struct CsHistDev {
-    unsigned long long *dic;          // [5][1001]
-    unsigned long long *err;          // [18] error_list, [3] first_error behind it
-    unsigned long long *misc;         // [0] max_match [1] match_list overflow [2] `=` items
-    unsigned long long *m2; uint32_t cap2;
-};
-#define NS_CSH_LDS_WORDS (5u * 1001u + 24u + 1u)
-struct CsAccDev {
-    uint32_t *l;                      // the workgroup's LDS counters: dic[5][1001], err[18], first[3], (3 spare), the largest match
-    const CsHistDev *H;
-    uint32_t mx;                      // largest length this thread handed to add_match
-    __device__ __forceinline__ void d1(uint32_t which, uint32_t v) { if (v <= NS_CS_DICT_MAX) atomicAdd(&l[which * 1001u + v], 1u); }
-    __device__ __forceinline__ void m2(uint32_t p, uint32_t s) {
-        const uint32_t m = p > s ? p : s;
-        mx = mx > m ? mx : m;
-        if (H->m2 && m < H->cap2) atomicAdd(&H->m2[(uint64_t)p * H->cap2 + s], 1ull);
-        else atomicAdd(&H->misc[1], 1ull);
-    }
-    __device__ __forceinline__ void err(uint32_t i) { atomicAdd(&l[5u * 1001u + i], 1u); }
-    __device__ __forceinline__ void first(uint32_t i) { atomicAdd(&l[5u * 1001u + 18u + i], 1u); }
-    __device__ __forceinline__ void skip() { atomicAdd(&H->misc[2], 1ull); }
-};
-__global__ void __launch_bounds__(256) k_cs_len(const uint64_t *__restrict__ off, uint32_t n_aln, uint32_t *__restrict__ key, uint32_t *__restrict__ idx) {
-    const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
-    if (a >= n_aln) return;
-    const uint64_t n = off[a + 1] - off[a];
-    key[a] = n > 0xffffffffull ? 0xffffffffu : (uint32_t)n; idx[a] = a;
-}
-// qry != nullptr: the MAF branch — cs holds the reference lines, qry the query lines (maf_hist_alignment)
-__global__ void __launch_bounds__(256) k_cs_hist(const uint8_t *__restrict__ cs, const uint64_t *__restrict__ off, uint32_t n_aln, CsHistDev H,
-                                                 const uint32_t *__restrict__ order, const uint8_t *__restrict__ qry) {
-    __shared__ uint32_t cnt[NS_CSH_LDS_WORDS];
-    for (uint32_t i = threadIdx.x; i < NS_CSH_LDS_WORDS; i += blockDim.x) cnt[i] = 0;
-    __syncthreads();
-    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid < n_aln) {
-        const uint64_t a = order ? order[tid] : tid;          // visited by descending length: the 64 walks of a wavefront have similar trip counts
-        const uint8_t *s = cs + off[a];
-        const uint64_t n = off[a + 1] - off[a];
-        // prev_match is only read before this alignment assigns it when its first op is an error: then it is what the alignments in
-        // front of it left (the reference never resets it between alignments)
-        CsAccDev acc{cnt, &H, 0u};
-        if (qry) maf_hist_alignment(s, qry + off[a], n, acc);
-        else {
-            uint32_t pm = 0;
-            CsBytes sb(s);                                   // (an 8-byte register window over the thread's string: ns_cs_hist.h)
-            { CsCursor c; cs_cursor_init(c); int t; uint32_t l; if (cs_next_op(sb, n, c, t, l) && t != CS_MATCH) pm = cs_carry_in(cs, off, a); }
-            cs_hist_alignment(sb, n, pm, nullptr, acc);
-        }
-        if (acc.mx) atomicMax(&cnt[NS_CSH_LDS_WORDS - 1u], acc.mx);
-    }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < NS_CSH_LDS_WORDS; i += blockDim.x) {
-        const uint32_t v = cnt[i];
-        if (!v) continue;
-        if (i < 5u * 1001u) atomicAdd(&H.dic[i], (unsigned long long)v);
-        else if (i < NS_CSH_LDS_WORDS - 1u) atomicAdd(&H.err[i - 5u * 1001u], (unsigned long long)v);
-        else atomicMax(&H.misc[0], (unsigned long long)v);          // one atomic per workgroup for the largest match
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// k_qual_mark, k_qual_count: the base-quality histograms of the training side (ns_qual_hist.h; src/model_base_qualities.py:23-79).
-// MARK, one alignment per thread: the cs walk records a 2-bit mark per mismatched / inserted base (16 bases per word of `marks`, zeroed
-// by the caller).  A thread meets its bases in ascending order, so it gathers a word's marks in a register and writes the word once:
-// with a plain store when the word lies inside its own quality string, with an atomic OR for the string's first and last word, which
-// a neighbouring alignment may share.
-// COUNT streams the quality bytes and the marks once: a thread takes 16 bytes + one mark word per load, four loads in flight, wherever
-// the alignments begin; the alignment of a position comes from a binary search of the offsets, then from a walk forward.  Counters:
-// 32 copies of the 5 x 94 (+ 1) table per workgroup in LDS, copy = lane mod 32 = the LDS bank — `match` at the modal quality takes
-// most bases, and one counter per workgroup would serialise every wavefront's 64 adds on it; a copy per bank leaves two lanes of a
-// wavefront (one per 32-lane half) and the four wavefronts on an address.  A workgroup counts a contiguous span of at most 2^31 bytes
-// (the caller's grid), so no 32-bit counter can wrap; the copies are summed and flushed once with 64-bit atomics.
-// ---------------------------------------------------------------------------------------------------------
-#define NS_QH_BINS (QH_CLASSES * NS_QUAL_VALUES + 1u)      // the last one: bytes that are no quality value
-#define NS_QH_COPIES 32u
-#define NS_QH_LOADS 4u
-#define NS_QH_SUBTILE 4096u                                // 256 threads x 16 bytes
-#define NS_QH_TILE (NS_QH_LOADS * NS_QH_SUBTILE)
-#define NS_QH_OUT_SHORT (QH_CLASSES * 128u)                // the device image of ns_qual_hist: hist[5][128], n_short, n_bad_qual
-#define NS_QH_OUT_BAD (QH_CLASSES * 128u + 1u)
-#define NS_QH_OUT_WORDS (QH_CLASSES * 128u + 2u)
-struct QualMarkDev {
-    uint32_t *marks;
-    uint64_t base;                    // where the aligned part begins in the quality bytes
-    uint64_t w_first, w_last;         // the words a neighbouring alignment may write too
-    uint64_t cur; uint32_t bits;
-    __device__ __forceinline__ void flush() {
-        if (!bits) return;
-        if (cur == w_first || cur == w_last) atomicOr(&marks[cur], bits); else marks[cur] = bits;
-    }
-    __device__ __forceinline__ void mark(uint64_t i, uint32_t m) {
-        const uint64_t pos = base + i, w = pos >> 4;
-        if (w != cur) { flush(); cur = w; bits = 0; }
-        bits |= m << (2u * (uint32_t)(pos & 15u));
-    }
-};
-__global__ void __launch_bounds__(256) k_qual_mark(const uint8_t *__restrict__ cs, const uint64_t *__restrict__ cs_off, const uint64_t *__restrict__ qual_off,
-                                                   const ns_qual_aln *__restrict__ aln, uint32_t n_aln, const uint32_t *__restrict__ order,
-                                                   uint32_t *__restrict__ marks, unsigned long long *__restrict__ out) {
-    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid >= n_aln) return;
-    const uint64_t a = order ? order[tid] : tid;              // by descending length of the cs strings, as k_cs_hist
-    const ns_qual_aln A = aln[a];
-    const uint64_t lo = qual_off[a], hi = qual_off[a + 1];
-    const uint64_t aligned = hi - lo - A.head - A.tail;
-    if (A.unmapped || !aligned) return;
-    QualMarkDev sink{marks, lo + A.head, lo >> 4, (hi - 1u) >> 4, ~0ull, 0u};
-    CsBytes sb(cs + cs_off[a]);
-    const bool covered = qual_mark_alignment(sb, cs_off[a + 1] - cs_off[a], aligned, sink);
-    sink.flush();
-    if (!covered) atomicAdd(&out[NS_QH_OUT_SHORT], 1ull);
-}
-__global__ void __launch_bounds__(256) k_qual_count(const uint8_t *__restrict__ qual, const uint32_t *__restrict__ marks, const uint64_t *__restrict__ off,
-                                                    const ns_qual_aln *__restrict__ aln, uint32_t n_aln, uint64_t tiles_per_wg, uint64_t n_tiles,
-                                                    unsigned long long *__restrict__ out) {
-    __shared__ uint32_t cnt[NS_QH_BINS * NS_QH_COPIES];
-    for (uint32_t i = threadIdx.x; i < NS_QH_BINS * NS_QH_COPIES; i += blockDim.x) cnt[i] = 0;
-    __syncthreads();
-    uint32_t *mine = cnt + (threadIdx.x & (NS_QH_COPIES - 1u));
-    const uint64_t begin = off[0], end = off[n_aln];
-    const uint64_t t0 = (uint64_t)blockIdx.x * tiles_per_wg, t1 = t0 + tiles_per_wg < n_tiles ? t0 + tiles_per_wg : n_tiles;
-    uint32_t a = 0, next = 0;                                 // the alignment of the last byte looked at; where the search for the next goes on
-    uint64_t lo = 0, hi = 0;                                  // its bytes (hi = 0: none yet)
-    ns_qual_aln A{0u, 0u, 0u, 0u};
-    for (uint64_t t = t0; t < t1; ++t) {
-        const uint64_t p0 = t * NS_QH_TILE + (uint64_t)threadIdx.x * 16u;
-        uint4 v[NS_QH_LOADS]; uint32_t m[NS_QH_LOADS];
-#pragma unroll
-        for (uint32_t j = 0; j < NS_QH_LOADS; ++j) {
-            const uint64_t p = p0 + (uint64_t)j * NS_QH_SUBTILE;
-            v[j] = make_uint4(0u, 0u, 0u, 0u); m[j] = 0u;
-            if (p < end) { v[j] = *reinterpret_cast<const uint4 *>(qual + p); m[j] = marks[p >> 4]; }     // (both buffers are padded to whole words)
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < NS_QH_LOADS; ++j) {
-            const uint64_t p = p0 + (uint64_t)j * NS_QH_SUBTILE;
-            const uint32_t w[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-#pragma unroll
-            for (uint32_t k = 0; k < 16u; ++k) {
-                const uint64_t pos = p + k;
-                if (pos < begin || pos >= end) continue;
-                if (pos >= hi) {                              // the next alignment that holds a byte: a few steps forward, else a search
-                    for (uint32_t s = 0; s < 4u && off[next + 1u] <= pos; ++s) ++next;
-                    if (off[next + 1u] <= pos) next = qual_locate(off, next + 1u, n_aln, pos);
-                    a = next; next = a + 1u;
-                    lo = off[a]; hi = off[a + 1u]; A = aln[a];
-                }
-                const uint32_t q = ((w[k >> 2] >> (8u * (k & 3u))) & 0xffu) - NS_QUAL_FIRST;
-                const uint32_t bin = q < NS_QUAL_VALUES ? qual_class(pos - lo, hi - lo, A.head, A.tail, A.unmapped, (m[j] >> (2u * k)) & 3u) * NS_QUAL_VALUES + q
-                                                        : NS_QH_BINS - 1u;
-                atomicAdd(&mine[bin * NS_QH_COPIES], 1u);
-            }
-        }
-    }
-    __syncthreads();
-    for (uint32_t bin = threadIdx.x; bin < NS_QH_BINS; bin += blockDim.x) {
-        unsigned long long sum = 0;
-        for (uint32_t c = 0; c < NS_QH_COPIES; ++c) sum += cnt[bin * NS_QH_COPIES + ((c + bin) & (NS_QH_COPIES - 1u))];   // (rotated: the lanes read 32 banks)
-        if (sum) atomicAdd(&out[bin < NS_QH_BINS - 1u ? (bin / NS_QUAL_VALUES) * 128u + bin % NS_QUAL_VALUES : NS_QH_OUT_BAD], sum);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// k_hp_count, k_hp_records: the homopolymer-length model of the training side (ns_hp_hist.h; src/model_homopolymer_lengths.py:9-119 —
-// not the -k stage of the simulation above).  One alignment per thread, both lines through 8-byte CsBytes windows, visited by
-// descending length as k_cs_hist.  The [2][ref_len][read_len] counts: the corner below NS_HPT_CORNER in both lengths — where almost
-// every homopolymer falls — is privatised per workgroup in LDS and flushed once; 2 x 48 x 48 x 4 B = 18 KB leaves eight workgroups
-// (32 wavefronts, the limit) on a compute unit's 160 KB.  What lies outside goes to the caller's dense table by global atomics, or,
-// beyond its caps, to the overflow counter.  A workgroup counts 256 alignments of fewer than 2^24 columns each (the host checks), so
-// no 32-bit counter can wrap.  The column counters, the number of homopolymers and the overflow are summed over the wavefront first.
-// k_hp_records repeats the walk and writes the homopolymers of alignment a from slot[a] on (the exclusive scan of k_hp_count's
-// per-alignment numbers; slot[n_aln] is their total): nothing when the caller's buffer is too small for all of them.
-// ---------------------------------------------------------------------------------------------------------
-#define NS_HPT_CORNER 48u
-#define NS_HPT_LDS_WORDS (2u * NS_HPT_CORNER * NS_HPT_CORNER)
-enum { HPT_COLUMNS = 0, HPT_N_HP = 4, HPT_OVERFLOW = 5, HPT_MAX_REF = 6, HPT_MAX_READ = 7, HPT_WORDS = 8 };   // the device image of the small results
-struct HpTrainDev {
-    unsigned long long *table;        // [2][cap_ref][cap_read]
-    unsigned long long *small;        // [HPT_WORDS]
-    uint32_t cap_ref, cap_read;
-};
-struct HpTrainAcc {
-    uint32_t *l;                      // the workgroup's corner of the table
-    const HpTrainDev *H;
-    uint32_t mx_ref, mx_read, over, col[4];
-    __device__ __forceinline__ void hp(uint32_t cls, uint8_t, uint32_t ref_len, uint32_t read_len, uint32_t, uint32_t) {
-        mx_ref = mx_ref > ref_len ? mx_ref : ref_len;
-        mx_read = mx_read > read_len ? mx_read : read_len;
-        if (ref_len >= H->cap_ref || read_len >= H->cap_read) ++over;
-        else if (ref_len < NS_HPT_CORNER && read_len < NS_HPT_CORNER) atomicAdd(&l[(cls * NS_HPT_CORNER + ref_len) * NS_HPT_CORNER + read_len], 1u);
-        else atomicAdd(&H->table[((uint64_t)cls * H->cap_ref + ref_len) * H->cap_read + read_len], 1ull);
-    }
-    __device__ __forceinline__ void columns(uint32_t ins, uint32_t del, uint32_t mis, uint32_t match) {
-        col[HPC_INS] = ins; col[HPC_DEL] = del; col[HPC_MIS] = mis; col[HPC_MATCH] = match;
-    }
-};
-__global__ void __launch_bounds__(256) k_hp_count(const uint8_t *__restrict__ ref, const uint8_t *__restrict__ qry, const uint64_t *__restrict__ off,
-                                                  uint32_t n_aln, uint32_t min_hp_len, HpTrainDev H, const uint32_t *__restrict__ order,
-                                                  unsigned long long *__restrict__ n_per_aln) {
-    __shared__ uint32_t cnt[NS_HPT_LDS_WORDS];
-    for (uint32_t i = threadIdx.x; i < NS_HPT_LDS_WORDS; i += blockDim.x) cnt[i] = 0;
-    __syncthreads();
-    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    HpTrainAcc acc{cnt, &H, 0u, 0u, 0u, {0u, 0u, 0u, 0u}};
-    uint32_t n_hp = 0;
-    if (tid < n_aln) {
-        const uint64_t a = order ? order[tid] : tid;
-        CsBytes rb(ref + off[a]), qb(qry + off[a]);
-        n_hp = hp_hist_alignment(rb, qb, off[a + 1] - off[a], min_hp_len, acc);
-        n_per_aln[a] = n_hp;
-    }
-    // (every lane of the workgroup comes here: the wavefront sums need them all)
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t sums[6] = {acc.col[0], acc.col[1], acc.col[2], acc.col[3], n_hp, acc.over};
-#pragma unroll
-    for (uint32_t j = 0; j < 6u; ++j) {
-        const unsigned long long s = wave_sum(sums[j]);
-        if (lane == 0 && s) atomicAdd(&H.small[j], s);          // HPT_COLUMNS .. HPT_OVERFLOW
-    }
-    uint32_t mr = acc.mx_ref, mq = acc.mx_read;
-    for (int o = 32; o > 0; o >>= 1) { mr = max(mr, (uint32_t)__shfl_xor((int)mr, o)); mq = max(mq, (uint32_t)__shfl_xor((int)mq, o)); }
-    if (lane == 0 && mr) atomicMax(&H.small[HPT_MAX_REF], (unsigned long long)mr);
-    if (lane == 0 && mq) atomicMax(&H.small[HPT_MAX_READ], (unsigned long long)mq);
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < NS_HPT_LDS_WORDS; i += blockDim.x) {
-        const uint32_t v = cnt[i];
-        if (!v) continue;                                           // (an entry counted here lies inside the caps: HpTrainAcc::hp)
-        const uint32_t cls = i / (NS_HPT_CORNER * NS_HPT_CORNER), r = i / NS_HPT_CORNER % NS_HPT_CORNER, q = i % NS_HPT_CORNER;
-        atomicAdd(&H.table[((uint64_t)cls * H.cap_ref + r) * H.cap_read + q], (unsigned long long)v);
-    }
-}
-struct HpRecordSink {
-    ns_hp_record *rec; uint64_t at, end; uint32_t aln;
-    __device__ __forceinline__ void hp(uint32_t, uint8_t base, uint32_t ref_len, uint32_t read_len, uint32_t start, uint32_t) {
-        const uint32_t code = base == 'A' ? 0u : base == 'C' ? 1u : base == 'G' ? 2u : 3u;
-        if (at < end) rec[at] = ns_hp_record{aln, start, ref_len, read_len << 2 | code};
-        ++at;
-    }
-    __device__ __forceinline__ void columns(uint32_t, uint32_t, uint32_t, uint32_t) {}
-};
-__global__ void __launch_bounds__(256) k_hp_records(const uint8_t *__restrict__ ref, const uint8_t *__restrict__ qry, const uint64_t *__restrict__ off,
-                                                    uint32_t n_aln, uint32_t min_hp_len, const uint32_t *__restrict__ order,
-                                                    const unsigned long long *__restrict__ slot, ns_hp_record *__restrict__ rec, uint64_t cap_records) {
-    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid >= n_aln || slot[n_aln] > cap_records) return;
-    const uint64_t a = order ? order[tid] : tid;
-    if (slot[a + 1] == slot[a]) return;
-    HpRecordSink sink{rec, slot[a], slot[a + 1], (uint32_t)a};
-    CsBytes rb(ref + off[a]), qb(qry + off[a]);
-    hp_hist_alignment(rb, qb, off[a + 1] - off[a], min_hp_len, sink);
-}
-
-// ---------------------------------------------------------------------------------------------------------
 // reference normalisation (once per ns_set_reference): upper-case, non-IUPAC -> N
 // ---------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_normalise(uint8_t *bases, uint64_t n) {
@@ -2559,6 +2297,61 @@ static int upload(ns_ctx *ctx, std::vector<void *> &pool, const T *src, size_t n
     return NS_OK;
 }
 
+static void free_pool(std::vector<void *> &pool) {
+    for (void *p : pool) { hipError_t e = hipFree(p); (void)e; }
+    pool.clear();
+}
+
+// The device memory of ONE training-side call (`call`: its public name, for the messages): a pool like those of upload(), taken per call
+// and given back when the call returns, whichever way it returns: the destructor is the only place where this memory is freed.  (Not
+// grow-only buffers of the context: the alignments of a training set are gigabytes, and the context simulates afterwards.)
+// A call asks for all of its buffers first and then has them filled (upload()): every allocation in front of the first copy, which
+// keeps the host from mapping memory while the stream works.  The first failure stays in `rc` (NS_ENOMEM for an allocation, NS_EHIP
+// otherwise, the message in the context) and turns what follows into no-ops that return nullptr: upload() reports it.
+struct CallScratch {
+    struct Fill { void *dst; const void *src; size_t bytes; };                    // (src == nullptr: zeroes)
+    ns_ctx *ctx; const char *call;
+    int rc = NS_OK;
+    std::vector<void *> pool;
+    std::vector<Fill> fills;
+    CallScratch(ns_ctx *c, const char *name) : ctx(c), call(name) {}
+    CallScratch(const CallScratch &) = delete;
+    ~CallScratch() { free_pool(pool); }
+    int check(hipError_t e) {
+        if (e != hipSuccess && !rc) rc = fail(ctx, NS_EHIP, std::string(call) + ": " + hipGetErrorString(e));
+        return rc;
+    }
+    template <typename T> T *alloc(size_t n, size_t pad = 0) {                    // n elements + pad bytes, as they are
+        void *p = nullptr;
+        if (rc) return nullptr;
+        const hipError_t e = hipMalloc(&p, n * sizeof(T) + pad);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();             // the failed allocation must not poison the next call
+            rc = fail(ctx, NS_ENOMEM, std::string(call) + ": hipMalloc: " + hipGetErrorString(e));
+            return nullptr;
+        }
+        pool.push_back(p);
+        return static_cast<T *>(p);
+    }
+    template <typename T> T *zeroed(size_t n, size_t pad = 0) {                   // ... the n elements zeroed by upload()
+        T *p = alloc<T>(n, pad);
+        if (p) fills.push_back({p, nullptr, n * sizeof(T)});
+        return p;
+    }
+    template <typename T> T *filled(const T *src, size_t n, size_t pad = 0) {     // ... the n elements copied from the host by upload()
+        T *p = alloc<T>(n, pad);
+        if (p && n) fills.push_back({p, src, n * sizeof(T)});
+        return p;
+    }
+    int upload() {                               // the copies and memsets asked for so far, on the main stream, in the order asked
+        for (const Fill &f : fills)
+            if (!rc) check(f.src ? hipMemcpyAsync(f.dst, f.src, f.bytes, hipMemcpyHostToDevice, ctx->stream) : hipMemsetAsync(f.dst, 0, f.bytes, ctx->stream));
+        fills.clear();
+        return rc;
+    }
+};
+#define CALLCHK(s, call) do { if (int rc_ = (s).check(call)) return rc_; } while (0)
+
 extern "C" {
 
 uint32_t ns_abi_version(void) { return NS_ABI_VERSION; }
@@ -2637,11 +2430,6 @@ static int read_small(ns_ctx *ctx, hipStream_t st, void *dst, const void *src, s
     memcpy(dst, ctx->pin_small, n);
     if (dst2) memcpy(dst2, ctx->pin_small + 512, n2);
     return NS_OK;
-}
-
-static void free_pool(std::vector<void *> &pool) {
-    for (void *p : pool) { hipError_t e = hipFree(p); (void)e; }
-    pool.clear();
 }
 
 void ns_destroy(ns_ctx *ctx) {
@@ -4271,8 +4059,83 @@ int ns_io_counters(ns_ctx *ctx, ns_io_stats *out, int reset) {
     return NS_OK;
 }
 
+// ---- the training side: three counting calls on one skeleton (check the arguments, a CallScratch: every buffer, then upload(),
+// EV_HIST_BEGIN, the visiting order, the kernels, timed_tail) ---------------------------------------------------------------------------
+// "ascending and not beyond the bytes" for the n + 1 offsets of a call's strings (`what`: what the message calls them)
+static int check_offsets(ns_ctx *ctx, const char *call, const char *what, const uint64_t *off, uint32_t n, uint64_t nbytes) {
+    for (uint32_t a = 0; a < n; ++a)
+        if (off[a] > off[a + 1] || off[a + 1] > nbytes) return fail(ctx, NS_EINVAL, std::string(call) + ": offsets not ascending / beyond the " + what);
+    return NS_OK;
+}
+// Alignments of 1 kb .. 100 kb on neighbouring lanes diverge like the thread-per-read chain did before its length sort: the walks are
+// visited by descending length of their cs strings (the counts are sums: any order gives the same tables).  *order: the visiting order
+// (nullptr for 64 alignments or fewer: index order).  It lies in the key block, which is the call's; only the sort's temporary storage is
+// the context's (with_tmp).  A later with_tmp of the same call (scan_sum in ns_hp_histograms) may regrow scan_tmp and free the storage
+// the sort is still using on the stream: hipFree waits for the device, and nothing of the result is in there.
+static int order_by_length(CallScratch &s, const uint64_t *d_off, uint32_t n_aln, uint32_t **order) {
+    *order = nullptr;
+    if (n_aln <= 64) return NS_OK;
+    ns_ctx *ctx = s.ctx;
+    hipStream_t st = ctx->stream;
+    uint32_t *key = s.alloc<uint32_t>((size_t)4 * n_aln);                 // key, index, sorted key, sorted index
+    if (!key) return s.rc;
+    uint32_t *idx = key + n_aln, *key2 = idx + n_aln, *idx2 = key2 + n_aln;
+    k_cs_len<<<dim3((n_aln + 255u) / 256u), dim3(256), 0, st>>>(d_off, n_aln, key, idx);
+    CALLCHK(s, hipGetLastError());
+    if (int rc = with_tmp(ctx, "DeviceRadixSort::SortPairsDescending", [&](void *tmp, size_t &bytes) {
+            return hipcub::DeviceRadixSort::SortPairsDescending(tmp, bytes, key, key2, idx, idx2, (int)n_aln, 0, 32, st); }))
+        return fail(ctx, rc, std::string(s.call) + ": " + ctx->err);
+    *order = idx2;
+    return NS_OK;
+}
+// the end of a call: EV_HIST_END, the small results back to the host, the stream drained; *ms = EV_HIST_BEGIN .. EV_HIST_END
+struct ReadBack { void *dst; const void *src; size_t bytes; };
+static int timed_tail(CallScratch &s, std::initializer_list<ReadBack> back, double *ms) {
+    ns_ctx *ctx = s.ctx;
+    CALLCHK(s, hipEventRecord(ctx->evt[EV_HIST_END], ctx->stream));
+    for (const ReadBack &b : back) if (b.bytes) CALLCHK(s, hipMemcpyAsync(b.dst, b.src, b.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    CALLCHK(s, hipStreamSynchronize(ctx->stream));
+    float f = 0;
+    CALLCHK(s, hipEventElapsedTime(&f, ctx->evt[EV_HIST_BEGIN], ctx->evt[EV_HIST_END]));
+    *ms = f;
+    return NS_OK;
+}
+
 // the characterisation stage's counting loop (include/nanosim_amd.h: ns_cs_hist; src/besthit_to_histogram.py:316-365)
-static int histograms(ns_ctx *ctx, const uint8_t *cs, const uint8_t *qry, bool maf, uint64_t nbytes, const uint64_t *aln_off, uint32_t n_aln, ns_cs_hist *h);
+struct CsSmall {                                 // what CsHistDev's dic, err and misc point into, on the device and read back
+    unsigned long long dic[5][1001], error_list[18], first_error[3], spare[3], max_match, n_match2d_overflow, n_skip, spare2[5];
+};
+static int histograms(ns_ctx *ctx, const uint8_t *cs, const uint8_t *qry, bool maf, uint64_t nbytes, const uint64_t *aln_off, uint32_t n_aln, ns_cs_hist *h) {
+    if (!ctx) return NS_EINVAL;
+    if (!h || (n_aln && (!aln_off || (!cs && nbytes)))) return fail(ctx, NS_EINVAL, "ns_cs_histograms: null argument");
+    if (int rc = check_offsets(ctx, "ns_cs_histograms", "strings", aln_off, n_aln, nbytes)) return rc;
+    const uint32_t cap = h->cap_match2d;
+    if (h->match_list && (!cap || cap > 65536u)) return fail(ctx, NS_EINVAL, "ns_cs_histograms: cap_match2d must be 1 .. 65536");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n_m2 = h->match_list ? (size_t)cap * cap : 0;
+    memset(h->dic, 0, sizeof h->dic); memset(h->error_list, 0, sizeof h->error_list); memset(h->first_error, 0, sizeof h->first_error);
+    h->max_match = h->n_match2d_overflow = h->n_skip = 0; h->ms_kernel = 0;
+    if (!n_aln) { if (n_m2) memset(h->match_list, 0, n_m2 * 8); return NS_OK; }
+    CsSmall small;
+    CallScratch s(ctx, "ns_cs_histograms");
+    const uint8_t *d_cs = s.filled(cs, (size_t)nbytes, 16);                  // (16 bytes to spare: the 8- and 16-byte window loads of CsBytes)
+    const uint8_t *d_qry = maf ? s.filled(qry, (size_t)nbytes, 16) : nullptr;
+    const uint64_t *d_off = s.filled(aln_off, (size_t)n_aln + 1);
+    CsSmall *d_small = s.zeroed<CsSmall>(1);
+    unsigned long long *d_m2 = n_m2 ? s.zeroed<unsigned long long>(n_m2) : nullptr;
+    if (int rc = s.upload()) return rc;
+    hipStream_t st = ctx->stream;
+    CALLCHK(s, hipEventRecord(ctx->evt[EV_HIST_BEGIN], st));
+    uint32_t *d_order;
+    if (int rc = order_by_length(s, d_off, n_aln, &d_order)) return rc;
+    const CsHistDev H{&d_small->dic[0][0], d_small->error_list, &d_small->max_match, d_m2, cap};
+    k_cs_hist<<<dim3((n_aln + 255u) / 256u), dim3(256), 0, st>>>(d_cs, d_off, n_aln, H, d_order, d_qry);
+    CALLCHK(s, hipGetLastError());
+    if (int rc = timed_tail(s, {{&small, d_small, sizeof small}, {h->match_list, d_m2, n_m2 * 8}}, &h->ms_kernel)) return rc;
+    memcpy(h->dic, small.dic, sizeof h->dic); memcpy(h->error_list, small.error_list, sizeof h->error_list); memcpy(h->first_error, small.first_error, sizeof h->first_error);
+    h->max_match = small.max_match; h->n_match2d_overflow = small.n_match2d_overflow; h->n_skip = small.n_skip;
+    return NS_OK;
+}
 int ns_cs_histograms(ns_ctx *ctx, const uint8_t *cs, uint64_t nbytes, const uint64_t *aln_off, uint32_t n_aln, ns_cs_hist *h) {
     return histograms(ctx, cs, nullptr, false, nbytes, aln_off, n_aln, h);
 }
@@ -4280,142 +4143,49 @@ int ns_maf_histograms(ns_ctx *ctx, const uint8_t *ref_lines, const uint8_t *quer
     if (ctx && n_aln && nbytes && !query_lines) return fail(ctx, NS_EINVAL, "ns_maf_histograms: null argument");
     return histograms(ctx, ref_lines, query_lines, true, nbytes, aln_off, n_aln, h);
 }
-// Alignments of 1 kb .. 100 kb on neighbouring lanes diverge like the thread-per-read chain did before its length sort: the walks are
-// visited by descending length of their cs strings (the counts are sums: any order gives the same tables).  *order: the visiting order
-// (nullptr for 64 alignments or fewer: index order); *key and *tmp are the caller's to free.
-static hipError_t order_by_length(hipStream_t st, const uint64_t *d_off, uint32_t n_aln, void **d_key, void **d_tmp, uint32_t **order) {
-    *order = nullptr;
-    if (n_aln <= 64) return hipSuccess;
-    size_t tmp = 0;
-    hipError_t e = hipMalloc(d_key, (size_t)n_aln * 16);                 // key, index, sorted key, sorted index
-    if (e != hipSuccess) return e;
-    uint32_t *key = (uint32_t *)*d_key, *idx = key + n_aln, *key2 = idx + n_aln, *idx2 = key2 + n_aln;
-    k_cs_len<<<dim3((n_aln + 255u) / 256u), dim3(256), 0, st>>>(d_off, n_aln, key, idx);
-    e = hipGetLastError();
-    auto sort = [&](void *t) { return hipcub::DeviceRadixSort::SortPairsDescending(t, tmp, key, key2, idx, idx2, (int)n_aln, 0, 32, st); };
-    if (e == hipSuccess) e = sort(nullptr);                               // (the size of its temporary storage)
-    if (e == hipSuccess) e = hipMalloc(d_tmp, tmp + 16);
-    if (e == hipSuccess) e = sort(*d_tmp);
-    *order = idx2;
-    return e;
-}
-static int histograms(ns_ctx *ctx, const uint8_t *cs, const uint8_t *qry, bool maf, uint64_t nbytes, const uint64_t *aln_off, uint32_t n_aln, ns_cs_hist *h) {
-    if (!ctx) return NS_EINVAL;
-    if (!h || (n_aln && (!aln_off || (!cs && nbytes)))) return fail(ctx, NS_EINVAL, "ns_cs_histograms: null argument");
-    for (uint32_t a = 0; a < n_aln; ++a)
-        if (aln_off[a] > aln_off[a + 1] || aln_off[a + 1] > nbytes) return fail(ctx, NS_EINVAL, "ns_cs_histograms: offsets not ascending / beyond the strings");
-    const uint32_t cap = h->cap_match2d;
-    if (h->match_list && (!cap || cap > 65536u)) return fail(ctx, NS_EINVAL, "ns_cs_histograms: cap_match2d must be 1 .. 65536");
-    HIPCHK(hipSetDevice(ctx->device));
-    uint64_t *m2_host = h->match_list;
-    memset(h->dic, 0, sizeof h->dic); memset(h->error_list, 0, sizeof h->error_list); memset(h->first_error, 0, sizeof h->first_error);
-    h->max_match = h->n_match2d_overflow = h->n_skip = 0; h->ms_kernel = 0;
-    if (!n_aln) { if (m2_host) memset(m2_host, 0, (size_t)cap * cap * 8); return NS_OK; }
-    const size_t n_small = 5 * 1001 + 24 + 8;
-    void *d_cs = nullptr, *d_off = nullptr, *d_small = nullptr, *d_m2 = nullptr, *d_key = nullptr, *d_tmp = nullptr, *d_qry = nullptr;
-    auto release = [&]() { for (void *p : {d_cs, d_off, d_small, d_m2, d_key, d_tmp, d_qry}) if (p) { hipError_t e = hipFree(p); (void)e; } };
-    hipError_t e = hipMalloc(&d_cs, (size_t)nbytes + 16);
-    if (e == hipSuccess && maf) e = hipMalloc(&d_qry, (size_t)nbytes + 16);
-    if (e == hipSuccess) e = hipMalloc(&d_off, ((size_t)n_aln + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_small, n_small * 8);
-    if (e == hipSuccess && m2_host) e = hipMalloc(&d_m2, (size_t)cap * cap * 8);
-    if (e != hipSuccess) { release(); (void)hipGetLastError(); return fail(ctx, NS_ENOMEM, std::string("ns_cs_histograms: hipMalloc: ") + hipGetErrorString(e)); }
-    hipStream_t st = ctx->stream;
-    e = hipMemcpyAsync(d_cs, cs, (size_t)nbytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && maf && nbytes) e = hipMemcpyAsync(d_qry, qry, (size_t)nbytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, aln_off, ((size_t)n_aln + 1) * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_small, 0, n_small * 8, st);
-    if (e == hipSuccess && d_m2) e = hipMemsetAsync(d_m2, 0, (size_t)cap * cap * 8, st);
-    if (e == hipSuccess) e = hipEventRecord(ctx->evt[EV_HIST_BEGIN], st);
-    uint32_t *d_order = nullptr;
-    if (e == hipSuccess) e = order_by_length(st, (const uint64_t *)d_off, n_aln, &d_key, &d_tmp, &d_order);
-    if (e == hipSuccess) {
-        CsHistDev H;
-        H.dic = (unsigned long long *)d_small; H.err = H.dic + 5 * 1001; H.misc = H.err + 24;
-        H.m2 = (unsigned long long *)d_m2; H.cap2 = cap;
-        k_cs_hist<<<dim3((n_aln + 255u) / 256u), dim3(256), 0, st>>>((const uint8_t *)d_cs, (const uint64_t *)d_off, n_aln, H, d_order, (const uint8_t *)d_qry);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(ctx->evt[EV_HIST_END], st);
-    std::vector<unsigned long long> small(n_small);
-    if (e == hipSuccess) e = hipMemcpyAsync(small.data(), d_small, n_small * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && d_m2) e = hipMemcpyAsync(m2_host, d_m2, (size_t)cap * cap * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ctx->evt[EV_HIST_BEGIN], ctx->evt[EV_HIST_END]);
-    release();
-    if (e != hipSuccess) return fail(ctx, NS_EHIP, std::string("ns_cs_histograms: ") + hipGetErrorString(e));
-    for (int w = 0; w < 5; ++w) for (int v = 0; v <= 1000; ++v) h->dic[w][v] = small[(size_t)w * 1001 + v];
-    for (int i = 0; i < 18; ++i) h->error_list[i] = small[5 * 1001 + i];
-    for (int i = 0; i < 3; ++i) h->first_error[i] = small[5 * 1001 + 18 + i];
-    h->max_match = small[5 * 1001 + 24]; h->n_match2d_overflow = small[5 * 1001 + 25]; h->n_skip = small[5 * 1001 + 26];
-    h->ms_kernel = ms;
-    return NS_OK;
-}
 
 // the base-quality histograms of the training side (include/nanosim_amd.h: ns_qual_hist; src/model_base_qualities.py:23-79)
 int ns_qual_histograms(ns_ctx *ctx, const uint8_t *cs, uint64_t cs_bytes, const uint64_t *cs_off, const uint8_t *qual, uint64_t qual_bytes,
                        const uint64_t *qual_off, const ns_qual_aln *aln, uint32_t n_aln, ns_qual_hist *out) {
     if (!ctx) return NS_EINVAL;
     if (!out || (n_aln && (!cs_off || !qual_off || !aln || (!cs && cs_bytes) || (!qual && qual_bytes)))) return fail(ctx, NS_EINVAL, "ns_qual_histograms: null argument");
-    for (uint32_t a = 0; a < n_aln; ++a) {
-        if (cs_off[a] > cs_off[a + 1] || cs_off[a + 1] > cs_bytes || qual_off[a] > qual_off[a + 1] || qual_off[a + 1] > qual_bytes)
-            return fail(ctx, NS_EINVAL, "ns_qual_histograms: offsets not ascending / beyond the strings");
+    if (int rc = check_offsets(ctx, "ns_qual_histograms", "strings", cs_off, n_aln, cs_bytes)) return rc;
+    if (int rc = check_offsets(ctx, "ns_qual_histograms", "strings", qual_off, n_aln, qual_bytes)) return rc;
+    for (uint32_t a = 0; a < n_aln; ++a)
         if ((uint64_t)aln[a].head + aln[a].tail > qual_off[a + 1] - qual_off[a])
             return fail(ctx, NS_EINVAL, "ns_qual_histograms: soft clips longer than the quality string of alignment " + std::to_string(a));
-    }
     memset(out, 0, sizeof *out);
     if (!n_aln) return NS_OK;
     HIPCHK(hipSetDevice(ctx->device));
     const size_t n_marks = (size_t)(qual_bytes / 16u) + 2u;               // 2 bits per quality byte, in whole words
-    void *d_cs = nullptr, *d_cs_off = nullptr, *d_qual = nullptr, *d_qual_off = nullptr, *d_aln = nullptr, *d_marks = nullptr, *d_out = nullptr,
-         *d_key = nullptr, *d_tmp = nullptr;
-    auto release = [&]() { for (void *p : {d_cs, d_cs_off, d_qual, d_qual_off, d_aln, d_marks, d_out, d_key, d_tmp}) if (p) { hipError_t e = hipFree(p); (void)e; } };
-    hipError_t e = hipMalloc(&d_cs, (size_t)cs_bytes + 16);               // (16 bytes to spare: the window loads of CsBytes and of k_qual_count)
-    if (e == hipSuccess) e = hipMalloc(&d_qual, (size_t)qual_bytes + 32);
-    if (e == hipSuccess) e = hipMalloc(&d_cs_off, ((size_t)n_aln + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_qual_off, ((size_t)n_aln + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_aln, (size_t)n_aln * sizeof(ns_qual_aln));
-    if (e == hipSuccess) e = hipMalloc(&d_marks, n_marks * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_out, NS_QH_OUT_WORDS * 8);
-    if (e != hipSuccess) { release(); (void)hipGetLastError(); return fail(ctx, NS_ENOMEM, std::string("ns_qual_histograms: hipMalloc: ") + hipGetErrorString(e)); }
+    unsigned long long res[NS_QH_OUT_WORDS];
+    CallScratch s(ctx, "ns_qual_histograms");
+    const uint8_t *d_cs = s.filled(cs, (size_t)cs_bytes, 16);             // (16 bytes to spare: the window loads of CsBytes and of k_qual_count)
+    const uint8_t *d_qual = s.filled(qual, (size_t)qual_bytes, 32);       // (32: k_qual_count loads 16-byte words, the last of which may begin at the last byte)
+    const uint64_t *d_cs_off = s.filled(cs_off, (size_t)n_aln + 1), *d_qual_off = s.filled(qual_off, (size_t)n_aln + 1);
+    const ns_qual_aln *d_aln = s.filled(aln, (size_t)n_aln);
+    uint32_t *d_marks = s.alloc<uint32_t>(n_marks);
+    unsigned long long *d_out = s.zeroed<unsigned long long>(NS_QH_OUT_WORDS);
+    if (int rc = s.upload()) return rc;
     hipStream_t st = ctx->stream;
-    if (cs_bytes) e = hipMemcpyAsync(d_cs, cs, (size_t)cs_bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && qual_bytes) e = hipMemcpyAsync(d_qual, qual, (size_t)qual_bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_cs_off, cs_off, ((size_t)n_aln + 1) * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_qual_off, qual_off, ((size_t)n_aln + 1) * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_aln, aln, (size_t)n_aln * sizeof(ns_qual_aln), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, NS_QH_OUT_WORDS * 8, st);
-    if (e == hipSuccess) e = hipEventRecord(ctx->evt[EV_HIST_BEGIN], st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_marks, 0, n_marks * 4, st);
-    uint32_t *d_order = nullptr;
-    if (e == hipSuccess) e = order_by_length(st, (const uint64_t *)d_cs_off, n_aln, &d_key, &d_tmp, &d_order);
-    if (e == hipSuccess) {
-        k_qual_mark<<<dim3((n_aln + 255u) / 256u), dim3(256), 0, st>>>((const uint8_t *)d_cs, (const uint64_t *)d_cs_off, (const uint64_t *)d_qual_off,
-                                                                       (const ns_qual_aln *)d_aln, n_aln, d_order, (uint32_t *)d_marks, (unsigned long long *)d_out);
-        e = hipGetLastError();
-    }
+    CALLCHK(s, hipEventRecord(ctx->evt[EV_HIST_BEGIN], st));
+    CALLCHK(s, hipMemsetAsync(d_marks, 0, n_marks * 4, st));              // (inside ms_kernel: the mark phase needs it on every call)
+    uint32_t *d_order;
+    if (int rc = order_by_length(s, d_cs_off, n_aln, &d_order)) return rc;
+    k_qual_mark<<<dim3((n_aln + 255u) / 256u), dim3(256), 0, st>>>(d_cs, d_cs_off, d_qual_off, d_aln, n_aln, d_order, d_marks, d_out);
+    CALLCHK(s, hipGetLastError());
     // a workgroup counts a contiguous span of tiles: at most 512 workgroups (its 60 KB of counters let two of them share a compute unit:
     // one resident set, one flush each), but never more than 2^31 bytes per workgroup (32-bit counters in LDS)
     const uint64_t n_tiles = (qual_off[n_aln] + NS_QH_TILE - 1u) / NS_QH_TILE;
     const uint64_t tiles_per_wg = std::min<uint64_t>(std::max<uint64_t>((n_tiles + 511u) / 512u, 1u), (1ull << 31) / NS_QH_TILE);
-    if (e == hipSuccess && n_tiles && !(ctx->knob.dbg & (1u << 20))) {    // (NS_DEBUG_SKIP 1 << 20, profiling only: the mark phase alone)
-        k_qual_count<<<dim3((uint32_t)((n_tiles + tiles_per_wg - 1u) / tiles_per_wg)), dim3(256), 0, st>>>(
-            (const uint8_t *)d_qual, (const uint32_t *)d_marks, (const uint64_t *)d_qual_off, (const ns_qual_aln *)d_aln, n_aln, tiles_per_wg, n_tiles,
-            (unsigned long long *)d_out);
-        e = hipGetLastError();
+    if (n_tiles && !(ctx->knob.dbg & (1u << 20))) {                       // (NS_DEBUG_SKIP 1 << 20, profiling only: the mark phase alone)
+        k_qual_count<<<dim3((uint32_t)((n_tiles + tiles_per_wg - 1u) / tiles_per_wg)), dim3(256), 0, st>>>(d_qual, d_marks, d_qual_off, d_aln, n_aln,
+                                                                                                            tiles_per_wg, n_tiles, d_out);
+        CALLCHK(s, hipGetLastError());
     }
-    if (e == hipSuccess) e = hipEventRecord(ctx->evt[EV_HIST_END], st);
-    std::vector<unsigned long long> res(NS_QH_OUT_WORDS);
-    if (e == hipSuccess) e = hipMemcpyAsync(res.data(), d_out, NS_QH_OUT_WORDS * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ctx->evt[EV_HIST_BEGIN], ctx->evt[EV_HIST_END]);
-    release();
-    if (e != hipSuccess) return fail(ctx, NS_EHIP, std::string("ns_qual_histograms: ") + hipGetErrorString(e));
+    if (int rc = timed_tail(s, {{res, d_out, sizeof res}}, &out->ms_kernel)) return rc;
     for (int c = 0; c < 5; ++c) for (int q = 0; q < 128; ++q) out->hist[c][q] = res[(size_t)c * 128 + q];
     out->n_short = res[NS_QH_OUT_SHORT]; out->n_bad_qual = res[NS_QH_OUT_BAD];
-    out->ms_kernel = ms;
     return NS_OK;
 }
 
@@ -4424,74 +4194,49 @@ int ns_hp_histograms(ns_ctx *ctx, const uint8_t *ref_lines, const uint8_t *query
                      uint32_t min_hp_len, ns_hp_hist *out) {
     if (!ctx) return NS_EINVAL;
     if (!out || !out->table || (n_aln && (!aln_off || ((!ref_lines || !query_lines) && nbytes)))) return fail(ctx, NS_EINVAL, "ns_hp_histograms: null argument");
-    for (uint32_t a = 0; a < n_aln; ++a) {
-        if (aln_off[a] > aln_off[a + 1] || aln_off[a + 1] > nbytes) return fail(ctx, NS_EINVAL, "ns_hp_histograms: offsets not ascending / beyond the lines");
+    if (int rc = check_offsets(ctx, "ns_hp_histograms", "lines", aln_off, n_aln, nbytes)) return rc;
+    for (uint32_t a = 0; a < n_aln; ++a)
         if (aln_off[a + 1] - aln_off[a] >= (1ull << 24))        // (the 32-bit counters of a workgroup of k_hp_count, the 30 bits of a record's read_len)
             return fail(ctx, NS_EINVAL, "ns_hp_histograms: alignment " + std::to_string(a) + " has 2^24 columns or more");
-    }
     if (!min_hp_len) return fail(ctx, NS_EINVAL, "ns_hp_histograms: min_hp_len must be at least 1");
     const uint32_t cap_ref = out->cap_ref, cap_read = out->cap_read;
     if (!cap_ref || cap_ref > 65536u || !cap_read || cap_read > 65536u) return fail(ctx, NS_EINVAL, "ns_hp_histograms: cap_ref and cap_read must be 1 .. 65536");
     if ((uint64_t)cap_ref * cap_read > (1ull << 26)) return fail(ctx, NS_EINVAL, "ns_hp_histograms: cap_ref * cap_read must not exceed 2^26");
-    const size_t table_bytes = (size_t)2 * cap_ref * cap_read * 8;
+    const size_t n_table = (size_t)2 * cap_ref * cap_read;
     const uint64_t cap_records = out->records ? out->cap_records : 0;
     out->n_hp = out->max_ref = out->max_read = out->n_overflow = 0; out->ms_kernel = 0;
     memset(out->columns, 0, sizeof out->columns);
-    if (!n_aln) { memset(out->table, 0, table_bytes); return NS_OK; }
+    if (!n_aln) { memset(out->table, 0, n_table * 8); return NS_OK; }
     HIPCHK(hipSetDevice(ctx->device));
-    void *d_ref = nullptr, *d_qry = nullptr, *d_off = nullptr, *d_small = nullptr, *d_table = nullptr, *d_cnt = nullptr, *d_slot = nullptr, *d_rec = nullptr,
-         *d_key = nullptr, *d_tmp = nullptr;
-    auto release = [&]() { for (void *p : {d_ref, d_qry, d_off, d_small, d_table, d_cnt, d_slot, d_rec, d_key, d_tmp}) if (p) { hipError_t e = hipFree(p); (void)e; } };
-    hipError_t e = hipMalloc(&d_ref, (size_t)nbytes + 16);                // (16 bytes to spare: the window loads of CsBytes)
-    if (e == hipSuccess) e = hipMalloc(&d_qry, (size_t)nbytes + 16);
-    if (e == hipSuccess) e = hipMalloc(&d_off, ((size_t)n_aln + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_small, HPT_WORDS * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_table, table_bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_cnt, ((size_t)n_aln + 1) * 8);
-    if (e == hipSuccess && out->records) e = hipMalloc(&d_slot, ((size_t)n_aln + 1) * 8);
-    if (e == hipSuccess && cap_records) e = hipMalloc(&d_rec, (size_t)cap_records * sizeof(ns_hp_record));
-    if (e != hipSuccess) { release(); (void)hipGetLastError(); return fail(ctx, NS_ENOMEM, std::string("ns_hp_histograms: hipMalloc: ") + hipGetErrorString(e)); }
+    unsigned long long small[HPT_WORDS] = {0};
+    CallScratch s(ctx, "ns_hp_histograms");
+    const uint8_t *d_ref = s.filled(ref_lines, (size_t)nbytes, 16), *d_qry = s.filled(query_lines, (size_t)nbytes, 16);   // (16 bytes to spare: the window loads of CsBytes)
+    const uint64_t *d_off = s.filled(aln_off, (size_t)n_aln + 1);
+    unsigned long long *d_small = s.zeroed<unsigned long long>(HPT_WORDS), *d_table = s.zeroed<unsigned long long>(n_table);
+    unsigned long long *d_cnt = s.zeroed<unsigned long long>((size_t)n_aln + 1);      // (entry n_aln stays 0: the scan leaves the total in slot[n_aln])
+    unsigned long long *d_slot = out->records ? s.alloc<unsigned long long>((size_t)n_aln + 1) : nullptr;
+    ns_hp_record *d_rec = cap_records ? s.alloc<ns_hp_record>((size_t)cap_records) : nullptr;
+    if (int rc = s.upload()) return rc;
     hipStream_t st = ctx->stream;
-    if (nbytes) e = hipMemcpyAsync(d_ref, ref_lines, (size_t)nbytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && nbytes) e = hipMemcpyAsync(d_qry, query_lines, (size_t)nbytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, aln_off, ((size_t)n_aln + 1) * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_small, 0, HPT_WORDS * 8, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_table, 0, table_bytes, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, ((size_t)n_aln + 1) * 8, st);      // (entry n_aln stays 0: the scan leaves the total in slot[n_aln])
-    if (e == hipSuccess) e = hipEventRecord(ctx->evt[EV_HIST_BEGIN], st);
-    uint32_t *d_order = nullptr;
-    if (e == hipSuccess) e = order_by_length(st, (const uint64_t *)d_off, n_aln, &d_key, &d_tmp, &d_order);
+    CALLCHK(s, hipEventRecord(ctx->evt[EV_HIST_BEGIN], st));
+    uint32_t *d_order;
+    if (int rc = order_by_length(s, d_off, n_aln, &d_order)) return rc;
     const dim3 grid((n_aln + 255u) / 256u), block(256);
-    if (e == hipSuccess) {
-        HpTrainDev H{(unsigned long long *)d_table, (unsigned long long *)d_small, cap_ref, cap_read};
-        k_hp_count<<<grid, block, 0, st>>>((const uint8_t *)d_ref, (const uint8_t *)d_qry, (const uint64_t *)d_off, n_aln, min_hp_len, H, d_order,
-                                           (unsigned long long *)d_cnt);
-        e = hipGetLastError();
-    }
-    int rc = NS_OK;
-    if (e == hipSuccess && out->records) {
-        rc = scan_sum(ctx, (const unsigned long long *)d_cnt, (unsigned long long *)d_slot, (size_t)n_aln + 1);
-        if (rc == NS_OK && cap_records) {
-            k_hp_records<<<grid, block, 0, st>>>((const uint8_t *)d_ref, (const uint8_t *)d_qry, (const uint64_t *)d_off, n_aln, min_hp_len, d_order,
-                                                 (const unsigned long long *)d_slot, (ns_hp_record *)d_rec, cap_records);
-            e = hipGetLastError();
+    const HpTrainDev H{d_table, d_small, cap_ref, cap_read};
+    k_hp_count<<<grid, block, 0, st>>>(d_ref, d_qry, d_off, n_aln, min_hp_len, H, d_order, d_cnt);
+    CALLCHK(s, hipGetLastError());
+    if (out->records) {
+        if (int rc = scan_sum(ctx, d_cnt, d_slot, (size_t)n_aln + 1)) return rc;       // (its own status and message, before any HIP error of this call)
+        if (cap_records) {
+            k_hp_records<<<grid, block, 0, st>>>(d_ref, d_qry, d_off, n_aln, min_hp_len, d_order, d_slot, d_rec, cap_records);
+            CALLCHK(s, hipGetLastError());
         }
     }
-    if (e == hipSuccess) e = hipEventRecord(ctx->evt[EV_HIST_END], st);
-    unsigned long long small[HPT_WORDS] = {0};
-    if (e == hipSuccess) e = hipMemcpyAsync(small, d_small, sizeof small, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(out->table, d_table, table_bytes, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && rc == NS_OK && small[HPT_N_HP] && small[HPT_N_HP] <= cap_records)
-        e = hipMemcpy(out->records, d_rec, (size_t)small[HPT_N_HP] * sizeof(ns_hp_record), hipMemcpyDeviceToHost);
-    float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ctx->evt[EV_HIST_BEGIN], ctx->evt[EV_HIST_END]);
-    release();
-    if (rc != NS_OK) return rc;
-    if (e != hipSuccess) return fail(ctx, NS_EHIP, std::string("ns_hp_histograms: ") + hipGetErrorString(e));
+    if (int rc = timed_tail(s, {{small, d_small, sizeof small}, {out->table, d_table, n_table * 8}}, &out->ms_kernel)) return rc;
+    if (small[HPT_N_HP] && small[HPT_N_HP] <= cap_records)
+        CALLCHK(s, hipMemcpy(out->records, d_rec, (size_t)small[HPT_N_HP] * sizeof(ns_hp_record), hipMemcpyDeviceToHost));
     for (int c = 0; c < 4; ++c) out->columns[c] = small[HPT_COLUMNS + c];
     out->n_hp = small[HPT_N_HP]; out->n_overflow = small[HPT_OVERFLOW]; out->max_ref = small[HPT_MAX_REF]; out->max_read = small[HPT_MAX_READ];
-    out->ms_kernel = ms;
     return NS_OK;
 }
 

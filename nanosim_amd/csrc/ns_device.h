@@ -469,3 +469,8 @@ __device__ __forceinline__ uint8_t *put_dec(uint8_t *p, uint64_t v) {
 __device__ __forceinline__ uint8_t complement(uint32_t x) {        // reverse_complement, S:1675-1680
     return x == 'A' ? 'T' : x == 'T' ? 'A' : x == 'C' ? 'G' : x == 'G' ? 'C' : (uint8_t)x;
 }
+// the sum of a value over the 64 lanes of the wavefront, in every lane
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}

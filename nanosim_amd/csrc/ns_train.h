@@ -1,0 +1,271 @@
+// ns_train.h — training side, the device kernels: the counting loops of the characterisation stage (k_cs_len, k_cs_hist),
+// of the base-quality model (k_qual_mark, k_qual_count) and of the homopolymer-length model (k_hp_count, k_hp_records).  The walks they
+// run are ns_cs_hist.h, ns_qual_hist.h and ns_hp_hist.h, which also compile for the host; the host side of the three calls
+// (ns_cs_histograms / ns_maf_histograms, ns_qual_histograms, ns_hp_histograms) is at the end of nanosim_amd.hip.  Nothing here uses
+// GenArgs or the simulation.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "ns_device.h"
+#include "ns_cs_hist.h"
+#include "ns_qual_hist.h"
+#include "ns_hp_hist.h"
+
+// ---------------------------------------------------------------------------------------------------------
+// k_cs_hist: the counting loop of the characterisation stage (ns_cs_hist.h; src/besthit_to_histogram.py:316-365), one alignment per
+// thread.  The 1-D histograms and the transition counters are privatised per workgroup in LDS (their hot bins — one-base mismatches,
+// short matches — would serialise millions of atomics on a few addresses) and flushed once; the (previous match, next match) matrix is
+// large and sparse: global atomics.
+// ---------------------------------------------------------------------------------------------------------
+struct CsHistDev {
+    unsigned long long *dic;          // [5][1001]
+    unsigned long long *err;          // [18] error_list, [3] first_error behind it
+    unsigned long long *misc;         // [0] max_match [1] match_list overflow [2] `=` items
+    unsigned long long *m2; uint32_t cap2;
+};
+#define NS_CSH_LDS_WORDS (5u * 1001u + 24u + 1u)
+struct CsAccDev {
+    uint32_t *l;                      // the workgroup's LDS counters: dic[5][1001], err[18], first[3], (3 spare), the largest match
+    const CsHistDev *H;
+    uint32_t mx;                      // largest length this thread handed to add_match
+    __device__ __forceinline__ void d1(uint32_t which, uint32_t v) { if (v <= NS_CS_DICT_MAX) atomicAdd(&l[which * 1001u + v], 1u); }
+    __device__ __forceinline__ void m2(uint32_t p, uint32_t s) {
+        const uint32_t m = p > s ? p : s;
+        mx = mx > m ? mx : m;
+        if (H->m2 && m < H->cap2) atomicAdd(&H->m2[(uint64_t)p * H->cap2 + s], 1ull);
+        else atomicAdd(&H->misc[1], 1ull);
+    }
+    __device__ __forceinline__ void err(uint32_t i) { atomicAdd(&l[5u * 1001u + i], 1u); }
+    __device__ __forceinline__ void first(uint32_t i) { atomicAdd(&l[5u * 1001u + 18u + i], 1u); }
+    __device__ __forceinline__ void skip() { atomicAdd(&H->misc[2], 1ull); }
+};
+__global__ void __launch_bounds__(256) k_cs_len(const uint64_t *__restrict__ off, uint32_t n_aln, uint32_t *__restrict__ key, uint32_t *__restrict__ idx) {
+    const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= n_aln) return;
+    const uint64_t n = off[a + 1] - off[a];
+    key[a] = n > 0xffffffffull ? 0xffffffffu : (uint32_t)n; idx[a] = a;
+}
+// qry != nullptr: the MAF branch — cs holds the reference lines, qry the query lines (maf_hist_alignment)
+__global__ void __launch_bounds__(256) k_cs_hist(const uint8_t *__restrict__ cs, const uint64_t *__restrict__ off, uint32_t n_aln, CsHistDev H,
+                                                 const uint32_t *__restrict__ order, const uint8_t *__restrict__ qry) {
+    __shared__ uint32_t cnt[NS_CSH_LDS_WORDS];
+    for (uint32_t i = threadIdx.x; i < NS_CSH_LDS_WORDS; i += blockDim.x) cnt[i] = 0;
+    __syncthreads();
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid < n_aln) {
+        const uint64_t a = order ? order[tid] : tid;          // visited by descending length: the 64 walks of a wavefront have similar trip counts
+        const uint8_t *s = cs + off[a];
+        const uint64_t n = off[a + 1] - off[a];
+        // prev_match is only read before this alignment assigns it when its first op is an error: then it is what the alignments in
+        // front of it left (the reference never resets it between alignments)
+        CsAccDev acc{cnt, &H, 0u};
+        if (qry) maf_hist_alignment(s, qry + off[a], n, acc);
+        else {
+            uint32_t pm = 0;
+            CsBytes sb(s);                                   // (an 8-byte register window over the thread's string: ns_cs_hist.h)
+            { CsCursor c; cs_cursor_init(c); int t; uint32_t l; if (cs_next_op(sb, n, c, t, l) && t != CS_MATCH) pm = cs_carry_in(cs, off, a); }
+            cs_hist_alignment(sb, n, pm, nullptr, acc);
+        }
+        if (acc.mx) atomicMax(&cnt[NS_CSH_LDS_WORDS - 1u], acc.mx);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < NS_CSH_LDS_WORDS; i += blockDim.x) {
+        const uint32_t v = cnt[i];
+        if (!v) continue;
+        if (i < 5u * 1001u) atomicAdd(&H.dic[i], (unsigned long long)v);
+        else if (i < NS_CSH_LDS_WORDS - 1u) atomicAdd(&H.err[i - 5u * 1001u], (unsigned long long)v);
+        else atomicMax(&H.misc[0], (unsigned long long)v);          // one atomic per workgroup for the largest match
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_qual_mark, k_qual_count: the base-quality histograms of the training side (ns_qual_hist.h; src/model_base_qualities.py:23-79).
+// MARK, one alignment per thread: the cs walk records a 2-bit mark per mismatched / inserted base (16 bases per word of `marks`, zeroed
+// by the caller).  A thread meets its bases in ascending order, so it gathers a word's marks in a register and writes the word once:
+// with a plain store when the word lies inside its own quality string, with an atomic OR for the string's first and last word, which
+// a neighbouring alignment may share.
+// COUNT streams the quality bytes and the marks once: a thread takes 16 bytes + one mark word per load, four loads in flight, wherever
+// the alignments begin; the alignment of a position comes from a binary search of the offsets, then from a walk forward.  Counters:
+// 32 copies of the 5 x 94 (+ 1) table per workgroup in LDS, copy = lane mod 32 = the LDS bank — `match` at the modal quality takes
+// most bases, and one counter per workgroup would serialise every wavefront's 64 adds on it; a copy per bank leaves two lanes of a
+// wavefront (one per 32-lane half) and the four wavefronts on an address.  A workgroup counts a contiguous span of at most 2^31 bytes
+// (the caller's grid), so no 32-bit counter can wrap; the copies are summed and flushed once with 64-bit atomics.
+// ---------------------------------------------------------------------------------------------------------
+#define NS_QH_BINS (QH_CLASSES * NS_QUAL_VALUES + 1u)      // the last one: bytes that are no quality value
+#define NS_QH_COPIES 32u
+#define NS_QH_LOADS 4u
+#define NS_QH_SUBTILE 4096u                                // 256 threads x 16 bytes
+#define NS_QH_TILE (NS_QH_LOADS * NS_QH_SUBTILE)
+#define NS_QH_OUT_SHORT (QH_CLASSES * 128u)                // the device image of ns_qual_hist: hist[5][128], n_short, n_bad_qual
+#define NS_QH_OUT_BAD (QH_CLASSES * 128u + 1u)
+#define NS_QH_OUT_WORDS (QH_CLASSES * 128u + 2u)
+struct QualMarkDev {
+    uint32_t *marks;
+    uint64_t base;                    // where the aligned part begins in the quality bytes
+    uint64_t w_first, w_last;         // the words a neighbouring alignment may write too
+    uint64_t cur; uint32_t bits;
+    __device__ __forceinline__ void flush() {
+        if (!bits) return;
+        if (cur == w_first || cur == w_last) atomicOr(&marks[cur], bits); else marks[cur] = bits;
+    }
+    __device__ __forceinline__ void mark(uint64_t i, uint32_t m) {
+        const uint64_t pos = base + i, w = pos >> 4;
+        if (w != cur) { flush(); cur = w; bits = 0; }
+        bits |= m << (2u * (uint32_t)(pos & 15u));
+    }
+};
+__global__ void __launch_bounds__(256) k_qual_mark(const uint8_t *__restrict__ cs, const uint64_t *__restrict__ cs_off, const uint64_t *__restrict__ qual_off,
+                                                   const ns_qual_aln *__restrict__ aln, uint32_t n_aln, const uint32_t *__restrict__ order,
+                                                   uint32_t *__restrict__ marks, unsigned long long *__restrict__ out) {
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= n_aln) return;
+    const uint64_t a = order ? order[tid] : tid;              // by descending length of the cs strings, as k_cs_hist
+    const ns_qual_aln A = aln[a];
+    const uint64_t lo = qual_off[a], hi = qual_off[a + 1];
+    const uint64_t aligned = hi - lo - A.head - A.tail;
+    if (A.unmapped || !aligned) return;
+    QualMarkDev sink{marks, lo + A.head, lo >> 4, (hi - 1u) >> 4, ~0ull, 0u};
+    CsBytes sb(cs + cs_off[a]);
+    const bool covered = qual_mark_alignment(sb, cs_off[a + 1] - cs_off[a], aligned, sink);
+    sink.flush();
+    if (!covered) atomicAdd(&out[NS_QH_OUT_SHORT], 1ull);
+}
+__global__ void __launch_bounds__(256) k_qual_count(const uint8_t *__restrict__ qual, const uint32_t *__restrict__ marks, const uint64_t *__restrict__ off,
+                                                    const ns_qual_aln *__restrict__ aln, uint32_t n_aln, uint64_t tiles_per_wg, uint64_t n_tiles,
+                                                    unsigned long long *__restrict__ out) {
+    __shared__ uint32_t cnt[NS_QH_BINS * NS_QH_COPIES];
+    for (uint32_t i = threadIdx.x; i < NS_QH_BINS * NS_QH_COPIES; i += blockDim.x) cnt[i] = 0;
+    __syncthreads();
+    uint32_t *mine = cnt + (threadIdx.x & (NS_QH_COPIES - 1u));
+    const uint64_t begin = off[0], end = off[n_aln];
+    const uint64_t t0 = (uint64_t)blockIdx.x * tiles_per_wg, t1 = t0 + tiles_per_wg < n_tiles ? t0 + tiles_per_wg : n_tiles;
+    uint32_t a = 0, next = 0;                                 // the alignment of the last byte looked at; where the search for the next goes on
+    uint64_t lo = 0, hi = 0;                                  // its bytes (hi = 0: none yet)
+    ns_qual_aln A{0u, 0u, 0u, 0u};
+    for (uint64_t t = t0; t < t1; ++t) {
+        const uint64_t p0 = t * NS_QH_TILE + (uint64_t)threadIdx.x * 16u;
+        uint4 v[NS_QH_LOADS]; uint32_t m[NS_QH_LOADS];
+#pragma unroll
+        for (uint32_t j = 0; j < NS_QH_LOADS; ++j) {
+            const uint64_t p = p0 + (uint64_t)j * NS_QH_SUBTILE;
+            v[j] = make_uint4(0u, 0u, 0u, 0u); m[j] = 0u;
+            if (p < end) { v[j] = *reinterpret_cast<const uint4 *>(qual + p); m[j] = marks[p >> 4]; }     // (both buffers are padded to whole words)
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < NS_QH_LOADS; ++j) {
+            const uint64_t p = p0 + (uint64_t)j * NS_QH_SUBTILE;
+            const uint32_t w[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+#pragma unroll
+            for (uint32_t k = 0; k < 16u; ++k) {
+                const uint64_t pos = p + k;
+                if (pos < begin || pos >= end) continue;
+                if (pos >= hi) {                              // the next alignment that holds a byte: a few steps forward, else a search
+                    for (uint32_t s = 0; s < 4u && off[next + 1u] <= pos; ++s) ++next;
+                    if (off[next + 1u] <= pos) next = qual_locate(off, next + 1u, n_aln, pos);
+                    a = next; next = a + 1u;
+                    lo = off[a]; hi = off[a + 1u]; A = aln[a];
+                }
+                const uint32_t q = ((w[k >> 2] >> (8u * (k & 3u))) & 0xffu) - NS_QUAL_FIRST;
+                const uint32_t bin = q < NS_QUAL_VALUES ? qual_class(pos - lo, hi - lo, A.head, A.tail, A.unmapped, (m[j] >> (2u * k)) & 3u) * NS_QUAL_VALUES + q
+                                                        : NS_QH_BINS - 1u;
+                atomicAdd(&mine[bin * NS_QH_COPIES], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t bin = threadIdx.x; bin < NS_QH_BINS; bin += blockDim.x) {
+        unsigned long long sum = 0;
+        for (uint32_t c = 0; c < NS_QH_COPIES; ++c) sum += cnt[bin * NS_QH_COPIES + ((c + bin) & (NS_QH_COPIES - 1u))];   // (rotated: the lanes read 32 banks)
+        if (sum) atomicAdd(&out[bin < NS_QH_BINS - 1u ? (bin / NS_QUAL_VALUES) * 128u + bin % NS_QUAL_VALUES : NS_QH_OUT_BAD], sum);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_hp_count, k_hp_records: the homopolymer-length model of the training side (ns_hp_hist.h; src/model_homopolymer_lengths.py:9-119 —
+// not the -k stage of the simulation above).  One alignment per thread, both lines through 8-byte CsBytes windows, visited by
+// descending length as k_cs_hist.  The [2][ref_len][read_len] counts: the corner below NS_HPT_CORNER in both lengths — where almost
+// every homopolymer falls — is privatised per workgroup in LDS and flushed once; 2 x 48 x 48 x 4 B = 18 KB leaves eight workgroups
+// (32 wavefronts, the limit) on a compute unit's 160 KB.  What lies outside goes to the caller's dense table by global atomics, or,
+// beyond its caps, to the overflow counter.  A workgroup counts 256 alignments of fewer than 2^24 columns each (the host checks), so
+// no 32-bit counter can wrap.  The column counters, the number of homopolymers and the overflow are summed over the wavefront first.
+// k_hp_records repeats the walk and writes the homopolymers of alignment a from slot[a] on (the exclusive scan of k_hp_count's
+// per-alignment numbers; slot[n_aln] is their total): nothing when the caller's buffer is too small for all of them.
+// ---------------------------------------------------------------------------------------------------------
+#define NS_HPT_CORNER 48u
+#define NS_HPT_LDS_WORDS (2u * NS_HPT_CORNER * NS_HPT_CORNER)
+enum { HPT_COLUMNS = 0, HPT_N_HP = 4, HPT_OVERFLOW = 5, HPT_MAX_REF = 6, HPT_MAX_READ = 7, HPT_WORDS = 8 };   // the device image of the small results
+struct HpTrainDev {
+    unsigned long long *table;        // [2][cap_ref][cap_read]
+    unsigned long long *small;        // [HPT_WORDS]
+    uint32_t cap_ref, cap_read;
+};
+struct HpTrainAcc {
+    uint32_t *l;                      // the workgroup's corner of the table
+    const HpTrainDev *H;
+    uint32_t mx_ref, mx_read, over, col[4];
+    __device__ __forceinline__ void hp(uint32_t cls, uint8_t, uint32_t ref_len, uint32_t read_len, uint32_t, uint32_t) {
+        mx_ref = mx_ref > ref_len ? mx_ref : ref_len;
+        mx_read = mx_read > read_len ? mx_read : read_len;
+        if (ref_len >= H->cap_ref || read_len >= H->cap_read) ++over;
+        else if (ref_len < NS_HPT_CORNER && read_len < NS_HPT_CORNER) atomicAdd(&l[(cls * NS_HPT_CORNER + ref_len) * NS_HPT_CORNER + read_len], 1u);
+        else atomicAdd(&H->table[((uint64_t)cls * H->cap_ref + ref_len) * H->cap_read + read_len], 1ull);
+    }
+    __device__ __forceinline__ void columns(uint32_t ins, uint32_t del, uint32_t mis, uint32_t match) {
+        col[HPC_INS] = ins; col[HPC_DEL] = del; col[HPC_MIS] = mis; col[HPC_MATCH] = match;
+    }
+};
+__global__ void __launch_bounds__(256) k_hp_count(const uint8_t *__restrict__ ref, const uint8_t *__restrict__ qry, const uint64_t *__restrict__ off,
+                                                  uint32_t n_aln, uint32_t min_hp_len, HpTrainDev H, const uint32_t *__restrict__ order,
+                                                  unsigned long long *__restrict__ n_per_aln) {
+    __shared__ uint32_t cnt[NS_HPT_LDS_WORDS];
+    for (uint32_t i = threadIdx.x; i < NS_HPT_LDS_WORDS; i += blockDim.x) cnt[i] = 0;
+    __syncthreads();
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    HpTrainAcc acc{cnt, &H, 0u, 0u, 0u, {0u, 0u, 0u, 0u}};
+    uint32_t n_hp = 0;
+    if (tid < n_aln) {
+        const uint64_t a = order ? order[tid] : tid;
+        CsBytes rb(ref + off[a]), qb(qry + off[a]);
+        n_hp = hp_hist_alignment(rb, qb, off[a + 1] - off[a], min_hp_len, acc);
+        n_per_aln[a] = n_hp;
+    }
+    // (every lane of the workgroup comes here: the wavefront sums need them all)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t sums[6] = {acc.col[0], acc.col[1], acc.col[2], acc.col[3], n_hp, acc.over};
+#pragma unroll
+    for (uint32_t j = 0; j < 6u; ++j) {
+        const unsigned long long s = wave_sum(sums[j]);
+        if (lane == 0 && s) atomicAdd(&H.small[j], s);          // HPT_COLUMNS .. HPT_OVERFLOW
+    }
+    uint32_t mr = acc.mx_ref, mq = acc.mx_read;
+    for (int o = 32; o > 0; o >>= 1) { mr = max(mr, (uint32_t)__shfl_xor((int)mr, o)); mq = max(mq, (uint32_t)__shfl_xor((int)mq, o)); }
+    if (lane == 0 && mr) atomicMax(&H.small[HPT_MAX_REF], (unsigned long long)mr);
+    if (lane == 0 && mq) atomicMax(&H.small[HPT_MAX_READ], (unsigned long long)mq);
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < NS_HPT_LDS_WORDS; i += blockDim.x) {
+        const uint32_t v = cnt[i];
+        if (!v) continue;                                           // (an entry counted here lies inside the caps: HpTrainAcc::hp)
+        const uint32_t cls = i / (NS_HPT_CORNER * NS_HPT_CORNER), r = i / NS_HPT_CORNER % NS_HPT_CORNER, q = i % NS_HPT_CORNER;
+        atomicAdd(&H.table[((uint64_t)cls * H.cap_ref + r) * H.cap_read + q], (unsigned long long)v);
+    }
+}
+struct HpRecordSink {
+    ns_hp_record *rec; uint64_t at, end; uint32_t aln;
+    __device__ __forceinline__ void hp(uint32_t, uint8_t base, uint32_t ref_len, uint32_t read_len, uint32_t start, uint32_t) {
+        const uint32_t code = base == 'A' ? 0u : base == 'C' ? 1u : base == 'G' ? 2u : 3u;
+        if (at < end) rec[at] = ns_hp_record{aln, start, ref_len, read_len << 2 | code};
+        ++at;
+    }
+    __device__ __forceinline__ void columns(uint32_t, uint32_t, uint32_t, uint32_t) {}
+};
+__global__ void __launch_bounds__(256) k_hp_records(const uint8_t *__restrict__ ref, const uint8_t *__restrict__ qry, const uint64_t *__restrict__ off,
+                                                    uint32_t n_aln, uint32_t min_hp_len, const uint32_t *__restrict__ order,
+                                                    const unsigned long long *__restrict__ slot, ns_hp_record *__restrict__ rec, uint64_t cap_records) {
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= n_aln || slot[n_aln] > cap_records) return;
+    const uint64_t a = order ? order[tid] : tid;
+    if (slot[a + 1] == slot[a]) return;
+    HpRecordSink sink{rec, slot[a], slot[a + 1], (uint32_t)a};
+    CsBytes rb(ref + off[a]), qb(qry + off[a]);
+    hp_hist_alignment(rb, qb, off[a + 1] - off[a], min_hp_len, sink);
+}

@@ -1,5 +1,5 @@
 """Training side, the base-quality model on CPU: the engine's walk over cs + QUAL (nanosim_amd/csrc/ns_qual_hist.h, compiled
-for the host), the closed-form log-normal fit and the host module around the call — pinned against what the REAL
+for the host; on the GPU the kernels of ns_train.h run it), the closed-form log-normal fit and the host module around the call — pinned against what the REAL
 src/model_base_qualities.py collected and wrote for the same alignments (tests/golden/reference_basequal.json.gz,
 tests/golden/make_basequal_golden.py) and against a per-base expansion written here."""
 import ctypes as C

@@ -1,5 +1,5 @@
 """Training-side histogramming (second half) on CPU: the oracle's restatement of parse_cs / hist()'s counting loop,
-the host formatting of the reference's tables, and the engine's one-pass walk (compiled for the host) — all pinned against what the REAL
+the host formatting of the reference's tables, and the engine's one-pass walk (nanosim_amd/csrc/ns_cs_hist.h, compiled for the host; on the GPU k_cs_hist of ns_train.h runs it) — all pinned against what the REAL
 src/besthit_to_histogram.py:hist() wrote for the same alignments (tests/golden/reference_hist.json.gz, tests/golden/make_hist_golden.py)."""
 import ctypes as C
 import gzip

@@ -1,4 +1,4 @@
-"""GPU parity of the training-side histogramming (second half): ns_cs_histograms (k_cs_hist, one alignment per thread)
+"""GPU parity of the training-side histogramming (second half): ns_cs_histograms (k_cs_hist of csrc/ns_train.h, one alignment per thread)
 against the oracle's two-list restatement of src/besthit_to_histogram.py:hist() and against the files the reference itself wrote
 (tests/golden/reference_hist.json.gz).  (The file sorts behind the other -m gpu files on purpose: it is the newest kernel of the engine — and for the same reason the file runs
 in a CHILD pytest first: a device fault or a hang there fails this file with the child's output, not the whole -m gpu run.)"""

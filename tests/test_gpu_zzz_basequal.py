@@ -1,4 +1,4 @@
-"""GPU parity of the training side's base-quality model: ns_qual_histograms (k_qual_mark + k_qual_count) against what the
+"""GPU parity of the training side's base-quality model: ns_qual_histograms (k_qual_mark + k_qual_count, csrc/ns_train.h) against what the
 REAL src/model_base_qualities.py collected and wrote (tests/golden/reference_basequal.json.gz), against the same walk compiled for the
 host and against the per-base expansion of tests/test_basequal.py.  (The file sorts behind every other -m gpu file: these are the
 newest kernels of the engine — and for the same reason it runs in a CHILD pytest first, like tests/test_gpu_zz_characterize.py: a

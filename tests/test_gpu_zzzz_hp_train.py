@@ -1,4 +1,4 @@
-"""GPU parity of the training side's homopolymer-length model: ns_hp_histograms (k_hp_count + k_hp_records) against what the
+"""GPU parity of the training side's homopolymer-length model: ns_hp_histograms (k_hp_count + k_hp_records, csrc/ns_train.h) against what the
 REAL src/model_homopolymer_lengths.py collected and wrote (tests/golden/reference_hp_train.json.gz) and against the same walk compiled
 for the host.  (The file sorts behind every other -m gpu file: these are the newest kernels of the engine — and for the same reason it
 runs in a CHILD pytest first, like tests/test_gpu_zzz_basequal.py: a device fault or a hang there fails this file with the child's

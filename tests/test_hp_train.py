@@ -1,5 +1,5 @@
 """Training side, the homopolymer-length model on CPU: the engine's walk over the two lines of a MAF alignment
-(nanosim_amd/csrc/ns_hp_hist.h, compiled for the host), the two fits and the host module around the call — pinned against what the REAL
+(nanosim_amd/csrc/ns_hp_hist.h, compiled for the host; on the GPU the kernels of ns_train.h run it), the two fits and the host module around the call — pinned against what the REAL
 src/model_homopolymer_lengths.py collected and wrote for the same alignments (tests/golden/reference_hp_train.json.gz,
 tests/golden/make_hp_train_golden.py), against the `regex` module for the fuzzy match, and against a brute force for the piecewise
 fit."""
