@@ -13,6 +13,7 @@ not processes, do the work (run under ``torch.distributed.run`` for several GPUs
 from __future__ import annotations
 
 import argparse
+import contextlib
 import os
 import sys
 import time
@@ -144,24 +145,35 @@ def calculate_read_number_from_coverage(ref: M.Reference, model_prefix: str, cov
     return int(ref.genome_len / mean * coverage)
 
 
-def validate_genome_args(a, parser_g):
-    """S:2251-2280: same messages, usage on stderr, exit code 1."""
+def validate_genome_args(a, parser_mode):
+    """For all three modes, despite its name: the checks of a mode's branch of main(), before anything is opened (genome S:2251-2280,
+    transcriptome S:2350-2374, metagenome S:2438-2467): same messages in the same order, usage on stderr, exit code 1.  The
+    transcriptome parser has no read-length distribution and no --chimeric, the other two no intron retention and no polyA tails: a
+    flag a mode lacks counts as not given."""
     def die(msg, to_err=True):
         (sys.stderr if to_err else sys.stdout).write("\n" + msg + "\n")
-        parser_g.print_help(sys.stderr)
+        parser_mode.print_help(sys.stderr)
         sys.exit(1)
+    median_len, sd_len, chimeric = (getattr(a, k, None) for k in ("median_len", "sd_len", "chimeric"))
     if a.homopolymer and (a.KmerBias is None or a.KmerBias < 0):
         die("Please input proper kmer bias value >= 0 to simulate homopolymer contraction and expansion events from", False)
     if a.strandness and (a.strandness < 0 or a.strandness > 1):
         die("Please input proper strandness value between 0 and 1", False)
-    if (a.median_len and not a.sd_len) or (a.sd_len and not a.median_len):
+    if (median_len and not sd_len) or (sd_len and not median_len):
         die("Please provide both mean and standard deviation of read length!")
-    if a.median_len and a.sd_len and a.chimeric:
+    if median_len and sd_len and chimeric:
         die("Lognormal distributed reads cannot be chimeric!")
     if a.max_len < a.min_len:
         die("Maximum read length must be longer than Minimum read length!")
-    if a.perfect and a.chimeric:
+    if a.perfect and chimeric:
         die("Perfect reads cannot be chimeric", False)
+    if getattr(a, "no_model_ir", False) and a.ref_g == '':                                      # (store_false: True unless --no_model_ir)
+        die("Please provide a reference genome to simulate intron retention events!")
+    if getattr(a, "polya", None) and a.basecaller is None:
+        die("Please input basecaller to simulate polyA tails from.", False)
+    if a.KmerBias and not a.homopolymer:                                                       # not in the reference
+        sys.stderr.write("\n-k/--KmerBias needs -hp (the reference crashes on the missing homopolymer parameters, S:504,639)\n")
+        sys.exit(1)
 
 
 def _cap_stripes(stripes: int, n_outputs: int) -> int:
@@ -305,18 +317,11 @@ def _run_phases(aligned, unaligned, rank, n_done, step_owner=None):
         sys.stdout.flush()
 
 
-def _batch_params(n, first, *, seed, kind, fastq, chimeric, min_len, max_len, median_len, sd_len, want_errlog, kmer_bias, meta, trx, uracil,
-                  model_ir, emit_records=True):
-    return E.make_params(seed=seed, first_read=first, n_reads=n, kind=kind, fastq=fastq, chimeric=chimeric, kmer_bias=kmer_bias, min_len=min_len,
-                         max_len=max_len, median_len=median_len, sd_len=sd_len, emit_records=emit_records, emit_errlog=want_errlog, meta=meta,
-                         trx=trx, uracil=uracil, model_ir=model_ir)
-
-
-def _write_batches(eng, out_path, err_path, *, seed, first, count, kind, fastq, chimeric, min_len, max_len, median_len,
-                   sd_len, want_errlog, kmer_bias=0, meta=False, err_header=b"", trx=False, uracil=False, model_ir=False, dist=None, stripes=1,
-                   quiet=False, tag="", batch_reads=None, gen=None):
+def _write_batches(eng, out_path, err_path, params, *, first, count, err_header=b"", dist=None, stripes=1, quiet=False, tag="",
+                   batch_reads=None, gen=None):
     """Reads [first, first + count) of this rank into out_path (and their error-profile rows into err_path), through the engine's output
     sinks (include/nanosim_amd.h: ns_sink_*): the images of batch i leave the GPU and reach the files while batch i + 1 is generated.
+    params: what every worker call of the phase has in common, as keywords of E.make_params (seed, kind, lengths, mode flags).
 
     stripes == 1: rank 0 writes the final files front to back, every other rank one sub-file per output.
     stripes > 1 (-t K; the reference's workers write K sub-files that are concatenated afterwards, S:1588-1639): every batch is cut at read
@@ -332,8 +337,6 @@ def _write_batches(eng, out_path, err_path, *, seed, first, count, kind, fastq, 
     world = dist.get_world_size() if dist is not None else 1
     trace = os.environ.get("NS_CLI_TRACE") is not None       # per-batch host timing on stderr
     keep = os.environ.get("NS_KEEP_SUBFILES", "0") != "0"      # (--no-merge sets it: main)
-    kw = dict(seed=seed, kind=kind, fastq=fastq, chimeric=chimeric, min_len=min_len, max_len=max_len, median_len=median_len, sd_len=sd_len,
-              want_errlog=err_path is not None, kmer_bias=kmer_bias, meta=meta, trx=trx, uracil=uracil, model_ir=model_ir)
     batch = min(getattr(eng, "_batch_reads", BATCH_READS), batch_reads or BATCH_READS)
     paths = [p for p in (out_path, err_path) if p]
     which = {out_path: E.NS_BUF_RECORDS, err_path: E.NS_BUF_ERRLOG}
@@ -375,9 +378,9 @@ def _write_batches(eng, out_path, err_path, *, seed, first, count, kind, fastq, 
             n = min(batch, count - done)
             t0 = time.perf_counter()
             try:
-                b = (gen or eng.generate)(_batch_params(n, first + done, **kw))
+                b = (gen or eng.generate)(E.make_params(first_read=first + done, n_reads=n, emit_errlog=err_path is not None, **params))
             except E.EngineError as ex:              # not enough free HBM for this batch size (shared GPU): halve it and go on
-                if getattr(ex, "code", 0) != E.NS_ENOMEM or n <= 1000 or meta:
+                if getattr(ex, "code", 0) != E.NS_ENOMEM or n <= 1000 or params.get("meta"):
                     raise                            # (metagenome workers: the batches are part of the result)
                 batch = eng._batch_reads = max(1000, n // 2)
                 continue
@@ -440,105 +443,161 @@ def _write_batches(eng, out_path, err_path, *, seed, first, count, kind, fastq, 
             shard.collect_parts(p, world, files[p], keep=keep)
 
 
+class _Run:
+    """What the three modes share of a run: where it runs (rank, world, dist, device of the broadcast), the engine of the aligned worker
+    calls and the one of the unaligned calls, seed, file extension and -t; and the procedure around a mode's own steps — prologue here,
+    then broadcast(), `with scope(outputs)`: load_model(), set_up(), simulate() once (metagenome: once per sample)."""
+
+    def __init__(self, a, shown):
+        """the process group, the parameter print (`shown`, in the reference's order: the name of a flag, or (label, value)), the output
+        directory, the seed"""
+        self.a = a
+        self.rank, self.device, self.world, self.dist, self.bdev = shard.init_dist()
+        if self.rank == 0:
+            print("\nrunning the code with following parameters:\n")
+            for x in shown:
+                print(*((x, getattr(a, x)) if isinstance(x, str) else x))
+            log(' '.join(sys.argv))
+        d = os.path.dirname(a.output)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        self.ext = ".fastq" if a.fastq else ".fasta"
+        self.seed = a.seed if a.seed is not None else int.from_bytes(os.urandom(8), "little") >> 1
+        self.stripes = max(a.num_threads, 1)
+        self.eng = self.eng_un = self.step_owner = None           # (the mode opens self.eng where it did before: E.Engine(self.device))
+        self.keep = None                                          # the broadcast bases on this GPU, while an engine may still copy them
+
+    def outputs(self, base):
+        return [base + "_aligned_reads" + self.ext, base + "_aligned_error_profile", base + "_unaligned_reads" + self.ext]
+
+    def broadcast(self, ref, extra=None, outputs=(), error=None):
+        """Rank 0's reference, its seed and the mode's small tables `extra` (a dict) for every rank: returns (ref, extra).  error: rank
+        0's failed check — every rank leaves together (the verdict travels in the header of the broadcast).  outputs: whose sub-files of
+        an earlier run to remove first.  One rank without a process group: nothing travels."""
+        if self.dist is None:
+            shard.agree(None, error is None, error or "")
+            return ref, extra
+        shard.clean_parts(outputs, self.rank)
+        ref, self.keep, extra = shard.broadcast_reference(ref, self.dist, device=self.bdev, error=error,
+                                                          extra=dict(extra or {}, seed=self.seed) if self.rank == 0 else None)
+        self.seed = extra["seed"]                                 # rank 0's: a read is a function of (seed, read index)
+        if self.bdev is None:                                     # (gloo: the bases arrived in host memory)
+            ref = M.Reference(ref.names, self.keep.numpy(), ref.chrom_off, ref.circular)
+            self.keep = None
+        return ref, extra
+
+    def dev_ptr(self):
+        """where the broadcast left the bases on this GPU; None: they are in ref.bases"""
+        return self.keep.data_ptr() if self.keep is not None else None
+
+    @contextlib.contextmanager
+    def scope(self, outputs):
+        """everything after the broadcast: a failure leaves a marker for every output (shard.failure_markers), both engines are closed
+        whatever happens, and the run ends as the reference's does"""
+        with shard.failure_markers(outputs, self.rank, self.world):
+            try:
+                yield
+            finally:
+                if self.eng_un is not None and self.eng_un is not self.eng:
+                    self.eng_un.close()
+                self.eng.close()
+        if self.dist is not None:
+            self.dist.destroy_process_group()
+        if self.rank == 0:
+            log("Finished!")
+
+    def load_model(self, **mode):
+        a = self.a
+        if self.rank == 0:
+            log("Read error profile" if not a.perfect else "Read KDF of aligned reads")
+        return M.load_model(a.model_prefix, perfect=a.perfect, strandness=a.strandness, homopolymer=a.homopolymer, fastq=a.fastq, **mode)
+
+    def set_up(self, setup, setup_unaligned=None):
+        """setup(engine) installs reference, mode tables and model; then the choice of where the unaligned worker calls run: on the same
+        engine (--perfect has none, NS_SERIAL=1 runs them afterwards) or next to the aligned ones (_background_engine; a second engine
+        of its own is set up by setup_unaligned, default `setup`)"""
+        setup(self.eng)
+        self.eng_un = self.eng
+        if not self.a.perfect and not _serial_schedule():
+            self.eng_un, self.step_owner = _background_engine(self.device, setup_unaligned or setup, self.eng)
+
+    def read_number(self, ref):
+        """-n, or what -x makes of it (S:2247-2249, 2346-2348); the note comes from rank 0, as every other line of the run does"""
+        if self.a.coverage is None:
+            return self.a.number
+        if self.rank == 0:
+            print("\nCalculating the number of reads to be simulated based on the coverage, if you specified the number of reads "
+                  "concurrently with the coverage, coverage will override number of reads.\n")
+        return calculate_read_number_from_coverage(ref, self.a.model_prefix, self.a.coverage)
+
+    def simulate(self, base, first, n_al, n_un, common, aligned_only):
+        """simulation() (S:1568-1672) for a genome, a transcriptome or one metagenome sample: reads [first, first + n_al) are the aligned
+        ones (<base>_aligned_reads, <base>_aligned_error_profile), the n_un after them the unaligned ones (<base>_unaligned_reads);
+        this rank writes its share of both.  common / aligned_only: keywords of E.make_params for every worker call / for the aligned
+        ones (seed and kind are set here)."""
+        a, rank = self.a, self.rank
+        if rank == 0:
+            log("Start simulation of aligned reads")
+        lo, hi = shard.partition(n_al, self.world)[rank]
+        ulo, uhi = shard.partition(n_un, self.world)[rank]
+        side_by_side = self.eng_un is not self.eng
+        out_al, out_err, out_un = self.outputs(base)
+        common = dict(common, seed=self.seed)
+        meta = bool(common.get("meta"))
+        stripes = 1 if meta else self.stripes      # -t has no effect in metagenome mode: not a decision, kept as it has always been
+        # deliberate: a metagenome worker call keeps its own species quotas, so its batches are part of the result, never the step's shares
+        b_al, b_un = _step_batches(n_al, n_un) if side_by_side and not meta else (None, None)
+
+        def aligned(gen=None):
+            _write_batches(self.eng, out_al, out_err, dict(common, kind=E.NS_KIND_PERFECT if a.perfect else E.NS_KIND_ALIGNED, **aligned_only),
+                           first=first + lo, count=hi - lo, err_header=ERR_HEADER, dist=self.dist, stripes=stripes, tag=" aligned",
+                           batch_reads=b_al, gen=gen)
+
+        def unaligned(gen=None, quiet=True):                                                    # S:1642-1672
+            _write_batches(self.eng_un, out_un, None, dict(common, kind=E.NS_KIND_UNALIGNED), first=first + n_al + ulo, count=uhi - ulo,
+                           dist=self.dist, stripes=stripes, quiet=quiet, tag=" unaligned", batch_reads=b_un, gen=gen)
+        if a.perfect:
+            aligned()
+        elif not side_by_side:
+            aligned()
+            if rank == 0:
+                log("Start simulation of random reads")
+            unaligned(quiet=False)
+        else:
+            _run_phases(aligned, unaligned, rank, first + n_al + uhi, self.step_owner)
+
+
 def run_genome(a, parser_g):
     validate_genome_args(a, parser_g)
-    rank, device, world, dist, bdev = shard.init_dist()
-    if a.KmerBias and not a.homopolymer:
-        sys.stderr.write("\n-k/--KmerBias needs -hp (the reference crashes on the missing homopolymer parameters, S:504,639)\n")
-        sys.exit(1)
-    if rank == 0:
-        print("\nrunning the code with following parameters:\n")
-        for k in ("ref_g", "model_prefix"):
-            print(k, getattr(a, k))
-        print("out", a.output); print("number", [a.number]); print("coverage", a.coverage); print("perfect", a.perfect)
-        print("homopolymer", a.homopolymer); print("dna_type", a.dna_type); print("strandness", a.strandness)
-        print("sd_len", a.sd_len); print("median_len", a.median_len); print("max_len", a.max_len); print("min_len", a.min_len)
-        print("fastq", a.fastq); print("chimeric", a.chimeric); print("num_threads", max(a.num_threads, 1))
-        log(' '.join(sys.argv))
-    out = a.output
-    d = os.path.dirname(out)
-    if d:
-        os.makedirs(d, exist_ok=True)
+    run = _Run(a, ["ref_g", "model_prefix", ("out", a.output), ("number", [a.number]), "coverage", "perfect", "homopolymer", "dna_type",
+                   "strandness", "sd_len", "median_len", "max_len", "min_len", "fastq", "chimeric", ("num_threads", max(a.num_threads, 1))])
+    rank = run.rank
     if rank == 0:
         log("Read in reference ")
-    eng = E.Engine(device)
+    run.eng = E.Engine(run.device)
     ref = M.read_fasta(a.ref_g, a.dna_type) if rank == 0 else None
-    ext = ".fastq" if a.fastq else ".fasta"
-    seed = a.seed if a.seed is not None else int.from_bytes(os.urandom(8), "little") >> 1
-    # S:354-356; every rank leaves together (the verdict of rank 0's check travels in the header of the broadcast)
-    bad = "Do not choose circular if there is more than one chromosome in the genome!\n" if (rank == 0 and len(ref.names) > 1 and a.dna_type == "circular") else None
-    keep = None
-    outputs = [out + "_aligned_reads" + ext, out + "_aligned_error_profile", out + "_unaligned_reads" + ext]
-    if dist is not None:
-        shard.clean_parts(outputs, rank)
-        ref, keep, extra = shard.broadcast_reference(ref, dist, device=bdev, extra=dict(seed=seed), error=bad)
-        seed = extra["seed"]               # rank 0's: a read is a function of (seed, read index)
-        if bdev is None:                                                                    # (gloo: the bases arrived in host memory)
-            ref = M.Reference(ref.names, keep.numpy(), ref.chrom_off, ref.circular)
-    else:
-        shard.agree(None, bad is None, bad or "")
-    with shard.failure_markers(outputs, rank, world):
-        if rank == 0:
-            log("Read error profile" if not a.perfect else "Read KDF of aligned reads")
-        mdl = M.load_model(a.model_prefix, perfect=a.perfect, strandness=a.strandness, chimeric=a.chimeric,
-                           homopolymer=a.homopolymer, fastq=a.fastq)
+    bad = None
+    if rank == 0 and len(ref.names) > 1 and a.dna_type == "circular":                         # S:354-356
+        bad = "Do not choose circular if there is more than one chromosome in the genome!\n"
+    outputs = run.outputs(a.output)
+    ref, _ = run.broadcast(ref, outputs=outputs, error=bad)
+    with run.scope(outputs):
+        mdl = run.load_model(chimeric=a.chimeric)
 
         def setup(e):
-            if dist is not None and bdev is not None:
-                e.set_reference_device(keep.data_ptr(), ref)
+            if run.dev_ptr() is not None:
+                e.set_reference_device(run.dev_ptr(), ref)
             else:
                 e.set_reference(ref)
             e.load_model(mdl)
-        setup(eng)
-        number = a.number
-        if a.coverage is not None:
-            if rank == 0:
-                print("\nCalculating the number of reads to be simulated based on the coverage, if you specified the number of reads "
-                      "concurrently with the coverage, coverage will override number of reads.\n")
-            number = calculate_read_number_from_coverage(ref, a.model_prefix, a.coverage)
-        n_al, n_un = mdl.split_counts(number)
+        run.set_up(setup)
+        n_al, n_un = mdl.split_counts(run.read_number(ref))
+        if rank == 0 and a.median_len and a.sd_len:
+            log("Simulating read length with log-normal distribution")
         max_len = int(min(a.max_len, ref.max_chrom))                                            # S:2318
-        kind = E.NS_KIND_PERFECT if a.perfect else E.NS_KIND_ALIGNED
-        if rank == 0:
-            if a.median_len and a.sd_len:
-                log("Simulating read length with log-normal distribution")
-            log("Start simulation of aligned reads")
-        lo, hi = shard.partition(n_al, world)[rank]
-        ulo, uhi = shard.partition(n_un, world)[rank]
-        stripes = max(a.num_threads, 1)
-        eng_un, step_owner = eng, None
-        if not a.perfect and not _serial_schedule():
-            eng_un, step_owner = _background_engine(device, setup, eng)
-        b_al, b_un = _step_batches(n_al, n_un) if eng_un is not eng else (None, None)
-
-        def aligned(gen=None):
-            _write_batches(eng, outputs[0], outputs[1], seed=seed, first=lo, count=hi - lo, kind=kind,
-                           fastq=a.fastq, chimeric=a.chimeric, min_len=a.min_len, max_len=max_len, median_len=a.median_len, sd_len=a.sd_len,
-                           want_errlog=True, kmer_bias=a.KmerBias or 0, err_header=ERR_HEADER, dist=dist, stripes=stripes, tag=" aligned",
-                           batch_reads=b_al, gen=gen)
-
-        def unaligned(quiet, gen=None):                                                         # S:1642-1672
-            _write_batches(eng_un, outputs[2], None, seed=seed, first=n_al + ulo, count=uhi - ulo, kind=E.NS_KIND_UNALIGNED,
-                           fastq=a.fastq, chimeric=False, min_len=a.min_len, max_len=max_len, median_len=a.median_len, sd_len=a.sd_len,
-                           want_errlog=False, dist=dist, stripes=stripes, quiet=quiet, tag=" unaligned", batch_reads=b_un, gen=gen)
-        try:
-            if a.perfect:
-                aligned()
-            elif eng_un is eng:
-                aligned()
-                if rank == 0:
-                    log("Start simulation of random reads")
-                unaligned(False)
-            else:
-                _run_phases(aligned, lambda gen=None: unaligned(True, gen), rank, n_al + uhi, step_owner)
-        finally:
-            if eng_un is not eng:
-                eng_un.close()
-            eng.close()
-    if dist is not None:
-        dist.destroy_process_group()
-    if rank == 0:
-        log("Finished!")
+        run.simulate(a.output, 0, n_al, n_un,
+                     dict(fastq=a.fastq, min_len=a.min_len, max_len=max_len, median_len=a.median_len, sd_len=a.sd_len),
+                     dict(chimeric=a.chimeric, kmer_bias=a.KmerBias or 0))
 
 
 def run_metagenome(a, parser_mg):
@@ -546,234 +605,97 @@ def run_metagenome(a, parser_mg):
     one worker of the reference: it keeps its own per-species base quota (S:835) and numbers its reads consecutively."""
     from . import metagenome as MG
     validate_genome_args(a, parser_mg)
-    if a.KmerBias and not a.homopolymer:
-        sys.stderr.write("\n-k/--KmerBias needs -hp (the reference crashes on the missing homopolymer parameters, S:504,639)\n")
-        sys.exit(1)
-    rank, device, world, dist, bdev = shard.init_dist()
-    if rank == 0:
-        print("\nrunning the code with following parameters:\n")
-        for k in ("genome_list", "abun", "dna_type_list", "model_prefix"):
-            print(k, getattr(a, k))
-        print("out", a.output); print("perfect", a.perfect); print("strandness", a.strandness); print("sd_len", a.sd_len)
-        print("median_len", a.median_len); print("max_len", a.max_len); print("min_len", a.min_len); print("abun_var", a.abun_var)
-        print("fastq", a.fastq); print("chimeric", a.chimeric); print("num_threads", max(a.num_threads, 1))
-        log(' '.join(sys.argv))
-    out = a.output
-    d = os.path.dirname(out)
-    if d:
-        os.makedirs(d, exist_ok=True)
-    eng = E.Engine(device)
-    keep = None
+    run = _Run(a, ["genome_list", "abun", "dna_type_list", "model_prefix", ("out", a.output), "perfect", "strandness", "sd_len", "median_len",
+                   "max_len", "min_len", "abun_var", "fastq", "chimeric", ("num_threads", max(a.num_threads, 1))])
+    rank = run.rank
+    run.eng = E.Engine(run.device)
+    mref = info = None
     if rank == 0:
         log("Read in reference ")
         mref = MG.read_metagenome(a.genome_list, a.dna_type_list)
         numbers, samples = MG.read_abundance(a.abun, mref.species)
-    seed = a.seed if a.seed is not None else int.from_bytes(os.urandom(8), "little") >> 1
-    ext = ".fastq" if a.fastq else ".fasta"
-    if dist is not None:
-        info = dict(species=mref.species, off=mref.species_chrom_off.tolist(), keys=mref.chrom_names, numbers=numbers,
-                    samples=samples, seed=seed) if rank == 0 else None
-        # (sub-files of every sample this rank may write: the sample count is only known after the broadcast, so by pattern —
-        # ".part<rank>" followed by the end of the name or a dot, so that rank 1 does not take rank 10's files)
+        info = dict(species=mref.species, off=mref.species_chrom_off.tolist(), keys=mref.chrom_names, numbers=numbers, samples=samples)
+    if run.dist is not None:
+        # sub-files of every sample this rank may write: the sample count is only known after the broadcast, so by pattern and not by
+        # shard.clean_parts — ".part<rank>" followed by the end of the name or a dot, so that rank 1 does not take rank 10's files
         import glob
         import re
         tail = re.compile(r"\.part%d(\.|$)" % rank)
         for q in glob.glob(glob.escape(a.output) + "_sample*.part%d*" % rank) if rank else ():
             if tail.search(q):
                 os.unlink(q)
-        ref, keep, info = shard.broadcast_reference(mref.ref if rank == 0 else None, dist, device=bdev, extra=info)
-        if bdev is None:
-            ref = M.Reference(ref.names, keep.numpy(), ref.chrom_off, ref.circular)
+        ref, info = run.broadcast(mref.ref if rank == 0 else None, info)
         mref = MG.MetaReference(ref, info["species"], np.array(info["off"], dtype=np.uint32), info["keys"])
-        numbers, samples, seed = info["numbers"], info["samples"], info["seed"]
-    tails = ("_aligned_reads" + ext, "_aligned_error_profile", "_unaligned_reads" + ext)
-    outputs = [out + "_sample%d%s" % (s, t) for s in range(len(samples)) for t in tails]
-    with shard.failure_markers(outputs, rank, world):
-        if rank == 0:
-            log("Read error profile" if not a.perfect else "Read KDF of aligned reads")
-        mdl = M.load_model(a.model_prefix, perfect=a.perfect, strandness=a.strandness, chimeric=a.chimeric, fastq=a.fastq,
-                           homopolymer=a.homopolymer)
+        numbers, samples = info["numbers"], info["samples"]
+    with run.scope([p for s in range(len(samples)) for p in run.outputs(a.output + "_sample%d" % s)]):
+        mdl = run.load_model(chimeric=a.chimeric)
 
         def setup(e):
-            e.set_metagenome(mref, dev_ptr=keep.data_ptr() if (dist is not None and bdev is not None) else None)
+            e.set_metagenome(mref, dev_ptr=run.dev_ptr())
             e.load_model(mdl)
-        setup(eng)
-        eng_un, step_owner = eng, None
-        if not a.perfect and not _serial_schedule():
-            eng_un, step_owner = _background_engine(device, setup, eng)      # (unaligned reads and gaps take any species: no abundances needed, S:1708)
+        run.set_up(setup)                         # (unaligned reads and gaps take any species: a second engine needs no abundances, S:1708)
         max_len = a.max_len
         total_len = mref.total_len()
         first = 0
-        try:
-            for s, abun in enumerate(samples):
-                sample = "sample" + str(s)
-                if a.abun_var:                                                                  # S:2497-2506: the species of THIS sample
-                    sample_len = {sp: total_len[sp] for sp in abun}
-                    u = np.random.default_rng([seed & 0xffffffff, seed >> 32, s]).random(len(sample_len))
-                    abun = MG.add_abundance_var(abun, sample_len, float(a.abun_var[0]), float(a.abun_var[1]), iter(u.tolist()))
-                infl = {sp: MG.inflate_abun(abun, sp, mdl.abun_inflation) for sp in abun} if a.chimeric else None   # S:2510-2514
-                eng.set_abundance(mref, abun, infl)
-                if rank == 0:
-                    log("Simulating sample " + sample)
-                    if a.median_len and a.sd_len:
-                        log("Simulating read length from log-normal distribution")
-                    log("Start simulation of aligned reads")
-                n_al, n_un = mdl.split_counts(numbers[s])
-                max_len = int(min(max_len, mref.max_chrom))                                     # S:2525
-                base = out + "_" + sample
-                lo, hi = shard.partition(n_al, world)[rank]
-                ulo, uhi = shard.partition(n_un, world)[rank]
-
-                def aligned(gen=None, base=base, first=first, lo=lo, hi=hi, max_len=max_len):
-                    _write_batches(eng, base + "_aligned_reads" + ext, base + "_aligned_error_profile", seed=seed, first=first + lo,
-                                   count=hi - lo, kind=E.NS_KIND_PERFECT if a.perfect else E.NS_KIND_ALIGNED, fastq=a.fastq, chimeric=a.chimeric,
-                                   min_len=a.min_len, max_len=max_len, median_len=a.median_len, sd_len=a.sd_len, want_errlog=True, meta=True,
-                                   kmer_bias=0 if a.perfect else (a.KmerBias or 0), err_header=ERR_HEADER, dist=dist, tag=" aligned", gen=gen)
-
-                def unaligned(quiet, gen=None, base=base, first=first, n_al=n_al, ulo=ulo, uhi=uhi, max_len=max_len):     # S:1642
-                    _write_batches(eng_un, base + "_unaligned_reads" + ext, None, seed=seed, first=first + n_al + ulo, count=uhi - ulo,
-                                   kind=E.NS_KIND_UNALIGNED, fastq=a.fastq, chimeric=False, min_len=a.min_len, max_len=max_len,
-                                   median_len=a.median_len, sd_len=a.sd_len, want_errlog=False, meta=True, dist=dist, quiet=quiet, tag=" unaligned",
-                                   gen=gen)
-                if a.perfect:
-                    aligned()
-                elif eng_un is eng:
-                    aligned()
-                    if rank == 0:
-                        log("Start simulation of random reads")
-                    unaligned(False)
-                else:
-                    _run_phases(aligned, lambda gen=None, un=unaligned: un(True, gen), rank, first + n_al + uhi, step_owner)
-                first += n_al + n_un            # samples draw from disjoint read-index ranges of the same seed
-        finally:
-            if eng_un is not eng:
-                eng_un.close()
-            eng.close()
-    if dist is not None:
-        dist.destroy_process_group()
-    if rank == 0:
-        log("Finished!")
+        for s, abun in enumerate(samples):
+            sample = "sample" + str(s)
+            if a.abun_var:                                                                  # S:2497-2506: the species of THIS sample
+                sample_len = {sp: total_len[sp] for sp in abun}
+                u = np.random.default_rng([run.seed & 0xffffffff, run.seed >> 32, s]).random(len(sample_len))
+                abun = MG.add_abundance_var(abun, sample_len, float(a.abun_var[0]), float(a.abun_var[1]), iter(u.tolist()))
+            infl = {sp: MG.inflate_abun(abun, sp, mdl.abun_inflation) for sp in abun} if a.chimeric else None   # S:2510-2514
+            run.eng.set_abundance(mref, abun, infl)
+            if rank == 0:
+                log("Simulating sample " + sample)
+                if a.median_len and a.sd_len:
+                    log("Simulating read length from log-normal distribution")
+            n_al, n_un = mdl.split_counts(numbers[s])
+            max_len = int(min(max_len, mref.max_chrom))                                     # S:2525
+            run.simulate(a.output + "_" + sample, first, n_al, n_un,
+                         dict(fastq=a.fastq, min_len=a.min_len, max_len=max_len, median_len=a.median_len, sd_len=a.sd_len, meta=True),
+                         dict(chimeric=a.chimeric, kmer_bias=0 if a.perfect else (a.KmerBias or 0)))
+            first += n_al + n_un                # samples draw from disjoint read-index ranges of the same seed
 
 
 def run_transcriptome(a, parser_t):
     """The transcriptome branch of main() (S:2322-2414) + simulation("transcriptome") (S:1568-1672)."""
     from . import intron_retention as IR
     from . import transcriptome as TR
-
-    def die(msg, to_err=True):
-        (sys.stderr if to_err else sys.stdout).write("\n" + msg + "\n")
-        parser_t.print_help(sys.stderr)
-        sys.exit(1)
-    if a.homopolymer and (a.KmerBias is None or a.KmerBias < 0):                              # S:2350-2354
-        die("Please input proper kmer bias value >= 0 to simulate homopolymer contraction and expansion events from", False)
-    if a.strandness and (a.strandness < 0 or a.strandness > 1):
-        die("Please input proper strandness value between 0 and 1", False)
-    if a.max_len < a.min_len:
-        die("Maximum read length must be longer than Minimum read length!")
+    validate_genome_args(a, parser_t)
     model_ir = a.no_model_ir                                                                  # store_false: True unless --no_model_ir
-    if model_ir and a.ref_g == '':
-        die("Please provide a reference genome to simulate intron retention events!")
-    if a.polya and a.basecaller is None:
-        die("Please input basecaller to simulate polyA tails from.", False)
-    if a.KmerBias and not a.homopolymer:
-        sys.stderr.write("\n-k/--KmerBias needs -hp (the reference crashes on the missing homopolymer parameters, S:504,639)\n")
-        sys.exit(1)
-    rank, device, world, dist, bdev = shard.init_dist()
-    if rank == 0:
-        print("\nrunning the code with following parameters:\n")
-        print("ref_g", a.ref_g); print("ref_t", a.ref_t); print("exp", a.exp); print("model_prefix", a.model_prefix); print("out", a.output)
-        print("number", [a.number]); print("coverage", a.coverage); print("perfect", a.perfect); print("homopolymer", a.homopolymer)
-        print("model_ir", model_ir); print("dna_type", "transcriptome"); print("strandness", a.strandness); print("max_len", a.max_len)
-        print("min_len", a.min_len); print("uracil", a.uracil); print("polya", a.polya)
-        if a.polya:
-            print("basecaller", a.basecaller)
-        print("fastq", a.fastq); print("num_threads", max(a.num_threads, 1))
-        log(' '.join(sys.argv))
-    out = a.output
-    d = os.path.dirname(out)
-    if d:
-        os.makedirs(d, exist_ok=True)
-    eng = E.Engine(device)
-    keep = None
+    run = _Run(a, ["ref_g", "ref_t", "exp", "model_prefix", ("out", a.output), ("number", [a.number]), "coverage", "perfect", "homopolymer",
+                   ("model_ir", model_ir), ("dna_type", "transcriptome"), "strandness", "max_len", "min_len", "uracil", "polya"]
+               + (["basecaller"] if a.polya else []) + ["fastq", ("num_threads", max(a.num_threads, 1))])
+    rank = run.rank
+    run.eng = E.Engine(run.device)
+    tr = info = None
     if rank == 0:
         log("Read in reference ")
         tr = TR.read_transcriptome(a.ref_t, a.exp, a.polya, a.basecaller)
-    seed = a.seed if a.seed is not None else int.from_bytes(os.urandom(8), "little") >> 1
-    ext = ".fastq" if a.fastq else ".fasta"
-    if dist is not None:
-        info = dict(ec=tr.expr_chrom, cum=tr.expr_cum, w=tr.expr_weight, pa=tr.polya, sc=tr.polya_scale, seed=seed) if rank == 0 else None
-        shard.clean_parts([out + "_aligned_reads" + ext, out + "_aligned_error_profile", out + "_unaligned_reads" + ext], rank)
-        ref, keep, info = shard.broadcast_reference(tr.ref if rank == 0 else None, dist, device=bdev, extra=info)
-        if bdev is None:
-            ref = M.Reference(ref.names, keep.numpy(), ref.chrom_off, ref.circular)
-            keep = None
+        info = dict(ec=tr.expr_chrom, cum=tr.expr_cum, w=tr.expr_weight, pa=tr.polya, sc=tr.polya_scale)
+    outputs = run.outputs(a.output)
+    if run.dist is not None:
+        ref, info = run.broadcast(tr.ref if rank == 0 else None, info, outputs)
         tr = TR.TranscriptomeReference(ref, info["ec"], info["cum"], info["w"], info["pa"], info["sc"])
-        seed = info["seed"]
     ir = None
     if model_ir:                                                                              # S:403-452
         if rank == 0:
             log("Read in reference genome, IR markov model and GFF3 annotation file")
         ir = IR.load(a.model_prefix, a.ref_g, tr.ref)
         tr = TR.restrict_expression(tr, ir.eligible)                                          # S:1093-1099
-    outputs = [out + "_aligned_reads" + ext, out + "_aligned_error_profile", out + "_unaligned_reads" + ext]
-    with shard.failure_markers(outputs, rank, world):
-        if rank == 0:
-            log("Read error profile" if not a.perfect else "Read KDF of aligned reads")
-        mdl = M.load_model(a.model_prefix, perfect=a.perfect, strandness=a.strandness, fastq=a.fastq, transcriptome=True,
-                           homopolymer=a.homopolymer)
+    with run.scope(outputs):
+        mdl = run.load_model(transcriptome=True)
 
         def setup(e, with_ir=True):
-            e.set_transcriptome(tr, dev_ptr=keep.data_ptr() if keep is not None else None)
+            e.set_transcriptome(tr, dev_ptr=run.dev_ptr())
             if ir is not None and with_ir:
                 e.set_intron_retention(ir)
             e.load_model(mdl)
-        setup(eng)
-        number = a.number
-        if a.coverage is not None:
-            print("\nCalculating the number of reads to be simulated based on the coverage, if you specified the number of reads "
-                  "concurrently with the coverage, coverage will override number of reads.\n")
-            number = calculate_read_number_from_coverage(tr.ref, a.model_prefix, a.coverage)
-        n_al, n_un = mdl.split_counts(number)
-        max_len = int(min(a.max_len, tr.ref.max_chrom))                                           # S:2411
-        if rank == 0:
-            log("Start simulation of aligned reads")
-        lo, hi = shard.partition(n_al, world)[rank]
-        ulo, uhi = shard.partition(n_un, world)[rank]
-        stripes = max(a.num_threads, 1)
-        eng_un, step_owner = eng, None
-        if not a.perfect and not _serial_schedule():
-            eng_un, step_owner = _background_engine(device, lambda e: setup(e, with_ir=False), eng)     # (S:1156: unaligned reads are never spliced)
-        b_al, b_un = _step_batches(n_al, n_un) if eng_un is not eng else (None, None)
-
-        def aligned(gen=None):
-            _write_batches(eng, outputs[0], outputs[1], seed=seed, first=lo, count=hi - lo,
-                           kind=E.NS_KIND_PERFECT if a.perfect else E.NS_KIND_ALIGNED, fastq=a.fastq, chimeric=False, min_len=a.min_len,
-                           max_len=max_len, median_len=None, sd_len=None, want_errlog=True, trx=True, uracil=a.uracil, kmer_bias=a.KmerBias or 0,
-                           err_header=ERR_HEADER, model_ir=model_ir, dist=dist, stripes=stripes, tag=" aligned", batch_reads=b_al, gen=gen)
-
-        def unaligned(quiet, gen=None):                                                           # S:1642-1672
-            _write_batches(eng_un, outputs[2], None, seed=seed, first=n_al + ulo, count=uhi - ulo,
-                           kind=E.NS_KIND_UNALIGNED, fastq=a.fastq, chimeric=False, min_len=a.min_len, max_len=max_len, median_len=None,
-                           sd_len=None, want_errlog=False, trx=True, uracil=a.uracil, dist=dist, stripes=stripes, quiet=quiet, tag=" unaligned",
-                           batch_reads=b_un, gen=gen)
-        try:
-            if a.perfect:
-                aligned()
-            elif eng_un is eng:
-                aligned()
-                if rank == 0:
-                    log("Start simulation of random reads")
-                unaligned(False)
-            else:
-                _run_phases(aligned, lambda gen=None: unaligned(True, gen), rank, n_al + uhi, step_owner)
-        finally:
-            if eng_un is not eng:
-                eng_un.close()
-            eng.close()
-    if dist is not None:
-        dist.destroy_process_group()
-    if rank == 0:
-        log("Finished!")
+        run.set_up(setup, lambda e: setup(e, with_ir=False))                                  # (S:1156: unaligned reads are never spliced)
+        n_al, n_un = mdl.split_counts(run.read_number(tr.ref))
+        max_len = int(min(a.max_len, tr.ref.max_chrom))                                         # S:2411
+        run.simulate(a.output, 0, n_al, n_un, dict(fastq=a.fastq, min_len=a.min_len, max_len=max_len, trx=True, uracil=a.uracil),
+                     dict(kmer_bias=a.KmerBias or 0, model_ir=model_ir))
 
 
 def main(argv=None):

@@ -203,6 +203,49 @@ def test_transcriptome_output_does_not_depend_on_the_number_of_ranks(tmp_path):
         assert open(out + f, "rb").read() == open(one + f, "rb").read(), f
 
 
+def test_metagenome_two_ranks_write_their_workers_in_rank_order(tmp_path):
+    """A metagenome worker call keeps its own species quotas, so the output depends on how the reads are cut into calls — but not on
+    anything else: with two ranks every merged file is rank 0's worker followed by rank 1's, each the oracle's worker for that rank's
+    read range of the sample; species, abundances and seed reach rank 1 with the reference broadcast; no sub-file is left behind."""
+    from nanosim_amd import metagenome as MG
+    from nanosim_amd import shard
+    meta = os.path.join(GOLDEN, "meta")
+    prefix = os.path.join(GOLDEN, "model_small", "training")
+    out = str(tmp_path / "mg2" / "sim")
+    lists = [os.path.join(meta, f) for f in ("genome_list.tsv", "abundance.tsv", "dna_type_list.tsv")]
+    _run_ranks(2, ["metagenome", "-gl", lists[0], "-a", lists[1], "-dl", lists[2], "-c", prefix, "-o", out, "--seed", "777", "--chimeric",
+                   "--fastq", "--merge"], tmp_path)                                  # (cwd = the repo root: the genome list's relative paths)
+    assert sorted(os.listdir(tmp_path / "mg2")) == sorted("sim_sample%d_%s" % (s, f) for s in (0, 1)
+                                                          for f in ("aligned_error_profile", "aligned_reads.fastq", "unaligned_reads.fastq"))
+    cwd = os.getcwd()
+    os.chdir(ROOT)
+    try:
+        mref = MG.read_metagenome(lists[0], lists[2])
+    finally:
+        os.chdir(cwd)
+    numbers, samples = MG.read_abundance(lists[1], mref.species)
+    mdl = M.load_model(prefix, chimeric=True, fastq=True)
+    first = 0
+    for s, abun in enumerate(samples):
+        n_al, n_un = mdl.split_counts(numbers[s])
+        infl = {sp: MG.inflate_abun(abun, sp, mdl.abun_inflation) for sp in abun}
+        rec, err, un = b"", simulator.ERR_HEADER, b""
+        for lo, hi in shard.partition(n_al, 2):
+            p = E.make_params(seed=777, first_read=first + lo, n_reads=hi - lo, fastq=True, chimeric=True, max_len=mref.max_chrom,
+                              emit_errlog=True, meta=True)
+            exp = O.generate_meta(mdl, mref, abun, infl, p)
+            rec, err = rec + exp["records"].tobytes(), err + exp["errlog"].tobytes()
+        for lo, hi in shard.partition(n_un, 2):
+            p = E.make_params(seed=777, first_read=first + n_al + lo, n_reads=hi - lo, kind=E.NS_KIND_UNALIGNED, fastq=True,
+                              max_len=mref.max_chrom, meta=True)
+            un += O.generate_meta(mdl, mref, abun, None, p)["records"].tobytes()
+        base = out + "_sample%d" % s
+        assert open(base + "_aligned_reads.fastq", "rb").read() == rec, s
+        assert open(base + "_aligned_error_profile", "rb").read() == err, s
+        assert open(base + "_unaligned_reads.fastq", "rb").read() == un, s
+        first += n_al + n_un
+
+
 def test_configs0_ecoli_circular_perfect_10k_reads(tmp_path):
     """BASELINE configs[0] as stated: E. coli-size CIRCULAR genome x --perfect x 10 000 reads x FASTA (S:1321-1343, 1750-1781).  The file
     equals the oracle's bytes, and every read — also those across the origin — is a substring of the doubled genome (or of its reverse

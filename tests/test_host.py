@@ -9,6 +9,7 @@ import pytest
 
 from nanosim_amd import model as M
 from nanosim_amd import shard, simulator
+from tests.fake_engine import _FakeEngine
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -278,66 +279,7 @@ def test_trained_pickles_load_like_the_npz(tmp_path, monkeypatch):
 
 
 # ---- the CLI's batch / sink / phase logic without a GPU: a stand-in engine with the methods _write_batches uses -------------------------
-class _FakeInfo:
-    def __init__(self, n, rec, err):
-        self.n_reads, self.record_bytes, self.errlog_bytes, self.ms_total = n, rec, err, 0.0
-
-
-class _FakeBatch:
-    def __init__(self, first, n, with_err):
-        self.rec = [b">read_%d\nACGT\n" % i for i in range(first, first + n)]
-        self.err = [b"read_%d\t0\tmis\t1\tA\tC\n" % i for i in range(first, first + n)] if with_err else []
-        self.info = _FakeInfo(n, sum(map(len, self.rec)), sum(map(len, self.err)))
-
-    def record_offsets(self, cuts):
-        ro = np.array([sum(map(len, self.rec[:c])) for c in cuts], dtype=np.uint64)
-        eo = np.array([sum(map(len, self.err[:c])) for c in cuts], dtype=np.uint64)
-        return ro, eo
-
-
-class _FakeSink:
-    def __init__(self, eng, fd):
-        self.eng, self.fd, self.closed = eng, fd, 0
-
-    def put(self, data):
-        os.write(self.fd, data)
-
-    def write(self, which, offset=0, nbytes=None):
-        b = self.eng.last
-        img = b"".join(b.rec if which == 0 else b.err)
-        os.write(self.fd, img[offset:] if nbytes is None else img[offset:offset + nbytes])
-
-    def drain(self):
-        return 0
-
-    def close(self):
-        self.closed += 1
-        assert self.closed == 1, "a sink was closed twice"
-        if self.eng.fail_close:
-            raise OSError(28, "No space left on device")
-
-
-class _FakeEngine:
-    def __init__(self, fail_close=False, fail_generate_at=None):
-        self.fail_close, self.fail_generate_at, self.sinks, self.calls = fail_close, fail_generate_at, [], 0
-
-    def generate(self, p):
-        self.calls += 1
-        if self.fail_generate_at is not None and self.calls >= self.fail_generate_at:
-            raise RuntimeError("device lost")
-        self.last = _FakeBatch(int(p.first_read), int(p.n_reads), bool(p.emit_errlog))
-        return self.last
-
-    def sink(self, fd):
-        s = _FakeSink(self, fd)
-        self.sinks.append(s)
-        return s
-
-    def io_counters(self):
-        return dict(bytes=0, d2h_gbs=None, wait_staging_s=0.0, write_s=0.0)
-
-
-_KW = dict(seed=1, kind=0, fastq=False, chimeric=False, min_len=50, max_len=1000, median_len=None, sd_len=None, want_errlog=True)
+_KW = dict(seed=1, kind=0, fastq=False, chimeric=False, min_len=50, max_len=1000, median_len=None, sd_len=None)
 
 
 @pytest.mark.parametrize("stripes", [1, 3])
@@ -345,7 +287,7 @@ def test_write_batches_cuts_batches_and_sub_files_at_read_boundaries(tmp_path, m
     monkeypatch.setattr(simulator, "BATCH_READS", 100)
     eng = _FakeEngine()
     out, err = str(tmp_path / "sim_aligned_reads.fasta"), str(tmp_path / "sim_aligned_error_profile")
-    simulator._write_batches(eng, out, err, first=7, count=333, err_header=simulator.ERR_HEADER, stripes=stripes, quiet=True, **_KW)
+    simulator._write_batches(eng, out, err, _KW, first=7, count=333, err_header=simulator.ERR_HEADER, stripes=stripes, quiet=True)
     assert open(out, "rb").read() == b"".join(b">read_%d\nACGT\n" % i for i in range(7, 340))
     assert open(err, "rb").read() == simulator.ERR_HEADER + b"".join(b"read_%d\t0\tmis\t1\tA\tC\n" % i for i in range(7, 340))
     assert sorted(os.listdir(tmp_path)) == ["sim_aligned_error_profile", "sim_aligned_reads.fasta"]
@@ -357,7 +299,7 @@ def test_write_batches_closes_every_sink_once_when_a_close_fails(tmp_path, monke
     monkeypatch.setattr(simulator, "BATCH_READS", 50)
     eng = _FakeEngine(fail_close=True)
     with pytest.raises(OSError):
-        simulator._write_batches(eng, str(tmp_path / "a.fasta"), str(tmp_path / "a_err"), first=0, count=120, stripes=4, quiet=True, **_KW)
+        simulator._write_batches(eng, str(tmp_path / "a.fasta"), str(tmp_path / "a_err"), _KW, first=0, count=120, stripes=4, quiet=True)
     assert eng.sinks and all(s.closed == 1 for s in eng.sinks)        # (_FakeSink.close asserts on a second call)
 
 
