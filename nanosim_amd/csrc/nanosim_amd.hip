@@ -1534,11 +1534,16 @@ __global__ void __launch_bounds__(64 * NS_WPB) k_hp_filter_w(GenArgs A) {
 }
 
 // final length check after the homopolymer stage (S:1429-1430 / metagenome S:1023-1024) and the record size of an accepted read
+// (final_len == NS_HP_LEN_RANGE: the homopolymer edits of a piece left the shift field of the event record, k_hp_drain — the attempt fails
+// like one of a wrong length, in every mode, and counts as a range redraw)
+#define NS_HP_LEN_RANGE (~0ull)
 __device__ inline void hp_final_length(const GenArgs &A, uint64_t r, ns_read &rd, uint32_t a, uint64_t final_len, unsigned long long &st_bases,
                                        unsigned long long &st_fail) {
     const bool trx_al = A.prm.trx && A.prm.kind != NS_KIND_UNALIGNED;       // no length limits on aligned transcriptome reads
+    const bool range = final_len == NS_HP_LEN_RANGE;
+    if (range) atomicAdd(&A.stats[NS_STAT_HP_RANGE], 1ull);
     if (A.meta && !A.key_pos && A.prm.kind != NS_KIND_UNALIGNED) {           // a pass of a metagenome worker (S:1023-1024): the
-        if ((int64_t)final_len < A.prm.min_len || (int64_t)final_len > A.prm.max_len) {   // read is not accepted by this pass
+        if (range || (int64_t)final_len < A.prm.min_len || (int64_t)final_len > A.prm.max_len) {   // read is not accepted by this pass
             A.accept[r] = 0; st_fail = 1;
             unsigned long long rb = 0;               // k_chain had counted it as accepted
             for (uint32_t pi = 0; pi < rd.n_pieces; ++pi) rb += A.pieces[rd.piece_off + pi].ref_len;
@@ -1550,7 +1555,7 @@ __device__ inline void hp_final_length(const GenArgs &A, uint64_t r, ns_read &rd
             A.rec_len[r] = A.prm.emit_records ? (uint64_t)A.name_len[r] + 2 + final_len + 1 + (A.prm.fastq ? final_len + 3 : 0) : 0;
         }
     } else
-    if (!trx_al && ((int64_t)final_len < A.prm.min_len || (int64_t)final_len > A.prm.max_len)) {      // S:1429-1430
+    if (range || (!trx_al && ((int64_t)final_len < A.prm.min_len || (int64_t)final_len > A.prm.max_len))) {      // S:1429-1430
         const uint32_t epoch = (A.rstate[r] & 0xffffu) + 1;
         A.rstate[r] = epoch & 0xffffu;
         A.att_base[r] = a + 1;
@@ -1711,7 +1716,7 @@ __global__ void __launch_bounds__(64 * NS_WPB, NS_HPD_WAVES) k_hp_drain(GenArgs 
     const ns_key key = read_key(A, r);
     const uint32_t a = rd.attempts;
     const uint64_t scr_off = uni64(A.scr_off[r]);
-    bool over = false;
+    bool over = false, range = false;                                          // (wave-uniform)
     uint64_t q = 0, final_len = (uint64_t)rd.head + rd.tail + (A.polya ? A.polya[r] : 0u);
     for (uint32_t pi = 0; pi < rd.n_pieces; ++pi) {
         const uint32_t gp = rd.piece_off + pi;
@@ -1736,7 +1741,9 @@ __global__ void __launch_bounds__(64 * NS_WPB, NS_HPD_WAVES) k_hp_drain(GenArgs 
                 if (on) { const uint2 rn = src[j]; s0 = rn.x; L = rn.y >> 8; base = rn.y & 0xffu; size = hp_new_size(A.m, key, sid, a, s0, L, base); }
                 // the run's edits: evaluated once — the first two (all that all but a few runs in a thousand have) wait in the lane's LDS
                 // slots while wavefront prefix sums give the event slots and shifts — then filed; a run with more is evaluated again
-                if (on) {
+                // a run that alone outgrows the shift field of an event (below): its read is dropped, its edits are not evaluated
+                const bool huge = on && size > L && size - L >= 2u * (uint32_t)NS_EV_SHIFT_BIAS;
+                if (on && !huge) {
                     uint32_t seen = 0;
                     ne = hp_run_events(A.m.hp_mis_rate, key, sid, a, s0, L, size, base, [&](uint32_t pos, uint32_t ty, uint32_t len, uint32_t word) {
                         if (seen < 2u) { S.pos[seen][lane] = pos; S.tl[seen][lane] = ty << 12 | len; S.wd[seen][lane] = word; }
@@ -1747,6 +1754,10 @@ __global__ void __launch_bounds__(64 * NS_WPB, NS_HPD_WAVES) k_hp_drain(GenArgs 
                     const uint32_t d = on ? size - L : 0u;                   // (mod 2^32)
                     ne_incl = wave_incl_scan(ne); d_incl = wave_incl_scan(d);
                     slot = n_ev + ne_incl - ne; sh = shift + d_incl - d;
+                    // The edits carry the piece's cumulative length change so far in the 18-bit shift field of the event record.
+                    // A piece whose change leaves the field behind any of its runs fails this attempt of its read, like a chain event that
+                    // does not fit (ev_shift_fits).  (The first run to leave it is seen exactly: the sums before it are in range, |d| < 2^31.)
+                    if (__ballot(huge || (on && !ev_shift_fits((int32_t)(sh + d))))) range = true;
                 }
                 if (on && ne && slot + ne <= cap) {
                     if (ne <= 2u) {
@@ -1778,8 +1789,8 @@ __global__ void __launch_bounds__(64 * NS_WPB, NS_HPD_WAVES) k_hp_drain(GenArgs 
         q += n;
     }
     if (lane == 0) {
-        hp_final[r] = final_len;                                                // (checked by k_hp_finalize, S:1429-1430)
-        if (over) atomicAdd(&A.stats[NS_STAT_HP_OVER], 1ull);                                 // a piece outgrew its event capacity: the stage is repeated with more
+        hp_final[r] = range ? NS_HP_LEN_RANGE : final_len;                      // (checked by k_hp_finalize, S:1429-1430)
+        if (over && !range) atomicAdd(&A.stats[NS_STAT_HP_OVER], 1ull);                       // a piece outgrew its event capacity: the stage is repeated with more
     }
 }
 
@@ -2147,6 +2158,7 @@ struct ns_ctx {
     ByteBuf slow_q;                  // SlowQueue: a 16-byte header (the counter), then the SlowTile items
     DevBuf<uint8_t> scr, hp_bm; DevBuf<uint64_t> scr_len, scr_off; DevBuf<ns_event> hp_ev; DevBuf<uint2> hp_runs;
     uint32_t hp_shift = 5, hp_pad = 64, hp_cap_k = 0;       // -k: event capacity of a piece (hp_ev_slot), planned for kmer_bias hp_cap_k
+    uint64_t hp_range_redraws = 0;                           // -k: attempts of this call dropped for the shift field of a homopolymer edit (hp_stage1)
     // metagenome: species view of the reference, abundances of the sample, per-pass scratch
     DevBuf<uint32_t> species_chrom_off, key_pos, m_segptr; DevBuf<ns_read> t_reads; DevBuf<ns_piece> t_pieces;
     DevBuf<uint16_t> t_name_len, m_species; DevBuf<uint64_t> t_rec_len, t_err_len, accept, accept_scan;
@@ -2768,6 +2780,7 @@ static int hp_stage1(ns_ctx *ctx, const ns_params *prm, GenArgs &A, size_t n, ui
         if (!A.meta || A.key_pos) HIPCHK(hipMemsetAsync(stat_at(ctx, NS_STAT_BASES), 0, sizeof(unsigned long long), st));   // (kept across metagenome passes)
         HIPCHK(hipMemsetAsync(stat_at(ctx, NS_STAT_HP_FAILED), 0, sizeof(unsigned long long), st));
         HIPCHK(hipMemsetAsync(stat_at(ctx, NS_STAT_HP_OVER), 0, sizeof(unsigned long long), st));
+        HIPCHK(hipMemsetAsync(stat_at(ctx, NS_STAT_HP_RANGE), 0, sizeof(unsigned long long), st));
         k_hp_scan<<<dim3((unsigned)((n + NS_WPB - 1) / NS_WPB)), dim3(64 * NS_WPB), 0, st>>>(A, ctx->hp_runs.data(), ctx->hp_nrun.data());
         k_hp_drain<<<dim3((unsigned)((n + NS_WPB - 1) / NS_WPB)), dim3(64 * NS_WPB), 0, st>>>(A, ctx->hp_runs.data(), ctx->hp_nrun.data(), A.l_cap);
         k_hp_finalize<<<grid_t, blk, 0, st>>>(A, A.l_cap);
@@ -2780,6 +2793,7 @@ static int hp_stage1(ns_ctx *ctx, const ns_params *prm, GenArgs &A, size_t n, ui
         if (ctx->hp_shift) --ctx->hp_shift;
         ctx->hp_pad *= 2;
     }
+    ctx->hp_range_redraws += stats[NS_STAT_HP_RANGE];       // (k_hp_finalize counts only in the run of the stage that did not overflow)
     HIPCHK(hipEventRecord(ctx->evt[EV_HP_END], st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipEventElapsedTime(&ms, ctx->evt[EV_HP_BEGIN], ctx->evt[EV_HP_END]));
@@ -3465,6 +3479,8 @@ static int trx_passes(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, Ge
     info->ms_kernel[NS_K_EVENTS] = ms_chain;
     if (A.ir_need && (rc = ir_splice(ctx, A, n))) return rc;
     if (A.hp && (rc = hp_stage1(ctx, prm, A, n, pl.tot_pieces, stats, &pl.ms_hp))) return rc;   // (no length limits on these reads: nothing fails S:1429)
+    // ... but the shift field of the event record: the candidates are committed by now, so the call fails instead of the attempt
+    if (A.hp && stats[NS_STAT_HP_FAILED]) return fail(ctx, NS_EINVAL, "-k: the homopolymer edits of a transcript leave the shift field of the event record");
     return NS_OK;
 }
 
@@ -3681,6 +3697,7 @@ static int batch_args(ns_ctx *ctx, const ns_params *prm, size_t n, GenArgs &A) {
                                {ctx->att_base, n + 1}, {ctx->scr_len, n + 1}, {ctx->scr_off, n + 1}})))
         return rc;
     memset(&A, 0, sizeof A);
+    ctx->hp_range_redraws = 0;
     A.prm = *prm; A.m = ctx->m; A.ref = ctx->ref;
     A.key_first = A.name_first = prm->first_read;
     A.cap_gap_mul = 2;
@@ -3788,7 +3805,7 @@ static int finish_call(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, c
     info->ms_kernel[NS_K_HP] = pl.ms_hp;
     info->n_reads = prm->n_reads; info->n_pieces = pl.tot_pieces; info->n_events = pl.tot_cap;
     info->total_bases = pl.stats[NS_STAT_BASES]; info->total_ref_bases = pl.stats[NS_STAT_REF_BASES]; info->events_used = pl.stats[NS_STAT_EVENTS];
-    info->n_range_redraws = pl.stats[NS_STAT_OVER] >> NS_RANGE_SHIFT;
+    info->n_range_redraws = (pl.stats[NS_STAT_OVER] >> NS_RANGE_SHIFT) + ctx->hp_range_redraws;
     info->spliced_bytes = ctx->spliced_bytes;
     ctx->last = *info;
     if (prm->emit_records != 1u) { ctx->last.record_bytes = 0; ctx->last.errlog_bytes = 0; }      // nothing to copy out

@@ -17,6 +17,7 @@ enum NsStat : uint32_t {
     NS_STAT_HP_FAILED,    // -k: reads that failed the final length check
     NS_STAT_NEXT_N,       // length of the next pass list: its low 32 bits are GenArgs::next_n
     NS_STAT_HP_OVER,      // -k: pieces that outgrew their event capacity
+    NS_STAT_HP_RANGE,     // -k: attempts dropped because a piece's homopolymer edits left the shift field of the event record
     NS_STAT_COUNT
 };
 #define NS_RANGE_SHIFT 40

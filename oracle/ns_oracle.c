@@ -510,12 +510,48 @@ int64_t nso_mutate_read(const uint8_t *seg_in, int64_t ref_len, const ns_event *
 /* ------------------------------------------------------------------------------------------------
  * -k: the homopolymer filter of mutate_read (S:1920-1947) and mutate_homo (S:618-705)
  * ---------------------------------------------------------------------------------------------- */
+/* Branch counters of the -k stage (test infrastructure, like nso_edge_counts): what nso_mutate_homo and nso_hp_filter met since the last reset. */
+enum { NSO_HP_RUNS = 0,           /* re-sampled runs (>= k bases of A, C, G or T) */
+       NSO_HP_GROW = 1,           /* ... whose new size is above the old one */
+       NSO_HP_GROW_15 = 2,        /* ... by more than 15 bases (several insertions of <= 15 letters at one position) */
+       NSO_HP_SHRINK = 3,         /* ... whose new size is below the old one */
+       NSO_HP_SHRINK_4095 = 4,    /* ... by more than NS_EV_LEN_MAX bases (the deletion is split) */
+       NSO_HP_SIZE0 = 5,          /* runs re-sampled to size 0 (S:652-654: a negative draw counts as 0) */
+       NSO_HP_L64 = 6,            /* runs of 64 bases or more */
+       NSO_HP_L1024 = 7,          /* runs of 1024 bases or more */
+       NSO_HP_L4096 = 8,          /* runs of more than NS_EV_LEN_MAX bases */
+       NSO_HP_AT_START = 9,       /* runs that start at the first base of the segment */
+       NSO_HP_AT_END = 10,        /* runs that end at the last base of the segment */
+       NSO_HP_MIS2 = 11,          /* runs with two or more mismatches */
+       NSO_HP_MIS_APPENDED = 12,  /* runs with a mismatch on an appended base */
+       NSO_HP_MIS_MID_INS = 13,   /* runs whose FIRST mismatch is an appended base that is not letter 0 of a 15-letter insertion counted from the run's end */
+       NSO_HP_EDITS3 = 14,        /* runs with more than 2 edits (deletions of <= NS_EV_LEN_MAX + kept mismatches + insertions of <= 15 letters) */
+       NSO_HP_EDITS_MAX = 15,     /* the largest number of edits of one run (a maximum, not a count) */
+       NSO_HP_TIE = 16,           /* draws exactly on n + 1/2 (round half to even decides) */
+       NSO_HP_ADJACENT = 17,      /* re-sampled runs that start where the previous re-sampled run ended */
+       NSO_HP_DROP_MIS = 18, NSO_HP_DROP_INS = 19, NSO_HP_DROP_DEL = 20,   /* filter: events dropped, by type */
+       NSO_HP_KEEP_MIS = 21, NSO_HP_KEEP_INS = 22, NSO_HP_KEEP_DEL = 23,   /* filter: events kept, by type */
+       NSO_HP_INS_KEY_BEFORE = 24,/* filter: an insertion dropped only because base pos - 1 is in a run (its float key pos - 1/2, S:1929-1937) */
+       NSO_HP_INS_KEY_BEYOND = 25,/* filter: an insertion dropped only because a base in (pos, pos + len - 1] is in a run */
+       NSO_HP_NEAR_END = 26,      /* filter: events tested within 16 bases of either end of the segment */
+       NSO_HP_RUN_CUT = 27,       /* filter: events tested on a run that touches an end of the segment and has fewer than k bases (k > 2: at least 2) */
+       NSO_HP_SHIFT_RANGE = 28,   /* pieces dropped because the cumulative shift of their homopolymer edits left the event record's shift field */
+       NSO_HP_N = 32 };
+static uint64_t nso_hp[NSO_HP_N];
+/* attempts dropped because an event left the fields of the 8-byte event record (ns_batch_info.n_range_redraws of the engine) */
+static uint64_t nso_range_redraws;
+uint64_t nso_range_redraw_count(int reset) { uint64_t v = nso_range_redraws; if (reset) nso_range_redraws = 0; return v; }
+void nso_hp_counts(uint64_t *out, int reset) {
+    for (int i = 0; i < NSO_HP_N; ++i) { if (out) out[i] = nso_hp[i]; if (reset) nso_hp[i] = 0; }
+}
+
 /* is base x of the (converted) segment inside a run of >= k identical bases? */
 static int in_hp_run(const uint8_t *seg, int64_t n, int64_t x, int64_t k) {
     if (x < 0 || x >= n) return 0;
     int64_t s = x, e = x + 1;
     while (s > 0 && seg[s - 1] == seg[x] && e - s < k) --s;
     while (e < n && seg[e] == seg[x] && e - s < k) ++e;
+    if (e - s < k && (s == 0 || e == n) && e - s >= (k > 2 ? 2 : 1)) ++nso_hp[NSO_HP_RUN_CUT];
     return e - s >= k;
 }
 /* Drops every event whose interval [key, key+len) (float keys: pos for mis/del, pos-0.5 for ins) overlaps a
@@ -527,9 +563,17 @@ uint64_t nso_hp_filter(const uint8_t *seg, int64_t ref_len, ns_event *ev, uint64
     for (uint64_t j = 0; j < n_ev; ++j) {
         int64_t pos = ev[j].pos, len = NS_EV_LEN(ev[j].info); int ty = (int)NS_EV_TYPE(ev[j].info);
         int64_t lo = ty == NS_INS ? pos - 1 : pos, hi = ty == NS_INS ? pos + len - 1 : pos + len - 1;
-        int hit = 0;
-        for (int64_t x = lo; x <= hi && !hit; ++x) hit = in_hp_run(seg, ref_len, x, k);
-        if (hit) continue;
+        int hit = 0, before = 0, at = 0, beyond = 0;
+        if (lo < 16 || hi >= ref_len - 16) ++nso_hp[NSO_HP_NEAR_END];
+        for (int64_t x = lo; x <= hi; ++x)
+            if (in_hp_run(seg, ref_len, x, k)) { hit = 1; if (x < pos) before = 1; else if (x == pos) at = 1; else beyond = 1; }
+        if (hit) {
+            ++nso_hp[NSO_HP_DROP_MIS + ty];
+            if (ty == NS_INS && before && !at && !beyond) ++nso_hp[NSO_HP_INS_KEY_BEFORE];
+            if (ty == NS_INS && beyond && !at && !before) ++nso_hp[NSO_HP_INS_KEY_BEYOND];
+            continue;
+        }
+        ++nso_hp[NSO_HP_KEEP_MIS + ty];
         ev[w].pos = (uint32_t)pos; ev[w].info = NS_EV_PACK(len, ty, shift);
         if (ty == NS_INS) shift += len; else if (ty == NS_DEL) shift -= len;
         ++w;
@@ -579,13 +623,14 @@ static uint8_t hp_base(const ns_model_tables *t, uint8_t base, nso_draw *d, uint
 }
 
 /* mutate_homo (S:618-705) on one mutated aligned segment.
- *   in/in_c: bases and their quality classes (or NULL) before; out/out_c after; returns the new length (or -1 if out_cap is too small).
+ *   in/in_c: bases and their quality classes (or NULL) before; out/out_c after; returns the new length (-1 if out_cap is too small,
+ *   -2 if the cumulative length change leaves the shift field of the event record).
  *   A kept base keeps its class (S:688-690: a contraction drops the FIRST |diff| qualities of the run), an appended base is 'ins'
  *   (S:692-695), the first mismatch of a run 'mis' (S:697-700).  The qualities themselves are drawn afterwards, by final position.
  *   Draw keys: new length of the run starting at s: ST_HPLEN idx=s; new base x of the run: hp_base. */
 int64_t nso_mutate_homo(const ns_model_tables *t, const uint8_t *in, const uint8_t *in_c, int64_t n, int64_t k, nso_draw *d,
                         uint32_t seg, uint32_t attempt, uint8_t *out, uint8_t *out_c, int64_t out_cap) {
-    int64_t w = 0, p = 0;
+    int64_t w = 0, p = 0, prev_end = -1;
     while (p < n) {
         int64_t s = p, e = p + 1;
         while (e < n && in[e] == in[s]) ++e;
@@ -604,8 +649,15 @@ int64_t nso_mutate_homo(const ns_model_tables *t, const uint8_t *in, const uint8
         else { uint32_t ww[4]; philox_at(d, ST_HPLEN, seg, attempt, (uint32_t)s, 0, ww); x = fma(sigma, nso_norminv(u32_to_p(ww[0])), mu); }
         if (x < 0) x = 0;                                             /* S:652-654 */
         const int64_t size = nso_f64_to_i64_sat(nearbyint(x));        /* int(round(.)), S:665 */
+        /* the engine files the run's edits as 8-byte event records that carry the piece's cumulative length change so far in an 18-bit
+         * field: a piece whose change leaves that field behind any of its runs is dropped with its attempt, like a
+         * chain event that does not fit */
+        if (size - L >= 2 * (int64_t)NS_EV_SHIFT_BIAS || w + size - e < -(int64_t)NS_EV_SHIFT_BIAS || w + size - e >= (int64_t)NS_EV_SHIFT_BIAS) {
+            ++nso_hp[NSO_HP_SHIFT_RANGE]; return -2;
+        }
         if (w + size > out_cap) return -1;
-        int64_t first_mis = -1;
+        int64_t first_mis = -1, n_mis = 0, n_kept_mis = 0, n_ins = 0, cnt = 0;
+        int mis_app = 0, mid_ins = 0;
         for (int64_t i = 0; i < size; ++i) {
             int is_mis; uint8_t nb;
             const int kept = (size <= L || i < L);
@@ -615,9 +667,38 @@ int64_t nso_mutate_homo(const ns_model_tables *t, const uint8_t *in, const uint8
                 else out_c[w + i] = (uint8_t)NS_Q_INS;                                        /* appended base (S:692-695) */
             }
             out[w + i] = nb;
+            if (!kept) {                                              /* (counters) appended bases travel as insertions of <= 15 letters; the */
+                if (is_mis && first_mis < 0 && cnt) { ++n_ins; cnt = 0; mid_ins = 1; }   /* run's first mismatch opens its own */
+                if (++cnt == 15) { ++n_ins; cnt = 0; }
+                if (is_mis) mis_app = 1;
+            } else if (is_mis) ++n_kept_mis;
+            if (is_mis) ++n_mis;
             if (is_mis && first_mis < 0) first_mis = i;
         }
+        if (cnt) ++n_ins;
         if (in_c && first_mis >= 0) out_c[w + first_mis] = (uint8_t)NS_Q_MIS;               /* S:697-700 */
+        {
+            const int64_t edits = (size < L ? (L - size + NS_EV_LEN_MAX - 1) / NS_EV_LEN_MAX : 0) + n_kept_mis + n_ins;
+            ++nso_hp[NSO_HP_RUNS];
+            if (size > L) ++nso_hp[NSO_HP_GROW];
+            if (size > L + 15) ++nso_hp[NSO_HP_GROW_15];
+            if (size < L) ++nso_hp[NSO_HP_SHRINK];
+            if (L - size > (int64_t)NS_EV_LEN_MAX) ++nso_hp[NSO_HP_SHRINK_4095];
+            if (size == 0) ++nso_hp[NSO_HP_SIZE0];
+            if (L >= 64) ++nso_hp[NSO_HP_L64];
+            if (L >= 1024) ++nso_hp[NSO_HP_L1024];
+            if (L > (int64_t)NS_EV_LEN_MAX) ++nso_hp[NSO_HP_L4096];
+            if (s == 0) ++nso_hp[NSO_HP_AT_START];
+            if (e == n) ++nso_hp[NSO_HP_AT_END];
+            if (n_mis >= 2) ++nso_hp[NSO_HP_MIS2];
+            if (mis_app) ++nso_hp[NSO_HP_MIS_APPENDED];
+            if (mid_ins) ++nso_hp[NSO_HP_MIS_MID_INS];
+            if (edits > 2) ++nso_hp[NSO_HP_EDITS3];
+            if ((uint64_t)edits > nso_hp[NSO_HP_EDITS_MAX]) nso_hp[NSO_HP_EDITS_MAX] = (uint64_t)edits;
+            if (x - floor(x) == 0.5) ++nso_hp[NSO_HP_TIE];
+            if (s == prev_end) ++nso_hp[NSO_HP_ADJACENT];
+            prev_end = e;
+        }
         w += size; p = e;
     }
     return w;
@@ -1124,7 +1205,7 @@ static int gen_read(const ns_model_tables *t, const nso_ref *ref, const ns_param
             if (!is_gap) total += r.l_new;                                  /* S:1362 (gaps are not counted) */
             if (kind == NS_KIND_UNALIGNED) total = r.middle_ref;            /* S:1503 */
         }
-        if (range) { if (!mr) { ++epoch; fails = 0; } continue; }       /* the attempt is dropped, new lengths (a limit of the 8-byte event record) */
+        if (range) { ++nso_range_redraws; if (!mr) { ++epoch; fails = 0; } continue; }       /* the attempt is dropped, new lengths (a limit of the 8-byte event record) */
         if (overflow) return -11;
         if (tx && kind != NS_KIND_UNALIGNED) {                              /* S:1143-1144: middle_ref > ref_trx_len -> start over */
             if ((int64_t)pc[0].ref_len > trx_len) continue;
@@ -1273,6 +1354,7 @@ static int gen_read(const ns_model_tables *t, const nso_ref *ref, const ns_param
         uint8_t *hp_seq[2 * NSO_MAX_SEG], *hp_q[2 * NSO_MAX_SEG];
         uint8_t *hp_log = NULL; uint64_t hp_log_len = 0, hp_log_cap = 0;
         const int hp_on = (prm->kmer_bias && kind == NS_KIND_ALIGNED);
+        int hp_range = 0;
         memset(hp_seq, 0, sizeof hp_seq); memset(hp_q, 0, sizeof hp_q);
         if (hp_on) {
             for (uint32_t pi = 0; pi < n_pieces; pi += 2) {
@@ -1306,17 +1388,25 @@ static int gen_read(const ns_model_tables *t, const nso_ref *ref, const ns_param
                         hp_log_len = (uint64_t)(q - hp_log);
                     }
                 }
-                int64_t cap2 = 2 * l1 + 4096;
-                hp_seq[pi] = (uint8_t *)malloc((size_t)cap2);
-                hp_q[pi] = prm->fastq ? (uint8_t *)malloc((size_t)cap2) : NULL;                     /* quality CLASS of every final base */
-                int64_t l2 = nso_mutate_homo(t, s1, prm->fastq ? c1 : NULL, l1, (int64_t)prm->kmer_bias, &d, sid, a, hp_seq[pi], hp_q[pi], cap2);   /* S:1413-1414 */
+                int64_t l2 = -1;
+                uint64_t cnt0[NSO_HP_N];
+                memcpy(cnt0, nso_hp, sizeof cnt0);
+                for (int64_t cap2 = 2 * l1 + 4096; l2 == -1; cap2 *= 4) {                             /* (a model may grow every run many times over) */
+                    free(hp_seq[pi]); free(hp_q[pi]);
+                    memcpy(nso_hp, cnt0, sizeof cnt0);                                                /* (the counters see the run that counts) */
+                    hp_seq[pi] = (uint8_t *)malloc((size_t)cap2);
+                    hp_q[pi] = prm->fastq ? (uint8_t *)malloc((size_t)cap2) : NULL;                 /* quality CLASS of every final base */
+                    l2 = nso_mutate_homo(t, s1, prm->fastq ? c1 : NULL, l1, (int64_t)prm->kmer_bias, &d, sid, a, hp_seq[pi], hp_q[pi], cap2);   /* S:1413-1414 */
+                }
                 free(segbuf); free(s1); free(c1); free(rows); free(txt);
-                if (l2 < 0) return -22;
+                if (l2 < 0) { hp_range = 1; break; }                                                  /* the edits left the shift field of the event record */
                 seq_len += l2 - (int64_t)pc[pi].out_len;
                 pc[pi].out_len = (uint32_t)l2;
             }
         }
 #define NSO_HP_FREE() do { for (uint32_t z_ = 0; z_ < n_pieces; ++z_) { free(hp_seq[z_]); free(hp_q[z_]); } free(hp_log); } while (0)
+        if (hp_range && tx) { NSO_HP_FREE(); free(ir_seq); free(ir_iv); return -23; }   /* (a transcriptome candidate is committed by then: the call fails) */
+        if (hp_range) { NSO_HP_FREE(); free(ir_seq); free(ir_iv); ++nso_range_redraws; ++epoch; fails = 0; continue; }   /* dropped like a failed final length check */
         if (!(tx && kind != NS_KIND_UNALIGNED) &&                                        /* (no length limits on aligned transcriptome reads) */
             (seq_len < prm->min_len || seq_len > prm->max_len)) { NSO_HP_FREE(); free(ir_seq); free(ir_iv); ++epoch; fails = 0; continue; }   /* S:1429-1430, S:1518-1519 */
 

@@ -287,6 +287,227 @@ def fixture_homopolymer(S, genome, k=5):
         S.model_base_quals.predict_base_qualities = orig_q
     return cases
 
+HP_EDGE_KS = (2, 3, 5, 8, 9, 16, 17)          # the switch points of the filter's window forms and of the run scan
+
+
+def _hp_edge_runs(k, long_runs):
+    """[(run length, injected draw or None)] of one hand-built mutate_homo input at k; None: the run is below k (no draw)"""
+    if long_runs:
+        runs = [(k, k + 1.0), (1100, 1100 + 16.0 if k in (5, 16) else 7.5), (k + 1, 0.5), (4200, 0.0), (64, 64 + 31.0), (k, k - 0.75), (130, 3.5)]
+    else:
+        ties = [n + 0.5 for n in range(6)]                                 # n even and odd: half to even decides
+        runs = [(k, ties[0])]                                              # (the run at position 0)
+        runs += [(k - 1, None), (k, ties[1]), (k + 1, ties[2])]
+        runs += [(k, x) for x in ties[3:]]
+        runs += [(k + 1, -0.0), (k, -1.75), (k + 2, 2.4999999999999996), (k + 2, 2.5000000000000004)]
+        runs += [(k, k + 1.0), (k + 1, k + 1 + 15.0), (k, k + 16.0), (k + 1, k + 1 + 31.0), (k, k + 500.0)]
+        for n in (15, 16, 17, 31, 32, 33, 63, 64, 65):
+            runs.append((n, None if n < k else n + (-1.0, 0.25, 2.0)[n % 3]))
+        runs += [(k, k - 0.25), (k + 3, k + 3 + 47.5), (65, 65 + 16.5), (33, 0.5), (k, float(k))]
+    return [(n, x) for n, x in runs if n >= 1]
+
+
+def _hp_edge_sequence(k, long_runs, rng):
+    """the sequence and the draws of its runs (by run start): runs of _hp_edge_runs separated by 1 .. 3 bases without a repeat, plus
+    adjacent runs of different bases, runs one base apart, N runs, a run at position 0 and a run at the last base"""
+    seq, draws = [], {}
+
+    def put_run(base, n, x):
+        if n >= k and base != "N":
+            draws[len(seq)] = x
+        seq.extend(base * n)
+
+    def put_gap(n, avoid):
+        for i in range(n):
+            seq.append(rng.choice([b for b in "ACGT" if b != seq[-1] and not (i == n - 1 and b == avoid)]))
+
+    spec = _hp_edge_runs(k, long_runs)
+    bases = "ATCG"
+    for i, (n, x) in enumerate(spec):
+        b = bases[i % 4]
+        if i:
+            put_gap(1 + i % 3 + (1 if seq[-1] == b else 0), b)
+        put_run(b, n, x)
+    if not long_runs:
+        put_gap(2, "A")
+        put_run("A", k, k - 1.0); put_run("C", k, k + 2.0); put_run("G", k + 1, 0.0); put_run("T", k, k + 17.0)      # AAAAACCCCC...: adjacent runs
+        put_gap(2, "A")
+        put_run("A", k, k + 1.0); put_run("C", 1, None); put_run("A", k, k - 1.0)                                      # one base apart
+        put_run("G", 1, None); put_run("C", k + 1, 1.5)
+        put_gap(1, "N")
+        put_run("N", k, None); put_run("T", k, k + 1.5); put_run("N", k + 3, None); put_run("A", 1, None); put_run("N", 1, None)
+        put_gap(2, "C")
+    else:
+        put_gap(3, "C")
+    put_run("C", k + 1, k + 1 + 16.0)                                      # (the run at the last base)
+    return "".join(seq), draws
+
+
+def _hp_edge_filter_case(k, variant, rng):
+    """a read and a hand-made e_dict around its runs: every type ending exactly where a run starts and starting exactly where it ends, on
+    its first and last base, insertions whose float key (pos - 1/2, S:1929-1937) alone decides, events at position 0 and on the last base,
+    and the read's ends cutting a run to k - 1 (variant 0) or leaving exactly k (variant 1)"""
+    seq, e_dict = [], {}
+
+    def gap(n, avoid):
+        for i in range(n):
+            seq.append(rng.choice([b for b in "ACGT" if not (seq and b == seq[-1]) and not (i == n - 1 and b == avoid)]))
+
+    def ev(pos, ty, n):
+        key = pos - 0.5 if ty == "ins" else pos
+        assert key not in e_dict and 0 <= pos
+        e_dict[key] = [ty, n]
+
+    edge = k - 1 + variant
+    seq.extend("A" * edge)                                                 # the run the read's start cuts (or not)
+    ev(0, ("mis", "ins", "del")[k % 3], 1)
+    gap(14, "C")
+    placements = []
+    for ty in ("mis", "ins", "del"):
+        for where in ("before_kept", "before_hit", "first", "inside", "last", "after_hit", "after_kept"):
+            placements.append((ty, where))
+    for i, (ty, where) in enumerate(placements):
+        b = "CGTA"[i % 4]
+        n_run = k + (i % 2)
+        s = len(seq); e = s + n_run
+        seq.extend(b * n_run)
+        n = 2 + (i % 2)
+        if where == "before_kept":
+            ev(s - n, ty, n)                                               # mis / del: [s - n, s); ins: ends 1/2 before the run
+        elif where == "before_hit":
+            ev(s - n + 1, ty, n)                                           # reaches base s; ins: only through a base beyond pos
+        elif where == "first":
+            ev(s, ty, 1)
+        elif where == "inside":
+            ev(s + n_run // 2, ty, 1)
+        elif where == "last":
+            ev(e - 1, ty, 1)
+        elif where == "after_hit":
+            ev(e if ty == "ins" else e - 1, ty, n)                         # ins at pos = e: only base pos - 1 is in the run
+        else:
+            ev(e + 1 if ty == "ins" else e, ty, n)
+        gap(13 + i % 3, "CGTA"[(i + 1) % 4])
+    gap(1, "T")
+    last = len(seq) + edge - 1
+    seq.extend("T" * edge)                                                 # the run the read's end cuts (or not)
+    ev(last, "del" if k % 2 else "mis", 1)
+    read = "".join(seq)
+    n_mis = sum(v[1] for v in e_dict.values() if v[0] == "mis")
+    n_ins = sum(v[1] for v in e_dict.values() if v[0] == "ins")
+    n_del = sum(v[1] for v in e_dict.values() if v[0] == "del")
+    return read, e_dict, {"mis": n_mis, "ins": n_ins, "match": len(read) - n_mis - n_del}
+
+
+# the counters (tests/oracle_lib.py HP_COUNTERS) the fixture is there to raise when the oracle replays it
+HP_EDGE_HOMO_COUNTERS = ("runs", "grow", "grow_15", "shrink", "shrink_4095", "size0", "l64", "l1024", "l4096", "at_start", "at_end",
+                         "mis2", "mis_appended", "mis_mid_ins", "edits3", "tie", "adjacent")
+HP_EDGE_FILTER_COUNTERS = ("drop_mis", "drop_ins", "drop_del", "keep_mis", "keep_ins", "keep_del", "ins_key_before", "ins_key_beyond",
+                           "near_end", "run_cut")
+
+
+def fixture_hp_edges(S):
+    """-k at the branches the sampled tapes of fixture_homopolymer do not reach: hand-built inputs at the k where the engine's kernels
+    switch form, mutate_homo with INJECTED np.random.normal draws (ties n + 1/2, -0.0, negative, growth by 1 .. 500, a 4200-base run
+    re-sampled to 0) at two mismatch rates, and hand-made e_dicts for mutate_read's filter.  Only the inputs and what the reference
+    returned are kept; get_nd_par is replaced (its values do not matter once the draws are injected)."""
+    import re as _re
+    orig_q = S.model_base_quals.predict_base_qualities
+    code = {S.lognorm_base_qual[name]["sd"]: cls for cls, name in enumerate(("match", "mis", "ins", "ht", "unmapped"))}
+    S.model_base_quals.predict_base_qualities = lambda sd, loc, scale, n: [code[sd]] * int(n)
+    orig_normal, orig_par, orig_rate = np.random.normal, S.model_hp_len.get_nd_par, S.hp_mis_rate
+    S.model_hp_len.get_nd_par = lambda length, pw, lr: (float(length), 1.0) * 4
+    homo, filt = [], []
+    rng = random.Random(4100)
+    try:
+        for k in HP_EDGE_KS:
+            pattern = "A{%d,}|C{%d,}|G{%d,}|T{%d,}" % (k, k, k, k)
+            for long_runs in (False, True):
+                for rate in ((0.03, 0.5) if not long_runs else (0.5,) if k in (3, 8, 16) else (0.03,)):
+                    seq, draws = _hp_edge_sequence(k, long_runs, rng)
+                    assert len(seq) <= 6000, len(seq)
+                    runs = [(mt.start(), mt.end(), mt.group()[0]) for mt in _re.finditer(pattern, seq)]
+                    assert [r[0] for r in runs] == sorted(draws), "the hand-built runs are not the runs the reference finds"
+                    # the groups np.random.normal is asked for (S:639-650): per length in order of first appearance, then A, T, C, G;
+                    # every group is consumed from the END (S:665-666)
+                    hist = {}
+                    for s0, e0, b in runs:
+                        hist.setdefault(e0 - s0, {"A": [], "T": [], "C": [], "G": []})[b].append(draws[s0])
+                    inject = [list(reversed(hist[length][b])) for length in hist for b in "ATCG" if hist[length][b]]
+                    calls = []
+
+                    def normal(mu, sigma, n):
+                        v = np.array(inject[len(calls)], dtype=np.float64)
+                        assert len(v) == n
+                        calls.append([float(x) for x in v])
+                        return v
+
+                    classes1 = [10 + (i * 7 + i // 5) % 9 for i in range(len(seq))]      # (no 1 = mis, no 2 = ins: those are the stage's own)
+                    S.hp_mis_rate = rate
+                    random.seed(4200 + 31 * k + (7 if long_runs else 0) + (1 if rate > 0.1 else 0))
+                    np.random.normal = normal
+                    try:
+                        with Recorder(S) as r2:
+                            out2, q2 = S.mutate_homo(seq, list(classes1), k)
+                    finally:
+                        np.random.normal = orig_normal
+                    assert len(calls) == len(inject)
+                    groups, ci = {}, 0
+                    for length in hist:
+                        for b in "ATCG":
+                            if hist[length][b]:
+                                groups[(length, b)] = list(calls[ci]); ci += 1
+                    x_runs = [groups[(e0 - s0, b)].pop() for s0, e0, b in runs]          # consumed from the END (S:665-666)
+                    homo.append(dict(k=k, hp_mis_rate=rate, out1=seq, classes1=classes1, x_runs=x_runs, u_homo=r2.u, out2=out2,
+                                     classes2=[int(x) for x in q2], runs=[[a, b_, c] for a, b_, c in runs]))
+            for variant in (0, 1):
+                read, e_dict, e_count = _hp_edge_filter_case(k, variant, rng)
+                random.seed(4300 + 2 * k + variant)
+                log = _Log()
+                with Recorder(S) as r1:
+                    out1, q1 = S.mutate_read(read, "name", log, {a: list(b) for a, b in e_dict.items()}, dict(e_count), True, k)
+                assert len(out1) == len(q1)
+                filt.append(dict(k=k, converted=read, e_dict=edict_list(e_dict), u_mutate=r1.u, out1=out1,
+                                 classes1=[int(x) for x in q1], log=log.rows))
+    finally:
+        S.model_base_quals.predict_base_qualities = orig_q
+        S.model_hp_len.get_nd_par = orig_par
+        S.hp_mis_rate = orig_rate
+    return dict(homo=homo, filter=filt)
+
+
+def check_hp_edges(fx):
+    """the generator's guard: the oracle, replaying the fixture, must raise every branch counter the fixture is there to reach"""
+    import ctypes as C
+    import copy
+    from nanosim_amd import model as M
+    from tests import oracle_lib as O
+    from tests.test_homopolymer import filter_events
+    from tests.test_oracle_pin import expected_events
+    L = O.lib()
+    mdl = M.load_model(os.path.join(HERE, "model_small", "training"), chimeric=True, homopolymer=True, fastq=True)
+    O.hp_counts()
+    for case in fx["homo"]:
+        m = copy.deepcopy(mdl)
+        m.hp_mis_rate = case["hp_mis_rate"]
+        t = m.to_c()
+        d, keep = O.make_tape(case["u_homo"], z=case["x_runs"])
+        seq = np.frombuffer(case["out1"].encode(), dtype=np.uint8).copy()
+        q = np.array(case["classes1"], dtype=np.uint8)
+        out = np.zeros(len(case["out2"]) + 64, dtype=np.uint8)
+        oq = np.zeros_like(out)
+        L.nso_mutate_homo(C.byref(t), seq.ctypes.data, q.ctypes.data, len(seq), case["k"], C.byref(d), 0, 0, out.ctypes.data,
+                          oq.ctypes.data, len(out))
+    cnt = O.hp_counts()
+    missed = [c for c in HP_EDGE_HOMO_COUNTERS if not cnt[c]]
+    for case in fx["filter"]:
+        filter_events(L, case["converted"], expected_events(case["e_dict"]), case["k"])
+    cnt2 = O.hp_counts()
+    missed += [c for c in HP_EDGE_FILTER_COUNTERS if not cnt2[c]]
+    assert not missed, "the fixture does not reach: %s" % ", ".join(missed)
+    assert cnt["edits_max"] > 6
+    return cnt, cnt2
+
+
 def fixture_unaligned(S):
     """unaligned_error_list + mutate_read STRUCTURE: an all-'A' read and a choice() that never returns 'A'
     make copied bases ('A') distinguishable from generated ones."""
@@ -1090,6 +1311,7 @@ def main():
     ap.add_argument("--only-hg002", action="store_true", help="write reference_hg002.json only: the bench-scale model (n_train 10^6, mean 8.4 kb) on the ecoli_like reference, --dist-reads aligned reads")
     ap.add_argument("--only-coverage", action="store_true", help="write reference_coverage.json only (-x / --coverage read counts)")
     ap.add_argument("--only-meta-runs", action="store_true", help="replace the whole-run part (runs) of reference_metagenome.json: 8 workers x 12 500 reads, plain and chimeric, + 8 x 6 000 perfect reads")
+    ap.add_argument("--only-hp-edges", action="store_true", help="write reference_hp_edges.json.gz only (-k: hand-built inputs and injected draws at the branches the sampled tapes do not reach)")
     a = ap.parse_args()
     workdir = tempfile.mkdtemp(prefix="nsgolden_")
     try:
@@ -1103,6 +1325,25 @@ def main():
             write_hg002(workdir, a.dist_reads)
             return
         prefix, fasta, circ = build_inputs(workdir)
+        if a.only_hp_edges:
+            import gzip
+            S = import_reference()
+            so = sys.stdout
+            sys.stdout = open(os.devnull, "w")
+            try:
+                S.read_profile(fasta, [1000], prefix, False, "genome", None, dna_type="linear", chimeric=True, homopolymer=True, fastq=True)
+            finally:
+                sys.stdout = so
+            fx = fixture_hp_edges(S)
+            cnt, cnt2 = check_hp_edges(fx)                    # a fixture that misses a branch is not written
+            path = os.path.join(HERE, "reference_hp_edges.json.gz")
+            with gzip.GzipFile(path, "wb", mtime=0) as f:
+                f.write(json.dumps(fx, separators=(",", ":")).encode())
+            print("reference_hp_edges.json.gz written:", len(fx["homo"]), "mutate_homo cases,", len(fx["filter"]), "filter cases,",
+                  os.path.getsize(path), "bytes")
+            print("counters (mutate_homo):", cnt)
+            print("counters (filter):", cnt2)
+            return
         if a.only_ir_splice:
             with open(os.path.join(HERE, "reference_ir_splice.json"), "w") as f:
                 json.dump(fixture_ir_splice(import_reference(), prefix), f)

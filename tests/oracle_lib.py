@@ -83,6 +83,8 @@ def lib():
         L.nso_f64_to_i64_sat.restype = C.c_int64; L.nso_f64_to_i64_sat.argtypes = [C.c_double]
         L.nso_eval_batch.restype = C.c_int; L.nso_eval_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64]
         L.nso_edge_counts.restype = None; L.nso_edge_counts.argtypes = [C.c_void_p, C.c_int]
+        L.nso_hp_counts.restype = None; L.nso_hp_counts.argtypes = [C.c_void_p, C.c_int]
+        L.nso_range_redraw_count.restype = C.c_uint64; L.nso_range_redraw_count.argtypes = [C.c_int]
         L.nso_ecdf_lookup.restype = C.c_int64
         L.nso_ecdf_lookup.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint32, C.c_double, C.c_double]
         L.nso_table_value.restype = C.c_int64
@@ -139,6 +141,19 @@ def lib():
         L.nso_case_convert.argtypes = [C.c_void_p, C.c_int64, C.POINTER(NsoDraw), C.c_uint32, C.c_uint32]
         _LIB = L
     return _LIB
+
+
+# the branch counters of the -k stage, in the order of the oracle's NSO_HP_* enum
+HP_COUNTERS = ("runs", "grow", "grow_15", "shrink", "shrink_4095", "size0", "l64", "l1024", "l4096", "at_start", "at_end", "mis2",
+               "mis_appended", "mis_mid_ins", "edits3", "edits_max", "tie", "adjacent", "drop_mis", "drop_ins", "drop_del", "keep_mis",
+               "keep_ins", "keep_del", "ins_key_before", "ins_key_beyond", "near_end", "run_cut", "shift_range")
+
+
+def hp_counts(reset=True) -> dict:
+    """nso_hp_counts as a dict by HP_COUNTERS name (edits_max is a maximum, the others count)"""
+    a = np.zeros(32, dtype=np.uint64)
+    lib().nso_hp_counts(a.ctypes.data, 1 if reset else 0)
+    return {name: int(a[i]) for i, name in enumerate(HP_COUNTERS)}
 
 
 def make_tape(u=(), n=(), z=()):
