@@ -439,6 +439,32 @@ enum { NS_HPC_INS = 0, NS_HPC_DEL = 1, NS_HPC_MIS = 2, NS_HPC_MATCH = 3 };
 int ns_hp_histograms(ns_ctx *ctx, const uint8_t *ref_lines, const uint8_t *query_lines, uint64_t nbytes, const uint64_t *aln_off,
                      uint32_t n_aln, uint32_t min_hp_len, ns_hp_hist *out);
 
+/* ---- training side: aligned line pairs from SAM records -----------------------------------------------------------------------------------
+ * replaces `samtools view | sam2pairwise` + src/pairwise2maf.py:38-82 (src/read_analysis.py:200-204): per record, from its CIGAR, its
+ * MD:Z tag and its SEQ (as SAM holds it), the aligned reference line and the aligned read line with `-` for gaps — the M/=/X/I/D columns
+ * only, clips cut — and its four figures.  Strings lie back to back with one table of n_aln + 1 offsets each, as in ns_qual_histograms.
+ * What makes a record BAD is listed in nanosim_amd/csrc/ns_sam_pairs.h: it gets zero columns and all-zero figures, is counted in n_bad,
+ * and first_bad is the index of the first one (n_aln when there is none).
+ * aln_off, aln (unless NULL), n_bytes and the bad counters are always written.  The lines are written only when buffers are given and
+ * n_bytes <= cap_bytes: size them from a first call with NULL lines.  Added without an ABI change.
+ * ns_hp_histograms_sam: the conversion, then ns_hp_histograms on the lines where they are, on the device; `pairs` may be NULL (nothing of
+ * the conversion goes back to the host) or carry buffers as above.  With n_bad > 0 nothing is counted (`out` is all zero). */
+typedef struct ns_sam_aln { uint32_t head, tail, ref_len, query_len; } ns_sam_aln;
+typedef struct ns_sam_pairs {
+    uint8_t *ref_lines, *query_lines;  /* in: host buffers of cap_bytes each, or both NULL */
+    uint64_t cap_bytes;                /* in */
+    uint64_t *aln_off;                 /* in: host buffer of n_aln + 1 offsets (out) */
+    ns_sam_aln *aln;                   /* in: host buffer of n_aln entries (out), or NULL */
+    uint64_t n_bytes;                  /* out: columns of all records = aln_off[n_aln] */
+    uint64_t n_bad, first_bad;         /* out */
+    double ms_kernel;
+} ns_sam_pairs;
+int ns_sam_pairs_build(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off, const uint8_t *md, const uint64_t *md_off,
+                       const uint8_t *seq, const uint64_t *seq_off, uint32_t n_aln, ns_sam_pairs *out);
+int ns_hp_histograms_sam(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off, const uint8_t *md, const uint64_t *md_off,
+                         const uint8_t *seq, const uint64_t *seq_off, uint32_t n_aln, uint32_t min_hp_len, ns_sam_pairs *pairs,
+                         ns_hp_hist *out);
+
 /* device address of a result buffer (for zero-copy consumers such as torch / RCCL); NULL if absent */
 const void *ns_device_ptr(ns_ctx *ctx, int which);
 

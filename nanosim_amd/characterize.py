@@ -36,8 +36,19 @@ Deviation: the reference fits the mean read length with ``piecewise_regression.F
 random starts with 100 bootstrap restarts, which the reference does not seed, so its text is not reproducible even by itself.  What is
 written here is the least-squares optimum that iteration approximates, computed exactly (Hudson 1966).  The library is not installed
 where this was developed, so nobody has compared the two fits.  ``min_hp_len < 1`` and input without any homopolymer raise ValueError
-(the reference's `A{0,}` matches empty strings; it divides by zero).  This model is trained from MAF pairs only: for BAM / SAM input the
-reference converts to MAF first (``pairwise2maf``), which is not covered here.
+(the reference's `A{0,}` matches empty strings; it divides by zero).
+
+SAM input of that model is the fourth piece.  The reference's default aligner writes SAM, and the reference turns it into MAF line pairs
+first: ``samtools view | sam2pairwise``, then src/pairwise2maf.py (P:38-82; src/read_analysis.py:200-204).  Here the two aligned lines of
+every record are built on the GPU from its CIGAR, MD:Z and SEQ (``ns_sam_pairs_build``, csrc/ns_sam_pairs.h) and stay packed — and, for
+the model, stay on the device (``ns_hp_histograms_sam``):
+
+    recs = characterize.sam_records("training_primary.sam")                 # FLAG 0 / 16, as pairwise2maf keeps them
+    characterize.homopolymer_lengths_from_sam("training", recs, eng, min_hp_len=5, maf_file=True)   # + training_processed.maf
+    packed = characterize.pairs_from_sam(eng, recs)                         # a PackedPairs: count_maf / count_homopolymers take it as it is
+
+Deviations: a record pairwise2maf would stop on (`H` in the CIGAR: its int() fails; a trailing clip behind an op other than M) or whose
+CIGAR, MD and SEQ contradict each other raises ValueError; `N` / `P` ops are not handled.
 
 Not covered: BAM input (pysam is not a dependency here: convert with ``samtools view -h``).
 """
@@ -152,8 +163,37 @@ def _pack(strings):
     return np.frombuffer(b"".join(blobs) + b"\0", dtype=np.uint8), off
 
 
-def _pack_pairs(ref_lines, query_lines):
-    """_pack of the two lines of every alignment: (reference bytes, query bytes, the offsets of both)"""
+class PackedPairs:
+    """Aligned line pairs that are packed already (pairs_from_sam): `ref`, `qry`, `off` as _pack_pairs returns them (a NUL byte behind
+    the lines), `aln` = the ns_sam_aln figures (SAM_ALN_DTYPE) and the records they come from.  _pack_pairs, count_maf and
+    count_homopolymers take it as it is; indexing or iterating gives maf_records' tuples (rname, pos - 1, reference line, query line)."""
+
+    def __init__(self, ref, qry, off, aln, sam_recs):
+        self.ref, self.qry, self.off, self.aln, self.sam_recs = ref, qry, off, aln, sam_recs
+
+    def __len__(self):
+        return len(self.off) - 1
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(len(self)))]
+        if i < 0:
+            i += len(self)
+        lo, hi = int(self.off[i]), int(self.off[i + 1])
+        return (self.sam_recs[i][2], self.sam_recs[i][3] - 1, self.ref[lo:hi].tobytes().decode(), self.qry[lo:hi].tobytes().decode())
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
+
+    def heads(self):
+        """[(rname, pos - 1)]: what <prefix>_hp_lengths.tsv needs of every alignment, without its lines"""
+        return [(r[2], r[3] - 1) for r in self.sam_recs]
+
+
+def _pack_pairs(ref_lines, query_lines=None):
+    """_pack of the two lines of every alignment: (reference bytes, query bytes, the offsets of both); a PackedPairs as it is"""
+    if isinstance(ref_lines, PackedPairs):
+        return ref_lines.ref, ref_lines.qry, ref_lines.off
     ref, off = _pack(ref_lines)
     qry, q_off = _pack(query_lines)
     if not np.array_equal(off, q_off):
@@ -212,7 +252,7 @@ def maf_pairs(path: str):
 
 def count_maf(eng, pairs, cap: int = 2048) -> dict:
     """the counts of hist()'s MAF loop for these alignments, from the GPU (ns_maf_histograms)"""
-    ref, qry, off = _pack_pairs([a for a, _ in pairs], [b for _, b in pairs])
+    ref, qry, off = _pack_pairs(pairs) if isinstance(pairs, PackedPairs) else _pack_pairs([a for a, _ in pairs], [b for _, b in pairs])
     return _count(lambda h: eng._check(eng.L.ns_maf_histograms(eng.ctx, ref.ctypes.data, qry.ctypes.data, int(off[-1]), off.ctypes.data,
                                                                len(off) - 1, C.byref(h))), cap)
 
@@ -453,18 +493,13 @@ def maf_records(path: str):
     return out
 
 
-def count_homopolymers(eng, pairs, min_hp_len: int = 5, records: bool = False, cap_ref: int = 64, cap_read: int = 64, cap_records=None) -> dict:
-    """what analyze_homopolymers (H:64-119) and calc_homopolymer_mis_rate (H:9-33) collect for these alignments, from the GPU
-    (ns_hp_histograms).  pairs: (reference line, query line) tuples, or maf_records' tuples (their last two entries are used).
-    {"table": uint64 (2, R, Q) — class AT / CG, reference length, read length; R, Q = the largest lengths met + 1 —, "columns": uint64 (4,)
-    in the order HP_COLUMNS, "n_hp", "ms_kernel"} and, with records, "records": int64 (n_hp, 5) — alignment index, first letter in the
-    dash-less reference line, reference length, read length, base (its character code) — in the order of the alignments.
-    The caps are first sizes only: a call that reports an overflow is repeated with what it asks for."""
+def _hp_count(call, nbytes_hint: int, min_hp_len: int, records: bool, cap_ref: int, cap_read: int, cap_records) -> dict:
+    """count_homopolymers and count_homopolymers_sam: `call(h)` makes the library's call on an NsHpHist (false: it counted nothing);
+    repeated with what it asks for while it reports an overflow"""
     if min_hp_len < 1:
         raise ValueError("min_hp_len must be at least 1 (the reference's `A{0,}` matches empty strings)")
-    ref, qry, off = _pack_pairs([p[-2] for p in pairs], [p[-1] for p in pairs])
     if cap_records is None:
-        cap_records = int(off[-1]) // (4 * min_hp_len) + 16
+        cap_records = nbytes_hint // (4 * min_hp_len) + 16
     while True:
         h = NsHpHist()
         table = np.zeros((2, cap_ref, cap_read), dtype=np.uint64)
@@ -472,7 +507,7 @@ def count_homopolymers(eng, pairs, min_hp_len: int = 5, records: bool = False, c
         h.cap_ref, h.cap_read, h.table = cap_ref, cap_read, table.ctypes.data
         if records:
             h.records, h.cap_records = rec.ctypes.data, len(rec)
-        eng._check(eng.L.ns_hp_histograms(eng.ctx, ref.ctypes.data, qry.ctypes.data, int(off[-1]), off.ctypes.data, len(off) - 1, int(min_hp_len), C.byref(h)))
+        call(h)
         again = False
         if h.n_overflow:
             cap_ref = max(cap_ref, 1 << int(h.max_ref).bit_length())           # the table has to hold index max_ref
@@ -490,6 +525,22 @@ def count_homopolymers(eng, pairs, min_hp_len: int = 5, records: bool = False, c
         out["records"] = np.stack([r["aln"], r["start"], r["ref_len"], r["read_base"] >> 2,
                                    np.frombuffer(b"ACGT", dtype=np.uint8)[r["read_base"] & 3]], axis=1).astype(np.int64).reshape(-1, 5)
     return out
+
+
+def count_homopolymers(eng, pairs, min_hp_len: int = 5, records: bool = False, cap_ref: int = 64, cap_read: int = 64, cap_records=None) -> dict:
+    """what analyze_homopolymers (H:64-119) and calc_homopolymer_mis_rate (H:9-33) collect for these alignments, from the GPU
+    (ns_hp_histograms).  pairs: (reference line, query line) tuples, maf_records' tuples (their last two entries are used), or a
+    PackedPairs (used as it is: no join, no re-pack).
+    {"table": uint64 (2, R, Q) — class AT / CG, reference length, read length; R, Q = the largest lengths met + 1 —, "columns": uint64 (4,)
+    in the order HP_COLUMNS, "n_hp", "ms_kernel"} and, with records, "records": int64 (n_hp, 5) — alignment index, first letter in the
+    dash-less reference line, reference length, read length, base (its character code) — in the order of the alignments.
+    The caps are first sizes only: a call that reports an overflow is repeated with what it asks for."""
+    if min_hp_len < 1:
+        raise ValueError("min_hp_len must be at least 1 (the reference's `A{0,}` matches empty strings)")
+    ref, qry, off = _pack_pairs(pairs) if isinstance(pairs, PackedPairs) else _pack_pairs([p[-2] for p in pairs], [p[-1] for p in pairs])
+    return _hp_count(lambda h: eng._check(eng.L.ns_hp_histograms(eng.ctx, ref.ctypes.data, qry.ctypes.data, int(off[-1]), off.ctypes.data, len(off) - 1,
+                                                                 int(min_hp_len), C.byref(h))),
+                     int(off[-1]), min_hp_len, records, cap_ref, cap_read, cap_records)
 
 
 def _piecewise_rss(x, y, const, alpha1, beta1, psi):
@@ -566,6 +617,8 @@ def format_hp_lengths(maf_recs, records) -> str:
     s = "Chrom:Ref pos\tType\tRef length\tRead length\tCount\n"
     if not len(records):
         return s
+    if isinstance(maf_recs, PackedPairs):
+        maf_recs = maf_recs.heads()
     names = sorted(set(r[0] for r in maf_recs))
     name_id = {n: i for i, n in enumerate(names)}
     aln = records[:, 0]
@@ -588,6 +641,131 @@ def homopolymer_lengths(prefix: str, records_or_pairs, eng, min_hp_len: int = 5,
     if lengths_file:
         with open(prefix + "_hp_lengths.tsv", "w") as f:
             f.write(format_hp_lengths(records_or_pairs, t["records"]))
+    with open(prefix + "_hp_lengths_model_parameters.tsv", "w") as f:
+        f.write(format_hp_model(fit_homopolymers(t["table"], t["columns"])))
+    return t
+
+
+# ---- SAM input: the line pairs (samtools view | sam2pairwise, then src/pairwise2maf.py) -------------------------------------------------
+class NsSamPairs(C.Structure):
+    """mirror of ns_sam_pairs (include/nanosim_amd.h)"""
+    _fields_ = [("ref_lines", C.c_void_p), ("query_lines", C.c_void_p), ("cap_bytes", C.c_uint64), ("aln_off", C.c_void_p), ("aln", C.c_void_p),
+                ("n_bytes", C.c_uint64), ("n_bad", C.c_uint64), ("first_bad", C.c_uint64), ("ms_kernel", C.c_double)]
+
+
+SAM_ALN_DTYPE = np.dtype([("head", "<u4"), ("tail", "<u4"), ("ref_len", "<u4"), ("query_len", "<u4")])      # ns_sam_aln
+
+
+def sam_records(path: str):
+    """[(qname, flag, rname, pos, cigar, md, seq)] of a SAM text file: the records pairwise2maf keeps — FLAG exactly 0 or 16 (P:46-51) —
+    in file order.  A kept record without MD:Z, or with `H` in its CIGAR (the reference's int() stops there, P:59-67), raises ValueError."""
+    out = []
+    with open(path) as f:
+        for line in f:
+            if line.startswith("@"):
+                continue
+            fld = line.rstrip("\n").split("\t")
+            if len(fld) < 11 or fld[1] not in ("0", "16"):
+                continue
+            md = None
+            for t in fld[11:]:
+                if t.startswith("MD:Z:"):
+                    md = t[5:]
+            if md is None:
+                raise ValueError("alignment %s has no MD tag" % fld[0])
+            if "H" in fld[5]:
+                raise ValueError("alignment %s has a hard clip in its CIGAR (src/pairwise2maf.py:59-67 stops on it)" % fld[0])
+            out.append((fld[0], int(fld[1]), fld[2], int(fld[3]), fld[5], md, fld[9]))
+    return out
+
+
+def _pack_sam(sam_recs):
+    """the six string arguments of the SAM calls and what keeps them alive"""
+    cg, cg_off = _pack([r[4] for r in sam_recs])
+    md, md_off = _pack([r[5] for r in sam_recs])
+    sq, sq_off = _pack([r[6] for r in sam_recs])
+    return (cg.ctypes.data, cg_off.ctypes.data, md.ctypes.data, md_off.ctypes.data, sq.ctypes.data, sq_off.ctypes.data), (cg, cg_off, md, md_off, sq, sq_off)
+
+
+def _sam_out(sam_recs, keep, lines: bool):
+    """an NsSamPairs with its buffers: the lines sized by what no record can exceed (a column per SEQ byte and per MD byte), so that
+    one call is enough"""
+    n = len(sam_recs)
+    cap = int(keep[3][-1]) + int(keep[5][-1]) if lines else 0
+    p = NsSamPairs()
+    bufs = dict(off=np.zeros(n + 1, dtype=np.uint64), aln=np.zeros(n, dtype=SAM_ALN_DTYPE),
+                ref=np.zeros(cap + 1 if lines else 0, dtype=np.uint8), qry=np.zeros(cap + 1 if lines else 0, dtype=np.uint8))
+    p.aln_off, p.aln = bufs["off"].ctypes.data, bufs["aln"].ctypes.data if n else None
+    if lines:
+        p.ref_lines, p.query_lines, p.cap_bytes = bufs["ref"].ctypes.data, bufs["qry"].ctypes.data, cap
+    return p, bufs
+
+
+def _sam_packed(sam_recs, p, bufs) -> PackedPairs:
+    if p.n_bad:
+        r = sam_recs[int(p.first_bad)]
+        raise ValueError("%d SAM record(s) whose CIGAR, MD and SEQ do not describe an alignment; the first is record %d (%s): CIGAR %.60s, MD %.60s, %d bases"
+                         % (p.n_bad, p.first_bad, r[0], r[4], r[5], len(r[6])))
+    n = int(p.n_bytes)
+    if not len(bufs["ref"]):
+        return PackedPairs(None, None, bufs["off"], bufs["aln"], sam_recs)
+    bufs["ref"][n] = bufs["qry"][n] = 0
+    return PackedPairs(bufs["ref"][:n + 1], bufs["qry"][:n + 1], bufs["off"], bufs["aln"], sam_recs)
+
+
+def pairs_from_sam(eng, sam_recs) -> PackedPairs:
+    """the aligned line pairs of these sam_records, built on the GPU (ns_sam_pairs_build); bad records raise ValueError naming the first"""
+    args, keep = _pack_sam(sam_recs)
+    p, bufs = _sam_out(sam_recs, keep, True)
+    eng._check(eng.L.ns_sam_pairs_build(eng.ctx, *args, len(sam_recs), C.byref(p)))
+    out = _sam_packed(sam_recs, p, bufs)
+    out.ms_kernel = float(p.ms_kernel)
+    return out
+
+
+def format_maf(sam_recs, packed) -> str:
+    """the text pairwise2maf writes for these records (P:80-82): two `s` lines per record"""
+    out = []
+    for i, (r, a) in enumerate(zip(sam_recs, packed.aln)):
+        lo, hi = int(packed.off[i]), int(packed.off[i + 1])
+        qlen, head, tail = int(a["query_len"]), int(a["head"]), int(a["tail"])
+        out.append("s " + r[2] + " " + str(r[3] - 1) + " " + str(int(a["ref_len"])) + " + * " + packed.ref[lo:hi].tobytes().decode() + "\n")
+        out.append("s " + r[0] + " " + str(head) + " " + str(qlen) + " " + ("+" if r[1] == 0 else "-") + " " + str(qlen + head + tail) + " " +
+                   packed.qry[lo:hi].tobytes().decode() + "\n")
+    return "".join(out)
+
+
+def write_maf(path: str, sam_recs, packed) -> None:
+    with open(path, "w") as f:
+        f.write(format_maf(sam_recs, packed))
+
+
+def count_homopolymers_sam(eng, sam_recs, min_hp_len: int = 5, records: bool = False, lines: bool = False, cap_ref: int = 64, cap_read: int = 64,
+                           cap_records=None) -> dict:
+    """count_homopolymers for sam_records in one call (ns_hp_histograms_sam): the lines are built and counted on the device and come
+    back only with `lines` ("pairs": a PackedPairs; without `lines` its ref / qry are None)"""
+    args, keep = _pack_sam(sam_recs)
+    state = {}
+
+    def call(h):
+        p, bufs = _sam_out(sam_recs, keep, lines)
+        eng._check(eng.L.ns_hp_histograms_sam(eng.ctx, *args, len(sam_recs), int(min_hp_len), C.byref(p), C.byref(h)))
+        state["pairs"] = _sam_packed(sam_recs, p, bufs)
+        state["ms_pairs"] = float(p.ms_kernel)
+    out = _hp_count(call, int(keep[5][-1]), min_hp_len, records, cap_ref, cap_read, cap_records)
+    out["pairs"], out["ms_kernel_pairs"] = state["pairs"], state["ms_pairs"]
+    return out
+
+
+def homopolymer_lengths_from_sam(prefix: str, sam_recs, eng, min_hp_len: int = 5, lengths_file: bool = True, maf_file: bool = False) -> dict:
+    """homopolymer_lengths for sam_records: the same two files, through ns_hp_histograms_sam; with maf_file also <prefix>_processed.maf
+    (what read_analysis.py:200-204 leaves behind); returns the counts"""
+    t = count_homopolymers_sam(eng, sam_recs, min_hp_len, records=lengths_file, lines=maf_file)
+    if maf_file:
+        write_maf(prefix + "_processed.maf", sam_recs, t["pairs"])
+    if lengths_file:
+        with open(prefix + "_hp_lengths.tsv", "w") as f:
+            f.write(format_hp_lengths(t["pairs"], t["records"]))
     with open(prefix + "_hp_lengths_model_parameters.tsv", "w") as f:
         f.write(format_hp_model(fit_homopolymers(t["table"], t["columns"])))
     return t

@@ -16,7 +16,7 @@
 //   k_errlog            wave/read     _aligned_error_profile rows                           (S:2006-2008)
 // Metagenome worker calls run k_lengths / k_chain per PASS of the reference's while loop (S:844-1040) with k_meta_* around them; the lists of a
 // pass are launched before the host has walked the species quotas (assign_species), k_meta_tail does positions + acceptance afterwards.
-// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms: at the end of the host part) has its kernels in ns_train.h.
+// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms, ns_sam_pairs_build: at the end of the host part) has its kernels in ns_train.h.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdio.h>
@@ -2094,6 +2094,7 @@ enum Evt {
     EV_HP_BEGIN, EV_HP_END,             // NS_K_HP: one -k stage, summed over the stages of the call (hp_stage1)
     EV_DRAWS_ON_HOST,                   // no timing pair: the filtered draws of a metagenome pass have reached the host
     EV_RECKERNEL_BEGIN, EV_RECKERNEL_END,   // NS_K_RECORD_KERNEL: the record kernel itself (when ns_ctx::rec_timed)
+    EV_SAM_END,                         // ns_sam_pairs.ms_kernel of ns_hp_histograms_sam: EV_HIST_BEGIN .. here
     EV_HIST_BEGIN, EV_HIST_END,         // ns_cs_hist.ms_kernel (histograms), ns_qual_hist.ms_kernel (ns_qual_histograms), ns_hp_hist.ms_kernel (ns_hp_histograms)
     EV_COUNT
 };
@@ -4206,7 +4207,61 @@ int ns_qual_histograms(ns_ctx *ctx, const uint8_t *cs, uint64_t cs_bytes, const 
     return NS_OK;
 }
 
-// the homopolymer-length model of the training side (include/nanosim_amd.h: ns_hp_hist; src/model_homopolymer_lengths.py:9-119)
+// the homopolymer-length model of the training side (include/nanosim_amd.h: ns_hp_hist; src/model_homopolymer_lengths.py:9-119).  Two entry
+// points — the lines come from the host (ns_hp_histograms) or are made on the device from SAM records (ns_hp_histograms_sam) — share
+// everything from the point where the lines are on the device: HpCall holds the call's counting buffers, hp_check its arguments,
+// hp_buffers asks for the memory (in front of upload()), hp_kernels runs k_hp_count (+ the scan and k_hp_records), hp_finish reads back.
+struct HpCall {
+    uint32_t cap_ref, cap_read; size_t n_table; uint64_t cap_records;
+    unsigned long long *d_small, *d_table, *d_cnt, *d_slot; ns_hp_record *d_rec;
+    unsigned long long small[HPT_WORDS];
+};
+static int hp_check(ns_ctx *ctx, const std::string &call, uint32_t min_hp_len, ns_hp_hist *out, HpCall &h) {
+    if (!min_hp_len) return fail(ctx, NS_EINVAL, call + ": min_hp_len must be at least 1");
+    h.cap_ref = out->cap_ref; h.cap_read = out->cap_read;
+    if (!h.cap_ref || h.cap_ref > 65536u || !h.cap_read || h.cap_read > 65536u) return fail(ctx, NS_EINVAL, call + ": cap_ref and cap_read must be 1 .. 65536");
+    if ((uint64_t)h.cap_ref * h.cap_read > (1ull << 26)) return fail(ctx, NS_EINVAL, call + ": cap_ref * cap_read must not exceed 2^26");
+    h.n_table = (size_t)2 * h.cap_ref * h.cap_read;
+    h.cap_records = out->records ? out->cap_records : 0;
+    out->n_hp = out->max_ref = out->max_read = out->n_overflow = 0; out->ms_kernel = 0;
+    memset(out->columns, 0, sizeof out->columns);
+    memset(h.small, 0, sizeof h.small);
+    return NS_OK;
+}
+static void hp_buffers(CallScratch &s, uint32_t n_aln, const ns_hp_hist *out, HpCall &h) {
+    h.d_small = s.zeroed<unsigned long long>(HPT_WORDS); h.d_table = s.zeroed<unsigned long long>(h.n_table);
+    h.d_cnt = s.zeroed<unsigned long long>((size_t)n_aln + 1);           // (entry n_aln stays 0: the scan leaves the total in slot[n_aln])
+    h.d_slot = out->records ? s.alloc<unsigned long long>((size_t)n_aln + 1) : nullptr;
+    h.d_rec = h.cap_records ? s.alloc<ns_hp_record>((size_t)h.cap_records) : nullptr;
+}
+// the lines are on the device (16 bytes to spare behind them: the window loads of CsBytes)
+static int hp_kernels(CallScratch &s, const uint8_t *d_ref, const uint8_t *d_qry, const uint64_t *d_off, uint32_t n_aln, uint32_t min_hp_len,
+                      const ns_hp_hist *out, HpCall &h) {
+    ns_ctx *ctx = s.ctx;
+    hipStream_t st = ctx->stream;
+    uint32_t *d_order;
+    if (int rc = order_by_length(s, d_off, n_aln, &d_order)) return rc;
+    const dim3 grid((n_aln + 255u) / 256u), block(256);
+    const HpTrainDev H{h.d_table, h.d_small, h.cap_ref, h.cap_read};
+    k_hp_count<<<grid, block, 0, st>>>(d_ref, d_qry, d_off, n_aln, min_hp_len, H, d_order, h.d_cnt);
+    CALLCHK(s, hipGetLastError());
+    if (out->records) {
+        if (int rc = scan_sum(ctx, h.d_cnt, h.d_slot, (size_t)n_aln + 1)) return rc;   // (its own status and message, before any HIP error of this call)
+        if (h.cap_records) {
+            k_hp_records<<<grid, block, 0, st>>>(d_ref, d_qry, d_off, n_aln, min_hp_len, d_order, h.d_slot, h.d_rec, h.cap_records);
+            CALLCHK(s, hipGetLastError());
+        }
+    }
+    return NS_OK;
+}
+// behind timed_tail (which has read h.small and the table back)
+static int hp_finish(CallScratch &s, ns_hp_hist *out, HpCall &h) {
+    if (h.small[HPT_N_HP] && h.small[HPT_N_HP] <= h.cap_records)
+        CALLCHK(s, hipMemcpy(out->records, h.d_rec, (size_t)h.small[HPT_N_HP] * sizeof(ns_hp_record), hipMemcpyDeviceToHost));
+    for (int c = 0; c < 4; ++c) out->columns[c] = h.small[HPT_COLUMNS + c];
+    out->n_hp = h.small[HPT_N_HP]; out->n_overflow = h.small[HPT_OVERFLOW]; out->max_ref = h.small[HPT_MAX_REF]; out->max_read = h.small[HPT_MAX_READ];
+    return NS_OK;
+}
 int ns_hp_histograms(ns_ctx *ctx, const uint8_t *ref_lines, const uint8_t *query_lines, uint64_t nbytes, const uint64_t *aln_off, uint32_t n_aln,
                      uint32_t min_hp_len, ns_hp_hist *out) {
     if (!ctx) return NS_EINVAL;
@@ -4215,46 +4270,142 @@ int ns_hp_histograms(ns_ctx *ctx, const uint8_t *ref_lines, const uint8_t *query
     for (uint32_t a = 0; a < n_aln; ++a)
         if (aln_off[a + 1] - aln_off[a] >= (1ull << 24))        // (the 32-bit counters of a workgroup of k_hp_count, the 30 bits of a record's read_len)
             return fail(ctx, NS_EINVAL, "ns_hp_histograms: alignment " + std::to_string(a) + " has 2^24 columns or more");
-    if (!min_hp_len) return fail(ctx, NS_EINVAL, "ns_hp_histograms: min_hp_len must be at least 1");
-    const uint32_t cap_ref = out->cap_ref, cap_read = out->cap_read;
-    if (!cap_ref || cap_ref > 65536u || !cap_read || cap_read > 65536u) return fail(ctx, NS_EINVAL, "ns_hp_histograms: cap_ref and cap_read must be 1 .. 65536");
-    if ((uint64_t)cap_ref * cap_read > (1ull << 26)) return fail(ctx, NS_EINVAL, "ns_hp_histograms: cap_ref * cap_read must not exceed 2^26");
-    const size_t n_table = (size_t)2 * cap_ref * cap_read;
-    const uint64_t cap_records = out->records ? out->cap_records : 0;
-    out->n_hp = out->max_ref = out->max_read = out->n_overflow = 0; out->ms_kernel = 0;
-    memset(out->columns, 0, sizeof out->columns);
-    if (!n_aln) { memset(out->table, 0, n_table * 8); return NS_OK; }
+    HpCall h;
+    if (int rc = hp_check(ctx, "ns_hp_histograms", min_hp_len, out, h)) return rc;
+    if (!n_aln) { memset(out->table, 0, h.n_table * 8); return NS_OK; }
     HIPCHK(hipSetDevice(ctx->device));
-    unsigned long long small[HPT_WORDS] = {0};
     CallScratch s(ctx, "ns_hp_histograms");
     const uint8_t *d_ref = s.filled(ref_lines, (size_t)nbytes, 16), *d_qry = s.filled(query_lines, (size_t)nbytes, 16);   // (16 bytes to spare: the window loads of CsBytes)
     const uint64_t *d_off = s.filled(aln_off, (size_t)n_aln + 1);
-    unsigned long long *d_small = s.zeroed<unsigned long long>(HPT_WORDS), *d_table = s.zeroed<unsigned long long>(n_table);
-    unsigned long long *d_cnt = s.zeroed<unsigned long long>((size_t)n_aln + 1);      // (entry n_aln stays 0: the scan leaves the total in slot[n_aln])
-    unsigned long long *d_slot = out->records ? s.alloc<unsigned long long>((size_t)n_aln + 1) : nullptr;
-    ns_hp_record *d_rec = cap_records ? s.alloc<ns_hp_record>((size_t)cap_records) : nullptr;
+    hp_buffers(s, n_aln, out, h);
+    if (int rc = s.upload()) return rc;
+    CALLCHK(s, hipEventRecord(ctx->evt[EV_HIST_BEGIN], ctx->stream));
+    if (int rc = hp_kernels(s, d_ref, d_qry, d_off, n_aln, min_hp_len, out, h)) return rc;
+    if (int rc = timed_tail(s, {{h.small, h.d_small, sizeof h.small}, {out->table, h.d_table, h.n_table * 8}}, &out->ms_kernel)) return rc;
+    return hp_finish(s, out, h);
+}
+
+// the line pairs of SAM records (include/nanosim_amd.h: ns_sam_pairs; ns_sam_pairs.h; src/pairwise2maf.py:38-82).  SamCall: the device side of
+// the conversion for both of its callers.  Every buffer is asked for in front of upload(), the lines too: a record has at most one
+// column per SEQ byte and per MD byte, so they are sized from the input and the stream never waits for the host between the phases
+// (k_sam_lines reads the total from the scan's last entry).
+struct SamCall {
+    const uint8_t *d_cigar, *d_md, *d_seq; const uint64_t *d_cigar_off, *d_md_off, *d_seq_off;
+    ns_sam_aln *d_aln; uint64_t *d_cols, *d_off; uint32_t *d_nexc; SamExc *d_exc; unsigned long long *d_small;
+    uint8_t *d_ref, *d_qry; uint64_t max_bytes;
+    unsigned long long small[SAMS_WORDS];
+};
+static int sam_check(ns_ctx *ctx, const std::string &call, const uint8_t *cigar, const uint64_t *cigar_off, const uint8_t *md, const uint64_t *md_off,
+                     const uint8_t *seq, const uint64_t *seq_off, uint32_t n_aln, ns_sam_pairs *p) {
+    if (n_aln && (!cigar_off || !md_off || !seq_off)) return fail(ctx, NS_EINVAL, call + ": null argument");
+    if (p && (!p->aln_off || !p->ref_lines != !p->query_lines)) return fail(ctx, NS_EINVAL, call + ": null argument");
+    if (!n_aln) return NS_OK;
+    if (int rc = check_offsets(ctx, call.c_str(), "CIGAR strings", cigar_off, n_aln, cigar_off[n_aln])) return rc;
+    if (int rc = check_offsets(ctx, call.c_str(), "MD strings", md_off, n_aln, md_off[n_aln])) return rc;
+    if (int rc = check_offsets(ctx, call.c_str(), "SEQ strings", seq_off, n_aln, seq_off[n_aln])) return rc;
+    if ((!cigar && cigar_off[n_aln]) || (!md && md_off[n_aln]) || (!seq && seq_off[n_aln])) return fail(ctx, NS_EINVAL, call + ": null argument");
+    return NS_OK;
+}
+static void sam_clear(ns_sam_pairs *p, uint32_t n_aln) {
+    if (!p) return;
+    p->n_bytes = p->n_bad = 0; p->first_bad = n_aln; p->ms_kernel = 0;
+    for (uint32_t a = 0; a <= n_aln; ++a) p->aln_off[a] = 0;
+    if (p->aln && n_aln) memset(p->aln, 0, (size_t)n_aln * sizeof(ns_sam_aln));
+}
+static void sam_buffers(CallScratch &s, const uint8_t *cigar, const uint64_t *cigar_off, const uint8_t *md, const uint64_t *md_off, const uint8_t *seq,
+                        const uint64_t *seq_off, uint32_t n_aln, bool lines, SamCall &c) {
+    const size_t n = (size_t)n_aln + 1;
+    c.d_cigar = s.filled(cigar, (size_t)cigar_off[n_aln], 16); c.d_md = s.filled(md, (size_t)md_off[n_aln], 16);     // (16 bytes to spare: the window
+    c.d_seq = s.filled(seq, (size_t)seq_off[n_aln], 16);                                                              // loads of CsBytes)
+    c.d_cigar_off = s.filled(cigar_off, n); c.d_md_off = s.filled(md_off, n); c.d_seq_off = s.filled(seq_off, n);
+    c.d_aln = s.alloc<ns_sam_aln>(n_aln);
+    c.d_cols = s.zeroed<uint64_t>(n);                                    // (entry n_aln stays 0: the scan leaves the total in d_off[n_aln])
+    c.d_off = s.alloc<uint64_t>(n);
+    c.d_nexc = s.alloc<uint32_t>(n_aln);
+    c.d_exc = s.alloc<SamExc>((size_t)((cigar_off[n_aln] >> 1) + md_off[n_aln] + n));      // (sam_exc_base of record n_aln)
+    c.small[SAMS_BAD] = 0; c.small[SAMS_FIRST] = ~0ull;                  // (what k_sam_scan's atomics start from)
+    c.d_small = s.filled(c.small, SAMS_WORDS);
+    c.max_bytes = (seq_off[n_aln] - seq_off[0]) + (md_off[n_aln] - md_off[0]);
+    c.d_ref = c.d_qry = nullptr;
+    if (lines) {                                                         // whole 16-byte words of k_sam_lines + the window loads of k_hp_count behind them
+        const size_t bytes = (size_t)((c.max_bytes + 15u) & ~(uint64_t)15u) + 16u;
+        c.d_ref = s.alloc<uint8_t>(bytes); c.d_qry = s.alloc<uint8_t>(bytes);
+    }
+}
+static int sam_kernels(CallScratch &s, uint32_t n_aln, SamCall &c) {
+    ns_ctx *ctx = s.ctx;
+    hipStream_t st = ctx->stream;
+    k_sam_scan<<<dim3((n_aln + 255u) / 256u), dim3(256), 0, st>>>(c.d_cigar, c.d_cigar_off, c.d_md, c.d_md_off, c.d_seq, c.d_seq_off, n_aln, c.d_aln,
+                                                                  c.d_cols, c.d_nexc, c.d_exc, c.d_small);
+    CALLCHK(s, hipGetLastError());
+    if (int rc = scan_sum(ctx, c.d_cols, c.d_off, (size_t)n_aln + 1)) return rc;
+    if (c.d_ref && c.max_bytes) {
+        const uint64_t words = (c.max_bytes + NS_SAM_WORD - 1u) / NS_SAM_WORD;
+        k_sam_lines<<<dim3((uint32_t)((words + 255u) / 256u)), dim3(256), 0, st>>>(c.d_md, c.d_md_off, c.d_seq, c.d_seq_off, c.d_cigar_off, c.d_aln, c.d_nexc,
+                                                                                   c.d_exc, c.d_off, n_aln, c.d_ref, c.d_qry);
+        CALLCHK(s, hipGetLastError());
+    }
+    return NS_OK;
+}
+// behind timed_tail (which has read c.small, the offsets and the figures back): the counters, and the lines when they fit
+static int sam_finish(CallScratch &s, uint32_t n_aln, ns_sam_pairs *p, SamCall &c) {
+    if (!p) return NS_OK;
+    p->n_bytes = p->aln_off[n_aln]; p->n_bad = c.small[SAMS_BAD]; p->first_bad = p->n_bad ? c.small[SAMS_FIRST] : n_aln;
+    if (p->ref_lines && p->n_bytes && p->n_bytes <= p->cap_bytes) {
+        CALLCHK(s, hipMemcpy(p->ref_lines, c.d_ref, (size_t)p->n_bytes, hipMemcpyDeviceToHost));
+        CALLCHK(s, hipMemcpy(p->query_lines, c.d_qry, (size_t)p->n_bytes, hipMemcpyDeviceToHost));
+    }
+    return NS_OK;
+}
+int ns_sam_pairs_build(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off, const uint8_t *md, const uint64_t *md_off,
+                       const uint8_t *seq, const uint64_t *seq_off, uint32_t n_aln, ns_sam_pairs *out) {
+    if (!ctx) return NS_EINVAL;
+    if (!out) return fail(ctx, NS_EINVAL, "ns_sam_pairs_build: null argument");
+    if (int rc = sam_check(ctx, "ns_sam_pairs_build", cigar, cigar_off, md, md_off, seq, seq_off, n_aln, out)) return rc;
+    sam_clear(out, n_aln);
+    if (!n_aln) return NS_OK;
+    if (seq_off[n_aln] - seq_off[0] + md_off[n_aln] - md_off[0] >= (1ull << 40)) return fail(ctx, NS_EINVAL, "ns_sam_pairs_build: more than 2^40 bytes of SEQ and MD");
+    HIPCHK(hipSetDevice(ctx->device));
+    SamCall c;
+    CallScratch s(ctx, "ns_sam_pairs_build");
+    sam_buffers(s, cigar, cigar_off, md, md_off, seq, seq_off, n_aln, out->ref_lines != nullptr, c);
+    if (int rc = s.upload()) return rc;
+    CALLCHK(s, hipEventRecord(ctx->evt[EV_HIST_BEGIN], ctx->stream));
+    if (int rc = sam_kernels(s, n_aln, c)) return rc;
+    if (int rc = timed_tail(s, {{c.small, c.d_small, sizeof c.small}, {out->aln_off, c.d_off, ((size_t)n_aln + 1) * 8},
+                                {out->aln, c.d_aln, out->aln ? (size_t)n_aln * sizeof(ns_sam_aln) : 0}}, &out->ms_kernel)) return rc;
+    return sam_finish(s, n_aln, out, c);
+}
+int ns_hp_histograms_sam(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off, const uint8_t *md, const uint64_t *md_off,
+                         const uint8_t *seq, const uint64_t *seq_off, uint32_t n_aln, uint32_t min_hp_len, ns_sam_pairs *pairs, ns_hp_hist *out) {
+    if (!ctx) return NS_EINVAL;
+    if (!out || !out->table) return fail(ctx, NS_EINVAL, "ns_hp_histograms_sam: null argument");
+    if (int rc = sam_check(ctx, "ns_hp_histograms_sam", cigar, cigar_off, md, md_off, seq, seq_off, n_aln, pairs)) return rc;
+    HpCall h;
+    if (int rc = hp_check(ctx, "ns_hp_histograms_sam", min_hp_len, out, h)) return rc;
+    sam_clear(pairs, n_aln);
+    memset(out->table, 0, h.n_table * 8);
+    if (!n_aln) return NS_OK;
+    if (seq_off[n_aln] - seq_off[0] + md_off[n_aln] - md_off[0] >= (1ull << 40)) return fail(ctx, NS_EINVAL, "ns_hp_histograms_sam: more than 2^40 bytes of SEQ and MD");
+    HIPCHK(hipSetDevice(ctx->device));
+    SamCall c;
+    CallScratch s(ctx, "ns_hp_histograms_sam");
+    sam_buffers(s, cigar, cigar_off, md, md_off, seq, seq_off, n_aln, true, c);
+    hp_buffers(s, n_aln, out, h);
     if (int rc = s.upload()) return rc;
     hipStream_t st = ctx->stream;
     CALLCHK(s, hipEventRecord(ctx->evt[EV_HIST_BEGIN], st));
-    uint32_t *d_order;
-    if (int rc = order_by_length(s, d_off, n_aln, &d_order)) return rc;
-    const dim3 grid((n_aln + 255u) / 256u), block(256);
-    const HpTrainDev H{d_table, d_small, cap_ref, cap_read};
-    k_hp_count<<<grid, block, 0, st>>>(d_ref, d_qry, d_off, n_aln, min_hp_len, H, d_order, d_cnt);
-    CALLCHK(s, hipGetLastError());
-    if (out->records) {
-        if (int rc = scan_sum(ctx, d_cnt, d_slot, (size_t)n_aln + 1)) return rc;       // (its own status and message, before any HIP error of this call)
-        if (cap_records) {
-            k_hp_records<<<grid, block, 0, st>>>(d_ref, d_qry, d_off, n_aln, min_hp_len, d_order, d_slot, d_rec, cap_records);
-            CALLCHK(s, hipGetLastError());
-        }
-    }
-    if (int rc = timed_tail(s, {{small, d_small, sizeof small}, {out->table, d_table, n_table * 8}}, &out->ms_kernel)) return rc;
-    if (small[HPT_N_HP] && small[HPT_N_HP] <= cap_records)
-        CALLCHK(s, hipMemcpy(out->records, d_rec, (size_t)small[HPT_N_HP] * sizeof(ns_hp_record), hipMemcpyDeviceToHost));
-    for (int c = 0; c < 4; ++c) out->columns[c] = small[HPT_COLUMNS + c];
-    out->n_hp = small[HPT_N_HP]; out->n_overflow = small[HPT_OVERFLOW]; out->max_ref = small[HPT_MAX_REF]; out->max_read = small[HPT_MAX_READ];
-    return NS_OK;
+    if (int rc = sam_kernels(s, n_aln, c)) return rc;
+    CALLCHK(s, hipEventRecord(ctx->evt[EV_SAM_END], st));
+    // (a bad record has no columns: the walks below are safe whatever the input was; their counts are dropped further down)
+    if (int rc = hp_kernels(s, c.d_ref, c.d_qry, c.d_off, n_aln, min_hp_len, out, h)) return rc;
+    if (int rc = timed_tail(s, {{c.small, c.d_small, sizeof c.small}, {h.small, h.d_small, sizeof h.small}, {out->table, h.d_table, h.n_table * 8},
+                                {pairs ? pairs->aln_off : nullptr, c.d_off, pairs ? ((size_t)n_aln + 1) * 8 : 0},
+                                {pairs ? (void *)pairs->aln : nullptr, c.d_aln, pairs && pairs->aln ? (size_t)n_aln * sizeof(ns_sam_aln) : 0}}, &out->ms_kernel)) return rc;
+    if (int rc = sam_finish(s, n_aln, pairs, c)) return rc;
+    if (pairs) { float f = 0; CALLCHK(s, hipEventElapsedTime(&f, ctx->evt[EV_HIST_BEGIN], ctx->evt[EV_SAM_END])); pairs->ms_kernel = f; }
+    if (c.small[SAMS_BAD]) { memset(out->table, 0, h.n_table * 8); return NS_OK; }       // nothing is counted: the caller reads pairs->n_bad
+    return hp_finish(s, out, h);
 }
 
 const void *ns_device_ptr(ns_ctx *ctx, int which) {

@@ -1,8 +1,8 @@
 // ns_train.h — training side, the device kernels: the counting loops of the characterisation stage (k_cs_len, k_cs_hist),
-// of the base-quality model (k_qual_mark, k_qual_count) and of the homopolymer-length model (k_hp_count, k_hp_records).  The walks they
-// run are ns_cs_hist.h, ns_qual_hist.h and ns_hp_hist.h, which also compile for the host; the host side of the three calls
-// (ns_cs_histograms / ns_maf_histograms, ns_qual_histograms, ns_hp_histograms) is at the end of nanosim_amd.hip.  Nothing here uses
-// GenArgs or the simulation.
+// of the base-quality model (k_qual_mark, k_qual_count) and of the homopolymer-length model (k_hp_count, k_hp_records), and the line pairs
+// of SAM records (k_sam_scan, k_sam_lines).  The walks they run are ns_cs_hist.h, ns_qual_hist.h, ns_hp_hist.h and ns_sam_pairs.h, which
+// also compile for the host; the host side of the calls (ns_cs_histograms / ns_maf_histograms, ns_qual_histograms, ns_hp_histograms /
+// ns_hp_histograms_sam, ns_sam_pairs_build) is at the end of nanosim_amd.hip.  Nothing here uses GenArgs or the simulation.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -10,6 +10,7 @@
 #include "ns_cs_hist.h"
 #include "ns_qual_hist.h"
 #include "ns_hp_hist.h"
+#include "ns_sam_pairs.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // k_cs_hist: the counting loop of the characterisation stage (ns_cs_hist.h; src/besthit_to_histogram.py:316-365), one alignment per
@@ -268,4 +269,74 @@ __global__ void __launch_bounds__(256) k_hp_records(const uint8_t *__restrict__ 
     HpRecordSink sink{rec, slot[a], slot[a + 1], (uint32_t)a};
     CsBytes rb(ref + off[a]), qb(qry + off[a]);
     hp_hist_alignment(rb, qb, off[a + 1] - off[a], min_hp_len, sink);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_sam_scan, k_sam_lines: the two aligned lines of every SAM record from CIGAR, MD and SEQ (ns_sam_pairs.h; src/pairwise2maf.py:38-82
+// behind sam2pairwise).  SCAN, one record per thread: CIGAR and MD through 8-byte CsBytes windows as k_cs_hist reads its strings; it
+// writes the record's figures, its number of columns (0 for a bad record: the exclusive scan of these is aln_off) and its exceptions.
+// LINES is the byte mover and is driven by the OUTPUT: a thread owns one aligned 16-byte word of each line, a wavefront 1 KiB of
+// consecutive bytes, wherever the records begin — so a wavefront is as busy on ten-column records as on one of 8 kb, and a word has
+// exactly one writer: the records whose bytes share it are all composed by that thread and leave in one 16-byte store per line (the
+// buffers are padded to whole words; nothing is read back, merged or stored bytewise).  The first record of a wavefront's KiB comes
+// from a binary search of aln_off that is the same for its 64 lanes, a lane's own from a few steps forward (else its own search),
+// the place in the record's exception list from a search (sam_cursor_at); from there the 16 columns walk forward, over record borders
+// too.  SEQ comes through an 8-byte window: 16 columns are two or three loads.
+// small[]: SAMS_BAD records that are bad, SAMS_FIRST the smallest index of one (preset to ~0).
+// ---------------------------------------------------------------------------------------------------------
+enum { SAMS_BAD = 0, SAMS_FIRST = 1, SAMS_WORDS = 2 };
+#define NS_SAM_WORD 16u
+__global__ void __launch_bounds__(256) k_sam_scan(const uint8_t *__restrict__ cigar, const uint64_t *__restrict__ cigar_off, const uint8_t *__restrict__ md,
+                                                  const uint64_t *__restrict__ md_off, const uint8_t *__restrict__ seq, const uint64_t *__restrict__ seq_off,
+                                                  uint32_t n_aln, ns_sam_aln *__restrict__ aln, uint64_t *__restrict__ cols,
+                                                  uint32_t *__restrict__ n_exc, SamExc *__restrict__ exc, unsigned long long *__restrict__ small) {
+    const uint64_t a = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= n_aln) return;
+    const uint64_t sn = seq_off[a + 1] - seq_off[a];
+    CsBytes cb(cigar + cigar_off[a]), mb(md + md_off[a]);
+    SamFigures F;
+    const bool ok = sam_scan_record(cb, cigar_off[a + 1] - cigar_off[a], mb, md_off[a + 1] - md_off[a], sn, sn == 1u && seq[seq_off[a]] == '*',
+                                    exc + sam_exc_base(cigar_off, md_off, a), F);
+    aln[a] = ns_sam_aln{F.head, F.tail, F.ref_len, F.query_len};
+    cols[a] = F.cols; n_exc[a] = F.n_exc;
+    if (!ok) { atomicAdd(&small[SAMS_BAD], 1ull); atomicMin(&small[SAMS_FIRST], (unsigned long long)a); }
+}
+__global__ void __launch_bounds__(256) k_sam_lines(const uint8_t *__restrict__ md, const uint64_t *__restrict__ md_off, const uint8_t *__restrict__ seq,
+                                                   const uint64_t *__restrict__ seq_off, const uint64_t *__restrict__ cigar_off,
+                                                   const ns_sam_aln *__restrict__ aln, const uint32_t *__restrict__ n_exc, const SamExc *__restrict__ exc,
+                                                   const uint64_t *__restrict__ off, uint32_t n_aln,
+                                                   uint8_t *__restrict__ ref_out, uint8_t *__restrict__ qry_out) {
+    const uint64_t n_bytes = off[n_aln];
+    const uint64_t g = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * NS_SAM_WORD;
+    if (g >= n_bytes) return;
+    uint32_t a = qual_locate(off, 0u, n_aln, g - (uint64_t)(threadIdx.x & 63u) * NS_SAM_WORD);      // (g < n_bytes: there is one)
+    for (uint32_t s = 0; s < 4u && off[a + 1u] <= g; ++s) ++a;
+    if (off[a + 1u] <= g) a = qual_locate(off, a + 1u, n_aln, g);
+    uint64_t lo = off[a], hi = off[a + 1u];
+    const SamExc *x = exc + sam_exc_base(cigar_off, md_off, a);
+    uint32_t nx = n_exc[a];
+    uint64_t seq_at = seq_off[a] + aln[a].head, md_at = md_off[a];
+    SamCursor k;
+    sam_cursor_at(k, x, nx, (uint32_t)(g - lo));
+    CsBytes sb(seq), mb(md);
+    uint32_t rw[4] = {0u, 0u, 0u, 0u}, qw[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (uint32_t b = 0; b < NS_SAM_WORD; ++b) {
+        const uint64_t pos = g + b;
+        if (pos < n_bytes) {
+            if (pos >= hi) {                                  // the next record that has a column: its first one
+                do ++a; while (off[a + 1u] <= pos);
+                lo = off[a]; hi = off[a + 1u];
+                x = exc + sam_exc_base(cigar_off, md_off, a); nx = n_exc[a];
+                seq_at = seq_off[a] + aln[a].head; md_at = md_off[a];
+                sam_cursor_at(k, x, nx, 0u);
+            }
+            uint8_t r, q;
+            sam_column(k, x, nx, (uint32_t)(pos - lo), sb, seq_at, mb, md_at, r, q);
+            rw[b >> 2] |= (uint32_t)r << (8u * (b & 3u));
+            qw[b >> 2] |= (uint32_t)q << (8u * (b & 3u));
+        }
+    }
+    *reinterpret_cast<uint4 *>(ref_out + g) = make_uint4(rw[0], rw[1], rw[2], rw[3]);
+    *reinterpret_cast<uint4 *>(qry_out + g) = make_uint4(qw[0], qw[1], qw[2], qw[3]);
 }

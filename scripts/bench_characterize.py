@@ -12,7 +12,13 @@ reference's letters along a piece, `-` for the gaps, the events as mismatched / 
 alignments/s, the kernels' time (k_hp_count alone; with --records also the scan and k_hp_records) and GB/s over both lines.
 --host-walk times the same walk compiled for the host (tests/hp_train_host.cpp) on one core over the same input; --dump-maf PATH writes
 the first 2 000 pairs as `s` lines (what the reference's analyze_homopolymers reads).
-    python scripts/bench_characterize.py --homopolymers [--records] [--host-walk] [--dump-maf PATH] [--alignments 200000]"""
+    python scripts/bench_characterize.py --homopolymers [--records] [--host-walk] [--dump-maf PATH] [--alignments 200000]
+--sam-pairs: the SAM route to that model (ns_sam_pairs_build, ns_hp_histograms_sam): the same line pairs turned into CIGAR, MD and SEQ
+(2 000 distinct reads, repeated), and from there back into lines on the GPU.  Prints the kernel milliseconds of the two phases (the scan
+phase from the call without line buffers, the line phase as the difference to the call with them), GB/s of lines written, the end-to-end
+time of pairs_from_sam with packing, and the fused call against pairs_from_sam followed by count_homopolymers — every figure with the
+values of the single steps, so that the spread shows.
+    python scripts/bench_characterize.py --sam-pairs [--alignments 50000] [--steps 5]"""
 import argparse
 import ctypes as C
 import json
@@ -32,6 +38,7 @@ ap.add_argument("--alignments", type=int, default=200_000)
 ap.add_argument("--steps", type=int, default=3)
 ap.add_argument("--qualities", action="store_true")
 ap.add_argument("--homopolymers", action="store_true")
+ap.add_argument("--sam-pairs", action="store_true")
 ap.add_argument("--records", action="store_true")
 ap.add_argument("--host-walk", action="store_true")
 ap.add_argument("--dump-maf", default=None)
@@ -46,12 +53,12 @@ ref = M.Reference(["ecoli-like"], seq, np.array([0, len(seq)], dtype=np.uint64),
 eng = E.Engine(0)
 eng.set_reference(ref)
 eng.load_model(mdl)
-n_src = min(a.alignments, 20_000)                       # cs strings of 20 000 reads, repeated up to the requested number
+n_src = min(a.alignments, 2_000 if a.sam_pairs else 20_000)   # cs strings of 20 000 reads, repeated up to the requested number
 b = eng.generate(E.make_params(seed=SEED, first_read=0, n_reads=n_src, max_len=ref.max_chrom, emit_records=False))
 pieces, events = b.pieces(), b.events()
 rng = np.random.default_rng(SEED)
 letters = np.frombuffer(b"acgt", dtype=np.uint8)
-if a.homopolymers:
+if a.homopolymers or a.sam_pairs:
     # the two lines of an alignment: the reference's letters from a random place of the genome (its homopolymer runs included), the
     # events of the piece as columns
     pairs = []
@@ -77,6 +84,72 @@ if a.homopolymers:
             where = np.repeat(np.minimum(ins_at, n), ins_n)
             r, q = np.insert(r, where, dash), np.insert(q, where, letters[rng.integers(0, 4, len(where))] - 32)
         pairs.append((r.tobytes(), q.tobytes()))
+    if a.sam_pairs:
+        def sam_of_columns(r, q):
+            """(CIGAR, MD, SEQ) of an aligned line pair (uint8 arrays)"""
+            op = np.where(r == dash, 1, np.where(q == dash, 2, 0))                     # M, I, D
+            starts = np.concatenate(([0], np.flatnonzero(np.diff(op)) + 1))
+            lens = np.diff(np.concatenate((starts, [len(op)])))
+            cigar = "".join("%d%s" % (n, "MID"[o]) for n, o in zip(lens.tolist(), op[starts].tolist()))
+            keep = op != 1
+            rr, dd = r[keep], op[keep] == 2
+            md, prev, in_del = [], -1, False
+            for i in np.flatnonzero(dd | (rr != q[keep])).tolist():
+                if dd[i] and in_del and i == prev + 1:
+                    md.append(chr(rr[i]))                                               # (a `^` run goes on over an insertion)
+                else:
+                    md.append("%d%s%s" % (i - prev - 1, "^" if dd[i] else "", chr(rr[i])))
+                in_del, prev = bool(dd[i]), i
+            md.append(str(len(rr) - prev - 1))
+            return cigar, "".join(md), q[q != dash].tobytes().decode()
+        src = [("read%d" % i, 0, "ref", 1) + sam_of_columns(np.frombuffer(r, dtype=np.uint8), np.frombuffer(q, dtype=np.uint8)) for i, (r, q) in enumerate(pairs)]
+        recs = (src * (a.alignments // len(src) + 1))[:a.alignments]
+        tuples = [("ref", 0, r.decode(), q.decode()) for r, q in (pairs * (a.alignments // len(pairs) + 1))[:a.alignments]]
+        in_bytes = sum(len(x[4]) + len(x[5]) + len(x[6]) for x in recs)
+        packed = characterize.pairs_from_sam(eng, recs)                                # warms up; the result is checked once
+        n_lines = int(packed.off[-1])
+        assert all(packed[i] == tuples[i] for i in range(0, len(recs), max(1, len(recs) // 50)))
+        args, keep_alive = characterize._pack_sam(recs)
+
+        def build_ms(lines):
+            p, bufs = characterize._sam_out(recs, keep_alive, lines)
+            eng._check(eng.L.ns_sam_pairs_build(eng.ctx, *args, len(recs), C.byref(p)))
+            return float(p.ms_kernel)
+        build_ms(True)
+        ms_scan = [build_ms(False) for _ in range(a.steps)]
+        ms_both = [build_ms(True) for _ in range(a.steps)]
+        e2e = []
+        for _ in range(a.steps):
+            t0 = time.perf_counter()
+            packed = characterize.pairs_from_sam(eng, recs)
+            e2e.append(time.perf_counter() - t0)
+        t = characterize.count_homopolymers_sam(eng, recs, 5)                          # sizes the table, warms up
+        caps = dict(cap_ref=max(64, 1 << int(t["table"].shape[1] - 1).bit_length()), cap_read=max(64, 1 << int(t["table"].shape[2] - 1).bit_length()))
+        fused_s, fused_ms, fused_pairs_ms, two_s, two_ms = [], [], [], [], []
+        for _ in range(a.steps):
+            t0 = time.perf_counter()
+            f = characterize.count_homopolymers_sam(eng, recs, 5, **caps)
+            fused_s.append(time.perf_counter() - t0)
+            fused_ms.append(f["ms_kernel"]); fused_pairs_ms.append(f["ms_kernel_pairs"])
+            t0 = time.perf_counter()
+            pk = characterize.pairs_from_sam(eng, recs)
+            g = characterize.count_homopolymers(eng, pk, 5, **caps)
+            two_s.append(time.perf_counter() - t0)
+            two_ms.append(pk.ms_kernel + g["ms_kernel"])
+            assert np.array_equal(f["table"], g["table"]) and np.array_equal(f["columns"], g["columns"])
+        med = lambda v: float(np.median(v))
+        ms_lines = med(ms_both) - med(ms_scan)
+        print(json.dumps({"metric": "SAM records to aligned line pairs, alignments/s (pairs_from_sam incl. packing + H2D + D2H)", "value": a.alignments / med(e2e),
+                          "alignments": a.alignments, "steps": a.steps, "input_bytes(cigar+md+seq)": in_bytes, "line_bytes(both lines)": 2 * n_lines,
+                          "line_bytes_per_alignment": 2 * n_lines / a.alignments,
+                          "scan_ms(k_sam_scan + scan)": ms_scan, "both_phases_ms": ms_both, "lines_ms(k_sam_lines, difference of medians)": ms_lines,
+                          "lines_gb_per_s(bytes written)": 2 * n_lines / (ms_lines * 1e-3) / 1e9 if ms_lines > 0 else None,
+                          "both_phases_gb_per_s(read + written)": (in_bytes + 2 * n_lines) / (med(ms_both) * 1e-3) / 1e9,
+                          "pairs_from_sam_end_to_end_s": e2e,
+                          "fused_end_to_end_s": fused_s, "fused_kernels_ms": fused_ms, "fused_kernels_ms_conversion_part": fused_pairs_ms,
+                          "pairs_then_count_end_to_end_s": two_s, "pairs_then_count_kernels_ms": two_ms, "homopolymers": t["n_hp"]}))
+        eng.close()
+        sys.exit(0)
     pairs = (pairs * (a.alignments // len(pairs) + 1))[:a.alignments]
     nbytes = 2 * sum(len(x[0]) for x in pairs)
     if a.dump_maf:
