@@ -3749,10 +3749,7 @@ static int write_images(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info, 
     // once its copies have left the device
     *slot = ctx->slot;
     const bool write_rec = prm->emit_records == 1u;            // (2 = NS_EMIT_SIZES: the sizes of the images only)
-    if (write_rec && ctx->io) {
-        if (ctx->io->slot_busy(*slot)) *slot ^= 1;
-        ctx->io->wait_slot(*slot);
-    }
+    if (write_rec && ctx->io) *slot = ctx->io->pick_slot(*slot);
     if (write_rec && (rc = ensure_all(ctx, {{ctx->rec_slot[*slot], (size_t)info->record_bytes, 64}, {ctx->err_slot[*slot], (size_t)info->errlog_bytes, 64}})))
         return rc;
     if (prm->emit_records == 0) info->errlog_bytes = 0;       // (no records: no error-profile image either; NS_EMIT_SIZES keeps the size)
@@ -3989,15 +3986,9 @@ int ns_sink_put(ns_ctx *ctx, ns_sink *s, const void *host, uint64_t n) {
     if (!ctx) return NS_EINVAL;
     if (!own_sink(ctx, s)) return fail(ctx, NS_EINVAL, "unknown sink");
     if (n && !host) return fail(ctx, NS_EINVAL, "ns_sink_put: null source");
-    uint64_t done = 0;
-    while (s->fd >= 0 && done < n) {
-        const ssize_t w = pwrite(s->fd, static_cast<const uint8_t *>(host) + done, (size_t)(n - done), (off_t)(s->off + done));
-        if (w < 0 && errno == EINTR) continue;
-        if (w <= 0) return fail(ctx, NS_EIO, std::string("write: ") + strerror(w < 0 ? errno : ENOSPC));
-        done += (uint64_t)w;
-    }
-    s->off += n; s->queued += n; s->written += n;
-    return NS_OK;
+    std::string msg;
+    const int rc = IoEngine::put(s, host, n, msg);
+    return rc ? fail(ctx, rc, msg) : NS_OK;
 }
 
 int ns_sink_write_range(ns_ctx *ctx, ns_sink *s, int which, uint64_t offset, uint64_t nbytes) {
@@ -4048,21 +4039,18 @@ int ns_record_offsets(ns_ctx *ctx, const uint64_t *read_index, uint32_t n, uint6
 int ns_sink_drain(ns_ctx *ctx, ns_sink *s, uint64_t *file_off) {
     if (!ctx) return NS_EINVAL;
     if (!own_sink(ctx, s)) return fail(ctx, NS_EINVAL, "unknown sink");
-    ctx->io->wait_sink(s);
-    if (file_off) *file_off = s->off;
-    { std::lock_guard<std::mutex> g(ctx->io->mu); if (!ctx->io->err.empty()) return fail(ctx, NS_EHIP, ctx->io->err); }
-    if (const int e = s->err.load()) return fail(ctx, NS_EIO, std::string("write: ") + strerror(e));
-    return NS_OK;
+    std::string msg;
+    const int rc = ctx->io->drain(s, file_off, msg);
+    return rc ? fail(ctx, rc, msg) : NS_OK;
 }
 
 int ns_sink_close(ns_ctx *ctx, ns_sink *s) {
     if (!ctx) return NS_EINVAL;
     if (!s) return NS_OK;
-    const int rc = ns_sink_drain(ctx, s, nullptr);
-    if (rc == NS_EINVAL) return rc;
-    ctx->sinks.erase(std::find(ctx->sinks.begin(), ctx->sinks.end(), s));
-    delete s;
-    return rc;
+    if (!own_sink(ctx, s)) return fail(ctx, NS_EINVAL, "unknown sink");
+    std::string msg;
+    const int rc = ctx->io->close(ctx->sinks, s, msg);
+    return rc ? fail(ctx, rc, msg) : NS_OK;
 }
 
 int ns_io_counters(ns_ctx *ctx, ns_io_stats *out, int reset) {
@@ -4070,10 +4058,7 @@ int ns_io_counters(ns_ctx *ctx, ns_io_stats *out, int reset) {
     if (!out) return fail(ctx, NS_EINVAL, "null destination");
     memset(out, 0, sizeof *out);
     if (!ctx->io) return NS_OK;
-    std::lock_guard<std::mutex> g(ctx->io->mu);
-    out->bytes = ctx->io->bytes; out->dma_ms = ctx->io->dma_ms; out->wait_staging_s = ctx->io->wait_free_s; out->write_s = ctx->io->write_s;
-    out->slice_bytes = ctx->io->slice_bytes; out->n_slices = (uint32_t)ctx->io->slices.size(); out->n_threads = (uint32_t)ctx->io->writers.size();
-    if (reset) { ctx->io->bytes = 0; ctx->io->dma_ms = ctx->io->wait_free_s = ctx->io->write_s = 0; }
+    ctx->io->counters(out, reset);
     return NS_OK;
 }
 

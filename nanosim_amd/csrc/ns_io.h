@@ -13,15 +13,19 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <errno.h>
+#include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
+#include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <deque>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
+#include "../../include/nanosim_amd.h"
 
 struct ns_sink {
     int fd = -1;                          // -1: the bytes are copied to the host and dropped (measures the device-to-host rate alone)
@@ -105,6 +109,48 @@ struct IoEngine {
     bool slot_busy(int slot) { std::lock_guard<std::mutex> g(mu); return slot_pending[slot] != 0; }
     void wait_all() { std::unique_lock<std::mutex> g(mu); cv_idle.wait(g, [&] { return jobs_open == 0; }); }
     void wait_sink(ns_sink *s) { std::unique_lock<std::mutex> g(mu); cv_idle.wait(g, [&] { return s->written.load() == s->queued.load(); }); }
+
+    // ---- the bodies of ns_generate's slot choice and of ns_sink_put / ns_sink_drain / ns_sink_close / ns_io_counters, free of the
+    // context (the entry points check their arguments and keep `msg` as the context's last error): what the host-only test programs
+    // drive is what the library runs ----
+    // result slot of the next batch: the other one while `slot` is still being copied out; returns once the choice has left the device
+    int pick_slot(int slot) {
+        if (slot_busy(slot)) slot ^= 1;
+        wait_slot(slot);
+        return slot;
+    }
+    // host bytes, in order with the queued buffers: written by the caller, at once
+    static int put(ns_sink *s, const void *host, uint64_t n, std::string &msg) {
+        uint64_t done = 0;
+        while (s->fd >= 0 && done < n) {
+            const ssize_t w = pwrite(s->fd, static_cast<const uint8_t *>(host) + done, (size_t)(n - done), (off_t)(s->off + done));
+            if (w < 0 && errno == EINTR) continue;
+            if (w <= 0) { msg = std::string("write: ") + strerror(w < 0 ? errno : ENOSPC); return NS_EIO; }
+            done += (uint64_t)w;
+        }
+        s->off += n; s->queued += n; s->written += n;
+        return NS_OK;
+    }
+    int drain(ns_sink *s, uint64_t *file_off, std::string &msg) {
+        wait_sink(s);
+        if (file_off) *file_off = s->off;
+        { std::lock_guard<std::mutex> g(mu); if (!err.empty()) { msg = err; return NS_EHIP; } }
+        if (const int e = s->err.load()) { msg = std::string("write: ") + strerror(e); return NS_EIO; }
+        return NS_OK;
+    }
+    // drain, then forget and delete the sink (`sinks`: the owner's list, which holds s)
+    int close(std::vector<ns_sink *> &sinks, ns_sink *s, std::string &msg) {
+        const int rc = drain(s, nullptr, msg);
+        sinks.erase(std::find(sinks.begin(), sinks.end(), s));
+        delete s;
+        return rc;
+    }
+    void counters(ns_io_stats *out, int reset) {
+        std::lock_guard<std::mutex> g(mu);
+        out->bytes = bytes; out->dma_ms = dma_ms; out->wait_staging_s = wait_free_s; out->write_s = write_s;
+        out->slice_bytes = slice_bytes; out->n_slices = (uint32_t)slices.size(); out->n_threads = (uint32_t)writers.size();
+        if (reset) { bytes = 0; dma_ms = wait_free_s = write_s = 0; }
+    }
 
     // The copier takes the slices of the queued buffers ROUND-ROBIN over the buffers (up to NS_IO_FANOUT of them): a batch cut into K
     // sub-files has slices of K files in flight, so K writers are busy — taken one buffer after the other, all staging slices would
