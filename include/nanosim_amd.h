@@ -465,6 +465,33 @@ int ns_hp_histograms_sam(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *ciga
                          const uint8_t *seq, const uint64_t *seq_off, uint32_t n_aln, uint32_t min_hp_len, ns_sam_pairs *pairs,
                          ns_hp_hist *out);
 
+/* ---- training side: the error-length mixtures ------------------------------------------------------------------------------------------------
+ * replaces the grid of Nelder-Mead searches of src/model_fitting.py (mis_fit / ins_fit / del_fit, F:59-105, run from F:116-214): one search
+ * per start, all of them in one kernel.  cdf[n_bins] is the empirical CDF of the run lengths (read_histogram, F:27-45), 1 .. 65536 bins.
+ *   NS_MIXFIT_MISMATCH   3 doubles per start (l, p, w): Poisson-geometric, bins are x = 0 .. n_bins-1 (mis_ll);
+ *   NS_MIXFIT_INDEL      4 doubles per start (l, k, p, w): Weibull-geometric, bins are x = 1 .. n_bins (ins_ll, del_ll).
+ * The objective is the largest |model CDF - cdf|; it is NaN when a parameter is not > 0 or p > 1 (scipy's argument checks).  The search is
+ * scipy's minimize(f, x0, method='Nelder-Mead') with its defaults; objective, evaluation order and search are written down in
+ * nanosim_amd/csrc/ns_mixfit.h.  NS_MIXFIT_EVALUATE returns the objective at each given point instead (fun = residual, nfev = 1, nit = 0).
+ * Selecting among the starts and writing <prefix>_model_profile is done on the host (nanosim_amd/characterize.py: fit_mixtures).
+ * Added without an ABI change. */
+enum { NS_MIXFIT_MISMATCH = 0, NS_MIXFIT_INDEL = 1 };
+enum { NS_MIXFIT_FIT = 0, NS_MIXFIT_EVALUATE = 1 };
+typedef struct ns_mixfit_fit {
+    double   x[4];              /* the result point sim[0]; entries beyond the kind's parameters are 0 */
+    double   fun;               /* scipy's result.fun = np.min(fsim): NaN as soon as one vertex of the last simplex is */
+    double   residual;          /* the objective at x (what mis_fit / ins_fit / del_fit return as diff) */
+    uint32_t nfev, nit;
+    int32_t  status;            /* 0 converged, 1 the evaluation limit, 2 the iteration limit (200 per parameter each) */
+    uint32_t reserved;
+} ns_mixfit_fit;
+typedef struct ns_mixfit_result {
+    ns_mixfit_fit *fits;        /* in: host buffer of n_starts entries (out) */
+    double ms_kernel;
+} ns_mixfit_result;
+int ns_mixture_fit(ns_ctx *ctx, int kind, const double *cdf, uint32_t n_bins, const double *starts, uint32_t n_starts, int mode,
+                   ns_mixfit_result *out);
+
 /* device address of a result buffer (for zero-copy consumers such as torch / RCCL); NULL if absent */
 const void *ns_device_ptr(ns_ctx *ctx, int which);
 

@@ -16,7 +16,7 @@
 //   k_errlog            wave/read     _aligned_error_profile rows                           (S:2006-2008)
 // Metagenome worker calls run k_lengths / k_chain per PASS of the reference's while loop (S:844-1040) with k_meta_* around them; the lists of a
 // pass are launched before the host has walked the species quotas (assign_species), k_meta_tail does positions + acceptance afterwards.
-// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms, ns_sam_pairs_build: at the end of the host part) has its kernels in ns_train.h.
+// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms, ns_sam_pairs_build, ns_mixture_fit: at the end of the host part) has its kernels in ns_train.h.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdio.h>
@@ -4391,6 +4391,33 @@ int ns_hp_histograms_sam(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *ciga
     if (pairs) { float f = 0; CALLCHK(s, hipEventElapsedTime(&f, ctx->evt[EV_HIST_BEGIN], ctx->evt[EV_SAM_END])); pairs->ms_kernel = f; }
     if (c.small[SAMS_BAD]) { memset(out->table, 0, h.n_table * 8); return NS_OK; }       // nothing is counted: the caller reads pairs->n_bad
     return hp_finish(s, out, h);
+}
+
+// the error-length mixtures (include/nanosim_amd.h: ns_mixfit_result; ns_mixfit.h; src/model_fitting.py:48-105): a wavefront per start
+int ns_mixture_fit(ns_ctx *ctx, int kind, const double *cdf, uint32_t n_bins, const double *starts, uint32_t n_starts, int mode, ns_mixfit_result *out) {
+    if (!ctx) return NS_EINVAL;
+    if (!out || !out->fits || !cdf || !starts) return fail(ctx, NS_EINVAL, "ns_mixture_fit: null argument");
+    if (kind != NS_MIXFIT_MISMATCH && kind != NS_MIXFIT_INDEL) return fail(ctx, NS_EINVAL, "ns_mixture_fit: unknown kind");
+    if (mode != NS_MIXFIT_FIT && mode != NS_MIXFIT_EVALUATE) return fail(ctx, NS_EINVAL, "ns_mixture_fit: unknown mode");
+    if (!n_bins || n_bins > MF_MAX_BINS) return fail(ctx, NS_EINVAL, "ns_mixture_fit: n_bins must be 1 .. 65536");
+    if (!n_starts) return fail(ctx, NS_EINVAL, "ns_mixture_fit: no starts");
+    out->ms_kernel = 0;
+    HIPCHK(hipSetDevice(ctx->device));
+    const bool mis = kind == NS_MIXFIT_MISMATCH;
+    std::vector<double> lnf(n_bins);
+    mf_lnfact_table(lnf.data(), n_bins);
+    CallScratch s(ctx, "ns_mixture_fit");
+    const double *d_cdf = s.filled(cdf, (size_t)n_bins), *d_lnf = s.filled(lnf.data(), (size_t)n_bins);
+    const double *d_starts = s.filled(starts, (size_t)n_starts * (mis ? 3u : 4u));
+    ns_mixfit_fit *d_out = s.alloc<ns_mixfit_fit>((size_t)n_starts);
+    if (int rc = s.upload()) return rc;
+    hipStream_t st = ctx->stream;
+    CALLCHK(s, hipEventRecord(ctx->evt[EV_HIST_BEGIN], st));
+    const dim3 grid((n_starts + NS_MF_WAVES - 1u) / NS_MF_WAVES), block(64u * NS_MF_WAVES);
+    if (mis) k_mixfit<MfMis><<<grid, block, 0, st>>>(d_cdf, d_lnf, n_bins, d_starts, n_starts, mode == NS_MIXFIT_EVALUATE, d_out);
+    else k_mixfit<MfIndel><<<grid, block, 0, st>>>(d_cdf, d_lnf, n_bins, d_starts, n_starts, mode == NS_MIXFIT_EVALUATE, d_out);
+    CALLCHK(s, hipGetLastError());
+    return timed_tail(s, {{out->fits, d_out, (size_t)n_starts * sizeof(ns_mixfit_fit)}}, &out->ms_kernel);
 }
 
 const void *ns_device_ptr(ns_ctx *ctx, int which) {

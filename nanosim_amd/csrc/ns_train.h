@@ -1,8 +1,9 @@
 // ns_train.h — training side, the device kernels: the counting loops of the characterisation stage (k_cs_len, k_cs_hist),
 // of the base-quality model (k_qual_mark, k_qual_count) and of the homopolymer-length model (k_hp_count, k_hp_records), and the line pairs
-// of SAM records (k_sam_scan, k_sam_lines).  The walks they run are ns_cs_hist.h, ns_qual_hist.h, ns_hp_hist.h and ns_sam_pairs.h, which
-// also compile for the host; the host side of the calls (ns_cs_histograms / ns_maf_histograms, ns_qual_histograms, ns_hp_histograms /
-// ns_hp_histograms_sam, ns_sam_pairs_build) is at the end of nanosim_amd.hip.  Nothing here uses GenArgs or the simulation.
+// of SAM records (k_sam_scan, k_sam_lines), and the fit of the error-length mixtures (k_mixfit).  The walks they run are ns_cs_hist.h,
+// ns_qual_hist.h, ns_hp_hist.h, ns_sam_pairs.h and ns_mixfit.h, which also compile for the host; the host side of the calls
+// (ns_cs_histograms / ns_maf_histograms, ns_qual_histograms, ns_hp_histograms / ns_hp_histograms_sam, ns_sam_pairs_build, ns_mixture_fit)
+// is at the end of nanosim_amd.hip.  Nothing here uses GenArgs or the simulation.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,6 +12,7 @@
 #include "ns_qual_hist.h"
 #include "ns_hp_hist.h"
 #include "ns_sam_pairs.h"
+#include "ns_mixfit.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // k_cs_hist: the counting loop of the characterisation stage (ns_cs_hist.h; src/besthit_to_histogram.py:316-365), one alignment per
@@ -339,4 +341,29 @@ __global__ void __launch_bounds__(256) k_sam_lines(const uint8_t *__restrict__ m
     }
     *reinterpret_cast<uint4 *>(ref_out + g) = make_uint4(rw[0], rw[1], rw[2], rw[3]);
     *reinterpret_cast<uint4 *>(qry_out + g) = make_uint4(qw[0], qw[1], qw[2], qw[3]);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_mixfit: the Nelder-Mead searches of the error-length mixtures (ns_mixfit.h; src/model_fitting.py:48-105), ONE WAVEFRONT PER START,
+// four per workgroup.  The simplex, its values and every decision of the search are the same in all 64 lanes (each lane carries them in
+// its own registers and takes the same branches); the lanes differ only inside an objective evaluation, where lane j has bin 64 t + j of
+// tile t: the scan of the mismatch CDF and the maximum are cross-lane operations in the order ns_mixfit.h fixes.  The empirical CDF and
+// the ln x! table (at most 8 KB each at the 1 000 bins a histogram can have) are read-only and shared by every wavefront: they come from
+// global memory through the caches, there is no LDS and no barrier.  Searches end after different numbers of evaluations: whole
+// wavefronts leave early, none diverges inside.  (One search per THREAD would put the 9 216 starts of an indel grid on 144 wavefronts of
+// a device that holds 8 192, with 64 different trip counts in each.)
+// ---------------------------------------------------------------------------------------------------------
+#define NS_MF_WAVES 4u
+template <class Obj>
+__global__ void __launch_bounds__(256) k_mixfit(const double *__restrict__ cdf, const double *__restrict__ lnf, uint32_t n_bins,
+                                                const double *__restrict__ starts, uint32_t n_starts, int evaluate, ns_mixfit_fit *__restrict__ out) {
+    const uint32_t start = blockIdx.x * NS_MF_WAVES + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (start >= n_starts) return;                            // (the whole wavefront)
+    const Obj obj{cdf, lnf, n_bins};
+    const double *x0 = starts + (size_t)start * Obj::N;
+    ns_mixfit_fit r;
+    r.reserved = 0;
+    if (evaluate) mf_evaluate(obj, x0, r);
+    else mf_nelder_mead(obj, x0, 200u * Obj::N, 200u * Obj::N, r);
+    if ((threadIdx.x & 63u) == 0) out[start] = r;
 }

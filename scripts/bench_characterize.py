@@ -18,7 +18,12 @@ the first 2 000 pairs as `s` lines (what the reference's analyze_homopolymers re
 phase from the call without line buffers, the line phase as the difference to the call with them), GB/s of lines written, the end-to-end
 time of pairs_from_sam with packing, and the fused call against pairs_from_sam followed by count_homopolymers — every figure with the
 values of the single steps, so that the spread shows.
-    python scripts/bench_characterize.py --sam-pairs [--alignments 50000] [--steps 5]"""
+    python scripts/bench_characterize.py --sam-pairs [--alignments 50000] [--steps 5]
+--mixfit: the fit of the error-length mixtures (ns_mixture_fit: 512 + 9 216 + 9 216 Nelder-Mead searches, one wavefront each) on the three
+histograms of the reference's fixture (7, 12 and 8 bins; tests/golden/reference_mixfit.json.gz) and on histograms of 1 000 bins: the
+kernel milliseconds per type (device events around each of the three calls) of every step, the evaluations the searches made, and the
+end-to-end time of fit_mixtures.
+    python scripts/bench_characterize.py --mixfit [--steps 3]"""
 import argparse
 import ctypes as C
 import json
@@ -39,11 +44,49 @@ ap.add_argument("--steps", type=int, default=3)
 ap.add_argument("--qualities", action="store_true")
 ap.add_argument("--homopolymers", action="store_true")
 ap.add_argument("--sam-pairs", action="store_true")
+ap.add_argument("--mixfit", action="store_true")
 ap.add_argument("--records", action="store_true")
 ap.add_argument("--host-walk", action="store_true")
 ap.add_argument("--dump-maf", default=None)
 a = ap.parse_args()
 SEED = 20260926
+if a.mixfit:
+    import gzip
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "reference_mixfit.json.gz"), "rt") as f:
+        fx = json.load(f)
+    rng = np.random.default_rng(SEED)
+
+    def long_hist(first):
+        """20 000 geometric lengths and a thin tail that reaches length 1 000 (mismatch: 1 001): 1 000 bins"""
+        h = {}
+        for v in np.concatenate((rng.geometric(0.02, 20000), rng.integers(1, 1001, 400), [1000])).tolist():
+            h[min(v, 1000) + first] = h.get(min(v, 1000) + first, 0) + 1
+        return h
+    sets = {"fixture": {t: {int(k): int(v) for k, v in fx["a"]["hist"][t]} for t in ("mis", "ins", "del")},
+            "1000 bins": {"mis": long_hist(1), "ins": long_hist(0), "del": long_hist(0)}}
+    eng = E.Engine(0)
+    res = {"metric": "error-length mixtures, kernel ms per type (ns_mixture_fit: 512 + 9216 + 9216 searches)", "steps": a.steps,
+           "reference_model_fitting_wall_s": fx["a"]["model_fitting_wall_s"], "reference_cores": fx["a"]["model_fitting_cores"]}
+    for name, hists in sets.items():
+        characterize.fit_mixtures(eng, hists)                 # warms up
+        ms, e2e = {"mis": [], "ins": [], "del": []}, []
+        for _ in range(a.steps):
+            t0 = time.perf_counter()
+            fit = characterize.fit_mixtures(eng, hists)
+            e2e.append(time.perf_counter() - t0)
+            for t in ms:
+                ms[t].append(fit[t]["ms_kernel"])
+        evals = {}
+        for t in ms:
+            e = "mis" if t == "mis" else "indel"
+            evals[t] = int(characterize.mixture_fit(eng, e, characterize.empirical_cdf(hists[t], e)[0], characterize.fit_starts(e))["nfev"].sum())
+        res[name] = {"bins": {t: len(characterize.empirical_cdf(hists[t], "mis" if t == "mis" else "indel")[0]) for t in ms}, "kernel_ms": ms,
+                     "kernel_ms_all_three(median)": float(sum(np.median(v) for v in ms.values())), "evaluations": evals,
+                     "fit_mixtures_end_to_end_s": e2e, "residual": {t: fit[t]["residual"] for t in ms}, "warning": {t: fit[t]["warning"] for t in ms}}
+    res["value"] = res["fixture"]["kernel_ms_all_three(median)"]
+    print(json.dumps(res))
+    eng.close()
+    sys.exit(0)
 tmp = tempfile.mkdtemp(prefix="nschar_")
 prefix = os.path.join(tmp, "hg002_like")
 synth.write_model(prefix, synth.SynthModelSpec(n_train=200_000, seed=SEED), write_pkl=False)
