@@ -492,6 +492,31 @@ typedef struct ns_mixfit_result {
 int ns_mixture_fit(ns_ctx *ctx, int kind, const double *cdf, uint32_t n_bins, const double *starts, uint32_t n_starts, int mode,
                    ns_mixfit_result *out);
 
+/* ---- training side: the lengths behind the read-length models ---------------------------------------------------------------------------------
+ * replaces the loop of src/head_align_tail_dist.py (head_align_tail, A:134-229) over the primary alignments: per record, from its CIGAR
+ * text, FLAG 0x10, POS and the LN of its reference, what pysam computes for it (ns_len_aln; nanosim_amd/csrc/ns_read_len.h says how, and
+ * what makes a record BAD: all figures 0, counted in n_bad, first_bad the smallest index of one, n_aln without); per read — the records
+ * read_off[r] .. read_off[r + 1] - 1, at least one — the largest read_len, the smallest head and tail (each also against extra_head /
+ * extra_tail of the read when given and not 0xffffffff) and its number of aligned segments; and the aligned segments themselves, in
+ * record order: the sum of ref_len over records that the reference joins as the two ends of a circular reference (NS_LEN_GENOME), or
+ * one per record (NS_LEN_TRANSCRIPTOME).  edge: bit 0 the alignment lies at the start of its reference, bit 1 at its end.
+ * ref_start is POS - 1.  Added without an ABI change. */
+typedef struct ns_len_aln  { uint32_t head, tail, read_len, ref_len, query_aln_len, edge; } ns_len_aln;
+typedef struct ns_len_read { uint32_t read_len, head, tail, n_segments; } ns_len_read;
+typedef struct ns_len_result {
+    ns_len_aln *aln;            /* in: host buffer of n_aln entries (out), or NULL */
+    ns_len_read *reads;         /* in: host buffer of n_reads entries (out) */
+    uint64_t *segments;         /* in: host buffer of n_aln entries; the first n_segments are written */
+    uint64_t n_segments;        /* out */
+    uint64_t n_bad, first_bad;  /* out */
+    double ms_kernel;
+} ns_len_result;
+#define NS_LEN_GENOME 0
+#define NS_LEN_TRANSCRIPTOME 1
+int ns_read_lengths(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off, const uint8_t *reverse, const uint32_t *ref_id,
+                    const uint64_t *ref_start, const uint64_t *ref_total, uint32_t n_refs, const uint64_t *read_off, uint32_t n_reads,
+                    uint32_t n_aln, int mode, const uint32_t *extra_head, const uint32_t *extra_tail, ns_len_result *out);
+
 /* device address of a result buffer (for zero-copy consumers such as torch / RCCL); NULL if absent */
 const void *ns_device_ptr(ns_ctx *ctx, int which);
 

@@ -16,7 +16,7 @@
 //   k_errlog            wave/read     _aligned_error_profile rows                           (S:2006-2008)
 // Metagenome worker calls run k_lengths / k_chain per PASS of the reference's while loop (S:844-1040) with k_meta_* around them; the lists of a
 // pass are launched before the host has walked the species quotas (assign_species), k_meta_tail does positions + acceptance afterwards.
-// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms, ns_sam_pairs_build, ns_mixture_fit: at the end of the host part) has its kernels in ns_train.h.
+// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms, ns_sam_pairs_build, ns_mixture_fit, ns_read_lengths: at the end of the host part) has its kernels in ns_train.h.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdio.h>
@@ -4418,6 +4418,68 @@ int ns_mixture_fit(ns_ctx *ctx, int kind, const double *cdf, uint32_t n_bins, co
     else k_mixfit<MfIndel><<<grid, block, 0, st>>>(d_cdf, d_lnf, n_bins, d_starts, n_starts, mode == NS_MIXFIT_EVALUATE, d_out);
     CALLCHK(s, hipGetLastError());
     return timed_tail(s, {{out->fits, d_out, (size_t)n_starts * sizeof(ns_mixfit_fit)}}, &out->ms_kernel);
+}
+
+// the lengths behind the read-length models (include/nanosim_amd.h: ns_len_result; ns_read_len.h; src/head_align_tail_dist.py:134-229):
+// k_len_scan, k_len_flag, the scan of the flags, k_len_reduce
+int ns_read_lengths(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off, const uint8_t *reverse, const uint32_t *ref_id,
+                    const uint64_t *ref_start, const uint64_t *ref_total, uint32_t n_refs, const uint64_t *read_off, uint32_t n_reads,
+                    uint32_t n_aln, int mode, const uint32_t *extra_head, const uint32_t *extra_tail, ns_len_result *out) {
+    if (!ctx) return NS_EINVAL;
+    if (!out || !read_off || (n_reads && !out->reads) || !extra_head != !extra_tail ||
+        (n_aln && (!out->segments || !cigar_off || !reverse || !ref_id || !ref_start || !ref_total)))
+        return fail(ctx, NS_EINVAL, "ns_read_lengths: null argument");
+    if (mode != NS_LEN_GENOME && mode != NS_LEN_TRANSCRIPTOME) return fail(ctx, NS_EINVAL, "ns_read_lengths: unknown mode");
+    if (n_aln >= (1u << 31)) return fail(ctx, NS_EINVAL, "ns_read_lengths: 2^31 records or more");
+    out->n_segments = out->n_bad = 0; out->first_bad = n_aln; out->ms_kernel = 0;
+    for (uint32_t r = 0; r < n_reads; ++r)
+        if (read_off[r] >= read_off[r + 1]) return fail(ctx, NS_EINVAL, "ns_read_lengths: read_off not ascending (a read has at least one record)");
+    if (read_off[0] != 0 || read_off[n_reads] != n_aln) return fail(ctx, NS_EINVAL, "ns_read_lengths: read_off does not run from 0 to n_aln");
+    if (!n_aln) return NS_OK;
+    if (int rc = check_offsets(ctx, "ns_read_lengths", "CIGAR strings", cigar_off, n_aln, cigar_off[n_aln])) return rc;
+    if (!cigar && cigar_off[n_aln]) return fail(ctx, NS_EINVAL, "ns_read_lengths: null argument");
+    for (uint32_t a = 0; a < n_aln; ++a) {
+        if (ref_id[a] >= n_refs) return fail(ctx, NS_EINVAL, "ns_read_lengths: ref_id of record " + std::to_string(a) + " is not below n_refs");
+        if (ref_start[a] >= (1ull << 62)) return fail(ctx, NS_EINVAL, "ns_read_lengths: ref_start of record " + std::to_string(a) + " is out of range");
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    std::vector<ns_len_read> preset(n_reads);
+    for (uint32_t r = 0; r < n_reads; ++r) preset[r] = ns_len_read{0u, extra_head ? extra_head[r] : NS_LEN_NONE, extra_tail ? extra_tail[r] : NS_LEN_NONE, 0u};
+    unsigned long long small[LENS_WORDS] = {0ull, ~0ull};                 // (what k_len_scan's atomics start from)
+    uint32_t n_seg = 0;
+    const size_t n = (size_t)n_aln + 1;
+    CallScratch s(ctx, "ns_read_lengths");
+    const uint8_t *d_cigar = s.filled(cigar, (size_t)cigar_off[n_aln], 16);           // (16 bytes to spare: the window loads of CsBytes)
+    const uint64_t *d_cigar_off = s.filled(cigar_off, n);
+    const uint8_t *d_reverse = s.filled(reverse, (size_t)n_aln);
+    const uint32_t *d_ref_id = s.filled(ref_id, (size_t)n_aln);
+    const uint64_t *d_ref_start = s.filled(ref_start, (size_t)n_aln), *d_ref_total = s.filled(ref_total, (size_t)n_refs);
+    const uint64_t *d_read_off = s.filled(read_off, (size_t)n_reads + 1);
+    ns_len_read *d_reads = s.filled(preset.data(), (size_t)n_reads);
+    ns_len_aln *d_aln = s.alloc<ns_len_aln>(n_aln);
+    uint32_t *d_rec_read = s.alloc<uint32_t>(n_aln);
+    uint32_t *d_flag = s.zeroed<uint32_t>(n);                             // (entry n_aln stays 0: the scan leaves the total in d_seg[n_aln])
+    uint32_t *d_seg = s.alloc<uint32_t>(n);
+    unsigned long long *d_segments = s.zeroed<unsigned long long>(n_aln);
+    unsigned long long *d_small = s.filled(small, LENS_WORDS);
+    if (int rc = s.upload()) return rc;
+    hipStream_t st = ctx->stream;
+    CALLCHK(s, hipEventRecord(ctx->evt[EV_HIST_BEGIN], st));
+    uint32_t *d_order;
+    if (int rc = order_by_length(s, d_cigar_off, n_aln, &d_order)) return rc;
+    const dim3 grid((n_aln + 255u) / 256u), block(256);
+    k_len_scan<<<grid, block, 0, st>>>(d_cigar, d_cigar_off, d_reverse, d_ref_id, d_ref_start, d_ref_total, n_aln, d_order, d_aln, d_small);
+    CALLCHK(s, hipGetLastError());
+    k_len_flag<<<grid, block, 0, st>>>(d_aln, d_ref_id, d_read_off, n_reads, n_aln, mode, d_rec_read, d_flag);
+    CALLCHK(s, hipGetLastError());
+    if (int rc = scan_sum(ctx, d_flag, d_seg, n)) return rc;
+    k_len_reduce<<<grid, block, 0, st>>>(d_aln, d_rec_read, d_flag, d_seg, n_aln, d_reads, d_segments);
+    CALLCHK(s, hipGetLastError());
+    if (int rc = timed_tail(s, {{small, d_small, sizeof small}, {&n_seg, d_seg + n_aln, sizeof n_seg}, {out->reads, d_reads, (size_t)n_reads * sizeof(ns_len_read)},
+                                {out->aln, d_aln, out->aln ? (size_t)n_aln * sizeof(ns_len_aln) : 0}}, &out->ms_kernel)) return rc;
+    out->n_segments = n_seg; out->n_bad = small[LENS_BAD]; out->first_bad = out->n_bad ? small[LENS_FIRST] : n_aln;
+    CALLCHK(s, hipMemcpy(out->segments, d_segments, (size_t)n_seg * 8, hipMemcpyDeviceToHost));
+    return NS_OK;
 }
 
 const void *ns_device_ptr(ns_ctx *ctx, int which) {

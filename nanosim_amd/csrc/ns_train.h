@@ -1,9 +1,10 @@
 // ns_train.h — training side, the device kernels: the counting loops of the characterisation stage (k_cs_len, k_cs_hist),
 // of the base-quality model (k_qual_mark, k_qual_count) and of the homopolymer-length model (k_hp_count, k_hp_records), and the line pairs
-// of SAM records (k_sam_scan, k_sam_lines), and the fit of the error-length mixtures (k_mixfit).  The walks they run are ns_cs_hist.h,
-// ns_qual_hist.h, ns_hp_hist.h, ns_sam_pairs.h and ns_mixfit.h, which also compile for the host; the host side of the calls
-// (ns_cs_histograms / ns_maf_histograms, ns_qual_histograms, ns_hp_histograms / ns_hp_histograms_sam, ns_sam_pairs_build, ns_mixture_fit)
-// is at the end of nanosim_amd.hip.  Nothing here uses GenArgs or the simulation.
+// of SAM records (k_sam_scan, k_sam_lines), the fit of the error-length mixtures (k_mixfit), and the lengths behind the read-length
+// models (k_len_scan, k_len_flag, k_len_reduce).  The walks they run are ns_cs_hist.h, ns_qual_hist.h, ns_hp_hist.h, ns_sam_pairs.h,
+// ns_mixfit.h and ns_read_len.h, which also compile for the host; the host side of the calls (ns_cs_histograms / ns_maf_histograms,
+// ns_qual_histograms, ns_hp_histograms / ns_hp_histograms_sam, ns_sam_pairs_build, ns_mixture_fit, ns_read_lengths) is at the end of
+// nanosim_amd.hip.  Nothing here uses GenArgs or the simulation.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -13,6 +14,7 @@
 #include "ns_hp_hist.h"
 #include "ns_sam_pairs.h"
 #include "ns_mixfit.h"
+#include "ns_read_len.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // k_cs_hist: the counting loop of the characterisation stage (ns_cs_hist.h; src/besthit_to_histogram.py:316-365), one alignment per
@@ -366,4 +368,54 @@ __global__ void __launch_bounds__(256) k_mixfit(const double *__restrict__ cdf, 
     if (evaluate) mf_evaluate(obj, x0, r);
     else mf_nelder_mead(obj, x0, 200u * Obj::N, 200u * Obj::N, r);
     if ((threadIdx.x & 63u) == 0) out[start] = r;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_len_scan, k_len_flag, k_len_reduce: the lengths behind the read-length models (ns_read_len.h; src/head_align_tail_dist.py:134-229).
+// SCAN, one record per thread, visited by descending CIGAR length as k_cs_hist: the CIGAR through an 8-byte CsBytes window; it writes the
+// record's six figures (all zero for a bad record).  FLAG, one record per thread: the record's read comes from a binary search of
+// read_off; whether it starts a segment depends on the figures of the read's first record and on the reference of the record in front
+// of it, which SCAN has written — hence a kernel of its own.  The exclusive scan of the flags numbers the segments in record order:
+// record a lies in segment seg[a] + flag[a] - 1.  REDUCE, one record per thread: ref_len is added to its segment, read_len / head / tail
+// go to its read by atomic max / min, a flag counts a segment of its read.  Integers only: the order of the atomics does not show.
+// reads[] is preset by the host side: read_len 0, head / tail = the read's extra_head / extra_tail (NS_LEN_NONE without), n_segments 0.
+// small[]: LENS_BAD records that are bad, LENS_FIRST the smallest index of one (preset to ~0).
+// ---------------------------------------------------------------------------------------------------------
+enum { LENS_BAD = 0, LENS_FIRST = 1, LENS_WORDS = 2 };
+__global__ void __launch_bounds__(256) k_len_scan(const uint8_t *__restrict__ cigar, const uint64_t *__restrict__ cigar_off, const uint8_t *__restrict__ reverse,
+                                                  const uint32_t *__restrict__ ref_id, const uint64_t *__restrict__ ref_start,
+                                                  const uint64_t *__restrict__ ref_total, uint32_t n_aln, const uint32_t *__restrict__ order,
+                                                  ns_len_aln *__restrict__ aln, unsigned long long *__restrict__ small) {
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= n_aln) return;
+    const uint64_t a = order ? order[tid] : tid;
+    CsBytes cb(cigar + cigar_off[a]);
+    LenFigures F;
+    const bool ok = len_scan_record(cb, cigar_off[a + 1] - cigar_off[a], reverse[a] != 0, ref_start[a], ref_total[ref_id[a]], F);      // (ref_id < n_refs: the host checks)
+    aln[a] = ns_len_aln{F.head, F.tail, F.read_len, F.ref_len, F.query_aln_len, F.edge};
+    if (!ok) { atomicAdd(&small[LENS_BAD], 1ull); atomicMin(&small[LENS_FIRST], (unsigned long long)a); }
+}
+__global__ void __launch_bounds__(256) k_len_flag(const ns_len_aln *__restrict__ aln, const uint32_t *__restrict__ ref_id, const uint64_t *__restrict__ read_off,
+                                                  uint32_t n_reads, uint32_t n_aln, int mode, uint32_t *__restrict__ rec_read, uint32_t *__restrict__ flag) {
+    const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= n_aln) return;
+    const uint32_t r = qual_locate(read_off, 0u, n_reads, a);            // (read_off ends at n_aln: there is one)
+    const uint64_t first = read_off[r];
+    const bool is_first = first == a;
+    rec_read[a] = r;
+    flag[a] = len_starts_segment(mode, is_first, !is_first && ref_id[a - 1u] == ref_id[a], aln[first].edge, aln[a].edge) ? 1u : 0u;
+}
+__global__ void __launch_bounds__(256) k_len_reduce(const ns_len_aln *__restrict__ aln, const uint32_t *__restrict__ rec_read, const uint32_t *__restrict__ flag,
+                                                    const uint32_t *__restrict__ seg, uint32_t n_aln, ns_len_read *__restrict__ reads,
+                                                    unsigned long long *__restrict__ segments) {
+    const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= n_aln) return;
+    const ns_len_aln A = aln[a];
+    const uint32_t f = flag[a];
+    ns_len_read *R = reads + rec_read[a];
+    atomicAdd(&segments[seg[a] + f - 1u], (unsigned long long)A.ref_len);      // (record 0 has a flag: seg[a] + f >= 1, and <= n_aln)
+    atomicMax(&R->read_len, A.read_len);
+    atomicMin(&R->head, A.head);
+    atomicMin(&R->tail, A.tail);
+    if (f) atomicAdd(&R->n_segments, 1u);
 }
