@@ -517,6 +517,43 @@ int ns_read_lengths(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off
                     const uint64_t *ref_start, const uint64_t *ref_total, uint32_t n_refs, const uint64_t *read_off, uint32_t n_reads,
                     uint32_t n_aln, int mode, const uint32_t *extra_head, const uint32_t *extra_tail, ns_len_result *out);
 
+/* ---- training side: chimeric reads, the split-alignment choice ----------------------------------------------------------------------------------
+ * replaces the decisions of primary_and_unaligned_chimeric (src/get_primary_sam.py, G:273-395) for every primary alignment and the
+ * entries of its SA:Z tag; nanosim_amd/csrc/ns_chimeric.h says how, with every corner of the reference that is kept.
+ * ns_cigar_spans: per CIGAR text what cigar_parser (G:16-31) gives — qstart, qend, qlen = M + I, rlen = M + D.  A BAD CIGAR has all
+ * figures 0, is counted in *n_bad, *first_bad the smallest index of one (n without).  The caller also runs it over the CIGARs of the
+ * file's supplementary and secondary records, which the reference matches to the chosen pieces by these figures (G:397-402).
+ * ns_chimeric_select: the reads r = 0 .. n_reads - 1 have the entries ent_off[r] .. ent_off[r + 1] - 1, at least one: the first is the
+ * primary alignment (its figures are pysam's: qstart = leading S, qlen = M + I + `=` + X, rlen = M + D + N + `=` + X), the others the SA
+ * entries in tag order.  Per entry: its CIGAR, ref_id (< n_refs), ref_start (0-based), nm, reverse (direction is not `+`); per reference
+ * ref_total (LN) and species (< n_species).  Out: ent[n_ent] the figures (optional), reads[n_reads], pieces[n_ent] — the pieces of read
+ * r in query order from pieces[ent_off[r]] on, reads[r].n_pieces of them: the entry's index inside the read, whether the reference takes
+ * it for the primary record (its qstart is the primary's), and the gap in front of it or NS_CHIM_NO_GAP —, species_count[n_species][2]
+ * (the gaps behind a piece of the species: [0] the next piece is of the same species, [1] of another), n_gaps, pos_strand.
+ * With a bad CIGAR (n_bad != 0) everything else is undefined.  Added without an ABI change. */
+typedef struct ns_chim_ent   { uint32_t qstart, qend, qlen, rlen; } ns_chim_ent;
+typedef struct ns_chim_piece { uint32_t entry, is_primary; int64_t gap; } ns_chim_piece;
+typedef struct ns_chim_read  { uint32_t n_pieces, flags; } ns_chim_read;
+#define NS_CHIM_NO_GAP (-1)
+#define NS_CHIM_POS_STRAND 1u      /* ns_chim_read.flags: the read adds to pos_strand */
+#define NS_CHIM_ALONE 2u           /* the winning list was one piece that is not the primary: the primary record is kept alone */
+#define NS_CHIM_HAS_SA 4u          /* the read has SA entries */
+typedef struct ns_chim_result {
+    ns_chim_ent *ent;           /* in: host buffer of n_ent entries (out), or NULL */
+    ns_chim_piece *pieces;      /* in: host buffer of n_ent entries (out) */
+    ns_chim_read *reads;        /* in: host buffer of n_reads entries (out) */
+    uint64_t *species_count;    /* in: host buffer of n_species * 2 entries (out) */
+    uint64_t n_gaps, pos_strand;/* out */
+    uint64_t n_bad, first_bad;  /* out */
+    double ms_kernel;           /* both kernels */
+    double ms_scan;             /* k_chim_scan (with the visiting order) alone */
+} ns_chim_result;
+int ns_cigar_spans(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off, uint32_t n, ns_chim_ent *out, uint64_t *n_bad,
+                   uint64_t *first_bad, double *ms_kernel);
+int ns_chimeric_select(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off, const uint64_t *ent_off, uint32_t n_reads,
+                       const uint32_t *ref_id, const uint64_t *ref_start, const uint32_t *nm, const uint8_t *reverse,
+                       const uint64_t *ref_total, const uint32_t *species, uint32_t n_refs, uint32_t n_species, ns_chim_result *out);
+
 /* device address of a result buffer (for zero-copy consumers such as torch / RCCL); NULL if absent */
 const void *ns_device_ptr(ns_ctx *ctx, int which);
 

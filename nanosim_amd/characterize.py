@@ -74,14 +74,34 @@ The KDEs always go to ``<prefix>_kde.npz`` (what ``model.load_model`` reads firs
 to the reference's pickles.  Deviations: a record whose CIGAR is not one, or that covers no reference base, raises ValueError (the
 reference silently drops the read that such a record ends, A:172); the seven debugging ``.txt`` files of A:81-87 are not written.
 
-Not covered: BAM input (pysam is not a dependency here: convert with ``samtools view -h``); chimeric training (``_gap_length.pkl``,
-``_chimeric_info``: primary_and_unaligned_chimeric, G:220-478) and quantification (the EM of G:44-142).
+Chimeric training (``primary_and_unaligned_chimeric`` of src/get_primary_sam.py, G:220-478) is the seventh piece: what ``--chimeric``
+and metagenome mode need next to the files above — ``<prefix>_chimeric_info`` and the ``gap_length`` KDE — and the choice of the records
+every later training step reads (``<prefix>_primary.bam`` there, ``<prefix>_primary.sam`` here).  For every primary alignment with an
+``SA:Z`` tag the reference parses the CIGAR of every entry, sorts the entries into lists of compatible pieces, keeps the best list and
+records the gaps between its pieces; here the CIGAR walks and the choice run on the GPU (``ns_cigar_spans``, ``ns_chimeric_select``;
+csrc/ns_chimeric.h names every corner of the reference that is kept), and this module matches the chosen pieces to SAM records and
+writes the files:
+
+    refs, recs, unaligned_len, strandness = characterize.chimeric("training", "training.sam", eng)
+    characterize.read_lengths("training", refs, recs, eng, unaligned_len, strandness, merge=True)
+
+``read_lengths`` writes ``<prefix>_kde.npz`` anew and ``chimeric`` merges into it: ``read_lengths(..., merge=True)`` keeps ``gap_length``.
+Deviations: SAM text instead of BAM; a primary record without ``NM``, an SA entry without six fields, a reference name without an
+``@SQ`` line, a supplementary or secondary record in front of the first primary, a chosen piece that no record matches (the reference
+hands ``None`` to pysam) and a file without a primary record raise ValueError where the reference stops with another exception; the
+abundances behind the shrinkage rate come from the caller.
+
+Not covered: BAM input (pysam is not a dependency here: convert with ``samtools view -h``) and quantification (the EM of G:44-142,
+``_quantification.tsv``, ``q_mode``).
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
+import os
 import re
+import statistics
 
 import numpy as np
 
@@ -1125,10 +1145,14 @@ def kde_models(figures: dict, unaligned_len=None) -> dict:
     return m
 
 
-def write_kde(prefix: str, models: dict, pickles=None) -> None:
+def write_kde(prefix: str, models: dict, pickles=None, merge: bool = False) -> None:
     """<prefix>_kde.npz with the keys <name>_data / <name>_bw that model.load_model reads; and <prefix>_<name>.pkl like the reference
-    (KernelDensity(bandwidth).fit, joblib.dump) — pickles=None: when scikit-learn and joblib import, True: they have to, False: never"""
+    (KernelDensity(bandwidth).fit, joblib.dump) — pickles=None: when scikit-learn and joblib import, True: they have to, False: never.
+    merge: the keys an existing <prefix>_kde.npz holds for other names are kept (without it the file holds `models` alone)"""
     arrays = {}
+    if merge and os.path.exists(prefix + "_kde.npz"):
+        with np.load(prefix + "_kde.npz") as old:
+            arrays.update((k, old[k]) for k in old.files)
     for name, (data, bw) in models.items():
         arrays[name + "_data"] = np.asarray(data, dtype=np.float64)
         arrays[name + "_bw"] = np.float64(bw)
@@ -1159,15 +1183,271 @@ def format_alignment_rate(num_aligned: int, num_unaligned: int) -> str:
     return "Aligned / Unaligned ratio:\t100%\n"
 
 
-def read_lengths(prefix: str, refs, records, eng, unaligned_len, strandness: float, mode: str = "genome", genome_records=None, pickles=None) -> dict:
+def read_lengths(prefix: str, refs, records, eng, unaligned_len, strandness: float, mode: str = "genome", genome_records=None, pickles=None,
+                 merge: bool = False) -> dict:
     """writes the KDE files (write_kde), <prefix>_strandness_rate and <prefix>_reads_alignment_rate like head_align_tail (A:239-281) and
     read_analysis.py (R:833-851) — num_aligned is the number of READS of the length figures, as at R:830 — and returns the figures.
     The seven debugging files of A:81-87 (<prefix>_total.txt, _middle.txt, _head.txt, _middle_ref.txt, _ht.txt, _ratio.txt, _tail.txt)
     are not written."""
     figures = count_read_lengths(eng, refs, records, mode, genome_records)
-    write_kde(prefix, kde_models(figures, unaligned_len), pickles)
+    write_kde(prefix, kde_models(figures, unaligned_len), pickles, merge)        # (merge: the keys of other models, gap_length of chimeric(), stay)
     with open(prefix + "_strandness_rate", "w") as f:
         f.write(format_strandness(strandness))
     with open(prefix + "_reads_alignment_rate", "w") as f:
         f.write(format_alignment_rate(len(figures["total_length"]), 0 if unaligned_len is None else len(unaligned_len)))
     return figures
+
+
+# ---- chimeric reads: the split-alignment choice (src/get_primary_sam.py:220-478) --------------------------------------------------------------
+class NsChimResult(C.Structure):
+    """mirror of ns_chim_result (include/nanosim_amd.h)"""
+    _fields_ = [("ent", C.c_void_p), ("pieces", C.c_void_p), ("reads", C.c_void_p), ("species_count", C.c_void_p), ("n_gaps", C.c_uint64),
+                ("pos_strand", C.c_uint64), ("n_bad", C.c_uint64), ("first_bad", C.c_uint64), ("ms_kernel", C.c_double), ("ms_scan", C.c_double)]
+
+
+CHIM_ENT_DTYPE = np.dtype([("qstart", "<u4"), ("qend", "<u4"), ("qlen", "<u4"), ("rlen", "<u4")])          # ns_chim_ent
+CHIM_PIECE_DTYPE = np.dtype([("entry", "<u4"), ("is_primary", "<u4"), ("gap", "<i8")])                     # ns_chim_piece
+CHIM_READ_DTYPE = np.dtype([("n_pieces", "<u4"), ("flags", "<u4")])                                        # ns_chim_read
+CHIM_NO_GAP = -1                                            # NS_CHIM_NO_GAP
+CHIM_POS_STRAND, CHIM_ALONE, CHIM_HAS_SA = 1, 2, 4          # NS_CHIM_*: ns_chim_read.flags
+
+# a record of chimeric_records; [:5] is a record of length_records.  nm: int or None; sa: the SA:Z text or None; seq_len: len(SEQ), 0 for `*`
+ChimRecord = collections.namedtuple("ChimRecord", "qname flag rname pos cigar nm sa seq_len line")
+
+
+def species_of_reference(name: str) -> str:
+    """the species of a metagenome reference `<species>_<chromosome>` (G:260)"""
+    return "_".join(name.split("_")[:-1])
+
+
+def sa_entries(sa: str, qname: str = "?"):
+    """[(rname, ref_start 0-based, reverse, cigar, nm)] of an SA:Z text as the reference takes it apart (G:290, 297-300): split at `;`,
+    the LAST part dropped (the empty one behind the closing `;` — an entry without it is lost, as there), six fields each"""
+    out = []
+    for part in sa.split(";")[:-1]:
+        fld = part.split(",")
+        if len(fld) != 6:
+            raise ValueError("read %s: an SA entry does not have six comma-separated fields: %.60s" % (qname, part))
+        try:
+            pos, nm = int(fld[1]), int(fld[5])
+        except ValueError:
+            raise ValueError("read %s: position or NM of an SA entry is no number: %.60s" % (qname, part)) from None
+        if pos < 1 or nm < 0:
+            raise ValueError("read %s: position or NM of an SA entry is out of range: %.60s" % (qname, part))
+        out.append((fld[0], pos - 1, fld[2] != "+", fld[3], nm))
+    return out
+
+
+def chimeric_records(path: str):
+    """(refs, records, unaligned_len, header) of a whole SAM text file, one pass: refs = [(SN, LN)] of the @SQ lines, records = a
+    ChimRecord for every record that is not unmapped, in file order, unaligned_len = int64 array of len(SEQ) of the 0x4 records (0 for
+    `*`), header = the `@` lines as they stand.  ValueError where the reference stops or misbehaves: a primary record without NM:i (its
+    get_tag raises outside the try, G:279), an SA entry without six fields (G:298), a reference name — of a record or of an SA entry —
+    without an @SQ line, a supplementary or secondary record in front of the first primary (a NameError at G:400), no primary at all."""
+    refs, records, unaligned, header = [], [], [], []
+    seen_primary = False
+    with open(path) as f:
+        for line in f:
+            if line.startswith("@"):
+                header.append(line)
+                fld = line.rstrip("\n").split("\t")
+                if fld[0] == "@SQ":
+                    _sam_refs(fld, refs)
+                continue
+            fld = line.rstrip("\n").split("\t")
+            if len(fld) < 11:
+                continue
+            flag = int(fld[1])
+            seq_len = 0 if fld[9] == "*" else len(fld[9])
+            if flag & 0x4:
+                unaligned.append(seq_len)
+                continue
+            nm = sa = None
+            for t in fld[11:]:
+                if t.startswith("NM:i:"):
+                    nm = int(t[5:])
+                elif t.startswith("SA:Z:"):
+                    sa = t[5:]
+            if not flag & (0x100 | 0x800):
+                seen_primary = True
+                if nm is None:
+                    raise ValueError("primary alignment of read %s has no NM:i tag" % fld[0])
+                if nm < 0:
+                    raise ValueError("primary alignment of read %s has a negative NM" % fld[0])
+            elif not seen_primary:
+                raise ValueError("record of read %s (FLAG %d) stands in front of the first primary alignment" % (fld[0], flag))
+            records.append(ChimRecord(fld[0], flag, fld[2], int(fld[3]), fld[5], nm, sa, seq_len, line))
+    if not seen_primary:
+        raise ValueError("%s holds no primary alignment" % path)
+    known = set(n for n, _ in refs)
+    for r in records:
+        if r.rname not in known:
+            raise ValueError("alignment %s lies on %s, which has no @SQ line" % (r.qname, r.rname))
+        if r.sa is not None and not r.flag & (0x100 | 0x800):
+            for e in sa_entries(r.sa, r.qname):
+                if e[0] not in known:
+                    raise ValueError("an SA entry of read %s lies on %s, which has no @SQ line" % (r.qname, e[0]))
+    return refs, records, np.array(unaligned, dtype=np.int64), header
+
+
+def cigar_spans(eng, cigars):
+    """ns_cigar_spans: (cigar_parser's figures per CIGAR (CHIM_ENT_DTYPE), n_bad, first_bad, ms_kernel)"""
+    n = len(cigars)
+    cg, cg_off = _pack(cigars)
+    out = np.zeros(n, dtype=CHIM_ENT_DTYPE)
+    n_bad, first_bad, ms = C.c_uint64(0), C.c_uint64(0), C.c_double(0)
+    eng._check(eng.L.ns_cigar_spans(eng.ctx, cg.ctypes.data, cg_off.ctypes.data, n, out.ctypes.data if n else None, C.addressof(n_bad),
+                                    C.addressof(first_bad), C.addressof(ms)))
+    return out, int(n_bad.value), int(first_bad.value), float(ms.value)
+
+
+def chimeric_call(eng, reads, ref_total, species, n_species: int):
+    """ns_chimeric_select on reads = [[(cigar, ref_id, ref_start, nm, reverse), ...]] (entry 0 of each the primary):
+    (the NsChimResult, ent, pieces, per read, species_count[n_species][2], ent_off); nothing is raised for bad CIGARs"""
+    ent_off = np.zeros(len(reads) + 1, dtype=np.uint64)
+    np.cumsum([len(r) for r in reads], out=ent_off[1:])
+    flat = [e for r in reads for e in r]
+    n = len(flat)
+    cg, cg_off = _pack([e[0] for e in flat])
+    ref_id = np.array([e[1] for e in flat], dtype=np.uint32)
+    ref_start = np.array([e[2] for e in flat], dtype=np.uint64)
+    nm = np.array([e[3] for e in flat], dtype=np.uint32)
+    reverse = np.array([1 if e[4] else 0 for e in flat], dtype=np.uint8)
+    ref_total = np.ascontiguousarray(ref_total, dtype=np.uint64)
+    species = np.ascontiguousarray(species, dtype=np.uint32)
+    ent, pieces = np.zeros(n, dtype=CHIM_ENT_DTYPE), np.zeros(n, dtype=CHIM_PIECE_DTYPE)
+    per_read = np.zeros(len(reads), dtype=CHIM_READ_DTYPE)
+    count = np.zeros((n_species, 2), dtype=np.uint64)
+    out = NsChimResult()
+    out.ent, out.pieces, out.reads, out.species_count = ent.ctypes.data, pieces.ctypes.data, per_read.ctypes.data, count.ctypes.data
+    eng._check(eng.L.ns_chimeric_select(eng.ctx, cg.ctypes.data, cg_off.ctypes.data, ent_off.ctypes.data, len(reads), ref_id.ctypes.data,
+                                        ref_start.ctypes.data, nm.ctypes.data, reverse.ctypes.data, ref_total.ctypes.data, species.ctypes.data,
+                                        len(ref_total), n_species, C.byref(out)))
+    return out, ent, pieces, per_read, count, ent_off
+
+
+def select_chimeric(eng, refs, records, species=None) -> dict:
+    """What primary_and_unaligned_chimeric decides (G:267-410) for the records of chimeric_records, from the GPU (ns_chimeric_select over
+    the primary alignments and their SA entries, ns_cigar_spans over the supplementary and secondary records).
+    species: None — every reference is of one species, which is what the reference's genome mode does in effect (`species` keeps the value
+    the header loop left, G:260, so only the "same" column moves); or {reference name: species}, e.g. built with species_of_reference.
+    "selected": indices into `records` in the reference's written order — reads in primary order, the pieces of a chimeric read in query
+    order (a piece the reference takes for the primary — its qstart is the primary's — is the primary record); "gap_length": int64, in
+    read order, then piece order; "num_aligned"; "pos_strand"; "strandness"; "species_count": {species: [same, other]} (the key None
+    without a mapping); "n_pieces" per read; "flags" per read (CHIM_*); "ent", "ent_off"; "ms_kernel", "ms_scan", "ms_spans".
+    A non-primary piece is matched as the reference does (G:397-402): among the supplementary and secondary records between this primary
+    and the next one, whatever their QNAME, the LAST one with equal (RNAME, cigar_parser qstart, qend, POS - 1).  A piece without a
+    record raises ValueError naming the read; so does a CIGAR that is not one."""
+    ref_index = {}
+    for i, (name, _) in enumerate(refs):
+        ref_index.setdefault(name, i)
+    if species is None:
+        names, sp_of = [None], [0] * len(refs)
+    else:
+        names = list(dict.fromkeys(species[name] for name, _ in refs))
+        sp_index = {s: i for i, s in enumerate(names)}
+        sp_of = [sp_index[species[name]] for name, _ in refs]
+    primaries = [i for i, r in enumerate(records) if not r.flag & (0x4 | 0x100 | 0x800)]
+    if not primaries:
+        raise ValueError("no primary alignment")
+    others = [i for i, r in enumerate(records) if r.flag & (0x100 | 0x800) and not r.flag & 0x4]
+    reads, tags = [], []
+    for i in primaries:
+        r = records[i]
+        if r.nm is None:
+            raise ValueError("primary alignment of read %s has no NM:i tag" % r.qname)
+        sa = sa_entries(r.sa, r.qname) if r.sa is not None else []
+        for e in [(r.rname,)] + sa:
+            if e[0] not in ref_index:
+                raise ValueError("an alignment of read %s lies on %s, which has no @SQ line" % (r.qname, e[0]))
+        if r.pos < 1:
+            raise ValueError("alignment %s has POS %d" % (r.qname, r.pos))
+        reads.append([(r.cigar, ref_index[r.rname], r.pos - 1, r.nm, bool(r.flag & 0x10))] + [(e[3], ref_index[e[0]], e[1], e[4], e[2]) for e in sa])
+        tags.append(sa)
+    out, ent, pieces, per_read, count, ent_off = chimeric_call(eng, reads, [ln for _, ln in refs], sp_of, len(names))
+    if out.n_bad:
+        bad = int(out.first_bad)
+        r = int(np.searchsorted(ent_off, bad, side="right")) - 1
+        raise ValueError("%d CIGAR(s) that are not one among the primary alignments and their SA entries; the first is entry %d of read %s: %.60s"
+                         % (out.n_bad, bad - int(ent_off[r]), records[primaries[r]].qname, reads[r][bad - int(ent_off[r])][0]))
+    spans, n_bad, first_bad, ms_spans = cigar_spans(eng, [records[i].cigar for i in others])
+    if n_bad:
+        r = records[others[first_bad]]
+        raise ValueError("%d supplementary / secondary record(s) whose CIGAR is not one; the first is a record of read %s: %.60s" % (n_bad, r.qname, r.cigar))
+    selected, gaps = [], []
+    at = 0                                                   # the next of `others` behind the current primary
+    for k, i in enumerate(primaries):
+        nxt = primaries[k + 1] if k + 1 < len(primaries) else len(records)
+        while at < len(others) and others[at] < i:
+            at += 1
+        e0, n = int(ent_off[k]), int(per_read["n_pieces"][k])
+        own = pieces[e0:e0 + n]
+        if not (own["is_primary"] == 1).all():
+            found = {}
+            j = at
+            while j < len(others) and others[j] < nxt:       # first to last: the last record with a key keeps it
+                o = records[others[j]]
+                found[(o.rname, int(spans["qstart"][j]), int(spans["qend"][j]), o.pos - 1)] = others[j]
+                j += 1
+        for p in own:
+            if p["gap"] != CHIM_NO_GAP:
+                gaps.append(int(p["gap"]))
+            if p["is_primary"]:
+                selected.append(i)
+                continue
+            e = int(p["entry"])
+            tag = tags[k][e - 1]
+            key = (tag[0], int(ent["qstart"][e0 + e]), int(ent["qend"][e0 + e]), tag[1])
+            if key not in found:
+                raise ValueError("read %s: no supplementary or secondary record matches the chosen SA entry %s,%d,%s (query %d-%d)"
+                                 % (records[i].qname, tag[0], tag[1] + 1, "-" if tag[2] else "+", key[1], key[2]))
+            selected.append(found[key])
+    assert len(gaps) == out.n_gaps
+    return dict(selected=selected, gap_length=np.array(gaps, dtype=np.int64), num_aligned=len(primaries), pos_strand=int(out.pos_strand),
+                strandness=float(out.pos_strand) / len(primaries), species_count={s: [int(count[i, 0]), int(count[i, 1])] for i, s in enumerate(names)},
+                n_pieces=per_read["n_pieces"].astype(np.int64), flags=per_read["flags"].copy(), ent=ent, ent_off=ent_off,
+                ms_kernel=float(out.ms_kernel), ms_scan=float(out.ms_scan), ms_spans=ms_spans)
+
+
+def chimeric_beta(species_count: dict, abundance: dict) -> float:
+    """the shrinkage rate (G:449-455, 475): the median over the species with a recorded gap of other / (same + other) * 100 /
+    (100 - abundance), abundance in percent (the reference's come from its EM, G:428: the caller's here)"""
+    betas = []
+    for sp, counts in species_count.items():
+        other_prob = 100 - abundance[sp]
+        if counts[0] + counts[1] == 0:
+            continue
+        betas.append(counts[1] / (counts[0] + counts[1]) * 100 / other_prob)
+    if not betas:
+        raise ValueError("no gap between pieces was recorded: there is no shrinkage rate")
+    return statistics.median(betas)
+
+
+def format_chimeric_info(n_gaps: int, num_aligned: int, beta=None) -> str:
+    """the text of <prefix>_chimeric_info (G:472-475); the second line, written in metagenome mode, has no newline"""
+    text = "Mean segments for each aligned read:\t" + str((n_gaps + num_aligned) / num_aligned) + "\n"
+    if beta is not None:
+        text += "Shrinkage rate (beta):\t" + str(beta)
+    return text
+
+
+def chimeric(prefix: str, path: str, eng, species=None, abundance=None, primary_sam: bool = True, pickles=None):
+    """primary_and_unaligned_chimeric (G:220-478) without its quantification: writes <prefix>_chimeric_info, adds gap_length —
+    log10(gap + 1), bandwidth 0.01 (G:465-469) — to <prefix>_kde.npz next to the keys it holds (and writes <prefix>_gap_length.pkl by
+    write_kde's rule), and, with primary_sam, <prefix>_primary.sam: the header and the selected lines, unchanged, in the reference's
+    order — what its later steps read from <prefix>_primary.bam, for cs_from_sam, quals_from_sam, sam_records and length_records.
+    abundance ({species: percent}, with a species mapping): the second line of _chimeric_info (chimeric_beta).
+    -> (refs, records, unaligned_len, strandness): read_lengths' arguments, the records being the selected ones."""
+    if abundance is not None and species is None:
+        raise ValueError("abundance needs the species mapping")
+    refs, records, unaligned_len, header = chimeric_records(path)
+    sel = select_chimeric(eng, refs, records, species)
+    beta = chimeric_beta(sel["species_count"], abundance) if abundance is not None else None
+    with open(prefix + "_chimeric_info", "w") as f:
+        f.write(format_chimeric_info(len(sel["gap_length"]), sel["num_aligned"], beta))
+    write_kde(prefix, {"gap_length": (np.log10(sel["gap_length"] + 1).astype(np.float64), 0.01)}, pickles, merge=True)
+    if primary_sam:
+        with open(prefix + "_primary.sam", "w") as f:
+            f.writelines(header)
+            f.writelines(records[i].line for i in sel["selected"])
+    return refs, [tuple(records[i][:5]) for i in sel["selected"]], unaligned_len, sel["strandness"]

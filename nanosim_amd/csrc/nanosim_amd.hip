@@ -16,7 +16,7 @@
 //   k_errlog            wave/read     _aligned_error_profile rows                           (S:2006-2008)
 // Metagenome worker calls run k_lengths / k_chain per PASS of the reference's while loop (S:844-1040) with k_meta_* around them; the lists of a
 // pass are launched before the host has walked the species quotas (assign_species), k_meta_tail does positions + acceptance afterwards.
-// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms, ns_sam_pairs_build, ns_mixture_fit, ns_read_lengths: at the end of the host part) has its kernels in ns_train.h.
+// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms, ns_sam_pairs_build, ns_mixture_fit, ns_read_lengths, ns_cigar_spans, ns_chimeric_select: at the end of the host part) has its kernels in ns_train.h.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdio.h>
@@ -4479,6 +4479,111 @@ int ns_read_lengths(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off
                                 {out->aln, d_aln, out->aln ? (size_t)n_aln * sizeof(ns_len_aln) : 0}}, &out->ms_kernel)) return rc;
     out->n_segments = n_seg; out->n_bad = small[LENS_BAD]; out->first_bad = out->n_bad ? small[LENS_FIRST] : n_aln;
     CALLCHK(s, hipMemcpy(out->segments, d_segments, (size_t)n_seg * 8, hipMemcpyDeviceToHost));
+    return NS_OK;
+}
+
+// the split-alignment choice of chimeric reads (include/nanosim_amd.h: ns_chim_result; ns_chimeric.h; src/get_primary_sam.py:16-31,
+// 273-395).  ns_cigar_spans: k_chim_scan alone
+int ns_cigar_spans(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off, uint32_t n, ns_chim_ent *out, uint64_t *n_bad,
+                   uint64_t *first_bad, double *ms_kernel) {
+    if (!ctx) return NS_EINVAL;
+    if (!n_bad || !first_bad || !ms_kernel || (n && (!cigar_off || !out))) return fail(ctx, NS_EINVAL, "ns_cigar_spans: null argument");
+    if (n >= (1u << 31)) return fail(ctx, NS_EINVAL, "ns_cigar_spans: 2^31 CIGARs or more");
+    *n_bad = 0; *first_bad = n; *ms_kernel = 0;
+    if (!n) return NS_OK;
+    if (int rc = check_offsets(ctx, "ns_cigar_spans", "CIGAR strings", cigar_off, n, cigar_off[n])) return rc;
+    if (!cigar && cigar_off[n]) return fail(ctx, NS_EINVAL, "ns_cigar_spans: null argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    unsigned long long small[CHIMS_WORDS] = {0ull, ~0ull, 0ull, 0ull};
+    CallScratch s(ctx, "ns_cigar_spans");
+    const uint8_t *d_cigar = s.filled(cigar, (size_t)cigar_off[n], 16);               // (16 bytes to spare: the window loads of CsBytes)
+    const uint64_t *d_off = s.filled(cigar_off, (size_t)n + 1);
+    ns_chim_ent *d_ent = s.alloc<ns_chim_ent>(n);
+    unsigned long long *d_small = s.filled(small, CHIMS_WORDS);
+    if (int rc = s.upload()) return rc;
+    hipStream_t st = ctx->stream;
+    CALLCHK(s, hipEventRecord(ctx->evt[EV_HIST_BEGIN], st));
+    uint32_t *d_order;
+    if (int rc = order_by_length(s, d_off, n, &d_order)) return rc;
+    k_chim_scan<<<dim3((n + 255u) / 256u), dim3(256), 0, st>>>(d_cigar, d_off, n, d_order, nullptr, d_ent, d_small);
+    CALLCHK(s, hipGetLastError());
+    if (int rc = timed_tail(s, {{small, d_small, sizeof small}, {out, d_ent, (size_t)n * sizeof(ns_chim_ent)}}, ms_kernel)) return rc;
+    *n_bad = small[CHIMS_BAD]; *first_bad = small[CHIMS_BAD] ? small[CHIMS_FIRST] : n;
+    return NS_OK;
+}
+
+// k_chim_scan over every entry (the primary of each read in pysam's reading), then k_chim_select: one read per thread
+int ns_chimeric_select(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off, const uint64_t *ent_off, uint32_t n_reads,
+                       const uint32_t *ref_id, const uint64_t *ref_start, const uint32_t *nm, const uint8_t *reverse,
+                       const uint64_t *ref_total, const uint32_t *species, uint32_t n_refs, uint32_t n_species, ns_chim_result *out) {
+    if (!ctx) return NS_EINVAL;
+    if (!out || !ent_off || (n_species && !out->species_count)) return fail(ctx, NS_EINVAL, "ns_chimeric_select: null argument");
+    out->n_gaps = out->pos_strand = out->n_bad = 0; out->first_bad = 0; out->ms_kernel = out->ms_scan = 0;
+    if (n_reads >= (1u << 31)) return fail(ctx, NS_EINVAL, "ns_chimeric_select: 2^31 reads or more");
+    if (ent_off[0] != 0) return fail(ctx, NS_EINVAL, "ns_chimeric_select: ent_off does not begin at 0");
+    for (uint32_t r = 0; r < n_reads; ++r) {
+        if (ent_off[r] > ent_off[r + 1]) return fail(ctx, NS_EINVAL, "ns_chimeric_select: ent_off decreases at read " + std::to_string(r));
+        if (ent_off[r] == ent_off[r + 1]) return fail(ctx, NS_EINVAL, "ns_chimeric_select: read " + std::to_string(r) + " has no entry (the first is its primary alignment)");
+    }
+    const uint64_t n_ent64 = ent_off[n_reads];
+    if (n_ent64 >= (1ull << 31)) return fail(ctx, NS_EINVAL, "ns_chimeric_select: 2^31 entries or more");
+    const uint32_t n_ent = (uint32_t)n_ent64;
+    out->first_bad = n_ent;
+    for (uint32_t i = 0; i < 2u * n_species; ++i) out->species_count[i] = 0;
+    if (n_refs && (!ref_total || !species)) return fail(ctx, NS_EINVAL, "ns_chimeric_select: null argument");
+    for (uint32_t i = 0; i < n_refs; ++i)
+        if (species[i] >= n_species) return fail(ctx, NS_EINVAL, "ns_chimeric_select: species of reference " + std::to_string(i) + " is not below n_species");
+    if (!n_reads) return NS_OK;
+    if (!out->reads || !out->pieces || !cigar_off || !ref_id || !ref_start || !nm || !reverse) return fail(ctx, NS_EINVAL, "ns_chimeric_select: null argument");
+    if (int rc = check_offsets(ctx, "ns_chimeric_select", "CIGAR strings", cigar_off, n_ent, cigar_off[n_ent])) return rc;
+    if (!cigar && cigar_off[n_ent]) return fail(ctx, NS_EINVAL, "ns_chimeric_select: null argument");
+    for (uint32_t a = 0; a < n_ent; ++a) {
+        if (ref_id[a] >= n_refs) return fail(ctx, NS_EINVAL, "ns_chimeric_select: ref_id of entry " + std::to_string(a) + " is not below n_refs");
+        if (ref_start[a] >= (1ull << 62)) return fail(ctx, NS_EINVAL, "ns_chimeric_select: ref_start of entry " + std::to_string(a) + " is out of range");
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    // the workspace of read r: (entries) * ceil(entries / 64) words from ws_off[r] on; which CIGARs are read as pysam reads them
+    std::vector<uint64_t> ws_off((size_t)n_reads + 1);
+    std::vector<uint8_t> pysam(n_ent, 0);
+    ws_off[0] = 0;
+    for (uint32_t r = 0; r < n_reads; ++r) {
+        ws_off[r + 1] = ws_off[r] + chim_ws_words(ent_off[r + 1] - ent_off[r]);
+        pysam[ent_off[r]] = 1;
+    }
+    unsigned long long small[CHIMS_WORDS] = {0ull, ~0ull, 0ull, 0ull};
+    CallScratch s(ctx, "ns_chimeric_select");
+    const uint8_t *d_cigar = s.filled(cigar, (size_t)cigar_off[n_ent], 16);           // (16 bytes to spare: the window loads of CsBytes)
+    const uint64_t *d_cigar_off = s.filled(cigar_off, (size_t)n_ent + 1);
+    const uint64_t *d_ent_off = s.filled(ent_off, (size_t)n_reads + 1), *d_ws_off = s.filled(ws_off.data(), (size_t)n_reads + 1);
+    const uint8_t *d_pysam = s.filled(pysam.data(), (size_t)n_ent), *d_reverse = s.filled(reverse, (size_t)n_ent);
+    const uint32_t *d_ref_id = s.filled(ref_id, (size_t)n_ent), *d_nm = s.filled(nm, (size_t)n_ent), *d_species = s.filled(species, (size_t)n_refs);
+    const uint64_t *d_ref_start = s.filled(ref_start, (size_t)n_ent), *d_ref_total = s.filled(ref_total, (size_t)n_refs);
+    ns_chim_ent *d_ent = s.alloc<ns_chim_ent>(n_ent);
+    ns_chim_piece *d_pieces = s.zeroed<ns_chim_piece>(n_ent);
+    ns_chim_read *d_reads = s.alloc<ns_chim_read>(n_reads);
+    uint64_t *d_ws = s.alloc<uint64_t>((size_t)ws_off[n_reads]);                      // (k_chim_select zeroes what it opens)
+    unsigned long long *d_species_count = s.zeroed<unsigned long long>((size_t)2 * n_species);
+    unsigned long long *d_small = s.filled(small, CHIMS_WORDS);
+    if (int rc = s.upload()) return rc;
+    hipStream_t st = ctx->stream;
+    CALLCHK(s, hipEventRecord(ctx->evt[EV_HIST_BEGIN], st));
+    uint32_t *d_order, *d_read_order;
+    if (int rc = order_by_length(s, d_cigar_off, n_ent, &d_order)) return rc;
+    k_chim_scan<<<dim3((n_ent + 255u) / 256u), dim3(256), 0, st>>>(d_cigar, d_cigar_off, n_ent, d_order, d_pysam, d_ent, d_small);
+    CALLCHK(s, hipGetLastError());
+    CALLCHK(s, hipEventRecord(ctx->evt[EV_SAM_END], st));
+    if (int rc = order_by_length(s, d_ent_off, n_reads, &d_read_order)) return rc;
+    k_chim_select<<<dim3((n_reads + 255u) / 256u), dim3(256), 0, st>>>(d_ent, d_ent_off, n_reads, d_read_order, d_ref_id, d_ref_start, d_nm, d_reverse,
+                                                                       d_ref_total, d_species, d_ws, d_ws_off, d_pieces, d_reads, d_species_count, d_small);
+    CALLCHK(s, hipGetLastError());
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "species_count is read back as it is");
+    if (int rc = timed_tail(s, {{small, d_small, sizeof small}, {out->reads, d_reads, (size_t)n_reads * sizeof(ns_chim_read)},
+                                {out->pieces, d_pieces, (size_t)n_ent * sizeof(ns_chim_piece)},
+                                {out->species_count, d_species_count, (size_t)2 * n_species * 8},
+                                {out->ent, d_ent, out->ent ? (size_t)n_ent * sizeof(ns_chim_ent) : 0}}, &out->ms_kernel)) return rc;
+    { float f = 0; CALLCHK(s, hipEventElapsedTime(&f, ctx->evt[EV_HIST_BEGIN], ctx->evt[EV_SAM_END])); out->ms_scan = f; }
+    out->n_gaps = small[CHIMS_GAPS]; out->pos_strand = small[CHIMS_POS];
+    out->n_bad = small[CHIMS_BAD]; out->first_bad = out->n_bad ? small[CHIMS_FIRST] : n_ent;
     return NS_OK;
 }
 

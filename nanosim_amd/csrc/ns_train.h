@@ -1,9 +1,10 @@
 // ns_train.h — training side, the device kernels: the counting loops of the characterisation stage (k_cs_len, k_cs_hist),
 // of the base-quality model (k_qual_mark, k_qual_count) and of the homopolymer-length model (k_hp_count, k_hp_records), and the line pairs
 // of SAM records (k_sam_scan, k_sam_lines), the fit of the error-length mixtures (k_mixfit), and the lengths behind the read-length
-// models (k_len_scan, k_len_flag, k_len_reduce).  The walks they run are ns_cs_hist.h, ns_qual_hist.h, ns_hp_hist.h, ns_sam_pairs.h,
-// ns_mixfit.h and ns_read_len.h, which also compile for the host; the host side of the calls (ns_cs_histograms / ns_maf_histograms,
-// ns_qual_histograms, ns_hp_histograms / ns_hp_histograms_sam, ns_sam_pairs_build, ns_mixture_fit, ns_read_lengths) is at the end of
+// models (k_len_scan, k_len_flag, k_len_reduce), and the split-alignment choice of chimeric reads (k_chim_scan, k_chim_select).  The walks
+// they run are ns_cs_hist.h, ns_qual_hist.h, ns_hp_hist.h, ns_sam_pairs.h, ns_mixfit.h, ns_read_len.h and ns_chimeric.h, which also compile
+// for the host; the host side of the calls (ns_cs_histograms / ns_maf_histograms, ns_qual_histograms, ns_hp_histograms /
+// ns_hp_histograms_sam, ns_sam_pairs_build, ns_mixture_fit, ns_read_lengths, ns_cigar_spans / ns_chimeric_select) is at the end of
 // nanosim_amd.hip.  Nothing here uses GenArgs or the simulation.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,6 +16,7 @@
 #include "ns_sam_pairs.h"
 #include "ns_mixfit.h"
 #include "ns_read_len.h"
+#include "ns_chimeric.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // k_cs_hist: the counting loop of the characterisation stage (ns_cs_hist.h; src/besthit_to_histogram.py:316-365), one alignment per
@@ -418,4 +420,59 @@ __global__ void __launch_bounds__(256) k_len_reduce(const ns_len_aln *__restrict
     atomicMin(&R->head, A.head);
     atomicMin(&R->tail, A.tail);
     if (f) atomicAdd(&R->n_segments, 1u);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_chim_scan, k_chim_select: the split-alignment choice of chimeric reads (ns_chimeric.h; src/get_primary_sam.py:273-395).
+// SCAN, one CIGAR per thread, visited by descending length as k_len_scan, through an 8-byte CsBytes window: the four figures of
+// cigar_parser, or — where pysam[a] is set: the primary alignment of a read — of pysam (all zero for a bad CIGAR).
+// SELECT, one read per thread, visited by descending number of entries (the same key and sort over ent_off): almost every read has no
+// SA entry or one or two, and a wavefront's trip count is that of its longest read.  The lists of a read are bit masks in its slice of
+// `ws` (ws_off[r], laid out by the host side from ent_off); its pieces go to the slice of `pieces` that starts at ent_off[r].  Every
+// lane stays to the end: n_gaps and pos_strand are summed over the wavefront and leave in one 64-bit atomic each; species_count takes
+// an atomic per recorded gap (chimeric reads are a few percent of a training set).  Integers only: the order of the atomics never shows.
+// small[]: CHIMS_BAD CIGARs that are bad, CHIMS_FIRST the smallest index of one (preset to ~0), CHIMS_GAPS, CHIMS_POS the totals.
+// ---------------------------------------------------------------------------------------------------------
+enum { CHIMS_BAD = 0, CHIMS_FIRST = 1, CHIMS_GAPS = 2, CHIMS_POS = 3, CHIMS_WORDS = 4 };
+__global__ void __launch_bounds__(256) k_chim_scan(const uint8_t *__restrict__ cigar, const uint64_t *__restrict__ cigar_off, uint32_t n,
+                                                   const uint32_t *__restrict__ order, const uint8_t *__restrict__ pysam, ns_chim_ent *__restrict__ ent,
+                                                   unsigned long long *__restrict__ small) {
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= n) return;
+    const uint64_t a = order ? order[tid] : tid;
+    CsBytes cb(cigar + cigar_off[a]);
+    ChimFigures F;
+    const bool ok = chim_scan_cigar(cb, cigar_off[a + 1] - cigar_off[a], pysam && pysam[a] ? CHIM_PYSAM : CHIM_PARSER, F);
+    ent[a] = ns_chim_ent{F.qstart, F.qend, F.qlen, F.rlen};
+    if (!ok) { atomicAdd(&small[CHIMS_BAD], 1ull); atomicMin(&small[CHIMS_FIRST], (unsigned long long)a); }
+}
+struct ChimAtomicAdd {
+    __device__ __forceinline__ void operator()(unsigned long long *p, unsigned long long v) const { atomicAdd(p, v); }
+};
+__global__ void __launch_bounds__(256) k_chim_select(const ns_chim_ent *__restrict__ ent, const uint64_t *__restrict__ ent_off, uint32_t n_reads,
+                                                     const uint32_t *__restrict__ order, const uint32_t *__restrict__ ref_id,
+                                                     const uint64_t *__restrict__ ref_start, const uint32_t *__restrict__ nm,
+                                                     const uint8_t *__restrict__ reverse, const uint64_t *__restrict__ ref_total,
+                                                     const uint32_t *__restrict__ species, uint64_t *__restrict__ ws, const uint64_t *__restrict__ ws_off,
+                                                     ns_chim_piece *__restrict__ pieces, ns_chim_read *__restrict__ reads,
+                                                     unsigned long long *__restrict__ species_count, unsigned long long *__restrict__ small) {
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    ChimTotals T{0u, 0u};
+    if (tid < n_reads) {
+        const uint64_t r = order ? order[tid] : tid;
+        const uint64_t e0 = ent_off[r];
+        ChimAtomicAdd add;
+        uint32_t flags = 0;
+        static_assert(sizeof(ChimFigures) == sizeof(ns_chim_ent) && sizeof(ChimPiece) == sizeof(ns_chim_piece), "ns_chimeric.h mirrors the ABI structs");
+        const uint32_t k = chim_select_read(ent_off[r + 1] - e0, reinterpret_cast<const ChimFigures *>(ent) + e0, ref_id + e0, ref_start + e0, nm + e0,
+                                            reverse + e0, ref_total, species, ws + ws_off[r], reinterpret_cast<ChimPiece *>(pieces) + e0, species_count,
+                                            add, T, flags);
+        reads[r] = ns_chim_read{k, flags};
+    }
+    // (every lane of the workgroup comes here: the wavefront sums need them all)
+    const unsigned long long gaps = wave_sum(T.n_gaps), pos = wave_sum(T.pos_strand);
+    if ((threadIdx.x & 63u) == 0) {
+        if (gaps) atomicAdd(&small[CHIMS_GAPS], gaps);
+        if (pos) atomicAdd(&small[CHIMS_POS], pos);
+    }
 }
