@@ -554,6 +554,39 @@ int ns_chimeric_select(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_
                        const uint32_t *ref_id, const uint64_t *ref_start, const uint32_t *nm, const uint8_t *reverse,
                        const uint64_t *ref_total, const uint32_t *species, uint32_t n_refs, uint32_t n_species, ns_chim_result *out);
 
+/* ---- training side: abundance quantification, the EM over multi-mapping reads --------------------------------------------------------------------
+ * replaces the loops of EM_meta and EM_trans (src/get_primary_sam.py, G:60-84, G:104-127); nanosim_amd/csrc/ns_em.h says how: every sum in
+ * the reference's order, so that abundance, count, the diff of every iteration and the iteration on which the loop ends are the
+ * reference's bit for bit.  The targets t = 0 .. n_targets - 1 are the species (meta) or transcripts (trans) in the order of the @SQ-derived
+ * dict; the items m = 0 .. n_multi - 1 are the entries of multi_mapping_list in its order, with the candidates
+ * target[multi_off[m] .. multi_off[m + 1]) (each < n_targets, duplicates kept, at least one) and weight[m] (the aligned length for meta,
+ * 1.0 for trans).  unique[t] is base_count_unique / read_count_unique (an integer below 2^53), total is total_base / total_reads (> 0, an
+ * integer below 2^53 / 100), max_iter and factor are 100 and 0.01 (meta) or 1000 and 0.001 (trans); the host enqueues `group` iterations
+ * between two looks at the device's stop flag (10 / 50, the reference's print cadence; 0 = 1).  n_multi == 0 is valid.
+ * Out: abundance[n_targets] in percent, count[n_targets] (base_count_tmp / read_count_tmp of the last executed iteration),
+ * diff_trace[max_iter] (diff_tmp of iteration i; entries from n_iter on are 0), n_iter (iterations executed, 1 .. max_iter), n_nonfinite
+ * (abundances of the last iteration that are NaN or infinite: the rest is then meaningless).  TPM and the file are the caller's
+ * (nanosim_amd/characterize.py: em_quantify, format_quantification).  NS_EINVAL for n_targets == 0 and total == 0 (not > 0).
+ * Added without an ABI change. */
+typedef struct ns_em_problem {
+    uint32_t n_targets, n_multi;
+    const uint64_t *multi_off;  /* n_multi + 1, from 0 */
+    const uint32_t *target;     /* multi_off[n_multi] */
+    const double *weight;       /* n_multi */
+    const double *unique;       /* n_targets */
+    double total, factor;
+    uint32_t max_iter, group;
+} ns_em_problem;
+typedef struct ns_em_result {
+    double *abundance;          /* in: host buffer of n_targets entries (out) */
+    double *count;              /* in: host buffer of n_targets entries (out) */
+    double *diff_trace;         /* in: host buffer of max_iter entries (out) */
+    uint32_t n_iter, reserved;  /* out */
+    uint64_t n_nonfinite;       /* out */
+    double ms_kernel;           /* the whole loop, with the reads of the flag */
+} ns_em_result;
+int ns_em_quantify(ns_ctx *ctx, const ns_em_problem *p, ns_em_result *out);
+
 /* device address of a result buffer (for zero-copy consumers such as torch / RCCL); NULL if absent */
 const void *ns_device_ptr(ns_ctx *ctx, int which);
 

@@ -16,7 +16,7 @@
 //   k_errlog            wave/read     _aligned_error_profile rows                           (S:2006-2008)
 // Metagenome worker calls run k_lengths / k_chain per PASS of the reference's while loop (S:844-1040) with k_meta_* around them; the lists of a
 // pass are launched before the host has walked the species quotas (assign_species), k_meta_tail does positions + acceptance afterwards.
-// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms, ns_sam_pairs_build, ns_mixture_fit, ns_read_lengths, ns_cigar_spans, ns_chimeric_select: at the end of the host part) has its kernels in ns_train.h.
+// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms, ns_sam_pairs_build, ns_mixture_fit, ns_read_lengths, ns_cigar_spans, ns_chimeric_select, ns_em_quantify: at the end of the host part) has its kernels in ns_train.h.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdio.h>
@@ -4584,6 +4584,75 @@ int ns_chimeric_select(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_
     { float f = 0; CALLCHK(s, hipEventElapsedTime(&f, ctx->evt[EV_HIST_BEGIN], ctx->evt[EV_SAM_END])); out->ms_scan = f; }
     out->n_gaps = small[CHIMS_GAPS]; out->pos_strand = small[CHIMS_POS];
     out->n_bad = small[CHIMS_BAD]; out->first_bad = out->n_bad ? small[CHIMS_FIRST] : n_ent;
+    return NS_OK;
+}
+
+// the EM of the abundance quantification (include/nanosim_amd.h: ns_em_problem; ns_em.h; src/get_primary_sam.py:60-84, 104-127).  The
+// slots are laid out here, once per call: a stable counting sort of the entries by target — the entries already stand in (item,
+// position) order.  Then groups of iterations, three kernels each, and one look at the state per group.
+int ns_em_quantify(ns_ctx *ctx, const ns_em_problem *p, ns_em_result *out) {
+    if (!ctx) return NS_EINVAL;
+    if (!p || !out) return fail(ctx, NS_EINVAL, "ns_em_quantify: null argument");
+    out->n_iter = 0; out->reserved = 0; out->n_nonfinite = 0; out->ms_kernel = 0;
+    const uint32_t nt = p->n_targets, nm = p->n_multi;
+    if (!nt) return fail(ctx, NS_EINVAL, "ns_em_quantify: no target");
+    if (!(p->total > 0.0) || !(p->total * 100.0 < 9007199254740992.0)) return fail(ctx, NS_EINVAL, "ns_em_quantify: total must be > 0 and below 2^53 / 100");
+    if (!p->max_iter || p->max_iter > (1u << 20)) return fail(ctx, NS_EINVAL, "ns_em_quantify: max_iter must be 1 .. 2^20");
+    if (nt >= (1u << 31) || nm >= (1u << 31)) return fail(ctx, NS_EINVAL, "ns_em_quantify: 2^31 targets or items or more");
+    if (!p->unique || !out->abundance || !out->count || !out->diff_trace || (nm && (!p->multi_off || !p->target || !p->weight)))
+        return fail(ctx, NS_EINVAL, "ns_em_quantify: null argument");
+    for (uint32_t t = 0; t < nt; ++t)
+        if (!(p->unique[t] >= 0.0 && p->unique[t] <= p->total)) return fail(ctx, NS_EINVAL, "ns_em_quantify: unique of target " + std::to_string(t) + " is not within 0 .. total");
+    uint64_t n_ent = 0;
+    if (nm) {
+        if (p->multi_off[0] != 0) return fail(ctx, NS_EINVAL, "ns_em_quantify: multi_off does not begin at 0");
+        for (uint32_t m = 0; m < nm; ++m)
+            if (p->multi_off[m] >= p->multi_off[m + 1]) return fail(ctx, NS_EINVAL, "ns_em_quantify: item " + std::to_string(m) + " has no candidate, or multi_off decreases");
+        n_ent = p->multi_off[nm];
+        if (n_ent >= (1ull << 40)) return fail(ctx, NS_EINVAL, "ns_em_quantify: 2^40 candidates or more");
+    }
+    std::vector<uint64_t> tgt_off((size_t)nt + 1, 0), slot((size_t)n_ent);
+    for (uint64_t e = 0; e < n_ent; ++e) {
+        if (p->target[e] >= nt) return fail(ctx, NS_EINVAL, "ns_em_quantify: candidate " + std::to_string(e) + " is not below n_targets");
+        ++tgt_off[p->target[e] + 1u];
+    }
+    for (uint32_t t = 0; t < nt; ++t) tgt_off[t + 1] += tgt_off[t];
+    {
+        std::vector<uint64_t> next(tgt_off.begin(), tgt_off.end() - 1);
+        for (uint64_t e = 0; e < n_ent; ++e) slot[e] = next[p->target[e]]++;
+    }
+    const std::vector<double> a0(nt, 100.0 / (double)nt);                              // G:60 / G:104
+    EmState st0{0u, 0u, 0ull, 100.0 * (double)nt};                                     // G:62 / G:106
+    for (uint32_t i = 0; i < p->max_iter; ++i) out->diff_trace[i] = 0.0;
+    HIPCHK(hipSetDevice(ctx->device));
+    CallScratch s(ctx, "ns_em_quantify");
+    const uint64_t *d_multi_off = s.filled(p->multi_off, nm ? (size_t)nm + 1 : 0), *d_slot = s.filled(slot.data(), (size_t)n_ent);
+    const uint64_t *d_tgt_off = s.filled(tgt_off.data(), (size_t)nt + 1);
+    const uint32_t *d_target = s.filled(p->target, (size_t)n_ent);
+    const double *d_weight = s.filled(p->weight, (size_t)nm), *d_unique = s.filled(p->unique, (size_t)nt);
+    double *d_a = s.filled(a0.data(), (size_t)nt);
+    double *d_count = s.zeroed<double>(nt), *d_dabs = s.zeroed<double>(nt);
+    double *d_contrib = s.zeroed<double>((size_t)n_ent), *d_trace = s.zeroed<double>(p->max_iter);
+    EmState *d_state = s.filled(&st0, 1);
+    if (int rc = s.upload()) return rc;
+    hipStream_t st = ctx->stream;
+    CALLCHK(s, hipEventRecord(ctx->evt[EV_HIST_BEGIN], st));
+    const uint32_t group = p->group ? p->group : 1u;
+    const uint32_t accum_blocks = std::min<uint32_t>((nt + NS_EM_WAVES - 1u) / NS_EM_WAVES, 8192u);
+    EmState now = st0;
+    while (!now.stop) {
+        for (uint32_t g = 0; g < group && now.n_iter + g < p->max_iter; ++g) {
+            if (nm) k_em_estep<<<dim3((nm + 255u) / 256u), dim3(256), 0, st>>>(d_state, d_a, d_target, d_slot, d_multi_off, d_weight, nm, d_contrib);
+            k_em_accum<<<dim3(accum_blocks), dim3(64u * NS_EM_WAVES), 0, st>>>(d_state, d_contrib, d_tgt_off, d_unique, p->total, nt, d_count, d_a, d_dabs);
+            k_em_stop<<<dim3(1), dim3(256), 0, st>>>(d_state, d_a, d_dabs, nt, p->factor, p->max_iter, d_trace);
+        }
+        CALLCHK(s, hipGetLastError());
+        CALLCHK(s, hipMemcpyAsync(&now, d_state, sizeof now, hipMemcpyDeviceToHost, st));
+        CALLCHK(s, hipStreamSynchronize(st));
+    }
+    if (int rc = timed_tail(s, {{out->abundance, d_a, (size_t)nt * 8}, {out->count, d_count, (size_t)nt * 8},
+                                {out->diff_trace, d_trace, (size_t)p->max_iter * 8}}, &out->ms_kernel)) return rc;
+    out->n_iter = now.n_iter; out->n_nonfinite = now.n_nonfinite;
     return NS_OK;
 }
 

@@ -1,11 +1,11 @@
 // ns_train.h — training side, the device kernels: the counting loops of the characterisation stage (k_cs_len, k_cs_hist),
 // of the base-quality model (k_qual_mark, k_qual_count) and of the homopolymer-length model (k_hp_count, k_hp_records), and the line pairs
 // of SAM records (k_sam_scan, k_sam_lines), the fit of the error-length mixtures (k_mixfit), and the lengths behind the read-length
-// models (k_len_scan, k_len_flag, k_len_reduce), and the split-alignment choice of chimeric reads (k_chim_scan, k_chim_select).  The walks
-// they run are ns_cs_hist.h, ns_qual_hist.h, ns_hp_hist.h, ns_sam_pairs.h, ns_mixfit.h, ns_read_len.h and ns_chimeric.h, which also compile
-// for the host; the host side of the calls (ns_cs_histograms / ns_maf_histograms, ns_qual_histograms, ns_hp_histograms /
-// ns_hp_histograms_sam, ns_sam_pairs_build, ns_mixture_fit, ns_read_lengths, ns_cigar_spans / ns_chimeric_select) is at the end of
-// nanosim_amd.hip.  Nothing here uses GenArgs or the simulation.
+// models (k_len_scan, k_len_flag, k_len_reduce), the split-alignment choice of chimeric reads (k_chim_scan, k_chim_select), and the EM of
+// the abundance quantification (k_em_estep, k_em_accum, k_em_stop).  The walks they run are ns_cs_hist.h, ns_qual_hist.h, ns_hp_hist.h,
+// ns_sam_pairs.h, ns_mixfit.h, ns_read_len.h, ns_chimeric.h and ns_em.h, which also compile for the host; the host side of the calls
+// (ns_cs_histograms / ns_maf_histograms, ns_qual_histograms, ns_hp_histograms / ns_hp_histograms_sam, ns_sam_pairs_build, ns_mixture_fit,
+// ns_read_lengths, ns_cigar_spans / ns_chimeric_select, ns_em_quantify) is at the end of nanosim_amd.hip.  Nothing here uses GenArgs or the simulation.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -17,6 +17,7 @@
 #include "ns_mixfit.h"
 #include "ns_read_len.h"
 #include "ns_chimeric.h"
+#include "ns_em.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // k_cs_hist: the counting loop of the characterisation stage (ns_cs_hist.h; src/besthit_to_histogram.py:316-365), one alignment per
@@ -475,4 +476,60 @@ __global__ void __launch_bounds__(256) k_chim_select(const ns_chim_ent *__restri
         if (gaps) atomicAdd(&small[CHIMS_GAPS], gaps);
         if (pos) atomicAdd(&small[CHIMS_POS], pos);
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_em_estep, k_em_accum, k_em_stop: one iteration of the quantification EM (ns_em.h; src/get_primary_sam.py:64-84, 108-127), bit for
+// bit in the reference's summation order.  ESTEP, one multi-mapping item per thread: a gather, a divide and a multiply per candidate;
+// the products go to slots that the host side laid out once per call, contiguous per target and ordered as the reference adds them.
+// ACCUM, one wavefront per target, grid-stride: the ordered fold of the target's slots onto unique[t] — a serial chain of dependent fp64
+// adds per target, which is the price of bit-identity —, then count[t], the new a[t] and dabs[t] = |new - old|.  STOP, one workgroup:
+// wavefront 0 folds dabs[] in target order — the other serial chain, over every expressed target — while the other three take the
+// minimum of a[] and count the non-finite ones; then one lane decides.  State (stop flag, iteration number, diff) stays on the device: the three kernels do nothing once the flag is set, so
+// the host enqueues iterations in groups and reads the flag once per group.  No atomics on doubles anywhere.
+// ---------------------------------------------------------------------------------------------------------
+#define NS_EM_WAVES 4u
+__global__ void __launch_bounds__(256) k_em_estep(const EmState *__restrict__ S, const double *__restrict__ a, const uint32_t *__restrict__ target,
+                                                  const uint64_t *__restrict__ slot, const uint64_t *__restrict__ multi_off,
+                                                  const double *__restrict__ weight, uint32_t n_multi, double *__restrict__ contrib) {
+    if (S->stop) return;
+    const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_multi) return;
+    em_item_estep(a, target, slot, multi_off[m], multi_off[m + 1], weight[m], contrib);
+}
+__global__ void __launch_bounds__(256) k_em_accum(const EmState *__restrict__ S, const double *__restrict__ contrib, const uint64_t *__restrict__ tgt_off,
+                                                  const double *__restrict__ unique, double total, uint32_t n_targets,
+                                                  double *__restrict__ count, double *__restrict__ a, double *__restrict__ dabs) {
+    if (S->stop) return;
+    const uint32_t wave = blockIdx.x * NS_EM_WAVES + (threadIdx.x >> 6), n_waves = gridDim.x * NS_EM_WAVES;
+    for (uint32_t t = wave; t < n_targets; t += n_waves) {                // (the whole wavefront)
+        const uint64_t lo = tgt_off[t];
+        const double acc = em_fold(unique[t], contrib + lo, tgt_off[t + 1] - lo);
+        if ((threadIdx.x & 63u) == 0) em_target_step(acc, total, count + t, a + t, dabs + t);
+    }
+}
+__global__ void __launch_bounds__(256) k_em_stop(EmState *__restrict__ S, const double *__restrict__ a, const double *__restrict__ dabs, uint32_t n_targets,
+                                                 double factor, uint32_t max_iter, double *__restrict__ diff_trace) {
+    __shared__ double mn_s[256];
+    __shared__ unsigned long long bad_s;
+    if (S->stop) return;
+    if (threadIdx.x == 0) bad_s = 0ull;
+    __syncthreads();
+    double mn = a[0], diff_tmp = 0.0;                                     // (n_targets >= 1: the host checks)
+    if (threadIdx.x < 64u) diff_tmp = em_fold(0.0, dabs, n_targets);      // wavefront 0: the chain
+    else {                                                                // the others, meanwhile: the minimum and the non-finite ones
+        uint32_t bad = 0;
+        for (uint32_t t = threadIdx.x - 64u; t < n_targets; t += blockDim.x - 64u) {
+            const double v = a[t];
+            mn = v < mn ? v : mn;
+            if (!em_finite(v)) ++bad;
+        }
+        if (bad) atomicAdd(&bad_s, (unsigned long long)bad);
+    }
+    mn_s[threadIdx.x] = mn;
+    __syncthreads();
+    if (threadIdx.x >= 64u) return;
+    for (uint32_t i = threadIdx.x + 64u; i < 256u; i += 64u) mn = mn_s[i] < mn ? mn_s[i] : mn;
+    for (int o = 32; o > 0; o >>= 1) { const double u = __shfl_xor(mn, o, 64); mn = u < mn ? u : mn; }
+    if (threadIdx.x == 0) em_decide(S, diff_tmp, mn, bad_s, factor, max_iter, diff_trace);
 }
