@@ -65,6 +65,17 @@ extern "C" int chim_host_chimeric_select(void *, const uint8_t *cigar, const uin
         for (uint64_t i = 0; i < n; ++i)
             out->pieces[e0 + i] = i < k ? ns_chim_piece{pieces[i].entry, pieces[i].is_primary, pieces[i].gap} : ns_chim_piece{0u, 0u, 0};
         out->n_gaps += T.n_gaps; out->pos_strand += T.pos_strand;
+        // "ws: contents undefined": the same read over a zeroed workspace has to choose the same (a walk that looks at a list it has
+        // not opened yet finds the primary in the pattern above and nothing here)
+        std::vector<uint64_t> ws0(chim_ws_words(n), 0ull);
+        std::vector<ChimPiece> pieces0(n);
+        std::vector<unsigned long long> count0((size_t)2 * n_species, 0ull);
+        ChimTotals T0; uint32_t flags0 = 0;
+        const uint32_t k0 = chim_select_read(n, fig.data() + e0, ref_id + e0, ref_start + e0, nm + e0, reverse + e0, ref_total, species, ws0.data(),
+                                             pieces0.data(), count0.data(), add, T0, flags0);
+        if (k0 != k || flags0 != flags || T0.n_gaps != T.n_gaps || T0.pos_strand != T.pos_strand) return -2;
+        for (uint32_t i = 0; i < k; ++i)
+            if (pieces0[i].entry != pieces[i].entry || pieces0[i].is_primary != pieces[i].is_primary || pieces0[i].gap != pieces[i].gap) return -2;
     }
     for (uint32_t i = 0; i < 2u * n_species; ++i) out->species_count[i] = count[i];
     return 0;

@@ -50,9 +50,24 @@ extern "C" int em_host_quantify(void *, const ns_em_problem *p, ns_em_result *ou
     return 0;
 }
 
+// em_decide alone, for a table of hand-chosen states (tests/test_quantify.py: the exact ties of G:82 are hard to reach through a whole
+// problem).  state: {diff, it} in, {diff, n_iter, stop} out; trace: max_iter doubles.
+extern "C" void em_host_decide(double *diff, uint32_t *it, uint32_t *stop, double diff_tmp, double mn, uint64_t n_nonfinite, double factor,
+                               uint32_t max_iter, double *trace) {
+    EmState S{0u, *it, 0ull, *diff};
+    em_decide(&S, diff_tmp, mn, n_nonfinite, factor, max_iter, trace);
+    *diff = S.diff; *it = S.n_iter; *stop = S.stop;
+}
+
 #ifdef EM_MAIN
 #include <stdio.h>
 int main() {
+    {   // em_host_decide at the last slot of an exact-size trace: iteration max_iter - 1 writes trace[max_iter - 1] and nothing behind it
+        std::vector<double> tr(3, 0.0);
+        double diff = 300.0; uint32_t it = 2, stop = 0;
+        em_host_decide(&diff, &it, &stop, 1.5, 2.0, 0, 0.01, 3, tr.data());
+        if (!(tr[2] == 1.5 && it == 3 && stop == 1 && diff == 1.5)) return 4;
+    }
     // 130 targets, 700 items of 2 .. 6 candidates (duplicates among them) from a small generator; targets 5 and 77 stay without a read
     const uint32_t nt = 130, nm = 700;
     uint64_t x = 88172645463325252ull;

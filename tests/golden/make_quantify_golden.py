@@ -39,9 +39,10 @@ W = 64                                                       # NS_EM_CHUNK: the 
 KINDS = {"meta": (100, 0.01), "trans": (1000, 0.001)}
 
 
-def restate(read_list, all_t, kind):
+def restate(read_list, all_t, kind, max_iter=None):
     """the EM restated for the asserts on the input: which condition ended it, and the contributions per target"""
     n_max, factor = KINDS[kind]
+    n_max = n_max if max_iter is None else max_iter
     names = list(all_t)
     unique, multi, total = dict.fromkeys(names, 0), {}, 0
     for read, cand in read_list.items():
@@ -83,25 +84,67 @@ def restate(read_list, all_t, kind):
 
 
 class Counter:
+    """stands in for `min` in the module's globals: the EM calls it once per iteration (G:81 / G:124), directly behind the `sum` of
+    G:75 / G:118 — so the last value of the recording `sum` is that iteration's diff_tmp, and what `min` returns is min(abundance)"""
     def __init__(self):
         self.n = 0
+        self.last_sum = None
+        self.trace, self.mins = [], []
 
     def __call__(self, *a, **k):
         self.n += 1
-        return min(*a, **k)
+        v = min(*a, **k)
+        self.trace.append(self.last_sum)
+        self.mins.append(v)
+        return v
+
+    def sum(self, *a, **k):
+        self.last_sum = sum(*a, **k)
+        return self.last_sum
 
 
-def run_em(G, kind, read_list, all_t, normalize=None):
-    """the reference's EM on copies of the input: (result, n_iter, Iteration lines)"""
+def run_em(G, kind, read_list, all_t, normalize=None, max_iter=None, counter_out=None):
+    """the reference's EM on copies of the input: (result, n_iter, Iteration lines).  max_iter: the EM's own `range(0, 100)` /
+    `range(0, 1000)` ends there instead (a `range` in the module's globals; every other range is the builtin)"""
     G.min = counter = Counter()
+    G.sum = counter.sum
+    if max_iter is not None:
+        G.range = lambda *a: range(0, max_iter) if a in ((0, 100), (0, 1000)) else range(*a)
     buf = io.StringIO()
     try:
         with contextlib.redirect_stdout(buf):
             res = G.EM_meta(dict(read_list), dict(all_t)) if kind == "meta" else G.EM_trans(dict(read_list), dict(all_t), normalize)
     finally:
-        del G.min
+        del G.min, G.sum
+        if max_iter is not None:
+            del G.range
     lines = "".join(line + "\n" for line in buf.getvalue().splitlines() if line.startswith("Iteration:"))
+    if counter_out is not None:
+        counter_out.append(counter)
     return res, counter.n, lines
+
+
+def edge_problems():
+    """[(name, kind, quant_dic, all_species, max_iter)]: problems that land on the edges of the stop rule (G:80-84)"""
+    out = []
+    # no multi-mapping item and a target without a read: the threshold is 0, the second iteration changes nothing, diff_tmp is exactly
+    # 0.0 and `diff_tmp <= diff_thres` holds with equality (with `<` the loop would run to its last iteration)
+    out.append(("meta_zero_diff", "meta", {("u%d" % i, (i, i + 90 + 11 * i)): ["z%d" % (i % 2)] for i in range(9)}, {"z0": 0, "z1": 0, "z2": 0}, None))
+    out.append(("trans_zero_diff", "trans", {("u%d" % i, (0, 50)): ["z%d" % (i % 2)] for i in range(7)}, {"z0": 700, "z1": 900, "z2": 400}, None))
+    # the iteration limit below the natural count (main() asserts it is above 3): 1, 2 and 3
+    q = {("x%d" % i, (0, 1000)): ["A", "B"] for i in range(90)}
+    q.update({("ua%d" % i, (0, 1000)): ["A"] for i in range(7)})
+    q.update({("ub%d" % i, (0, 1000)): ["B"] for i in range(3)})
+    q[("uc", (0, 1))] = ["C"]
+    for k in (1, 2, 3):
+        out.append(("meta_max_iter_%d" % k, "meta", q, {"A": 0, "B": 0, "C": 0}, k))
+    qt = {("x%d" % i, (0, 1000)): ["A", "B"] for i in range(40)}
+    qt.update({("ua%d" % i, (0, 1000)): ["A"] for i in range(5)})
+    qt.update({("ub%d" % i, (0, 1000)): ["B", "C", "C"] for i in range(3)})
+    qt[("uc", (0, 1))] = ["C"]
+    for k in (1, 2, 3):
+        out.append(("trans_max_iter_%d" % k, "trans", qt, {"A": 1000, "B": 1500, "C": 700}, k))
+    return out
 
 
 def direct_problems():
@@ -237,12 +280,19 @@ def main():
     # ---- EM_meta / EM_trans directly ------------------------------------------------------------------------------------------------------
     direct = []
     seen_branches, sizes = set(), set()
-    for name, kind, q, all_t in direct_problems():
-        R = restate(q, all_t, kind)
+    for name, kind, q, all_t, max_iter in [p + (None,) for p in direct_problems()] + edge_problems():
+        R = restate(q, all_t, kind, max_iter)
         sizes.add(len(all_t))
         for normalize in ((True, False) if kind == "trans" else (None,)):
-            res, n_iter, lines = run_em(G, kind, q, all_t, normalize)
+            seen_counter = []
+            res, n_iter, lines = run_em(G, kind, q, all_t, normalize, max_iter, seen_counter)
             assert n_iter == R["n_iter"], (name, n_iter, R["n_iter"])
+            trace, mins = seen_counter[0].trace, seen_counter[0].mins
+            assert len(trace) == len(mins) == n_iter and lines.startswith("Iteration: 0, Diff: " + str(trace[0]) + "\n")
+            if max_iter is not None:
+                assert n_iter == max_iter and R["branch"] is None and restate(q, all_t, kind)["n_iter"] > 3, name
+            if name.endswith("_zero_diff"):
+                assert n_iter == 2 and trace[1] == 0.0 and mins[1] == 0 and R["branch"] == "le" and not R["multi"] and R["thres0"], name
             if kind == "meta":
                 assert list(res) == list(all_t) and all(res[t].hex() == R["a"][t].hex() for t in res), name
                 result = [[t, hexes(v)] for t, v in res.items()]
@@ -251,7 +301,8 @@ def main():
                 result = [[t, repr(c), hexes(c), hexes(tpm)] for t, (c, tpm) in res.items()]
             assert lines.count("\n") == (n_iter + (9 if kind == "meta" else 49)) // (10 if kind == "meta" else 50)
             direct.append(dict(name=name, kind=kind, normalize=normalize, items=pack_quant(q), targets=[[t, v] for t, v in all_t.items()], result=result,
-                               n_iter=n_iter, lines=lines, branch=R["branch"], multi_keys=[list(k) if kind == "meta" else k for k in R["multi"]],
+                               n_iter=n_iter, lines=lines, branch=R["branch"], max_iter=max_iter, trace=[hexes(v) for v in trace],
+                               mins=[hexes(v) for v in mins], multi_keys=[list(k) if kind == "meta" else k for k in R["multi"]],
                                unique=[R["unique"][t] for t in all_t], total=R["total"], per_target=[R["per_target"][t] for t in all_t]))
         seen_branches.add(R["branch"])
         if name == "trans_300":

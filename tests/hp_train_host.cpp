@@ -50,3 +50,34 @@ extern "C" int hp_host_histograms(void *, const uint8_t *ref, const uint8_t *qry
 
 // read_len of a read segment alone: the restated `(BB+){s<=1}` scan
 extern "C" uint32_t hp_host_fuzzy_len(const uint8_t *seg, uint64_t n, uint8_t base) { return hp_fuzzy_len(seg, n, base); }
+
+#ifdef HP_MAIN
+// The walk as a stand-alone program for -fsanitize=address,undefined (tests/test_hp_train.py): the pairs of a file, `reference-line
+// query-line` per row, in exact-size buffers; prints n_hp, the four column sums, max_ref and max_read for the k of argv[2].
+#include <stdio.h>
+#include <stdlib.h>
+#include <string>
+#include <vector>
+int main(int argc, char **argv) {
+    if (argc < 3) return 2;
+    FILE *f = fopen(argv[1], "r");
+    if (!f) return 2;
+    std::vector<uint8_t> ref, qry; std::vector<uint64_t> off{0};
+    std::vector<char> a(1 << 20), b(1 << 20);
+    while (fscanf(f, "%1048575s %1048575s", a.data(), b.data()) == 2) {
+        if (strlen(a.data()) != strlen(b.data())) return 2;
+        ref.insert(ref.end(), a.data(), a.data() + strlen(a.data()));
+        qry.insert(qry.end(), b.data(), b.data() + strlen(b.data()));
+        off.push_back(ref.size());
+    }
+    fclose(f);
+    const uint32_t cap = 64;
+    std::vector<uint64_t> table((size_t)2 * cap * cap);
+    ns_hp_hist h; memset(&h, 0, sizeof h);
+    h.table = table.data(); h.cap_ref = h.cap_read = cap;
+    if (hp_host_histograms(nullptr, ref.data(), qry.data(), ref.size(), off.data(), (uint32_t)off.size() - 1u, (uint32_t)atoi(argv[2]), &h)) return 3;
+    printf("%llu %llu %llu %llu %llu %u %u\n", (unsigned long long)h.n_hp, (unsigned long long)h.columns[0], (unsigned long long)h.columns[1],
+           (unsigned long long)h.columns[2], (unsigned long long)h.columns[3], h.max_ref, h.max_read);
+    return 0;
+}
+#endif

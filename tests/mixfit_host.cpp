@@ -2,7 +2,7 @@
 // compiled for the HOST behind the signature of ns_mixture_fit, so that the objectives, the search and the host module around the call are
 // checked against the reference's fixture and against scipy without a GPU: one thread walks the 64 lanes of a tile as a 64-entry array, in
 // the order the header fixes.  Built by tests/test_mixfit.py (the compiler's host pass only, -ffp-contract=off) into tests/_tmp/.
-// mixfit_host_hand puts two hand-made functions behind the same simplex code.  With -DMIXFIT_MAIN the file is a stand-alone program for
+// mixfit_host_hand puts hand-made functions behind the same simplex code.  With -DMIXFIT_MAIN the file is a stand-alone program for
 // the sanitizer run: it reads `kind n_bins n_starts`, the CDF and the starts from standard input into heap buffers of exactly that size.
 #include <stdint.h>
 #include <stdio.h>
@@ -43,7 +43,7 @@ extern "C" int mixfit_host_fit(void *, int kind, const double *cdf, uint32_t n_b
     return 0;
 }
 
-// ---- hand cases on the search skeleton: tests/test_mixfit.py restates the two functions operation by operation ----
+// ---- hand cases on the search skeleton: tests/test_mixfit.py restates the functions operation by operation ----
 static const double HAND_A[4] = {0.3, -1.25, 2.0, 0.75}, HAND_B[4] = {1.0, 3.5, 0.5, 10.0};
 template <int D> struct HandQuadratic {                       // sum of b (x - a)^2, accumulated left to right
     static constexpr int N = D;
@@ -60,12 +60,34 @@ template <int D> struct HandBox {                             // the same, NaN o
         return HandQuadratic<D>()(x);
     }
 };
+template <int D> struct HandSteps {                           // the same in steps of 1/4, rounded down: vertices, reflections and contractions TIE
+    static constexpr int N = D;
+    double operator()(const double (&x)[4]) const { return floor(HandQuadratic<D>()(x) * 4.0) / 4.0; }
+};
+struct HandSlope {                                             // steep below x[0] = -2e-5, gentle above it, the other two coordinates break ties:
+    static constexpr int N = 3;                               // the simplex GROWS down the slope until its size meets the 1e-4 of the x test
+    double operator()(const double (&x)[4]) const {
+        const double a = x[0], t = -2e-5;
+        const double g = a < t ? -1000.0 * a : -1000.0 * t - 0.5 * (a - t);
+        return (g - 0.01 * x[1]) - 0.001 * x[2];
+    }
+};
+struct HandCliff {                                             // `height` where x[0] > 1.02e-3, else 0: the first simplex's values differ by exactly `height`
+    static constexpr int N = 3;
+    double height;
+    double operator()(const double (&x)[4]) const { return x[0] > 1.02e-3 ? height : 0.0; }
+};
 extern "C" int mixfit_host_hand(int which, int dim, const double *x0, uint32_t maxiter, uint32_t maxfev, ns_mixfit_fit *out) {
     out->reserved = 0;
     if (which == 0 && dim == 3) mf_nelder_mead(HandQuadratic<3>(), x0, maxiter, maxfev, *out);
     else if (which == 0 && dim == 4) mf_nelder_mead(HandQuadratic<4>(), x0, maxiter, maxfev, *out);
     else if (which == 1 && dim == 3) mf_nelder_mead(HandBox<3>(), x0, maxiter, maxfev, *out);
     else if (which == 1 && dim == 4) mf_nelder_mead(HandBox<4>(), x0, maxiter, maxfev, *out);
+    else if (which == 2 && dim == 3) mf_nelder_mead(HandSteps<3>(), x0, maxiter, maxfev, *out);
+    else if (which == 2 && dim == 4) mf_nelder_mead(HandSteps<4>(), x0, maxiter, maxfev, *out);
+    else if (which == 3 && dim == 3) mf_nelder_mead(HandSlope(), x0, maxiter, maxfev, *out);
+    else if (which == 4 && dim == 3) mf_nelder_mead(HandCliff{1e-4}, x0, maxiter, maxfev, *out);
+    else if (which == 5 && dim == 3) mf_nelder_mead(HandCliff{1.0000000000000002e-4}, x0, maxiter, maxfev, *out);
     else return -1;
     return 0;
 }

@@ -95,7 +95,10 @@ def brute_force(entries):
 
 CORNERS = [(":57", 57), ("*ag", 1), ("+acgt", 4), ("*ag:5*ct", 7), ("+a:5+c", 7), (":3+acgtacgtacgtacgtacgtacg:4", 30), (":10+ACGT:5~gt12ag:6", 25),
            ("x:4??*ag;:3", 8), (":50*ag:50", 30), (":5+acgtacgt:5", 8), (":6-acg:6-t*ag:2", 15), (":4=ACG:2", 6), (":12", 0), ("", 0),
-           ("::7*a1*ab:3", 11), (":0:0*ag:0", 1), (":100000", 100)]
+           ("::7*a1*ab:3", 11), (":0:0*ag:0", 1), (":100000", 100),
+           # items left over exactly when the cursor stands AT the aligned length (a mismatch or an insertion taken there would mark the
+           # first base of the next alignment: each of these is followed by one that begins with a match), and strings that end exactly there
+           (":4*ag:2", 4), (":3*ag+acg", 4), (":2+ac*ag:1", 4), (":4*ag", 5), (":1*ag*ct+a", 2), (":5+ac", 7), (":3+acg+t*ag", 6), (":7", 7)]
 
 
 def random_entries(rng, n):
@@ -131,6 +134,30 @@ def random_entries(rng, n):
 def brute_cover(cs):
     return [1 for item in re.findall(r'(:[0-9]+|\*[a-z][a-z]|[=\+\-][A-Za-z]+)', cs)
             for _ in range(int(item[1:]) if item[0] == ":" else len(item) - 1 if item[0] == "+" else 1 if item[0] == "*" else 0)]
+
+
+def offset_entries(rng):
+    """one call whose cs strings begin at every offset 0 .. 7 mod 8 of the packed bytes with every length 0 .. 17
+    (tests/test_characterize.py: every_offset_and_length), each with a QUAL of the length it covers: so do the quality strings, nearly"""
+    from tests.test_characterize import CS_FILLER, CS_PATTERN, every_offset_and_length
+    cs, where = every_offset_and_length(CS_PATTERN, CS_FILLER)
+    off = np.cumsum([0] + [len(c) for c in cs])
+    assert {(int(off[i]) % 8, len(cs[i])) for i in where} == {(o, n) for o in range(8) for n in range(18)}
+    return [(c, "".join(chr(33 + int(v)) for v in rng.integers(0, 94, len(brute_cover(c)))), 0, 0, 0) for c in cs]
+
+
+def check_offset_entries(eng):
+    rng = np.random.default_rng(17)
+    entries = offset_entries(rng)
+    for e in (entries, entries[::-1]):
+        hist, n_short, n_bad = raw_counts(eng, e)
+        exp, exp_short = brute_force(e)
+        assert n_bad == 0 and n_short == exp_short == 0 and np.array_equal(hist, exp)
+        assert hist[0].sum() > 100 and hist[1].sum() > 100
+
+
+def test_cs_strings_at_every_offset_and_length(host):
+    check_offset_entries(host)
 
 
 def fixture_entries(fx):

@@ -5,6 +5,7 @@ import ctypes as C
 import gzip
 import json
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -98,6 +99,149 @@ def test_walk_edge_cases(host_walk):
     for cs in cases:
         same_counts(host_walk(cs, cap=64), O.cs_hist(cs, cap=64))
     assert host_walk([":4=ACG:2"])["n_skip"] == 1
+
+
+# ---- the tokeniser's edges ---------------------------------------------------------------------------------------------------------------
+CS_TOKEN = re.compile(r":[0-9]+|\*[a-z]{2}|[+\-=][A-Za-z]+")   # the cs grammar (minimap2's manual); what stands between items is skipped
+CS_ROW = {"M": 0, "first": 1, "X": 2, "I": 3, "D": 4}           # rows of `dic`; columns of error_list / first_error are X, I, D = 0, 1, 2
+
+
+def cs_runs(cs):
+    """a cs string -> its runs [(kind, length)]: M a match, X consecutive substitutions, I / D one insertion / deletion"""
+    runs = []
+    for t in CS_TOKEN.findall(cs):
+        assert t[0] != "=", "no `=` items here"
+        if t[0] == "*" and runs and runs[-1][0] == "X":
+            runs[-1] = ("X", runs[-1][1] + 1)
+        else:
+            runs.append({":": ("M", int(t[1:]) if t[0] == ":" else 0), "*": ("X", 1), "+": ("I", len(t) - 1), "-": ("D", len(t) - 1)}[t[0]])
+    return runs
+
+
+def py_cs_hist(cs_list, cap=64):
+    """The counts of DESIGN section 9 restated over the runs of each string, in plain Python over Python strings: it shares no text with
+    the walk or with the oracle, and a str has no neighbour to read into.  The rules, as the fixture's files show them:
+    a match in front of the alignment's first error goes to row `first`; a later match is paired with the match before it, and is
+    tallied unless it ends the alignment; an alignment's first error goes to first_error, a later one to error_list by the error before
+    it and by whether it touches its neighbour in front (for the first run that neighbour is the alignment's LAST run); substitutions
+    that touch an error in front count a match of length 0 between the two.  The last match length lives on across alignments (0 at
+    the start); lengths above 1 000 are not tallied."""
+    dic = np.zeros((5, 1001), dtype=np.uint64)
+    err, first, pairs, last_match = np.zeros((6, 3), dtype=np.uint64), np.zeros(3, dtype=np.uint64), [], 0
+
+    def tally(row, length):
+        if length <= 1000:
+            dic[CS_ROW[row], length] += 1
+    for runs in map(cs_runs, cs_list):
+        errors = []                                           # the kinds of the errors seen in this alignment
+        for i, (kind, length) in enumerate(runs):
+            touches = runs[i - 1][0] != "M"
+            if kind == "M":
+                if not errors:
+                    tally("first", length)
+                else:
+                    pairs.append((last_match, length))
+                    if i == len(runs) - 1:
+                        continue
+                    tally("M", length)
+                last_match = length
+                continue
+            col = "XID".index(kind)
+            if errors:
+                err["XID".index(errors[-1]) + 3 * touches, col] += 1
+            else:
+                first[col] += 1
+            errors.append(kind)
+            tally(kind, length)
+            if kind == "X" and touches:
+                tally("M", 0)
+                pairs.append((last_match, 0))
+                last_match = 0
+    max_match = max([max(p) for p in pairs] + [0])
+    cap = max(cap, 1 << max_match.bit_length())               # (the matrix is sized by what it has to hold)
+    m2 = np.zeros((cap, cap), dtype=np.uint64)
+    for a_, b_ in pairs:
+        m2[a_, b_] += 1
+    return dict(dic=dic, match_list=m2, error_list=err, first_error=first, max_match=max_match)
+
+
+# a string that ends where an item could go on, directly in front of a string that begins with what the item would take (the strings of a
+# call lie one behind the other); bare `+`, `-`, `=`; the last letters of both alphabets in every place a letter can stand
+CS_EDGES = [
+    [":5*ag:3*a", "c:4*ag:2", ":6"],                           # `*a` at the end, a lower-case letter next door
+    [":5*ag:3*", "ac:4*ag:2", ":6"],
+    [":7-a:12", "3*ag:4", ":2"],                               # digits next door
+    [":7-a:", "12*ag:4", ":2"],
+    [":3*ct:2+ac", "gt:3*ag:1", ":9"],                         # letters next door, behind `+` and behind `-`
+    [":3*ct:2-ac", "GT:3*ag:1", ":9"],
+    [":3*ct:2+", "ac:3*ag:1", ":9"],
+    [":4+:2*ag:3", ":4-:2*ag:3", ":4=:2*ag:3", "+", "-", "=", ":5+-=*:1*ag:2"],   # bare signs are no items
+    [":2*za:3*az:2*zz:1", ":2+zZ:3-Zz:1+z:2-Z:5", ":1+az:1-AZ:3"],
+    [":4294967295"], [":4294967296"], [":99999999999999999999"],    # a first match no table holds, as text: above 1 000, never 0
+    [":4*ag:1000", ":1000*ag:1001", ":1001*ag:5"],             # add_dict's limit
+]
+MAF_EDGES = [[("ACzZGTzzaAC", "ACZzGTZzAaC"), ("ACGT", "ACGT")], [("zzz-ZZ", "ZZZz-z"), ("zAz", "ZaZ")], [("AC", "AC"), ("", ""), ("A-C", "AT-")]]
+
+
+def check_tokeniser_edges(count_cs, count_maf):
+    """count_cs(cs_list) / count_maf(pairs) -> the counts (cap 64) of the walk under test: against the plain-Python restatement and
+    against the oracle, the list as one call and every string of it alone"""
+    for cs in CS_EDGES:
+        want = py_cs_hist(cs)
+        same_counts(O.cs_hist(cs, cap=64), want)
+        got = count_cs(cs)
+        same_counts(got, want)
+        assert got.get("n_skip", 0) == 0, cs
+        for one in cs:
+            same_counts(count_cs([one]), py_cs_hist([one]))
+    for cs in ([":4294967295"], [":4294967296"]):
+        assert not count_cs(cs)["dic"].any()
+    for pairs in MAF_EDGES:
+        same_counts(count_maf(pairs), O.maf_hist(pairs, cap=64))
+    # soft-masked letters count as their capitals, `z` included: the same counts as the line in capitals
+    same_counts(count_maf(MAF_EDGES[0]), O.maf_hist([(r.upper(), q.upper()) for r, q in MAF_EDGES[0]], cap=64))
+    assert count_maf(MAF_EDGES[0])["dic"][2:].sum() == 0
+
+
+def every_offset_and_length(pattern, filler, lengths=range(18)):
+    """strings for ONE call in which a prefix of `pattern` of every length in `lengths` begins at every offset 0 .. 7 mod 8 of the packed
+    bytes (the device reads them through aligned 8-byte windows): a prefix of `filler` in front where the offset has to move;
+    -> (the strings, the indices of the prefixes)"""
+    out, at, where = [], 0, []
+    for length in lengths:
+        for o in range(8):
+            if at % 8 != o:
+                out.append(filler[:(o - at) % 8])
+                at += len(out[-1])
+            where.append(len(out))
+            out.append(pattern[:length])
+            at += length
+    return out, where
+
+
+CS_PATTERN, CS_FILLER = ":2*ct+ag:1-t*ga:3", ":3*ag-c"                # (every prefix is a cs string with, at most, junk at its end)
+
+
+def check_every_offset_and_length(count_cs):
+    cs, where = every_offset_and_length(CS_PATTERN, CS_FILLER)
+    off = np.cumsum([0] + [len(c) for c in cs])
+    assert len(where) == 144 and {(int(off[i]) % 8, len(cs[i])) for i in where} == {(o, n) for o in range(8) for n in range(18)}
+    want = py_cs_hist(cs)
+    same_counts(O.cs_hist(cs, cap=64), want)
+    same_counts(count_cs(cs), want)
+    same_counts(count_cs(cs[::-1]), py_cs_hist(cs[::-1]))
+
+
+def test_every_offset_and_length(host_walk):
+    check_every_offset_and_length(lambda cs: host_walk(cs, cap=64))
+
+
+def test_tokeniser_edges(host_walk):
+    check_tokeniser_edges(lambda cs: host_walk(cs, cap=64), lambda pairs: host_walk(pairs, cap=64, maf=True))
+
+
+def test_python_restatement_equals_the_oracle_on_the_fixture(fx):
+    same_counts(py_cs_hist(fx["cs"], cap=2048), O.cs_hist(fx["cs"]))
 
 
 def test_get_cs_and_sam_reader(fx, tmp_path):

@@ -168,6 +168,19 @@ HAND = [
     ("stable order among equal (qstart, qend)", [E("200S100M"), E("5S5M", 1), E("5S5M", 2), E("5S5M", 1, 9000)], 4, HAS_SA | POS,
      [(1, 0, NO), (2, 0, 0), (3, 0, 0), (0, 1, 190)], 3, 1, [[1, 1], [0, 1]]),
     ("two pieces with the primary's qstart count twice", [E("5S5M90S"), E("5S5M", 1)], 2, HAS_SA | POS, [(0, 1, NO), (1, 1, 0)], 1, 2, [[1, 0], [0, 0]]),
+    # the SECOND inequality of G:38, `interval[1] - overlap_base > member[0]`, met with equality (the cases above meet the first with it):
+    # the entry lies in FRONT of the member and ends 10 bases behind the member's start
+    ("query axis: the entry ends 10 behind the primary's start: compatible", [E("100S100M50S"), E("50S60M", 1)], 2, HAS_SA | POS, [(1, 0, NO), (0, 1, 0)], 1, 1,
+     [[1, 0], [0, 0]]),
+    ("... 11 behind: a second list, which loses", [E("100S100M50S"), E("50S61M", 1)], 1, HAS_SA | POS, [(0, 1, NO)], 0, 1, [[0, 0], [0, 0]]),
+    ("reference axis: the entry ends 10 behind the primary's start: compatible", [E("100M80S", 0, 5000), E("130S50M", 0, 4960)], 2, HAS_SA | POS,
+     [(0, 1, NO), (1, 0, 30)], 1, 1, [[1, 0], [0, 0]]),
+    ("... 11 behind: a second list, which loses", [E("100M80S", 0, 5000), E("130S50M", 0, 4961)], 1, HAS_SA | POS, [(0, 1, NO)], 0, 1, [[0, 0], [0, 0]]),
+    # sorted() of G:338 compares (qstart, qend) tuples: among equal qstart the smaller qend comes first, whatever the entry order
+    ("equal qstart, qend descending in entry order: sorted by qend", [E("200S100M"), E("5S8M", 1), E("5S5M", 2)], 3, HAS_SA | POS,
+     [(2, 0, NO), (1, 0, 0), (0, 1, 187)], 2, 1, [[1, 0], [0, 1]]),
+    ("... three of them, the middle one last", [E("200S100M"), E("5S9M", 1), E("5S3M", 2), E("5S6M", 1, 9000)], 4, HAS_SA | POS,
+     [(2, 0, NO), (3, 0, 0), (1, 0, 0), (0, 1, 186)], 3, 1, [[2, 0], [0, 1]]),
 ]
 
 
@@ -267,6 +280,21 @@ def check_bad(eng, bad):
         reads[1][where] = E(bad, reads[1][where][1])
         r = call(eng, reads)
         assert (r.n_bad, r.first_bad) == (1, 1 + where) and not r.ent[1 + where].tolist()[0] and not any(r.ent[1 + where].tolist())
+
+
+def check_cigar_bleed(eng):
+    """a count without an op directly in front of a CIGAR that begins with an op letter (the CIGARs of a call lie one behind the other):
+    both are bad, each on its own, in both readings"""
+    cigars = ["7M", "10", "M", "3S4M", "12M5", "S5M", "6", "I2M", "9M"]
+    want = [(0, 7, 7, 7), (0, 0, 0, 0), (0, 0, 0, 0), (3, 7, 4, 4), (0, 0, 0, 0), (0, 0, 0, 0), (0, 0, 0, 0), (0, 0, 0, 0), (0, 9, 9, 9)]
+    got, n_bad, first_bad, _ = characterize.cigar_spans(eng, cigars)
+    assert (n_bad, first_bad) == (6, 1) and [tuple(int(v) for v in g) for g in got] == want
+    r = call(eng, [[E("10")], [E("M")], [E("50M")], [E("100M80S"), E("130S5", 1), E("M50M", 2)]])          # ... and as a read's entries
+    assert (r.n_bad, r.first_bad) == (4, 0) and [tuple(int(v) for v in e) for e in r.ent] == [(0, 0, 0, 0)] * 2 + [(0, 50, 50, 50), (0, 100, 100, 100)] + [(0, 0, 0, 0)] * 2
+
+
+def test_a_cigar_that_ends_early_does_not_borrow_from_its_neighbour(host):
+    check_cigar_bleed(host)
 
 
 # ---- the host module ---------------------------------------------------------------------------------------------------------------------------

@@ -14,7 +14,7 @@ import pytest
 from nanosim_amd import characterize
 from nanosim_amd import engine as E
 from tests import oracle_lib as O
-from tests.test_characterize import same_counts
+from tests.test_characterize import check_every_offset_and_length, check_tokeniser_edges, same_counts
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -87,3 +87,10 @@ def test_gpu_maf_counts_equal_the_oracle_and_the_reference_files(eng, tmp_path):
     rng = np.random.default_rng(9)
     many = [pairs[i] for i in rng.integers(0, len(pairs), 20 * len(pairs))] + [("", ""), ("A-C", "AT-")]
     same_counts(characterize.count_maf(eng, many), O.maf_hist(many))
+
+
+def test_gpu_tokeniser_edges_and_every_offset_and_length(eng):
+    """the walk's string ends on the device, where the strings of a call really lie one behind the other and are read through aligned
+    8-byte windows (CsBytes): a neighbour's first byte is in the same window — against the plain-Python restatement and the oracle"""
+    check_tokeniser_edges(lambda cs: characterize.count(eng, cs, cap=64), lambda pairs: characterize.count_maf(eng, pairs, cap=64))
+    check_every_offset_and_length(lambda cs: characterize.count(eng, cs, cap=64))

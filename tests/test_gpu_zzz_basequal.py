@@ -13,7 +13,7 @@ import pytest
 
 from nanosim_amd import characterize
 from nanosim_amd import engine as E
-from tests.test_basequal import brute_force, build_host_walk, fixture_entries, load_fixture, raw_counts, same_file
+from tests.test_basequal import CORNERS, brute_force, build_host_walk, check_offset_entries, fixture_entries, load_fixture, raw_counts, same_file
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -86,6 +86,20 @@ def test_gpu_small_shapes_back_to_back(eng, host):
         assert got[1] == exp_short == 0 and got[2] == 0
         assert np.array_equal(got[0], exp)
         assert np.array_equal(got[0], raw_counts(host, entries)[0])
+
+
+def test_gpu_corners_and_cs_strings_at_every_offset_and_length(eng):
+    """the per-base expansion on the device for the corners of tests/test_basequal.py (items left over exactly at the aligned length among
+    them: a mark taken there would land on the next alignment's first base) and for cs strings at every offset mod 8 and every length
+    0 .. 17 of the packed bytes (CsBytes reads them through aligned 8-byte windows)"""
+    rng = np.random.default_rng(11)
+    corners = [(cs, "".join(chr(33 + int(v)) for v in rng.integers(1, 94, n)), 0, 0, 0) for cs, n in CORNERS]
+    corners += [(cs, "".join(chr(33 + int(v)) for v in rng.integers(1, 94, 3 + n + 2)), 3, 2, 0) for cs, n in CORNERS]
+    for entries in (corners, [e for e in corners if e[1]][::-1]):
+        got = raw_counts(eng, entries)
+        exp, exp_short = brute_force(entries)
+        assert got[1] == exp_short and got[2] == 0 and np.array_equal(got[0], exp)
+    check_offset_entries(eng)
 
 
 def test_gpu_short_cs_bad_bytes_and_no_alignments(eng, host):

@@ -14,7 +14,7 @@ import pytest
 from nanosim_amd import characterize, model
 from nanosim_amd import engine as EN
 from tests import oracle_lib
-from tests.test_chimeric_train import (BAD_CIGARS, CIRCULAR, HAND, SPECIES, E, build_host_walk, call, check_bad, check_circular, check_fixture, check_hand,
+from tests.test_chimeric_train import (BAD_CIGARS, CIRCULAR, HAND, SPECIES, E, build_host_walk, call, check_bad, check_cigar_bleed, check_circular, check_fixture, check_hand,
                                        check_mask_borders, load_fixture, many_compatible, many_overlapping, sam_file)
 
 pytestmark = pytest.mark.gpu
@@ -106,6 +106,7 @@ def test_gpu_hand_made_reads(eng, host):
 def test_gpu_bad_cigars(eng, host):
     for bad in BAD_CIGARS:
         check_bad(eng, bad)
+    check_cigar_bleed(eng)
     cigars = ["50M"] * 300 + ["50M7"] + ["%dS50M" % i for i in range(10)] + ["Z"]
     got, n_bad, first_bad, ms = characterize.cigar_spans(eng, cigars)
     want = characterize.cigar_spans(host, cigars)

@@ -11,7 +11,7 @@ import pytest
 
 from nanosim_amd import characterize
 from nanosim_amd import engine as EN
-from tests.test_quantify import build_host_engine, check_direct, items_of, load_fixture, sam_file
+from tests.test_quantify import build_host_engine, check_direct, check_fold_problems, items_of, load_fixture, sam_file
 
 pytestmark = pytest.mark.gpu
 W = 64
@@ -73,6 +73,14 @@ def test_gpu_fixture_problems(fx, eng, host):
         same_bits(g, characterize.em_call(host, prob))
         assert g["ms_kernel"] > 0
         print("%s: %d iterations, %.3f ms" % (d["name"], g["n_iter"], g["ms_kernel"]))
+
+
+def test_gpu_fold_patterns_of_the_stop_sum(eng, host):
+    """em_fold's device branch (chunks of 64 terms through cross-lane reads, two ways to fold a chunk) where only k_em_stop meets mixed
+    chunks: dabs[] non-zero at none, one, 20, 21 or all lanes of a chunk, at 1 .. 200 targets — against the plain-Python EM, and against
+    the host build, whose fold is a plain loop: another text"""
+    for name, prob, got in check_fold_problems(eng):
+        same_bits(got, characterize.em_call(host, prob))
 
 
 def test_gpu_random_problems_equal_the_host_build(eng, host):

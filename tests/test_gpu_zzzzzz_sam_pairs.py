@@ -14,7 +14,7 @@ import pytest
 from nanosim_amd import characterize
 from nanosim_amd import engine as E
 from tests.test_hp_train import KS
-from tests.test_sam_pairs import (BAD, HAND, SENTINEL, build_host_walk, check_bad_records, check_fixture, check_sizing, lines_of, load_fixture,
+from tests.test_sam_pairs import (BAD, HAND, SENTINEL, build_host_walk, check_bad_records, check_bleed, check_every_offset_and_length, check_fixture, check_sizing, lines_of, load_fixture,
                                   raw_build, rec, same)
 
 pytestmark = pytest.mark.gpu
@@ -160,9 +160,14 @@ def test_gpu_40_records_in_index_order_and_a_call_of_3(fx, eng, host):
 
 def test_gpu_bad_records_in_the_middle_of_a_call(eng, host):
     check_bad_records(eng, BAD)
+    check_bleed(eng)                                             # (the packed device buffers: a neighbour's bytes really are adjacent)
     recs = [rec(c, m, s) for c, m, s in BAD if len(s) < 100]
     g = equal_to_host(eng, host, recs)
     assert g[1].n_bad == len(recs) and g[1].n_bytes == 0 and (g[2] == SENTINEL).all() and not g[5].view(np.uint32).any()
+
+
+def test_gpu_md_strings_at_every_offset_and_length(eng):
+    check_every_offset_and_length(eng)
 
 
 @pytest.fixture(scope="module")

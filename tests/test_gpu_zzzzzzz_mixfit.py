@@ -89,7 +89,7 @@ def test_gpu_objective_fixture_points(fx, eng, host):
     assert n == 600
 
 
-@pytest.mark.parametrize("n_bins", [1, 2, 63, 64, 65, 128, 129, 1000])
+@pytest.mark.parametrize("n_bins", [1, 2, 63, 64, 65, 127, 128, 129, 1000])
 def test_gpu_objective_tile_borders(eng, host, n_bins):
     rng = np.random.default_rng(1000 + n_bins)
     cdf = seeded_cdf(rng, n_bins)

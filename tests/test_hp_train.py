@@ -124,6 +124,24 @@ def test_host_walk_equals_the_reference(fx, host, k):
     assert characterize.fit_homopolymers(t["table"], t["columns"])["mis_rate"] == fx["k"][str(k)]["mis_rate"]
 
 
+@pytest.mark.parametrize("k", (1, 5))
+def test_host_walk_is_clean_under_the_sanitizers(fx, tmp_path, k):
+    """the walk as a stand-alone program with -fsanitize=address,undefined (exact-size line buffers, the bounds of its local arrays) on
+    the fixture's alignments; what it prints is the reference's: the number of spans and calc_homopolymer_mis_rate's four counters"""
+    pairs = [(r[2], r[3]) for r in fx["records"] if r[2]]
+    path = os.path.join(str(tmp_path), "pairs.txt")
+    with open(path, "w") as f:
+        f.write("".join("%s %s\n" % p for p in pairs))
+    exe = os.path.join(str(tmp_path), "hp_train_host_san")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DHP_MAIN", "-o", exe,
+                           os.path.join(ROOT, "tests", "hp_train_host.cpp")])
+    out = subprocess.run([exe, path, str(k)], capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-2000:]
+    got = [int(v) for v in out.stdout.split()]
+    exp = expected_table(fx, k)
+    assert got[:5] == [len(fx["k"][str(k)]["spans"])] + expected_columns(fx, k) and got[5:] == [exp.shape[1] - 1, exp.shape[2] - 1]
+
+
 def test_fixture_holds_the_cases_the_kernel_has_paths_for(fx):
     lens = [len(r[2]) for r in fx["records"]]
     assert len(lens) > 256 + 64 and 0 in lens and max(lens) > 4096

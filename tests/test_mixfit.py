@@ -199,20 +199,38 @@ def box(x):
     return quadratic(x)
 
 
+def steps(x):
+    return math.floor(quadratic(x) * 4.0) / 4.0
+
+
+def slope(x):
+    a, t = float(x[0]), -2e-5
+    g = -1000.0 * a if a < t else -1000.0 * t - 0.5 * (a - t)
+    return (g - 0.01 * float(x[1])) - 0.001 * float(x[2])
+
+
+def cliff(height):
+    return lambda x: height if float(x[0]) > 1.02e-3 else 0.0
+
+
+HAND = (quadratic, box, steps, slope, cliff(1e-4), cliff(1.0000000000000002e-4))      # tests/mixfit_host.cpp: mixfit_host_hand's `which`
+
+
 def against_scipy(host, which, x0, maxiter=None, maxfev=None):
     from scipy.optimize import minimize
     n = len(x0)
     opt = {k: v for k, v in (("maxiter", maxiter), ("maxfev", maxfev)) if v is not None}
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        r = minimize((quadratic, box)[which], np.array(x0, dtype=np.float64), method="Nelder-Mead", options=opt)
+        r = minimize(HAND[which], np.array(x0, dtype=np.float64), method="Nelder-Mead", options=opt)
     big = 0xffffffff                                          # scipy: a limit that is not given is infinite once the other one is
     h = host.hand(which, x0, (maxiter or big) if opt else 200 * n, (maxfev or big) if opt else 200 * n)
     what = (which, x0, opt)
     assert np.array_equal(ML.bits(r.x), ML.bits(list(h.x)[:n])), what
     assert (r.nfev, r.nit, r.status) == (h.nfev, h.nit, h.status), (what, r.nfev, h.nfev, r.nit, h.nit, r.status, h.status)
     assert (np.isnan(r.fun) and np.isnan(h.fun)) or r.fun == h.fun, what
-    assert (np.isnan(h.residual) and np.isnan((quadratic, box)[which](r.x))) or h.residual == (quadratic, box)[which](r.x), what
+    if maxfev is None or maxfev > n:                          # (below that the first simplex is not evaluated in full: its best may be an `inf` never replaced)
+        assert (np.isnan(h.residual) and np.isnan(HAND[which](r.x))) or h.residual == HAND[which](r.x), what
     return r
 
 
@@ -226,11 +244,47 @@ def test_skeleton_equals_scipy(host):
         against_scipy(host, 1, x0)
 
 
+def test_skeleton_on_ties_equals_scipy(host):
+    """a function in steps of 1/4: the reflected, expanded and contracted values TIE with the vertices, so every `<` and `<=` of the
+    iteration decides (fxr < f[0], fxr < f[-2], fxr < f[-1], fxc <= fxr, fxcc < f[-1]), and so does the order of equal values"""
+    ties = 0
+    for x0 in ([1.0, 1.0, 1.0], [0.0, -1.0, 2.5], [2.3, 0.75, 2.0], [1.0, 0.0, 1.0, 0.0], [0.5, -2.0, 3.0, 1.0], [0.0, 0.0, 0.0, 0.0], [0.3, -1.25, 2.0, 4.75]):
+        for maxiter in (None, 1, 2, 3, 5, 8, 13, 21, 34):
+            r = against_scipy(host, 2, x0, maxiter=maxiter)
+            ties += len(set(r.final_simplex[1].tolist())) < len(x0) + 1
+    assert ties >= 10
+
+
+def test_stop_test_at_equality_equals_scipy(host):
+    """scipy stops when the largest coordinate difference AND the largest value difference to the best vertex are `<= 1e-4`
+    (xatol, fatol); both are met here with EQUALITY, which no search of the fixture does.
+    Values: a cliff of exactly the double 1e-4 under one vertex of the first simplex (whose coordinate steps are 5e-5): the search
+    stops before its first iteration; with a cliff one ulp higher it goes on.
+    Coordinates: a difference of two doubles is the double 1e-4 (an odd multiple of 2^-66) only where one of them lies below 2^-13, so
+    the first simplex (steps of 0.05 x, or 0.00025) cannot tie.  `slope` makes a simplex that starts at -4.76e-5 GROW by expansions —
+    steep below -2e-5, where the values differ by far more than 1e-4, gentle above — and the start is the double at which its size,
+    once every vertex is on the gentle part, is 1e-4 to the bit (found by a scan over neighbouring doubles under scipy 1.15.3); the
+    next double up makes it larger and the search runs on."""
+    r = against_scipy(host, 4, [1e-3, 1e-3, 1e-3])
+    assert (r.nfev, r.nit, r.status) == (4, 1, 0) and sorted(r.final_simplex[1].tolist()) == [0.0, 0.0, 0.0, 1e-4]
+    r = against_scipy(host, 5, [1e-3, 1e-3, 1e-3])
+    assert r.nfev > 4 and r.nit > 1
+    tie = float.fromhex("-0x1.8f752047c70c1p-15")
+    r = against_scipy(host, 3, [tie, 1e-6, 1e-6])
+    sim, fsim = r.final_simplex
+    assert (r.nfev, r.nit, r.status) == (21, 10, 0)
+    assert float(np.max(np.abs(sim[1:] - sim[0]))) == 1e-4 and float(np.max(np.abs(fsim[0] - fsim[1:]))) < 6e-5      # the x test decides, with equality
+    r = against_scipy(host, 3, [float(np.nextafter(tie, 0.0)), 1e-6, 1e-6])
+    assert r.nit > 10 and r.status == 1                        # (nothing holds it once it is past: it runs down the slope to maxfev)
+    r = against_scipy(host, 3, [float(np.nextafter(tie, -1.0)), 1e-6, 1e-6])
+    assert (r.nfev, r.nit, r.status) == (21, 10, 0) and float(np.max(np.abs(r.final_simplex[0][1:] - r.final_simplex[0][0]))) < 1e-4
+
+
 def test_skeleton_limits_equal_scipy(host):
     for x0 in ([1.0, 1.0, 1.0], [0.5, -2.0, 3.0, 1.0]):
         n = len(x0)
         for which in (0, 1):
-            for maxfev in range(n + 1, n + 40):               # every place an evaluation can be refused: reflection, expansion, both
+            for maxfev in range(1, n + 40):                   # the first simplex, then every place an evaluation can be refused: reflection, expansion, both
                 r = against_scipy(host, which, x0, maxfev=maxfev)      # contractions, and each vertex of a shrink
                 assert r.status == 1 and r.nfev == maxfev
             for maxiter in (1, 2, 3, 10, 37):

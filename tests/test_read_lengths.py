@@ -176,6 +176,10 @@ def check_bad_records(eng):
     assert aln["ref_len"][:70].all() and not aln.view(np.uint32).reshape(-1, 6)[70:70 + len(BAD)].any() and aln["ref_len"][-3:].tolist() == [12] * 3
     with pytest.raises(ValueError, match=r"%d SAM record\(s\).*first is record 70 \(r\)" % len(BAD)):
         characterize.count_read_lengths(eng, REF, recs)
+    # a count without an op directly in front of a CIGAR that begins with an op letter (the CIGARs of a call lie one behind the other)
+    recs = [rec("7M"), rec("10M5"), rec("M3M"), rec("12"), rec("S5M"), rec("9M")]
+    rc, out, aln, _, _ = raw_call(eng, REF, recs)
+    assert rc == 0 and (out.n_bad, out.first_bad) == (4, 1) and aln["ref_len"].tolist() == [7, 0, 0, 0, 0, 9] and aln["read_len"].tolist() == [7, 0, 0, 0, 0, 9]
     a = raw_call(eng, REF, [rec(GOOD[-1])])[2][0]
     assert (a["head"], a["tail"], a["read_len"], a["ref_len"], a["query_aln_len"]) == (5, 2, 5 + 10 + 3 + 2 + 4 + 9 + 1 + 2, 3 + 2 + 1 + 7 + 9, 3 + 2 + 4 + 9)
 

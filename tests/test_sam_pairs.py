@@ -6,6 +6,7 @@ import ctypes as C
 import gzip
 import json
 import os
+import re
 import subprocess
 import types
 
@@ -176,6 +177,8 @@ HAND = [   # CIGAR, MD, SEQ, reference line, query line, (head, tail, ref_len, q
     ("2M3I1M", "0C0G1", "TTAAAG", "CG---G", "TTAAAG", (0, 0, 3, 6)),                    # mismatches in front of an insertion
     ("1D3M", "0^T3", "ACG", "TACG", "-ACG", (0, 0, 4, 3)),                              # a deletion as the first op
     ("3M2D", "3^gt0", "ACG", "ACGgt", "ACG--", (0, 0, 5, 3)),                           # ... and as the last op
+    ("4M", "1z1Z0", "ACGT", "AzGZ", "ACGT", (0, 0, 4, 4)),                              # the last letters of both alphabets, as mismatches
+    ("1M4D1M", "1^zZAa1", "CG", "CzZAaG", "C----G", (0, 0, 6, 2)),                      # ... and the first, in a ^ run
 ]
 
 
@@ -203,6 +206,10 @@ BAD = [   # CIGAR, MD, SEQ: every kind of bad record
     ("4M", "3", "ACGT"), ("4M", "2A", "ACGT"), ("4M", "", "ACGT"), ("2M1D2M", "2", "ACGT"),                         # MD ends early
     ("4M", "5", "ACGT"), ("4M", "4A0", "ACGT"), ("4M", "4^A0", "ACGT"), ("4M", "A3", "ACGT"), ("4M", "4 ", "ACGT"),  # MD has items left over / is no MD
     ("%dM" % BIG, "%d" % BIG, "A" * BIG),                                                                           # 2^24 columns
+    # a second trailing S — with a SEQ that fits the last S alone, with one that fits both —, an S behind the trailing H, a second leading S
+    ("4M2S3S", "4", "ACGTCCC"), ("4M2S3S", "4", "ACGTTTCCC"), ("4M2H3S", "4", "ACGTCCC"), ("4M2S1H3S", "4", "ACGTTTCCC"), ("2S3S4M", "4", "CCCACGT"),
+    # an MD that ends where its next number has to stand, in front of a record whose MD begins with a digit (check_bad_records: `2^GG3`)
+    ("2I", "", "AC"), ("3M", "2A", "ACG"), ("2M1D", "2^A", "AC"), ("1M2I1M", "0T", "ACGT"),
 ]
 
 
@@ -230,6 +237,103 @@ def check_bad_records(eng, records):
     assert rc == 0 and (p.n_bad, p.first_bad) == (3, 1) and lines_of(ref, qry, off) == [exp[0], ("", ""), exp[1], ("", ""), ("", ""), exp[2]]
     with pytest.raises(ValueError, match="first is record 1 "):
         characterize.pairs_from_sam(eng, recs)
+
+
+# The strings of a call lie one behind the other: a walk that looks one byte too far sees the FIRST byte of the next record's string.
+# Every case: records whose CIGAR or MD ends early, each directly in front of a neighbour whose string begins with what the walk would
+# have wanted next; (records, which of them are good).  The bad one stays bad and the neighbour is judged on its own.
+BLEED = [
+    # MD ends one item early; the neighbour's MD begins with a letter (itself no MD), with `^X` (itself no MD), with a digit (a good one)
+    ([("4M", "2", "ACGT"), ("4M", "A3", "ACGT")], [False, False]),
+    ([("4M", "2", "ACGT"), ("4M", "4", "ACGT")], [False, True]),
+    ([("2M1D2M", "2", "ACGT"), ("2M1D2M", "^A4", "ACGT")], [False, False]),
+    ([("2M1D2M", "2^", "ACGT"), ("4M", "A3", "ACGT")], [False, False]),
+    ([("2M2D1M", "2^A", "ACG"), ("4M", "C3", "ACGT")], [False, False]),
+    ([("2M1D", "2^A", "AC"), ("4M", "C3", "ACGT")], [False, False]),
+    ([("2M1D", "2^A", "AC"), ("4M", "4", "ACGT")], [False, True]),
+    ([("3M", "2A", "ACG"), ("4M", "4", "ACGT")], [False, True]),
+    ([("3M", "2A", "ACG"), ("2M1D2M", "2^G2", "ACGT")], [False, True]),
+    ([("2I", "", "AC"), ("4M", "4", "ACGT")], [False, True]),
+    ([("2I", "", "AC"), ("2I", "0", "AC")], [False, True]),
+    ([("4M", "1", "ACGT"), ("3M", "3", "ACG")], [False, True]),                          # (1 + 3 would be the four columns)
+    # CIGAR: a count without an op; the neighbour's CIGAR begins with an op letter (itself no CIGAR), or with a digit
+    ([("4", "4", "ACGT"), ("M", "1", "A")], [False, False]),
+    ([("4", "4", "ACGT"), ("M4M", "4", "ACGT")], [False, False]),
+    ([("2M2", "4", "ACGT"), ("I1M", "1", "A")], [False, False]),
+    ([("2M2", "4", "ACGT"), ("2M", "2", "AC")], [False, True]),
+    ([("4", "4", "ACGT"), ("4M", "4", "ACGT")], [False, True]),
+]
+BLEED_LINES = {("4M", "4", "ACGT"): ("ACGT", "ACGT"), ("2M1D2M", "2^G2", "ACGT"): ("ACGGT", "AC-GT"), ("2I", "0", "AC"): ("--", "AC"),
+               ("3M", "3", "ACG"): ("ACG", "ACG"), ("2M", "2", "AC"): ("AC", "AC")}
+
+
+def check_bleed(eng):
+    """every BLEED case alone between `H S .. S H` and a plain record, then all of them in one call: the verdicts, the lines and the figures"""
+    first, last = rec("2H3S4M1S5H", "4", "TTTACGTA"), rec("1M", "1", "N")
+    def expect(records, good):
+        return [("ACGT", "ACGT")] + [BLEED_LINES[r] if g else ("", "") for r, g in zip(records, good)] + [("N", "N")]
+    everything, verdicts = [], []
+    for records, good in BLEED:
+        assert all(r in BLEED_LINES for r, g in zip(records, good) if g)
+        rc, p, ref, qry, off, aln = raw_build(eng, [first] + [rec(*r) for r in records] + [last])
+        assert rc == 0 and lines_of(ref, qry, off) == expect(records, good), records
+        bad = [i + 1 for i, g in enumerate(good) if not g]
+        assert (p.n_bad, p.first_bad) == (len(bad), bad[0]), records
+        assert [tuple(map(int, a)) for a in aln.tolist()][0] == (3, 1, 4, 4) and all(tuple(map(int, aln[i])) == (0, 0, 0, 0) for i in bad)
+        assert (ref[int(p.n_bytes):] == SENTINEL).all() and (qry[int(p.n_bytes):] == SENTINEL).all()
+        everything += records
+        verdicts += good
+    rc, p, ref, qry, off, aln = raw_build(eng, [first] + [rec(*r) for r in everything] + [last])
+    assert rc == 0 and lines_of(ref, qry, off) == expect(everything, verdicts) and p.n_bad == verdicts.count(False) and p.first_bad == 1
+
+
+def md_record(n, letters="ACGazZ"):
+    """an M-only record whose MD has n bytes: `1` or `10`, then n // 2 (less one) pairs of a letter and `1`; n == 0: an empty MD, a bad record"""
+    md = ("1" if n % 2 else "10" if n else "") + "".join(letters[k % len(letters)] + "1" for k in range((n - 1) // 2))
+    cols = sum(int(t) if t.isdigit() else 1 for t in re.findall(r"\d+|[A-Za-z]", md)) or 3
+    assert len(md) == n
+    return ("%dM" % cols, md, "T" * cols)
+
+
+def plain_lines(md, seq):
+    """the two lines of an M-only record, from its MD alone: digits copy SEQ, a letter stands in the reference line"""
+    ref, i = [], 0
+    for t in re.findall(r"\d+|[A-Za-z]", md):
+        ref.append(seq[i:i + int(t)] if t.isdigit() else t)
+        i += int(t) if t.isdigit() else 1
+    return "".join(ref), seq
+
+
+def check_every_offset_and_length(eng):
+    """one call in which an MD of every length 0 .. 17 begins at every offset 0 .. 7 mod 8 of the packed MD bytes (the device reads
+    CIGAR, MD and SEQ through aligned 8-byte windows); the CIGARs, two or three bytes each, come by every offset on the way"""
+    recs, at, where = [], 0, []
+    for n in range(18):
+        for o in range(8):
+            if at % 8 != o:
+                recs.append(md_record((o - at) % 8, "C"))
+                at += len(recs[-1][1])
+            where.append(len(recs))
+            recs.append(md_record(n))
+            at += n
+    md_off = np.cumsum([0] + [len(r[1]) for r in recs])
+    cg_off = np.cumsum([0] + [len(r[0]) for r in recs])
+    assert {(int(md_off[i]) % 8, len(recs[i][1])) for i in where} == {(o, n) for o in range(8) for n in range(18)}
+    assert {int(o) % 8 for o in cg_off[:-1]} == set(range(8))
+    want = [plain_lines(m, q) if m else ("", "") for _, m, q in recs]
+    for order in (recs, recs[::-1]):
+        rc, p, ref, qry, off, aln = raw_build(eng, [rec(*r) for r in order])
+        assert rc == 0 and p.n_bad == 8 and lines_of(ref, qry, off) == (want if order is recs else want[::-1])
+        assert [tuple(map(int, a)) for a in aln.tolist()] == [(0, 0, len(q), len(q)) if m else (0, 0, 0, 0) for _, m, q in order]
+        assert (ref[int(p.n_bytes):] == SENTINEL).all() and (qry[int(p.n_bytes):] == SENTINEL).all()
+
+
+def test_md_strings_at_every_offset_and_length(host):
+    check_every_offset_and_length(host)
+
+
+def test_a_string_that_ends_early_does_not_borrow_from_its_neighbour(host):
+    check_bleed(host)
 
 
 def test_bad_records(host):
