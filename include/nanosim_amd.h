@@ -587,6 +587,42 @@ typedef struct ns_em_result {
 } ns_em_result;
 int ns_em_quantify(ns_ctx *ctx, const ns_em_problem *p, ns_em_result *out);
 
+/* ---- training side: the intron-retention model, the Markov counts ---------------------------------------------------------------------------------
+ * replaces the loop of intron_retention (src/model_intron_retention.py, M:104-176) over every read that has a genome alignment and a
+ * transcriptome alignment; nanosim_amd/csrc/ns_ir_train.h says how, with every corner of the reference that is kept.
+ * Per read r = 0 .. n_reads - 1: the CIGAR text of its genome alignment, start[r] its 0-based reference start, chrom[r] the id of its
+ * chromosome among those that carry introns (< n_chrom) or NS_IR_NONE when none lives on it, trx[r] the id of its transcript (< n_trx)
+ * or NS_IR_NONE when the annotation has no intron for it.  Per transcript t (ns_ir_introns): its introns intr_off[t] .. intr_off[t + 1] - 1
+ * in the order of the annotation (chromosome id, 0-based start, end) and the union of them as intervals merged_off[t] ..
+ * merged_off[t + 1] - 1, sorted by (chromosome, start), none empty, no two overlapping or touching.
+ * Out: first[2] (the first intron of a counted read: [0] not retained, [1] retained), states[4] ([2 * previous + current] for every later
+ * intron), state[n_reads] (NS_IR_READ_NONE: nothing counted, NS_IR_READ_NO_IR: counted without a retained intron, NS_IR_READ_IR:
+ * counted with one or more), retained[ceil(introns / 32)] (bit i & 31 of word i >> 5: intron i — an index into intr_* — is retained by at
+ * least one read).  A BAD CIGAR (empty, an unknown op, a count without an op or the reverse, a reference position beyond 2^32 - 1) is
+ * counted in n_bad, first_bad the smallest index of one (n_reads without); such a read counts nothing.  n_reads == 0 is valid.
+ * NS_EINVAL for offsets that do not ascend from 0 and ids out of range.  Added without an ABI change. */
+#define NS_IR_NONE 0xFFFFFFFFu
+#define NS_IR_READ_NONE 0
+#define NS_IR_READ_NO_IR 1
+#define NS_IR_READ_IR 2
+typedef struct ns_ir_introns {
+    uint32_t n_trx, n_chrom;
+    const uint64_t *intr_off;       /* n_trx + 1, from 0 */
+    const uint32_t *intr_chrom, *intr_start, *intr_end;          /* intr_off[n_trx] each */
+    const uint64_t *merged_off;     /* n_trx + 1, from 0 */
+    const uint32_t *merged_chrom, *merged_start, *merged_end;    /* merged_off[n_trx] each */
+} ns_ir_introns;
+typedef struct ns_ir_train_result {
+    uint8_t *state;             /* in: host buffer of n_reads entries (out) */
+    uint32_t *retained;         /* in: host buffer of ceil(intr_off[n_trx] / 32) words (out) */
+    uint64_t first[2];          /* out */
+    uint64_t states[4];         /* out */
+    uint64_t n_bad, first_bad;  /* out */
+    double ms_kernel;
+} ns_ir_train_result;
+int ns_ir_train(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off, const uint32_t *start, const uint32_t *chrom,
+                const uint32_t *trx, uint32_t n_reads, const ns_ir_introns *introns, ns_ir_train_result *out);
+
 /* device address of a result buffer (for zero-copy consumers such as torch / RCCL); NULL if absent */
 const void *ns_device_ptr(ns_ctx *ctx, int which);
 

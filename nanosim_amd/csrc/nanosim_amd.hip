@@ -16,7 +16,7 @@
 //   k_errlog            wave/read     _aligned_error_profile rows                           (S:2006-2008)
 // Metagenome worker calls run k_lengths / k_chain per PASS of the reference's while loop (S:844-1040) with k_meta_* around them; the lists of a
 // pass are launched before the host has walked the species quotas (assign_species), k_meta_tail does positions + acceptance afterwards.
-// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms, ns_sam_pairs_build, ns_mixture_fit, ns_read_lengths, ns_cigar_spans, ns_chimeric_select, ns_em_quantify: at the end of the host part) has its kernels in ns_train.h.
+// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms, ns_sam_pairs_build, ns_mixture_fit, ns_read_lengths, ns_cigar_spans, ns_chimeric_select, ns_em_quantify, ns_ir_train: at the end of the host part) has its kernels in ns_train.h.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdio.h>
@@ -4653,6 +4653,64 @@ int ns_em_quantify(ns_ctx *ctx, const ns_em_problem *p, ns_em_result *out) {
     if (int rc = timed_tail(s, {{out->abundance, d_a, (size_t)nt * 8}, {out->count, d_count, (size_t)nt * 8},
                                 {out->diff_trace, d_trace, (size_t)p->max_iter * 8}}, &out->ms_kernel)) return rc;
     out->n_iter = now.n_iter; out->n_nonfinite = now.n_nonfinite;
+    return NS_OK;
+}
+
+// the Markov counts of the intron-retention model (include/nanosim_amd.h: ns_ir_train_result; ns_ir_train.h;
+// src/model_intron_retention.py:104-176): the rows are laid out here — a prefix sum of the row words of every read's transcript —, then
+// k_ir_walk, one read per thread
+int ns_ir_train(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off, const uint32_t *start, const uint32_t *chrom,
+                const uint32_t *trx, uint32_t n_reads, const ns_ir_introns *introns, ns_ir_train_result *out) {
+    if (!ctx) return NS_EINVAL;
+    if (!out || !introns) return fail(ctx, NS_EINVAL, "ns_ir_train: null argument");
+    out->first[0] = out->first[1] = 0; out->states[0] = out->states[1] = out->states[2] = out->states[3] = 0;
+    out->n_bad = 0; out->first_bad = n_reads; out->ms_kernel = 0;
+    if (n_reads >= (1u << 31)) return fail(ctx, NS_EINVAL, "ns_ir_train: 2^31 reads or more");
+    static_assert(sizeof(IrTables) == sizeof(ns_ir_introns), "ns_ir_train.h mirrors the ABI struct");
+    const IrTables T{introns->n_trx, introns->n_chrom, introns->intr_off, introns->intr_chrom, introns->intr_start, introns->intr_end,
+                     introns->merged_off, introns->merged_chrom, introns->merged_start, introns->merged_end};
+    if (const char *why = ir_check_tables(T)) return fail(ctx, NS_EINVAL, std::string("ns_ir_train: ") + why);
+    const uint64_t n_intr = T.intr_off[T.n_trx], n_merged = T.merged_off[T.n_trx], bm_words = ir_row_words(n_intr);
+    if (n_intr && !out->retained) return fail(ctx, NS_EINVAL, "ns_ir_train: null argument");
+    for (uint64_t w = 0; w < bm_words; ++w) out->retained[w] = 0;
+    if (!n_reads) return NS_OK;
+    if (!out->state || !cigar_off || !start || !chrom || !trx) return fail(ctx, NS_EINVAL, "ns_ir_train: null argument");
+    if (int rc = check_offsets(ctx, "ns_ir_train", "CIGAR strings", cigar_off, n_reads, cigar_off[n_reads])) return rc;
+    if (!cigar && cigar_off[n_reads]) return fail(ctx, NS_EINVAL, "ns_ir_train: null argument");
+    if (const char *why = ir_check_reads(T, chrom, trx, n_reads)) return fail(ctx, NS_EINVAL, std::string("ns_ir_train: ") + why);
+    HIPCHK(hipSetDevice(ctx->device));
+    std::vector<uint64_t> row_off((size_t)n_reads + 1);
+    row_off[0] = 0;
+    for (uint32_t r = 0; r < n_reads; ++r)
+        row_off[r + 1] = row_off[r] + (trx[r] == NS_IR_NONE ? 0u : ir_row_words(T.intr_off[trx[r] + 1u] - T.intr_off[trx[r]]));
+    unsigned long long small[IRS_WORDS] = {0ull, ~0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+    CallScratch s(ctx, "ns_ir_train");
+    const uint8_t *d_cigar = s.filled(cigar, (size_t)cigar_off[n_reads], 16);         // (16 bytes to spare: the window loads of CsBytes)
+    const uint64_t *d_cigar_off = s.filled(cigar_off, (size_t)n_reads + 1), *d_row_off = s.filled(row_off.data(), (size_t)n_reads + 1);
+    const uint32_t *d_start = s.filled(start, (size_t)n_reads), *d_chrom = s.filled(chrom, (size_t)n_reads), *d_trx = s.filled(trx, (size_t)n_reads);
+    IrTables D = T;                                                                    // (intr_chrom stays on the host: the walk does not read it)
+    D.intr_chrom = nullptr;
+    D.intr_off = s.filled(T.intr_off, (size_t)T.n_trx + 1); D.merged_off = s.filled(T.merged_off, (size_t)T.n_trx + 1);
+    D.intr_start = s.filled(T.intr_start, (size_t)n_intr, 4); D.intr_end = s.filled(T.intr_end, (size_t)n_intr, 4);
+    D.merged_chrom = s.filled(T.merged_chrom, (size_t)n_merged, 4); D.merged_start = s.filled(T.merged_start, (size_t)n_merged, 4);
+    D.merged_end = s.filled(T.merged_end, (size_t)n_merged, 4);
+    uint32_t *d_rows = s.zeroed<uint32_t>((size_t)row_off[n_reads], 4);
+    uint32_t *d_bitmap = s.zeroed<uint32_t>((size_t)bm_words + 1);
+    uint8_t *d_state = s.alloc<uint8_t>(n_reads);
+    unsigned long long *d_small = s.filled(small, IRS_WORDS);
+    if (int rc = s.upload()) return rc;
+    hipStream_t st = ctx->stream;
+    CALLCHK(s, hipEventRecord(ctx->evt[EV_HIST_BEGIN], st));
+    uint32_t *d_order;
+    if (int rc = order_by_length(s, d_cigar_off, n_reads, &d_order)) return rc;
+    k_ir_walk<<<dim3((n_reads + 255u) / 256u), dim3(256), 0, st>>>(d_cigar, d_cigar_off, d_start, d_chrom, d_trx, n_reads, d_order, D, d_rows, d_row_off,
+                                                                   d_bitmap, d_state, d_small);
+    CALLCHK(s, hipGetLastError());
+    if (int rc = timed_tail(s, {{small, d_small, sizeof small}, {out->state, d_state, (size_t)n_reads}, {out->retained, d_bitmap, (size_t)bm_words * 4}},
+                            &out->ms_kernel)) return rc;
+    out->first[0] = small[IRS_COUNT + IRC_FIRST]; out->first[1] = small[IRS_COUNT + IRC_FIRST + 1];
+    for (int i = 0; i < 4; ++i) out->states[i] = small[IRS_COUNT + IRC_STATES + i];
+    out->n_bad = small[IRS_BAD]; out->first_bad = out->n_bad ? small[IRS_FIRST] : n_reads;
     return NS_OK;
 }
 

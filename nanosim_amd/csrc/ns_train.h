@@ -1,11 +1,12 @@
 // ns_train.h — training side, the device kernels: the counting loops of the characterisation stage (k_cs_len, k_cs_hist),
 // of the base-quality model (k_qual_mark, k_qual_count) and of the homopolymer-length model (k_hp_count, k_hp_records), and the line pairs
 // of SAM records (k_sam_scan, k_sam_lines), the fit of the error-length mixtures (k_mixfit), and the lengths behind the read-length
-// models (k_len_scan, k_len_flag, k_len_reduce), the split-alignment choice of chimeric reads (k_chim_scan, k_chim_select), and the EM of
-// the abundance quantification (k_em_estep, k_em_accum, k_em_stop).  The walks they run are ns_cs_hist.h, ns_qual_hist.h, ns_hp_hist.h,
-// ns_sam_pairs.h, ns_mixfit.h, ns_read_len.h, ns_chimeric.h and ns_em.h, which also compile for the host; the host side of the calls
+// models (k_len_scan, k_len_flag, k_len_reduce), the split-alignment choice of chimeric reads (k_chim_scan, k_chim_select), the EM of
+// the abundance quantification (k_em_estep, k_em_accum, k_em_stop), and the Markov counts of the intron-retention model (k_ir_walk).  The
+// walks they run are ns_cs_hist.h, ns_qual_hist.h, ns_hp_hist.h, ns_sam_pairs.h, ns_mixfit.h, ns_read_len.h, ns_chimeric.h, ns_em.h and
+// ns_ir_train.h, which also compile for the host; the host side of the calls
 // (ns_cs_histograms / ns_maf_histograms, ns_qual_histograms, ns_hp_histograms / ns_hp_histograms_sam, ns_sam_pairs_build, ns_mixture_fit,
-// ns_read_lengths, ns_cigar_spans / ns_chimeric_select, ns_em_quantify) is at the end of nanosim_amd.hip.  Nothing here uses GenArgs or the simulation.
+// ns_read_lengths, ns_cigar_spans / ns_chimeric_select, ns_em_quantify, ns_ir_train) is at the end of nanosim_amd.hip.  Nothing here uses GenArgs or the simulation.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,6 +19,7 @@
 #include "ns_read_len.h"
 #include "ns_chimeric.h"
 #include "ns_em.h"
+#include "ns_ir_train.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // k_cs_hist: the counting loop of the characterisation stage (ns_cs_hist.h; src/besthit_to_histogram.py:316-365), one alignment per
@@ -532,4 +534,54 @@ __global__ void __launch_bounds__(256) k_em_stop(EmState *__restrict__ S, const 
     for (uint32_t i = threadIdx.x + 64u; i < 256u; i += 64u) mn = mn_s[i] < mn ? mn_s[i] : mn;
     for (int o = 32; o > 0; o >>= 1) { const double u = __shfl_xor(mn, o, 64); mn = u < mn ? u : mn; }
     if (threadIdx.x == 0) em_decide(S, diff_tmp, mn, bad_s, factor, max_iter, diff_trace);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_ir_walk: the Markov counts of the intron-retention model (ns_ir_train.h; src/model_intron_retention.py:104-176), one read per
+// thread, visited by descending CIGAR length as k_len_scan, through an 8-byte CsBytes window.  A read marks the introns it retains in
+// its own bit row (rows + row_off[r], ir_row_words(introns of its transcript) words, zeroed by the caller: a read can retain every
+// intron of its transcript, and no list of fixed size stands between it and that), counts from the row, and ORs the row into the
+// bitmap over all introns — the row's bit 0 is bit intr_off[t] there, so a word of the row goes to two words of the bitmap (which has
+// one word to spare).  The six counters are privatised per workgroup in LDS and leave in one 64-bit atomic each.  A bad CIGAR leaves
+// state 0, no count and no bit.  Integers only: the order of the atomics never shows.
+// small[]: IRS_BAD CIGARs that are bad, IRS_FIRST the smallest index of one (preset to ~0), IRS_COUNT the six counts (IRC_*).
+// ---------------------------------------------------------------------------------------------------------
+enum { IRS_BAD = 0, IRS_FIRST = 1, IRS_COUNT = 2, IRS_WORDS = IRS_COUNT + IRC_WORDS };
+__global__ void __launch_bounds__(256) k_ir_walk(const uint8_t *__restrict__ cigar, const uint64_t *__restrict__ cigar_off, const uint32_t *__restrict__ start,
+                                                 const uint32_t *__restrict__ chrom, const uint32_t *__restrict__ trx, uint32_t n_reads,
+                                                 const uint32_t *__restrict__ order, IrTables T, uint32_t *__restrict__ rows,
+                                                 const uint64_t *__restrict__ row_off, uint32_t *__restrict__ bitmap, uint8_t *__restrict__ state,
+                                                 unsigned long long *__restrict__ small) {
+    __shared__ unsigned long long cnt[IRC_WORDS];
+    if (threadIdx.x < IRC_WORDS) cnt[threadIdx.x] = 0ull;
+    __syncthreads();
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid < n_reads) {
+        const uint64_t r = order ? order[tid] : tid;
+        const uint32_t t = trx[r];
+        const IrTrx X = ir_trx(T, t);                              // (trx < n_trx or NS_IR_NONE: the host checks)
+        uint32_t *row = rows + row_off[r];
+        CsBytes cb(cigar + cigar_off[r]);
+        bool ir_info;
+        uint32_t st = IR_READ_NONE;
+        if (ir_walk_read(cb, cigar_off[r + 1] - cigar_off[r], start[r], chrom[r], X, row, ir_info)) {
+            unsigned long long c[IRC_WORDS] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+            st = ir_markov_read(X.n, row, ir_info, c);
+            for (uint32_t i = 0; i < IRC_WORDS; ++i) if (c[i]) atomicAdd(&cnt[i], c[i]);
+            if (st == IR_READ_IR) {
+                const uint64_t bit0 = T.intr_off[t];
+                for (uint64_t w = 0, nw = ir_row_words(X.n); w < nw; ++w) {
+                    const uint32_t v = row[w];
+                    if (!v) continue;
+                    const uint64_t bit = bit0 + 32u * w;
+                    const uint32_t sh = (uint32_t)(bit & 31u);
+                    atomicOr(&bitmap[bit >> 5], v << sh);
+                    if (sh && (v >> (32u - sh))) atomicOr(&bitmap[(bit >> 5) + 1u], v >> (32u - sh));
+                }
+            }
+        } else { atomicAdd(&small[IRS_BAD], 1ull); atomicMin(&small[IRS_FIRST], (unsigned long long)r); }
+        state[r] = (uint8_t)st;
+    }
+    __syncthreads();
+    if (threadIdx.x < IRC_WORDS && cnt[threadIdx.x]) atomicAdd(&small[IRS_COUNT + threadIdx.x], cnt[threadIdx.x]);
 }

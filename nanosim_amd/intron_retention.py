@@ -73,9 +73,12 @@ def parse_gff_attributes(text: str):
     return d, first
 
 
-def read_structure(gff_path: str) -> dict:
-    """dict_ref_structure (S:425-452): {transcript id: [(type, chrom, start, end, length, strand), ...]} in file order"""
-    out: dict = {}
+def gff_features(gff_path: str, types=None):
+    """(transcript id, type, chromosome, start, end, strand) of every row of a GFF3 whose id resolves, in file order, as both
+    read_profile (S:425-452) and model_intron_retention (M:38-66) read it through HTSeq: the id is ``transcript_id``, else — with a
+    ``Parent`` — the first attribute's value, `transcript:` cut off, and cut at the first `.`; the chromosome goes through
+    ``str.strip("chr")`` (a set of characters: `chr1c` becomes `1`); start = column 4 - 1, end = column 5.  types: the feature types
+    wanted (None: all)"""
     with open(gff_path) as f:
         for line in f:
             if line == "\n" or line.startswith("#"):
@@ -84,7 +87,7 @@ def read_structure(gff_path: str) -> dict:
             if len(cols) < 9:
                 raise ValueError("GFF3 line with fewer than 9 columns: " + line.strip())
             ftype = cols[2]
-            if ftype != "exon" and ftype != "intron":
+            if types is not None and ftype not in types:
                 continue
             attr, name = parse_gff_attributes(cols[8])
             if "transcript_id" in attr:
@@ -103,8 +106,14 @@ def read_structure(gff_path: str) -> dict:
             chrom = cols[0]
             if "chr" in chrom:
                 chrom = chrom.strip("chr")                                     # S:448-449 (str.strip: a set of characters)
-            start, end = int(cols[3]) - 1, int(cols[4])
-            out.setdefault(fid, []).append((ftype, chrom, start, end, end - start, cols[6]))
+            yield fid, ftype, chrom, int(cols[3]) - 1, int(cols[4]), cols[6]
+
+
+def read_structure(gff_path: str) -> dict:
+    """dict_ref_structure (S:425-452): {transcript id: [(type, chrom, start, end, length, strand), ...]} in file order"""
+    out: dict = {}
+    for fid, ftype, chrom, start, end, strand in gff_features(gff_path, ("exon", "intron")):
+        out.setdefault(fid, []).append((ftype, chrom, start, end, end - start, strand))
     return out
 
 
