@@ -343,22 +343,35 @@ NS_DEV uint8_t bases_atcg(uint32_t j) { return (uint8_t)(0x47435441u >> (8 * j))
 NS_DEV int base_rank(uint32_t c) { return c == 'A' ? 0 : c == 'T' ? 1 : c == 'C' ? 2 : c == 'G' ? 3 : -1; }
 NS_DEV bool is_acgt(uint32_t c) { return ((1u << ((c - 65u) & 31u)) & 0x00080045u) != 0 && (c - 65u) < 26u; }
 
-// case_convert (S:743-755): members in the reference's list order, packed little-endian; count in the top byte index
-NS_DEV uint32_t iupac_members(uint32_t c, uint32_t &n) {
-    switch (c) {
-        case 'Y': n = 2; return 'C' | 'T' << 8;
-        case 'R': n = 2; return 'A' | 'G' << 8;
-        case 'W': n = 2; return 'A' | 'T' << 8;
-        case 'S': n = 2; return 'G' | 'C' << 8;
-        case 'K': n = 2; return 'T' | 'G' << 8;
-        case 'M': n = 2; return 'C' | 'A' << 8;
-        case 'D': n = 3; return 'A' | 'G' << 8 | 'T' << 16;
-        case 'V': n = 3; return 'A' | 'C' << 8 | 'G' << 16;
-        case 'H': n = 3; return 'A' | 'C' << 8 | 'T' << 16;
-        case 'B': n = 3; return 'C' | 'G' << 8 | 'T' << 16;
-        case 'N': case 'X': n = 4; return 0x47435441u;
-        default: n = 0; return 0;
+// case_convert (S:743-755): members in the reference's list order, packed little-endian; n = how many (0: c is no code).
+// Straight-line: every code is a letter of 64..95, so c & 31 indexes five 64-bit immediates of one 2-bit field per letter — n - 1 and,
+// per member slot, the member's index in "ATCG".  (As a switch this was a compare-and-branch tree of ~150 instructions that a whole
+// wavefront issued for the one lane that held a code.)
+struct IupacPack { uint64_t cnt, slot[4]; };
+constexpr IupacPack iupac_pack() {
+    constexpr struct { char code; const char *mem; } list[12] = {
+        {'Y', "CT"}, {'R', "AG"}, {'W', "AT"}, {'S', "GC"}, {'K', "TG"}, {'M', "CA"},
+        {'D', "AGT"}, {'V', "ACG"}, {'H', "ACT"}, {'B', "CGT"}, {'N', "ATCG"}, {'X', "ATCG"}};
+    IupacPack p{0, {0, 0, 0, 0}};
+    for (int e = 0; e < 12; ++e) {
+        const uint32_t i = (uint32_t)list[e].code & 31u;
+        uint32_t k = 0;
+        for (; list[e].mem[k]; ++k) {
+            const char b = list[e].mem[k];
+            p.slot[k] |= (uint64_t)(b == 'A' ? 0 : b == 'T' ? 1 : b == 'C' ? 2 : 3) << (2u * i);      // BASES, S:49
+        }
+        p.cnt |= (uint64_t)(k - 1u) << (2u * i);
     }
+    return p;
+}
+NS_DEV uint32_t iupac_members(uint32_t c, uint32_t &n) {
+    constexpr IupacPack P = iupac_pack();
+    const uint32_t sh = 2u * (c & 31u);
+    const uint32_t code = (c >> 5) == 2u ? (uint32_t)(P.cnt >> sh) & 3u : 0u;              // n - 1; 0: not a code
+    n = code + (code != 0u);
+    uint32_t mem = 0;
+    for (uint32_t k = 0; k < 4u; ++k) mem |= ((0x47435441u >> (8u * ((uint32_t)(P.slot[k] >> sh) & 3u))) & 0xffu) << (8u * k);
+    return code ? mem & (0xffffffffu >> (8u * (3u - code))) : 0u;
 }
 // device form of the reference: upper-case ASCII; IUPAC ambiguity codes (and anything else, as N) carry bit 7
 // so that "needs case_convert's random choice" is one AND per 4 bases

@@ -384,6 +384,34 @@ __device__ __forceinline__ void lds_put_bytes(LdsBytes d, uint32_t x0, uint32_t 
     if (tail > 2) e[2] = (uint8_t)(yt >> 16);
 }
 
+// IUPAC codes in a masked 16-byte group whose byte b lies at segment position x0 + b (case_convert, S:743-755: rare).
+// The group arrives MASKED to the bytes in question (every caller zeroes the others), so bit 7 of a byte says "code to resolve" by itself:
+// the loop takes the marked bytes one by one, lowest first — one iteration per code and none for a plain byte.  (A walk over every byte of
+// the range was 20 instructions per plain byte, issued by the whole wavefront whenever one of its lanes held a code.)  `among`: bit b set =
+// byte b may be resolved (the dense pieces load 16 bytes and copy fewer).
+NS_DEV uint32_t marked4(uint32_t w) { return (((w >> 7) & 0x01010101u) * 0x01020408u) >> 24; }   // bit 7 of byte k -> bit k (no two terms of the product meet)
+NS_DEV void resolve16(uint32_t &a0, uint32_t &a1, uint32_t &a2, uint32_t &a3, uint32_t among, uint32_t x0,
+                      const ns_key &key, uint32_t sid, uint32_t a) {
+    uint32_t mk = (marked4(a0) | marked4(a1) << 4 | marked4(a2) << 8 | marked4(a3) << 12) & among;
+    while (mk) {
+        const uint32_t b = (uint32_t)__builtin_ctz(mk), sh = 8u * (b & 3u);
+        mk &= mk - 1u;
+        uint32_t wk = b < 8 ? (b < 4 ? a0 : a1) : (b < 12 ? a2 : a3);
+        const uint32_t r = resolve_base((wk >> sh) & 0xffu, key, sid, a, x0 + b);
+        wk = (wk & ~(0xffu << sh)) | r << sh;
+        if (b < 4) a0 = wk; else if (b < 8) a1 = wk; else if (b < 12) a2 = wk; else a3 = wk;
+    }
+}
+// the same for one dword of four bases (the bases under a group of four substitution letters)
+NS_DEV void resolve4(uint32_t &w, uint32_t among, uint32_t x0, const ns_key &key, uint32_t sid, uint32_t a) {
+    uint32_t mk = marked4(w) & among;
+    while (mk) {
+        const uint32_t b = (uint32_t)__builtin_ctz(mk), sh = 8u * b;
+        mk &= mk - 1u;
+        w = (w & ~(0xffu << sh)) | (uint32_t)resolve_base((w >> sh) & 0xffu, key, sid, a, x0 + b) << sh;
+    }
+}
+
 // ---- dense pieces: lane per event -----------------------------------------------------------------------------
 // Unaligned reads (S:1482-1549) and the gaps of chimeric reads carry ~0.55 events per base: an event owns two output bytes on
 // average — its letters, then the reference bases copied behind them up to the next event.  One lane per event (item 0 = the stretch
@@ -424,13 +452,14 @@ __device__ inline void dense_piece(const DevModel &m, const DevRef &ref, DenseLd
             const uint32_t cn = act && c_lo < hi ? hi - c_lo : 0u;                    // copied bases behind them
             const uint32_t x0 = rp + (c_lo - os - pl);                                // output byte mm <- segment position rp + (mm - os - pl)
             // ---- straight-line path: the letters four at a time (byte permutes, as the tiled kernel), the copied bases from one
-            // 16-byte load, stored with aligned LDS stores (lds_put_bytes).  Items cut by the tile border, stretches of > 16 bases, IUPAC codes under
-            // the copy and the origin of a circular chromosome take the per-byte walk below.
+            // 16-byte load, stored with aligned LDS stores (lds_put_bytes).  Items cut by the tile border, stretches of > 16 bases and
+            // the origin of a circular chromosome take the per-byte walk below.
             const bool fast_l = n_let && os >= M0 && (ty == NS_INS || (uint64_t)pos + n_let <= lin);
-            bool fast_c = cn && cn <= 16u && (uint64_t)x0 + 16u <= lin;
+            const bool fast_c = cn && cn <= 16u && (uint64_t)x0 + 16u <= lin;
             uint4 f = make_uint4(0, 0, 0, 0);
             if (fast_c) __builtin_memcpy(&f, seg0 + x0, 16);
-            if ((f.x | f.y | f.z | f.w) & 0x80808080u) fast_c = false;             // IUPAC codes (case_convert, S:743-755)
+            // IUPAC codes (case_convert, S:743-755) among the cn bytes that are copied — not among all 16 loaded — are resolved in place
+            if ((f.x | f.y | f.z | f.w) & 0x80808080u) resolve16(f.x, f.y, f.z, f.w, 0xffffu >> (16u - cn), x0, key, pc.sid, a);
             {
                 uint32_t nl_max = fast_l ? n_let : 0u;
                 nl_max = max(nl_max, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)nl_max, 0x111, 0xf, 0xf, false));   // row_shr:1
@@ -449,11 +478,9 @@ __device__ inline void dense_piece(const DevModel &m, const DevRef &ref, DenseLd
                     uint32_t cur4 = 0x41414141u;
                     if (on && ty != NS_INS) {
                         __builtin_memcpy(&cur4, seg0 + pos + i0, 4);
-                        if (cur4 & 0x80808080u) {                                      // IUPAC code under a substitution: case_convert first
-                            uint32_t rs = 0;
-                            for (uint32_t t = 0; t < 4u; ++t) rs |= (uint32_t)resolve_base((cur4 >> (8u * t)) & 0xffu, key, pc.sid, a, pos + i0 + t) << (8u * t);
-                            cur4 = rs;
-                        }
+                        // IUPAC code under a substitution: case_convert first (only the bases under the group's letters: the others of the
+                        // four loaded give letters that are not stored)
+                        if (cur4 & 0x80808080u) resolve4(cur4, 0xfu >> (4u - min(4u, n_let - i0)), pos + i0, key, pc.sid, a);
                     }
                     const uint32_t ins4 = ins_letters4(frac, g & 3u);
                     // substitution: the next four base-3 digits pick among the three other bases (S:1968-1972)
@@ -664,18 +691,6 @@ __device__ __forceinline__ void tile_lds_init(TileLds<TC> &T, uint32_t lane) {
             T.mlut[lane][k] = lane <= 4 * k ? 0xffffffffu : lane >= 4 * k + 4 ? 0u : 0xffffffffu << (8 * (lane - 4 * k));
     }
 }
-// IUPAC codes among the bytes [i0, i1) of a masked 16-byte group whose byte b lies at segment position x0 + b (case_convert, S:743-755: rare)
-__device__ __forceinline__ void resolve16(uint32_t &a0, uint32_t &a1, uint32_t &a2, uint32_t &a3, uint32_t i0, uint32_t i1, uint32_t x0,
-                                          const ns_key &key, uint32_t sid, uint32_t a) {
-    for (uint32_t b = i0; b < i1; ++b) {
-        uint32_t wk = b < 8 ? (b < 4 ? a0 : a1) : (b < 12 ? a2 : a3);
-        const uint32_t ch = (wk >> (8 * (b & 3))) & 0xff;
-        if (!(ch & 0x80u)) continue;
-        const uint32_t r = resolve_base(ch, key, sid, a, x0 + b);
-        wk = (wk & ~(0xffu << (8 * (b & 3)))) | r << (8 * (b & 3));
-        if (b < 4) a0 = wk; else if (b < 8) a1 = wk; else if (b < 12) a2 = wk; else a3 = wk;
-    }
-}
 // Phase-ablation bits of the record kernel (NS_DEBUG_SKIP: 1 no chunk loads / final step, 2 no letters, 16 no stores, 32 no event sub-run merge,
 // 64 no letter-word Philox, 128 no event sub-run loads, 256 no chunk-lane look-ups and loads): compiled in only with -DNS_ABLATE (scripts/ablate_materialise.sh builds that variant) — every test of a
 // run-time flag in the tile loop is a branch and a live SGPR in a kernel that spills ~80 of them.
@@ -843,7 +858,9 @@ __device__ inline void materialise_piece(const DevModel &m, const DevRef &ref, T
             bool fast_l = on && b_pl <= 8 && b_os >= M0 && b_os + b_pl <= M1 && !wraps;
             uint2 cur8 = make_uint2(0x41414141u, 0x41414141u);
             if (fast_l && mis) __builtin_memcpy(&cur8, seg0 + xs, 8);
-            if constexpr (!HPF) fast_l = fast_l && !((cur8.x | cur8.y) & 0x80808080u);
+            const uint64_t keep = b_pl >= 8u ? ~0ull : ~(~0ull << (8u * b_pl));      // the bytes under the letters (eight are loaded)
+            // a code UNDER the substitution leaves the fast path (one next to it does not: its letter is never kept)
+            if constexpr (!HPF) fast_l = fast_l && !(((uint64_t)cur8.x | (uint64_t)cur8.y << 32) & keep & 0x8080808080808080ull);
             if (fast_l) {
                 uint32_t f3 = frac, L2[2];
 #pragma unroll
@@ -869,7 +886,6 @@ __device__ inline void materialise_piece(const DevModel &m, const DevRef &ref, T
                 }
                 // the <= 8 letters leave as three aligned dword ORs into the (zeroed) tile instead of eight predicated byte stores: no other
                 // sub-run or letter shares a byte with them, so the OR is a store
-                const uint64_t keep = b_pl >= 8u ? ~0ull : ~(~0ull << (8u * b_pl));
                 const uint64_t v = ((uint64_t)L2[0] | (uint64_t)L2[1] << 32) & keep;
                 const uint32_t o = b_os - A0, sh = 8u * (o & 3u);
                 const uint64_t lo64 = v << sh;
@@ -908,7 +924,7 @@ __device__ inline void materialise_piece(const DevModel &m, const DevRef &ref, T
             const uint4 m0 = *reinterpret_cast<const uint4 *>(&T.mlut[ei0][0]), m1 = *reinterpret_cast<const uint4 *>(&T.mlut[ei1][0]);
             uint32_t a0 = and_andn(fe.x, m0.x, m1.x), a1 = and_andn(fe.y, m0.y, m1.y), a2 = and_andn(fe.z, m0.z, m1.z), a3 = and_andn(fe.w, m0.w, m1.w);
             if constexpr (!HPF) {
-                if ((a0 | a1 | a2 | a3) & 0x80808080u) resolve16(a0, a1, a2, a3, ei0, ei1, A0 + eoc + y1, key, pc.sid, a);
+                if ((a0 | a1 | a2 | a3) & 0x80808080u) resolve16(a0, a1, a2, a3, 0xffffu, A0 + eoc + y1, key, pc.sid, a);
             }
             lds_or64(&T.out[eoc], (uint64_t)a0 | (uint64_t)a1 << 32);
             lds_or64(&T.out[eoc + 8], (uint64_t)a2 | (uint64_t)a3 << 32);
@@ -930,7 +946,7 @@ __device__ inline void materialise_piece(const DevModel &m, const DevRef &ref, T
                 const uint4 m0 = *reinterpret_cast<const uint4 *>(&T.mlut[i0][0]), m1 = *reinterpret_cast<const uint4 *>(&T.mlut[i1][0]);
                 uint32_t a0 = and_andn(f[t].x, m0.x, m1.x), a1 = and_andn(f[t].y, m0.y, m1.y), a2 = and_andn(f[t].z, m0.z, m1.z), a3 = and_andn(f[t].w, m0.w, m1.w);
                 if constexpr (!HPF) {
-                    if ((a0 | a1 | a2 | a3) & 0x80808080u) resolve16(a0, a1, a2, a3, i0, i1, c0 + fy[t], key, pc.sid, a);
+                    if ((a0 | a1 | a2 | a3) & 0x80808080u) resolve16(a0, a1, a2, a3, 0xffffu, c0 + fy[t], key, pc.sid, a);
                 }
                 if (NS_DBG(512u)) { a0 = a1 = a2 = a3 = 0x41414141u; }
                 uint32_t r0 = v.x | a0, r1 = v.y | a1, r2 = v.z | a2, r3 = v.w | a3;
