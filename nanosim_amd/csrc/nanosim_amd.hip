@@ -1188,7 +1188,8 @@ __device__ __forceinline__ bool load_read_uniform(const GenArgs &A, uint64_t r, 
 // first event slot / capacity of the homopolymer edits of the piece whose scratch bytes start at `pos` (bytes from the start of the
 // scratch buffer) and that is the `piece`-th piece of the batch IN READ ORDER (A.hp_pord[read] + its number in the read — the order of
 // the scratch buffer): a monotone function of both, so the slots of no two pieces overlap
-__device__ __forceinline__ uint64_t hp_ev_slot(const GenArgs &A, uint64_t pos, uint32_t piece) { return (pos >> A.hp_shift) + (uint64_t)A.hp_pad * piece; }
+__device__ __forceinline__ uint64_t hp_ev_slot(uint32_t hp_shift, uint32_t hp_pad, uint64_t pos, uint32_t piece) { return (pos >> hp_shift) + (uint64_t)hp_pad * piece; }
+__device__ __forceinline__ uint64_t hp_ev_slot(const GenArgs &A, uint64_t pos, uint32_t piece) { return hp_ev_slot(A.hp_shift, A.hp_pad, pos, piece); }
 
 // chunks per lane and tile: two (2 KB tiles) where a tile's ~63 events span about that much; the second pass of -k has an event every
 // ~300 bytes, so its tiles are byte-limited and a larger one amortises the per-tile work — by little: 4.78 ms with 2 KB tiles, 4.66 with
@@ -1200,60 +1201,108 @@ __device__ __forceinline__ uint64_t hp_ev_slot(const GenArgs &A, uint64_t pos, u
 #ifndef NS_MAT_WAVES_FINAL
 #define NS_MAT_WAVES_FINAL 6
 #endif
-template <bool FASTQ, int MODE>
-__global__ void __launch_bounds__(64, MODE == MAT_HP_FINAL ? NS_MAT_WAVES_FINAL : NS_MAT_WAVES)
-k_materialise(GenArgs A, uint32_t dbg, SlowQueue sq, const uint32_t *order) {
+// The arguments of k_materialise are ONE block, so that a rare path of the tile loop can read what it needs from the kernel-argument
+// segment when it runs: the slow-tile queue, the visiting order (for the read's number) and, through the piece record, the length of the
+// chromosome.  Held in SGPRs from the kernel's entry they are live across a tile loop that has ~50 scalars too many, and every one of
+// those is a v_writelane per read and a v_readlane per use.
+struct MatArgs { GenArgs A; SlowQueue sq; const uint32_t *order; uint32_t dbg; };
+typedef const __attribute__((address_space(4))) MatArgs *MatArgsPtr;
+__device__ __forceinline__ MatArgsPtr mat_args_now() {
+    MatArgsPtr p = (MatArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();     // (the block is the kernel's only argument: it starts the segment)
+    asm volatile("" : "+s"(p));                   // opaque: a load through it happens where it is written, not at the kernel's entry
+    return p;
+}
+// materialise_piece's `cold`: the piece by its index in A.pieces and its number in the read
+struct MatCold {
+    uint32_t gp, pi;
+    __device__ __forceinline__ void push(uint32_t lane, uint32_t m0, uint32_t m1) const {
+        // (two looks at the block: read as one, order and queue arrive as ONE eight-register load that has to find eight free SGPRs here)
+        const uint32_t *order = mat_args_now()->order;
+        const uint32_t r = order ? uni(order[blockIdx.x]) : blockIdx.x;
+        const MatArgsPtr K = mat_args_now();
+        SlowQueue sq; sq.items = K->sq.items; sq.count = K->sq.count; sq.cap = K->sq.cap;
+        slow_queue_push(sq, lane, SlowTile{r, pi, m0, m1});
+    }
+    __device__ __forceinline__ uint64_t chrom_len() const {      // (asked for a piece across the origin only: never a spliced stretch)
+        const MatArgsPtr K = mat_args_now();
+        const ns_piece *pieces = K->A.pieces;
+        const uint64_t *off = K->A.ref.chrom_off;
+        const uint32_t chrom = uni(pieces[gp].chrom);
+        return uni64(off[chrom + 1]) - uni64(off[chrom]);
+    }
+};
+
+// the pieces of one read: the tile loop is instantiated per strand and chosen with ONE scalar branch per piece (as a run-time flag
+// inside the loop the strand was a 64-bit lane mask, spilled, and two v_readlane per chunk to test it)
+template <bool FASTQ, int MODE, uint32_t TC, bool URACIL>
+__device__ __forceinline__ uint32_t materialise_pieces(const GenArgs &A, TileLds<TC> &T, const ReadOut &ro, const ns_key &key, const ns_read &rd,
+                                                       uint64_t r, uint32_t q, uint32_t lane, uint32_t dbg) {
     constexpr bool CLSOUT = FASTQ && MODE != MAT_HP_SCRATCH;           // FASTQ: the bases here, the quality line in k_qualities
-    constexpr uint32_t TC = MODE == MAT_HP_FINAL ? NS_TILE_CHUNKS_FINAL : NS_TILE_CHUNKS;
-    __shared__ TileLds<TC> T;
-    const uint32_t lane = threadIdx.x;
-    const uint64_t slot = blockIdx.x;
-    if (slot >= A.prm.n_reads) return;
-    const uint64_t r = order ? (uint64_t)uni(order[slot]) : slot;
-    ns_read rd; ns_key key; ReadOut ro;
-    if (!load_read_uniform(A, r, false, rd, key, ro)) return;
     const uint32_t a = rd.attempts;
-    tile_lds_init(T, lane);
     uint32_t *cls = nullptr;
     if constexpr (CLSOUT) cls = A.cls + cls_word0(rd.rec_off, r, cls_per_read(A.prm));
-    if constexpr (MODE == MAT_HP_SCRATCH) {
-        // -k, first pass: the pieces of the read before mutate_homo, forward strand, one after the other in the scratch buffer
-        // (head, tail and polyA are written by the second pass; strand and T -> U are applied there)
-        ro.seq = A.scr + uni64(A.scr_off[r]); ro.qual = nullptr; ro.reversed = false; ro.uracil = false;
-        uint32_t q = 0;
-        for (uint32_t pi = 0; pi < rd.n_pieces; ++pi) {
-            const PieceCtx pc = load_piece_uniform(A.events, A.ref, A.pieces[rd.piece_off + pi], pi);
-            materialise_piece<FASTQ, MODE, TC>(A.m, A.ref, T, ro, key, a, pc, q, lane, dbg, sq, (uint32_t)r, pi, nullptr);
-            q += pc.out_len;
-        }
-        return;
-    }
-#ifdef NS_ABLATE
-    if (!(dbg & 8))
-#endif
-    emit_head_tail(ro, key, a, rd.head, rd.tail, lane);                                                                   // S:1426-1427
-    uint32_t q = rd.head;
     uint64_t q_in = MODE == MAT_HP_FINAL ? uni64(A.scr_off[r]) : 0;
     for (uint32_t pi = 0; pi < rd.n_pieces; ++pi) {
         PieceCtx pc;
+        const uint32_t gp = rd.piece_off + pi;
         if constexpr (MODE == MAT_HP_FINAL) {
             // the source is the scratch piece, the events are the homopolymer edits k_hp_drain filed for it (mutate_homo, S:618-705)
-            const uint32_t gp = rd.piece_off + pi;
-            const ns_piece p = A.pieces[gp];
-            const uint64_t eo = hp_ev_slot(A, q_in, uni(A.hp_pord[r]) + pi);
+            // (the arguments of this pass are read HERE, piece by piece: loaded at the kernel's entry they are eight-register groups that
+            // live across the tile loop)
+            const MatArgsPtr K = mat_args_now();
+            const ns_piece *pieces = K->A.pieces;
+            const uint32_t *hp_pord = K->A.hp_pord, *hp_nev = K->A.hp_nev, *hp_len = K->A.hp_len;
+            const ns_piece p = pieces[gp];
+            const uint64_t eo = hp_ev_slot(K->A.hp_shift, K->A.hp_pad, q_in, uni(hp_pord[r]) + pi);
             pc.kind = uni(p.kind);
-            pc.ev = A.hp_ev + eo; pc.wd = A.hp_wd + eo; pc.n_ev = pc.kind ? 0u : uni(A.hp_nev[gp]);
-            pc.ref_len = uni(p.out_len); pc.out_len = pc.kind ? pc.ref_len : uni(A.hp_len[gp]);
-            pc.chrom_base = (uint64_t)((uintptr_t)A.scr - (uintptr_t)A.ref.bases) + q_in; pc.chrom_len = ~0ull; pc.pos = 0;
+            pc.ev = K->A.hp_ev + eo; pc.wd = K->A.hp_wd + eo; pc.n_ev = pc.kind ? 0u : uni(hp_nev[gp]);
+            pc.ref_len = uni(p.out_len); pc.out_len = pc.kind ? pc.ref_len : uni(hp_len[gp]);
+            pc.chrom_base = (uint64_t)((uintptr_t)K->A.scr - (uintptr_t)K->A.ref.bases) + q_in; pc.chrom_len = ~0ull; pc.pos = 0;
             pc.sid = pc.kind ? NS_GAP_SEG + (pi >> 1) : (pi >> 1);
             q_in += pc.ref_len;
-        } else pc = load_piece_uniform(A.events, A.ref, A.pieces[rd.piece_off + pi], pi);
-        materialise_piece<FASTQ, MODE, TC>(A.m, A.ref, T, ro, key, a, pc, q, lane, dbg, sq, (uint32_t)r, pi, CLSOUT ? cls + (q >> 4) + 2u * pi : nullptr);
+        } else pc = load_piece_uniform(A.events, A.ref, A.pieces[gp], pi);
+        uint32_t *const pcls = CLSOUT ? cls + (q >> 4) + 2u * pi : nullptr;
+        if (ro.reversed) materialise_piece<FASTQ, MODE, TC, true, URACIL>(A.ref, T, PieceOut<true>(ro, q), key, a, pc, lane, dbg, MatCold{gp, pi}, pcls);
+        else materialise_piece<FASTQ, MODE, TC, false, URACIL>(A.ref, T, PieceOut<false>(ro, q), key, a, pc, lane, dbg, MatCold{gp, pi}, pcls);
         q += pc.out_len;                                 // (-k: k_hp_report files the emitted length in the piece once the record kernels are done)
     }
-    if (A.polya) {                                                                          // transcriptome: polyA tail (S:1224-1225)
-        const uint32_t pl = uni(A.polya[r]);
-        if (pl) emit_polya(ro, q, pl, lane);
+    return q;
+}
+
+// URACIL: --uracil, an option of the run that no batch changes — dispatched next to FASTQ and MODE (launch_materialise)
+template <bool FASTQ, int MODE, bool URACIL>
+__global__ void __launch_bounds__(64, MODE == MAT_HP_FINAL ? NS_MAT_WAVES_FINAL : NS_MAT_WAVES)
+k_materialise(MatArgs K) {
+    // K must stay the ONLY argument (mat_args_now reads it at offset 0 of the kernel-argument segment), and a workgroup must stay one read
+    // at slot blockIdx.x (MatCold::push finds the read's number again from there): a second argument or a grid-stride loop has to change both
+    static_assert(std::is_trivially_copyable<MatArgs>::value && offsetof(MatArgs, A) == 0, "MatArgs is read back from the kernel-argument segment as it was passed");
+    constexpr uint32_t TC = MODE == MAT_HP_FINAL ? NS_TILE_CHUNKS_FINAL : NS_TILE_CHUNKS;
+    __shared__ TileLds<TC> T;
+    const GenArgs &A = K.A;
+    const uint32_t lane = threadIdx.x;
+    const uint64_t slot = blockIdx.x;
+    if (slot >= A.prm.n_reads) return;
+    const uint64_t r = K.order ? (uint64_t)uni(K.order[slot]) : slot;
+    ns_read rd; ns_key key; ReadOut ro;
+    if (!load_read_uniform(A, r, false, rd, key, ro)) return;
+    tile_lds_init(T, lane);
+    if constexpr (MODE == MAT_HP_SCRATCH) {
+        // -k, first pass: the pieces of the read before mutate_homo, forward strand, one after the other in the scratch buffer
+        // (head, tail and polyA are written by the second pass; strand and T -> U are applied there)
+        static_assert(MODE != MAT_HP_SCRATCH || !URACIL, "the scratch pass of -k writes T");
+        ro.seq = A.scr + uni64(A.scr_off[r]); ro.qual = nullptr; ro.reversed = false; ro.uracil = false;
+        materialise_pieces<FASTQ, MODE, TC, false>(A, T, ro, key, rd, r, 0u, lane, K.dbg);
+    } else {
+        ro.uracil = URACIL;
+#ifdef NS_ABLATE
+        if (!(K.dbg & 8))
+#endif
+        emit_head_tail(ro, key, rd.attempts, rd.head, rd.tail, lane);                                                      // S:1426-1427
+        const uint32_t q = materialise_pieces<FASTQ, MODE, TC, URACIL>(A, T, ro, key, rd, r, rd.head, lane, K.dbg);
+        if (A.polya) {                                                                      // transcriptome: polyA tail (S:1224-1225)
+            const uint32_t pl = uni(A.polya[r]);
+            if (pl) emit_polya(ro, q, pl, lane);
+        }
     }
 }
 
@@ -2696,7 +2745,10 @@ static int launch_materialise(ns_ctx *ctx, const GenArgs &A, size_t n, bool fast
         if (round == 0) HIPCHK(hipEventRecord(ctx->evt[EV_RECKERNEL_BEGIN], st));            // the record kernel itself (ns_batch_info.ms_kernel[NS_K_RECORD_KERNEL])
         by_fastq_mode(fastq, mode, [&](auto fq, auto md) {      // (reads in order_b's order: from the reference, and the FASTQ second pass of -k)
             constexpr bool FQ = decltype(fq)::value; constexpr int MD = decltype(md)::value;
-            k_materialise<FQ, MD><<<grid_1, blk_1, 0, st>>>(A, ctx->knob.dbg, sq, (MD == MAT_REF || (FQ && MD == MAT_HP_FINAL)) ? order_b : nullptr);
+            const MatArgs K{A, sq, (MD == MAT_REF || (FQ && MD == MAT_HP_FINAL)) ? order_b : nullptr, ctx->knob.dbg};
+            // --uracil is applied where the record is written: not by the scratch pass of -k
+            if (MD != MAT_HP_SCRATCH && A.prm.uracil) k_materialise<FQ, MD, MD != MAT_HP_SCRATCH><<<grid_1, blk_1, 0, st>>>(K);
+            else k_materialise<FQ, MD, false><<<grid_1, blk_1, 0, st>>>(K);
         });
         HIPCHK(hipGetLastError());
         if (round == 0) { HIPCHK(hipEventRecord(ctx->evt[EV_RECKERNEL_END], st)); ctx->rec_timed = true; }

@@ -57,6 +57,11 @@ __device__ __forceinline__ uint32_t dpp_wave_shl1(uint32_t lane63_value, uint32_
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ uint64_t uni64(uint64_t v) { return (uint64_t)uni((uint32_t)v) | (uint64_t)uni((uint32_t)(v >> 32)) << 32; }
 
+// A wave-uniform value as it stands HERE: what is computed from the result is computed here.  A comparison of a loop-invariant scalar is
+// otherwise hoisted out of the tile loop as a boolean — a 64-bit lane mask that is spilled with the rest and costs two v_readlane per
+// test, against one s_cmp of the value itself.
+__device__ __forceinline__ uint32_t here(uint32_t v) { asm volatile("" : "+s"(v)); return v; }
+
 struct ReadOut {
     uint8_t *seq;        // first base of the record's sequence line
     uint8_t *qual;       // first quality character, or nullptr
@@ -123,16 +128,12 @@ __device__ __forceinline__ void store_chunk(const ReadOut &ro, uint32_t q0, uint
         store16(ro.qual + o0, count, qlo, qhi);
     }
 }
-// The chunks of the tiled kernel (materialise_piece, step 4: prep_chunk and flush_chunk back to back).  ro.qual is null there, so the
-// quality halves never run — but they are alive while the compiler optimises materialise_piece on its own, before it is inlined into
-// k_materialise, and without them (or with the two folded into one function) the vectoriser pairs other values of the two chunks of a lane
-// and the instruction streams of k_materialise<., MAT_REF> and <., MAT_HP_SCRATCH> change.  They go with the next change of that kernel
-// that is timed on a GPU.
-struct PendingChunk { uint64_t lo, hi, qlo, qhi; uint32_t o0, count; };
-__device__ __forceinline__ PendingChunk prep_chunk(const ReadOut &ro, uint32_t q0, uint32_t count, uint64_t lo, uint64_t hi,
-                                                   uint64_t qlo, uint64_t qhi) {
-    PendingChunk p; p.count = count; p.o0 = q0;
-    if (ro.reversed) {
+// The chunks of the tiled kernel (materialise_piece, step 4): strand and T -> U are compile-time there — the tile loop exists once per
+// strand, chosen per read by a scalar branch, and --uracil is a parameter of the kernel — and the destination is the piece's PieceOut
+// below: `count` bases (bytes 0 .. count - 1 of (lo, hi), piece order) to dst, the address of the first byte WRITTEN.
+template <bool REV, bool URACIL>
+__device__ __forceinline__ void emit_chunk(uint8_t *dst, uint32_t count, uint64_t lo, uint64_t hi) {
+    if constexpr (REV) {
         if (count == 16) {              // full group: complement through a byte-permute look-up (A 1, C 3, T 4, G 7 after & 7), then reverse
             const uint32_t w0 = (uint32_t)lo, w1 = (uint32_t)(lo >> 32), w2 = (uint32_t)hi, w3 = (uint32_t)(hi >> 32);
             const uint32_t c0 = __builtin_amdgcn_perm(0x43000041u, 0x47005400u, w0 & 0x07070707u), c1 = __builtin_amdgcn_perm(0x43000041u, 0x47005400u, w1 & 0x07070707u);
@@ -144,23 +145,21 @@ __device__ __forceinline__ PendingChunk prep_chunk(const ReadOut &ro, uint32_t q
             lo = complement8(lo); hi = complement8(hi);
             reverse_bytes(lo, hi, count);
         }
-        p.o0 = ro.seq_len - q0 - count;
     }
-    if (ro.uracil) { lo = t_to_u8(lo); hi = t_to_u8(hi); }
-    p.lo = lo; p.hi = hi; p.qlo = 0; p.qhi = 0;
-    if (ro.qual) {
-        qlo += 0x2121212121212121ull; qhi += 0x2121212121212121ull;         // chr(q + 33), S:1441
-        if (ro.reversed) reverse_bytes(qlo, qhi, count);
-        p.qlo = qlo; p.qhi = qhi;
-    }
-    return p;
+    if constexpr (URACIL) { lo = t_to_u8(lo); hi = t_to_u8(hi); }
+    store16(dst, count, lo, hi);
 }
-__device__ __forceinline__ void flush_chunk(const ReadOut &ro, PendingChunk &p) {
-    if (!p.count) return;
-    store16(ro.seq + p.o0, p.count, p.lo, p.hi);
-    if (ro.qual) store16(ro.qual + p.o0, p.count, p.qlo, p.qhi);
-    p.count = 0;
-}
+// Where the bytes of a piece go, folded once per piece from the record's sequence line (ro.seq, ro.seq_len) and the piece's offset pq in the
+// read: bytes [lo_m, hi_m) of the piece are written forward from base + lo_m, or — reverse strand, the read's last base first — from
+// base - hi_m.  A chunk needs one add.
+template <bool REV>
+struct PieceOut {
+    uint8_t *base;
+    __device__ __forceinline__ PieceOut(const ReadOut &ro, uint32_t pq) : base(REV ? ro.seq + (ro.seq_len - pq) : ro.seq + pq) {}
+    __device__ __forceinline__ uint8_t *at(uint32_t lo_m, uint32_t hi_m) const { return REV ? base - hi_m : base + lo_m; }
+    // output offsets m with m = phi (mod 16) start an aligned 16-byte group of the destination
+    __device__ __forceinline__ uint32_t phi() const { return (REV ? (uint32_t)(uintptr_t)base : 0u - (uint32_t)(uintptr_t)base) & 15u; }
+};
 __device__ __forceinline__ void put_byte(uint64_t &lo, uint64_t &hi, uint32_t i, uint32_t b) {
     if (i < 8) lo |= (uint64_t)b << (8 * i); else hi |= (uint64_t)b << (8 * (i - 8));
 }
@@ -320,7 +319,10 @@ __device__ __forceinline__ PieceCtx load_piece_uniform(const ns_event *events, c
     pc.chrom_len = uni64(ref.chrom_off[chrom + 1]) - pc.chrom_base;
     pc.pos = uni(p.pos); pc.kind = uni(p.kind);
     const uint64_t gpos = uni64(p.ref_gpos);
-    if (gpos >= NS_SPLICED_BASE) {
+    // (the high word alone, as it stands: there is no scalar >= of 64 bits, and the vector one wants the constant in two VGPRs, which were
+    // hoisted out of the piece loop and spilled to scratch)
+    static_assert((uint32_t)NS_SPLICED_BASE == 0, "the test below reads the high word only");
+    if (here((uint32_t)(gpos >> 32)) >= (uint32_t)(NS_SPLICED_BASE >> 32)) {
         pc.chrom_base = (uint64_t)((uintptr_t)ref.spliced - (uintptr_t)ref.bases) + (gpos - NS_SPLICED_BASE) - pc.pos;
         pc.chrom_len = ~0ull;
     }
@@ -701,20 +703,28 @@ __device__ __forceinline__ void tile_lds_init(TileLds<TC> &T, uint32_t lane) {
 #endif
 // a & b & ~c in one instruction (v_bitop3_b32, truth table 0x40 for inputs 0xF0, 0xCC, 0xAA; the compiler emits not + and + and)
 __device__ __forceinline__ uint32_t and_andn(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x40); }
-template <bool FASTQ, int MODE, uint32_t TC>
-__device__ inline void materialise_piece(const DevModel &m, const DevRef &ref, TileLds<TC> &T, const ReadOut &ro, const ns_key &key,
-                                         uint32_t a, const PieceCtx &pc, uint32_t pq, uint32_t lane, uint32_t dbg, const SlowQueue &sq,
-                                         uint32_t read_idx, uint32_t piece_idx, uint32_t *__restrict__ cls) {
+// REV, URACIL: strand and T -> U of the record (emit_chunk).  `cold` is what only a tile for the slow queue and a piece across the origin of
+// a circular chromosome read — cold.push(lane, m0, m1) queues bytes [m0, m1) of this piece, cold.chrom_len() is the length of its
+// chromosome: the caller fetches both where they already lie in memory (its kernel arguments, the piece record) WHEN they are called for, so
+// that the queue, the read and piece numbers and the chromosome's geometry hold no SGPRs across a tile loop that spills them.  Of the piece
+// itself the loop keeps seg0 and wrap_at.
+template <bool FASTQ, int MODE, uint32_t TC, bool REV, bool URACIL, typename Cold>
+__device__ inline void materialise_piece(const DevRef &ref, TileLds<TC> &T, const PieceOut<REV> out, const ns_key &key,
+                                         uint32_t a, const PieceCtx &pc, uint32_t lane, uint32_t dbg, const Cold &cold,
+                                         uint32_t *__restrict__ cls) {
     constexpr bool CLSOUT = FASTQ && MODE != MAT_HP_SCRATCH;           // the class of every base leaves as 2 bits for k_qualities (cls: the piece's words)
     constexpr bool HPF = MODE == MAT_HP_FINAL;
     constexpr uint32_t T_OUT_ = 1024u * TC;
     uint32_t jb = 0;                       // events with out_start < M0
     uint32_t L0_out = 0, L0_rp = 0, L0_pt = 3u << 12, L0_wd = 0, L0_j = 0;   // the event in force at M0 (synthetic start: no payload, copy from 0)
     const uint8_t *seg0 = ref.bases + pc.chrom_base + pc.pos;           // segment position 0
-    const bool wraps = !HPF && pc.pos + pc.ref_len > pc.chrom_len;
-    const uint32_t wrap_at = wraps ? (uint32_t)(pc.chrom_len - pc.pos) : 0xffffffffu;   // first segment position beyond the origin
-    // output offsets m with m = phi (mod 16) start an aligned 16-byte group of the destination
-    const uint32_t phi = ro.reversed ? ((uint32_t)(uintptr_t)ro.seq + ro.seq_len - pq) & 15u : (0u - ((uint32_t)(uintptr_t)ro.seq + pq)) & 15u;
+    // first segment position beyond the origin of a circular chromosome (a piece that does not reach it: none); one scalar, compared where
+    // a tile or a letter has to know
+    const uint32_t wrap_at = (!HPF && pc.pos + pc.ref_len > pc.chrom_len) ? (uint32_t)(pc.chrom_len - pc.pos) : 0xffffffffu;
+    const uint32_t fast_pl = wrap_at != 0xffffffffu ? 0u : 8u;          // longest payload the letter fast path takes (a piece across the origin: none)
+    // the base at segment position x, per byte (the slow letter path)
+    auto base_at = [&](uint32_t x) -> uint32_t { const uint8_t *s = seg0; if (!HPF && x >= wrap_at) s -= cold.chrom_len(); return s[x]; };
+    const uint32_t phi = out.phi();
     ns_event e_pre; e_pre.pos = 0; e_pre.info = 0; uint32_t w_pre = 0;
     if (lane < pc.n_ev) e_pre = pc.ev[lane];
     auto cached_word = [&](uint32_t j0) -> uint32_t { if (NS_DBG(64u)) return 0u; const uint32_t j = j0 + lane; return event_word<MODE>(pc, key, a, j < pc.n_ev ? j : 0u); };
@@ -743,7 +753,7 @@ __device__ inline void materialise_piece(const DevModel &m, const DevRef &ref, T
             M1 = min(M0 + T_OUT_, pc.out_len);
             uint32_t j2 = jb;
             while (j2 < pc.n_ev && ev_out_start(pc.ev[j2]) < M1) ++j2;
-            slow_queue_push(sq, lane, SlowTile{read_idx, piece_idx, M0, M1});
+            cold.push(lane, M0, M1);
             if (j2 > jb) {
                 const ns_event le = pc.ev[j2 - 1];
                 const uint32_t ll = ns_ev_len(le.info), lt = ns_ev_type(le.info);
@@ -792,18 +802,18 @@ __device__ inline void materialise_piece(const DevModel &m, const DevRef &ref, T
         }
         const uint8_t *tb = seg0 - 32;                             // + 32 in the lane offsets: they never go negative
         bool fast = true;
-        if (wraps) {                                               // reference span of the tile only matters next to the origin
+        if (!HPF && here(wrap_at) != 0xffffffffu) {                // reference span of the tile only matters next to the origin
             const uint32_t pl0 = L0_pt & 0xfffu, ty0 = L0_pt >> 12, d0 = M0 - L0_out;
             const uint32_t x0 = (d0 < pl0 && ty0 == NS_INS) ? L0_rp : L0_rp + d0 - pl0;
             const uint32_t pll = ptl & 0xfffu, dl = M1 - osl;
             uint32_t x1 = dl <= pll ? rpl : rpl + (dl - pll);
             if (x1 < x0) x1 = x0;
-            if (x0 >= wrap_at) tb -= pc.chrom_len;                 // whole tile beyond the origin
+            if (x0 >= wrap_at) tb -= cold.chrom_len();             // whole tile beyond the origin
             else if (x1 > wrap_at) fast = false;                   // tile straddles the origin
         }
         if (!fast) {
             cls_carry = 0;
-            slow_queue_push(sq, lane, SlowTile{read_idx, piece_idx, M0, M1});
+            cold.push(lane, M0, M1);
             L0_out = osl; L0_rp = rpl; L0_pt = ptl; L0_wd = wdl; L0_j = jl;
             jb = jb_next; M0 = M1;
             wave_sync();
@@ -855,7 +865,7 @@ __device__ inline void materialise_piece(const DevModel &m, const DevRef &ref, T
             const uint32_t xs = b_rp - b_pl;                      // segment position under the first substituted base
             // fast path (branch-free): up to EIGHT letters, all inside the tile, plain bases under a substitution
             const bool mis = b_ty == NS_MIS;
-            bool fast_l = on && b_pl <= 8 && b_os >= M0 && b_os + b_pl <= M1 && !wraps;
+            bool fast_l = on && b_pl <= fast_pl && b_os >= M0 && b_os + b_pl <= M1;
             uint2 cur8 = make_uint2(0x41414141u, 0x41414141u);
             if (fast_l && mis) __builtin_memcpy(&cur8, seg0 + xs, 8);
             const uint64_t keep = b_pl >= 8u ? ~0ull : ~(~0ull << (8u * b_pl));      // the bytes under the letters (eight are loaded)
@@ -905,7 +915,7 @@ __device__ inline void materialise_piece(const DevModel &m, const DevRef &ref, T
                         if constexpr (FASTQ) b |= (HPF && i == 0 && (word0 >> 31)) ? NS_CLS_MIS_BIT : NS_CLS_INS_BIT;
                     } else {
                         const uint32_t x = xs + i;
-                        const uint32_t src = ref_base_at(ref, pc, x);
+                        const uint32_t src = base_at(x);
                         if constexpr (HPF) {
                             b = mis_from_digit(src & ~(NS_CLS_MIS_BIT | NS_CLS_INS_BIT), next_digit3(frac));
                             if constexpr (FASTQ) b |= (word0 & 1u) ? NS_CLS_MIS_BIT : (src & (NS_CLS_MIS_BIT | NS_CLS_INS_BIT));
@@ -963,7 +973,7 @@ __device__ inline void materialise_piece(const DevModel &m, const DevRef &ref, T
                     if (sh < 64) { lo = (lo >> sh) | (hi << (64 - sh)); hi >>= sh; }
                     else { lo = hi >> (sh - 64); hi = 0; }
                 }
-                if (!NS_DBG(16u)) { PendingChunk pd = prep_chunk(ro, pq + lo_m, count, lo, hi, 0, 0); flush_chunk(ro, pd); }
+                if (!NS_DBG(16u)) emit_chunk<REV, URACIL>(out.at(lo_m, hi_m), count, lo, hi);
             }
             if constexpr (CLSOUT) {                                    // the tile ends inside a chunk: its word goes on in the next tile's chunk 0
                 const uint32_t cl = (M1 - 1u - A0) >> 4;
