@@ -623,6 +623,45 @@ typedef struct ns_ir_train_result {
 int ns_ir_train(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off, const uint32_t *start, const uint32_t *chrom,
                 const uint32_t *trx, uint32_t n_reads, const ns_ir_introns *introns, ns_ir_train_result *out);
 
+/* ---- training side: the best hit per read of LAST's MAF alignments -------------------------------------------------------------------------------
+ * replaces besthit_and_unaligned of src/get_besthit_maf.py (G:8-56) up to the lengths of the unaligned reads; nanosim_amd/csrc/ns_maf_best.h
+ * says how.  text[nbytes]: a MAF file as it is, or what `grep '^s '` leaves of it.  An `s` line begins at the first byte of the text or
+ * behind a '\n' with `s` and a space or a tab; everything else is skipped.  The `s` lines are pairs (reference line, query line); fields
+ * are separated like Python's split(); `start`, `size` and `srcSize` are decimal digits that fit 32 bits, a line with anything else there or
+ * with fewer than 7 fields is BAD.  Of the pairs of a query name the one with the largest `size` is KEPT, of several the first in the text.
+ * names / names_off / n_names (optional; n_names == 0 without): the names of a reads file one behind the other, name i the bytes
+ * names_off[i] .. names_off[i + 1] - 1; found[i] = 1 when name i is the query name of a pair, else 0.
+ * Out: n_lines, n_pairs, n_kept (= the reference's num_aligned), pos_strand (kept pairs whose two strand fields are equal byte strings), and
+ * per kept pair, in the order of the text, lines / records / figures — all offsets are offsets into text.  These three arrays belong to
+ * the context and stay valid until the next ns_maf_besthit on it or ns_destroy.
+ * An odd n_lines is NS_EINVAL (n_lines is set).  With a bad line the call returns NS_OK, first_bad_line is the index of the first one among the
+ * `s` lines and first_bad_offset where it begins (n_lines and ~0 without), and nothing is counted: n_kept == 0, found untouched.
+ * NS_EINVAL for 2^31 pairs or more and offsets that do not ascend from 0, NS_ENOMEM when the device cannot hold the text and the
+ * tables.  nbytes == 0 is valid and keeps nothing.  ms_kernel: from the first kernel to the last, the waits of the host for the number of
+ * lines and for the bad-line check included.  Added without an ABI change. */
+typedef struct ns_maf_best_lines {      /* the two lines of a kept pair, each with its '\n' where it has one */
+    uint64_t ref_begin, ref_end, qry_begin, qry_end;
+} ns_maf_best_lines;
+typedef struct ns_maf_best_record {     /* what characterize.maf_records takes from the two lines: name and start of the reference, the two sequences */
+    uint64_t ref_name_at, ref_seq_at, qry_seq_at;
+    uint32_t ref_name_len, ref_seq_len, qry_seq_len, ref_start;
+} ns_maf_best_record;
+typedef struct ns_maf_best_figures {    /* src/head_align_tail_dist.py:91-110: r[3], r[5], q[2], q[5], q[5] - q[3] */
+    uint32_t aligned_ref, ref_total, head, total;
+    int64_t ht;
+} ns_maf_best_figures;
+typedef struct ns_maf_best_result {
+    uint8_t *found;                         /* in: host buffer of n_names bytes (out); may be NULL when n_names == 0 */
+    const ns_maf_best_lines *lines;         /* out: n_kept entries each, owned by the context */
+    const ns_maf_best_record *records;
+    const ns_maf_best_figures *figures;
+    uint64_t n_lines, n_pairs, n_kept, pos_strand;          /* out */
+    uint64_t first_bad_line, first_bad_offset;              /* out */
+    double ms_kernel;
+} ns_maf_best_result;
+int ns_maf_besthit(ns_ctx *ctx, const uint8_t *text, uint64_t nbytes, const uint8_t *names, const uint64_t *names_off, uint32_t n_names,
+                   ns_maf_best_result *out);
+
 /* device address of a result buffer (for zero-copy consumers such as torch / RCCL); NULL if absent */
 const void *ns_device_ptr(ns_ctx *ctx, int which);
 

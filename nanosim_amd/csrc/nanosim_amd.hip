@@ -16,7 +16,7 @@
 //   k_errlog            wave/read     _aligned_error_profile rows                           (S:2006-2008)
 // Metagenome worker calls run k_lengths / k_chain per PASS of the reference's while loop (S:844-1040) with k_meta_* around them; the lists of a
 // pass are launched before the host has walked the species quotas (assign_species), k_meta_tail does positions + acceptance afterwards.
-// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms, ns_sam_pairs_build, ns_mixture_fit, ns_read_lengths, ns_cigar_spans, ns_chimeric_select, ns_em_quantify, ns_ir_train: at the end of the host part) has its kernels in ns_train.h.
+// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms, ns_sam_pairs_build, ns_mixture_fit, ns_read_lengths, ns_cigar_spans, ns_chimeric_select, ns_em_quantify, ns_ir_train, ns_maf_besthit: at the end of the host part) has its kernels in ns_train.h.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdio.h>
@@ -2224,6 +2224,7 @@ struct ns_ctx {
     std::vector<void *> ir_allocs;
     DevBuf<uint64_t> ir_need, ir_off; DevBuf<uint8_t> spliced;
     uint64_t spliced_bytes = 0;
+    std::vector<ns_maf_best_lines> maf_lines; std::vector<ns_maf_best_record> maf_records; std::vector<ns_maf_best_figures> maf_figures;   // the result of the last ns_maf_besthit
     uint8_t *pin_small = nullptr;    // page-locked slots for the scalar read-backs of a call (read_small)
     PinBuf pin_a, pin_b, pin_c;      // pinned host staging of the metagenome passes: draws (then species ids), sorted lengths, words
     uint32_t nspecies = 0;
@@ -4763,6 +4764,109 @@ int ns_ir_train(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off, co
     out->first[0] = small[IRS_COUNT + IRC_FIRST]; out->first[1] = small[IRS_COUNT + IRC_FIRST + 1];
     for (int i = 0; i < 4; ++i) out->states[i] = small[IRS_COUNT + IRC_STATES + i];
     out->n_bad = small[IRS_BAD]; out->first_bad = out->n_bad ? small[IRS_FIRST] : n_reads;
+    return NS_OK;
+}
+
+// the best hit per read of a MAF file (include/nanosim_amd.h: ns_maf_best_result; ns_maf_best.h; src/get_besthit_maf.py:8-56).  The host
+// waits twice inside the call: for the number of `s` lines, which sizes everything behind it, and for the bad-line check, so that no
+// kernel ever walks the fields of a line that has none.
+int ns_maf_besthit(ns_ctx *ctx, const uint8_t *text, uint64_t nbytes, const uint8_t *names, const uint64_t *names_off, uint32_t n_names,
+                   ns_maf_best_result *out) {
+    if (!ctx) return NS_EINVAL;
+    if (!out) return fail(ctx, NS_EINVAL, "ns_maf_besthit: null argument");
+    static_assert(sizeof(MafOutLines) == sizeof(ns_maf_best_lines) && sizeof(MafOutRecord) == sizeof(ns_maf_best_record) &&
+                  sizeof(MafOutFigures) == sizeof(ns_maf_best_figures), "ns_maf_best.h mirrors the ABI structs");
+    ctx->maf_lines.clear(); ctx->maf_records.clear(); ctx->maf_figures.clear();
+    out->lines = nullptr; out->records = nullptr; out->figures = nullptr;
+    out->n_lines = out->n_pairs = out->n_kept = out->pos_strand = 0; out->first_bad_line = 0; out->first_bad_offset = ~0ull; out->ms_kernel = 0;
+    if ((nbytes && !text) || (n_names && (!names_off || !out->found))) return fail(ctx, NS_EINVAL, "ns_maf_besthit: null argument");
+    const uint64_t name_bytes = n_names ? names_off[n_names] : 0;
+    if (n_names) {
+        if (names_off[0]) return fail(ctx, NS_EINVAL, "ns_maf_besthit: offsets not ascending / beyond the names");
+        if (int rc = check_offsets(ctx, "ns_maf_besthit", "names", names_off, n_names, name_bytes)) return rc;
+        if (name_bytes && !names) return fail(ctx, NS_EINVAL, "ns_maf_besthit: null argument");
+        memset(out->found, 0, n_names);
+    }
+    if (!nbytes) return NS_OK;
+    const uint64_t n_wg = (nbytes + MAF_LINE_SPAN - 1u) / MAF_LINE_SPAN;
+    if (n_wg >= (1ull << 31)) return fail(ctx, NS_EINVAL, "ns_maf_besthit: 2^45 bytes of text or more");
+    HIPCHK(hipSetDevice(ctx->device));
+    unsigned long long small[MAFS_WORDS] = {~0ull, 0ull, 0ull, 0ull};
+    CallScratch s(ctx, "ns_maf_besthit");
+    const uint8_t *d_text = s.filled(text, (size_t)nbytes, 16);                         // (16 bytes to spare: the window loads of CsBytes)
+    unsigned long long *d_wg_count = s.zeroed<unsigned long long>((size_t)n_wg + 1), *d_wg_base = s.alloc<unsigned long long>((size_t)n_wg + 1);
+    const uint8_t *d_names = n_names ? s.filled(names, (size_t)name_bytes, 16) : nullptr;
+    const uint64_t *d_names_off = n_names ? s.filled(names_off, (size_t)n_names + 1) : nullptr;
+    uint8_t *d_found = n_names ? s.alloc<uint8_t>(n_names) : nullptr;
+    unsigned long long *d_small = s.filled(small, MAFS_WORDS);
+    if (int rc = s.upload()) return rc;
+    hipStream_t st = ctx->stream;
+    CALLCHK(s, hipEventRecord(ctx->evt[EV_HIST_BEGIN], st));
+    // ---- the lines ----
+    k_maf_line_count<<<dim3((unsigned)n_wg), dim3(256), 0, st>>>(d_text, nbytes, d_wg_count);
+    CALLCHK(s, hipGetLastError());
+    if (int rc = scan_sum(ctx, d_wg_count, d_wg_base, (size_t)n_wg + 1)) return fail(ctx, rc, std::string("ns_maf_besthit: ") + ctx->err);
+    unsigned long long n_lines = 0;
+    CALLCHK(s, hipMemcpyAsync(&n_lines, d_wg_base + n_wg, 8, hipMemcpyDeviceToHost, st));
+    CALLCHK(s, hipStreamSynchronize(st));
+    out->n_lines = out->first_bad_line = n_lines;
+    if (n_lines & 1u) return fail(ctx, NS_EINVAL, "ns_maf_besthit: an odd number of `s` lines: one is without its partner");
+    if (n_lines >= (1ull << 32)) return fail(ctx, NS_EINVAL, "ns_maf_besthit: 2^31 pairs or more");
+    const uint32_t n_pairs = (uint32_t)(n_lines / 2u);
+    out->n_pairs = n_pairs;
+    uint64_t slots = 2;
+    while (slots < 2ull * n_pairs) slots <<= 1;
+    const unsigned pair_grid = (n_pairs + 255u) / 256u;
+    uint64_t *d_starts = nullptr; MafLine *d_lines = nullptr; uint32_t *d_slot_of = nullptr, *d_flag = nullptr, *d_rank = nullptr;
+    MafOutLines *d_out_lines = nullptr; MafOutRecord *d_out_records = nullptr; MafOutFigures *d_out_figures = nullptr;
+    MafTable T{s.alloc<uint32_t>((size_t)slots), s.zeroed<unsigned long long>((size_t)slots), slots};
+    if (n_pairs) {
+        d_starts = s.alloc<uint64_t>((size_t)n_lines); d_lines = s.alloc<MafLine>((size_t)n_lines);
+        d_slot_of = s.alloc<uint32_t>(n_pairs); d_flag = s.zeroed<uint32_t>((size_t)n_pairs + 1); d_rank = s.alloc<uint32_t>((size_t)n_pairs + 1);
+        d_out_lines = s.alloc<MafOutLines>(n_pairs); d_out_records = s.alloc<MafOutRecord>(n_pairs); d_out_figures = s.alloc<MafOutFigures>(n_pairs);
+    }
+    if (int rc = s.upload()) return rc;
+    CALLCHK(s, hipMemsetAsync(T.owner, 0xff, (size_t)slots * 4, st));                   // MAF_EMPTY
+    uint32_t n_kept = 0;
+    if (n_pairs) {
+        k_maf_line_write<<<dim3((unsigned)n_wg), dim3(256), 0, st>>>(d_text, nbytes, d_wg_base, n_lines, d_starts);
+        CALLCHK(s, hipGetLastError());
+        k_maf_fields<<<dim3((unsigned)((n_lines + 255u) / 256u)), dim3(256), 0, st>>>(d_text, nbytes, d_starts, n_lines, d_lines, d_small);
+        CALLCHK(s, hipGetLastError());
+        CALLCHK(s, hipMemcpyAsync(small, d_small, 8, hipMemcpyDeviceToHost, st));
+        CALLCHK(s, hipStreamSynchronize(st));
+        if (small[MAFS_FIRST_BAD] != ~0ull) {                                           // a bad line: nothing is counted
+            out->first_bad_line = small[MAFS_FIRST_BAD];
+            CALLCHK(s, hipMemcpy(&out->first_bad_offset, d_starts + small[MAFS_FIRST_BAD], 8, hipMemcpyDeviceToHost));
+            return NS_OK;
+        }
+        // ---- the choice, the result ----
+        k_maf_choose<<<dim3(pair_grid), dim3(256), 0, st>>>(d_text, d_lines, n_pairs, T, d_slot_of, d_small);
+        CALLCHK(s, hipGetLastError());
+        k_maf_result<<<dim3(pair_grid), dim3(256), 0, st>>>(d_text, d_lines, n_pairs, T, d_slot_of, d_flag, d_small);
+        CALLCHK(s, hipGetLastError());
+        if (int rc = scan_sum(ctx, d_flag, d_rank, (size_t)n_pairs + 1)) return fail(ctx, rc, std::string("ns_maf_besthit: ") + ctx->err);
+        k_maf_emit<<<dim3(pair_grid), dim3(256), 0, st>>>(nbytes, d_starts, d_lines, n_pairs, d_flag, d_rank, d_out_lines, d_out_records, d_out_figures);
+        CALLCHK(s, hipGetLastError());
+    }
+    if (n_names) {
+        k_maf_names<<<dim3((n_names + 255u) / 256u), dim3(256), 0, st>>>(d_text, d_lines, T, d_names, d_names_off, n_names, d_found);
+        CALLCHK(s, hipGetLastError());
+    }
+    if (int rc = timed_tail(s, {{small, d_small, sizeof small}, {&n_kept, n_pairs ? d_rank + n_pairs : nullptr, n_pairs ? (size_t)4 : (size_t)0},
+                                {out->found, d_found, (size_t)n_names}}, &out->ms_kernel)) return rc;
+    if (small[MAFS_FULL]) return fail(ctx, NS_EHIP, "ns_maf_besthit: the name table was exhausted");
+    if (n_kept != small[MAFS_ALIGNED]) return fail(ctx, NS_EHIP, "ns_maf_besthit: the kept pairs and their ranks disagree");
+    if (n_kept) {
+        try { ctx->maf_lines.resize(n_kept); ctx->maf_records.resize(n_kept); ctx->maf_figures.resize(n_kept); }
+        catch (const std::bad_alloc &) { return fail(ctx, NS_ENOMEM, "ns_maf_besthit: no host memory for the result"); }
+        CALLCHK(s, hipMemcpyAsync(ctx->maf_lines.data(), d_out_lines, (size_t)n_kept * sizeof(MafOutLines), hipMemcpyDeviceToHost, st));
+        CALLCHK(s, hipMemcpyAsync(ctx->maf_records.data(), d_out_records, (size_t)n_kept * sizeof(MafOutRecord), hipMemcpyDeviceToHost, st));
+        CALLCHK(s, hipMemcpyAsync(ctx->maf_figures.data(), d_out_figures, (size_t)n_kept * sizeof(MafOutFigures), hipMemcpyDeviceToHost, st));
+        CALLCHK(s, hipStreamSynchronize(st));
+    }
+    out->lines = ctx->maf_lines.data(); out->records = ctx->maf_records.data(); out->figures = ctx->maf_figures.data();
+    out->n_kept = n_kept; out->pos_strand = small[MAFS_POS];
     return NS_OK;
 }
 

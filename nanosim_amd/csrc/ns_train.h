@@ -2,11 +2,12 @@
 // of the base-quality model (k_qual_mark, k_qual_count) and of the homopolymer-length model (k_hp_count, k_hp_records), and the line pairs
 // of SAM records (k_sam_scan, k_sam_lines), the fit of the error-length mixtures (k_mixfit), and the lengths behind the read-length
 // models (k_len_scan, k_len_flag, k_len_reduce), the split-alignment choice of chimeric reads (k_chim_scan, k_chim_select), the EM of
-// the abundance quantification (k_em_estep, k_em_accum, k_em_stop), and the Markov counts of the intron-retention model (k_ir_walk).  The
-// walks they run are ns_cs_hist.h, ns_qual_hist.h, ns_hp_hist.h, ns_sam_pairs.h, ns_mixfit.h, ns_read_len.h, ns_chimeric.h, ns_em.h and
-// ns_ir_train.h, which also compile for the host; the host side of the calls
+// the abundance quantification (k_em_estep, k_em_accum, k_em_stop), the Markov counts of the intron-retention model (k_ir_walk), and the
+// best hit per read of a MAF file (k_maf_*).  The
+// walks they run are ns_cs_hist.h, ns_qual_hist.h, ns_hp_hist.h, ns_sam_pairs.h, ns_mixfit.h, ns_read_len.h, ns_chimeric.h, ns_em.h,
+// ns_ir_train.h and ns_maf_best.h, which also compile for the host; the host side of the calls
 // (ns_cs_histograms / ns_maf_histograms, ns_qual_histograms, ns_hp_histograms / ns_hp_histograms_sam, ns_sam_pairs_build, ns_mixture_fit,
-// ns_read_lengths, ns_cigar_spans / ns_chimeric_select, ns_em_quantify, ns_ir_train) is at the end of nanosim_amd.hip.  Nothing here uses GenArgs or the simulation.
+// ns_read_lengths, ns_cigar_spans / ns_chimeric_select, ns_em_quantify, ns_ir_train, ns_maf_besthit) is at the end of nanosim_amd.hip.  Nothing here uses GenArgs or the simulation.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,6 +21,7 @@
 #include "ns_chimeric.h"
 #include "ns_em.h"
 #include "ns_ir_train.h"
+#include "ns_maf_best.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // k_cs_hist: the counting loop of the characterisation stage (ns_cs_hist.h; src/besthit_to_histogram.py:316-365), one alignment per
@@ -584,4 +586,129 @@ __global__ void __launch_bounds__(256) k_ir_walk(const uint8_t *__restrict__ cig
     }
     __syncthreads();
     if (threadIdx.x < IRC_WORDS && cnt[threadIdx.x]) atomicAdd(&small[IRS_COUNT + threadIdx.x], cnt[threadIdx.x]);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_maf_line_count, k_maf_line_write, k_maf_fields, k_maf_choose, k_maf_result, k_maf_emit, k_maf_names: the best hit per read of a MAF
+// file (ns_maf_best.h; src/get_besthit_maf.py:8-56), from the bytes of the file.
+// LINE_COUNT / LINE_WRITE: a workgroup looks at MAF_LINE_SPAN consecutive bytes of the text, a thread at 64 of them through an 8-byte
+// window, and counts the `s`-line starts among them (the test looks one byte back and one ahead, over the span's border too: a span
+// knows nothing else about its neighbours, and where a line ENDS is not its business — a line of 60 kb crosses four spans and is one
+// start in the first).  The exclusive scan of the workgroups' counts (hipcub, between the two) says where a workgroup's starts go; WRITE
+// repeats the test and places them by a scan over the workgroup: the starts are 64-bit offsets in the order of the text.
+// FIELDS, one line per thread: maf_parse_line to the line's '\n'; the smallest index of a bad line by atomic min.
+// CHOOSE, one pair per thread: maf_claim — the owner words only through atomicCAS — and maf_offer, one 64-bit atomicMax; the pair's slot
+// goes to slot_of.  No loop waits for another thread; the probe walk is bounded by the table (MAFS_FULL if it ever ends there).
+// RESULT, one pair per thread, in the NEXT kernel (the table is settled by the kernel boundary): kept iff the slot's key names the pair;
+// num_aligned and pos_strand are summed per wavefront, then per workgroup in LDS, and leave in one atomic each per workgroup.
+// EMIT, one pair per thread, behind the exclusive scan of the kept flags: the three records of a kept pair at its rank, in file order.
+// NAMES, one name of the reads file per thread: maf_find in the settled table.
+// small[]: MAFS_FIRST_BAD the smallest index of a bad line (preset to ~0), MAFS_ALIGNED, MAFS_POS, MAFS_FULL.
+// ---------------------------------------------------------------------------------------------------------
+enum { MAFS_FIRST_BAD = 0, MAFS_ALIGNED = 1, MAFS_POS = 2, MAFS_FULL = 3, MAFS_WORDS = 4 };
+static_assert(MAF_LINE_SPAN == 256u * MAF_LINE_PER_THREAD, "a workgroup of the line kernels is 256 threads");
+struct MafDevOps {
+    __device__ __forceinline__ uint32_t cas(uint32_t *w, uint32_t expected, uint32_t desired) const { return atomicCAS(w, expected, desired); }
+    __device__ __forceinline__ void max64(unsigned long long *w, unsigned long long v) const { atomicMax(w, v); }
+};
+// the `s`-line starts among a thread's 64 bytes as a bit mask
+__device__ __forceinline__ uint64_t maf_thread_starts(const uint8_t *__restrict__ text, uint64_t nbytes) {
+    const uint64_t b0 = (uint64_t)blockIdx.x * MAF_LINE_SPAN + (uint64_t)threadIdx.x * MAF_LINE_PER_THREAD;
+    uint64_t mask = 0;
+    if (b0 >= nbytes) return 0;
+    CsBytes t(text), side(text);                                  // (`side`: the bytes in front of and behind a candidate keep their own window)
+    for (uint32_t k = 0; k < MAF_LINE_PER_THREAD; ++k) {
+        const uint64_t i = b0 + k;
+        if (i + 1u >= nbytes) break;                              // (a start has a byte behind it)
+        if (t[i] == 's' && maf_is_start(side, nbytes, i)) mask |= 1ull << k;
+    }
+    return mask;
+}
+__global__ void __launch_bounds__(256) k_maf_line_count(const uint8_t *__restrict__ text, uint64_t nbytes, unsigned long long *__restrict__ wg_count) {
+    __shared__ unsigned long long part[4];
+    const unsigned long long n = wave_sum((unsigned long long)__popcll(maf_thread_starts(text, nbytes)));
+    if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) wg_count[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+__global__ void __launch_bounds__(256) k_maf_line_write(const uint8_t *__restrict__ text, uint64_t nbytes, const unsigned long long *__restrict__ wg_base,
+                                                        uint64_t n_lines, uint64_t *__restrict__ starts) {
+    __shared__ uint32_t part[4];
+    uint64_t mask = maf_thread_starts(text, nbytes);
+    const uint32_t mine = (uint32_t)__popcll(mask), lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t incl = mine;                                          // the inclusive scan over the wavefront
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t u = (uint32_t)__shfl_up((int)incl, o, 64); if (lane >= (uint32_t)o) incl += u; }
+    if (lane == 63u) part[wave] = incl;
+    __syncthreads();
+    uint64_t at = wg_base[blockIdx.x] + (incl - mine);
+    for (uint32_t w = 0; w < wave; ++w) at += part[w];
+    const uint64_t b0 = (uint64_t)blockIdx.x * MAF_LINE_SPAN + (uint64_t)threadIdx.x * MAF_LINE_PER_THREAD;
+    while (mask) {
+        const uint32_t k = (uint32_t)__ffsll((unsigned long long)mask) - 1u;
+        mask &= mask - 1u;
+        if (at < n_lines) starts[at] = b0 + k;                     // (at < n_lines: the count kernel saw the same bytes)
+        ++at;
+    }
+}
+__global__ void __launch_bounds__(256) k_maf_fields(const uint8_t *__restrict__ text, uint64_t nbytes, const uint64_t *__restrict__ starts, uint64_t n_lines,
+                                                    MafLine *__restrict__ lines, unsigned long long *__restrict__ small) {
+    const uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= n_lines) return;
+    CsBytes t(text);
+    MafLine L;
+    const bool ok = maf_parse_line(t, nbytes, starts[l], L);
+    lines[l] = L;
+    if (!ok) atomicMin(&small[MAFS_FIRST_BAD], (unsigned long long)l);
+}
+__global__ void __launch_bounds__(256) k_maf_choose(const uint8_t *__restrict__ text, const MafLine *__restrict__ lines, uint32_t n_pairs, MafTable T,
+                                                    uint32_t *__restrict__ slot_of, unsigned long long *__restrict__ small) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pairs) return;
+    CsBytes t(text), u(text);
+    const MafLine Q = lines[2ull * p + 1u];
+    MafDevOps ops;
+    uint64_t slot = maf_claim(t, u, lines, T, p, Q, ops);
+    if (slot >= T.slots) { atomicAdd(&small[MAFS_FULL], 1ull); slot = 0; }
+    else maf_offer(T, slot, p, Q.size, ops);
+    slot_of[p] = (uint32_t)slot;                                   // (slots <= 2^32: a slot fits)
+}
+__global__ void __launch_bounds__(256) k_maf_result(const uint8_t *__restrict__ text, const MafLine *__restrict__ lines, uint32_t n_pairs, MafTable T,
+                                                    const uint32_t *__restrict__ slot_of, uint32_t *__restrict__ flag, unsigned long long *__restrict__ small) {
+    __shared__ unsigned long long cnt[2];
+    if (threadIdx.x < 2u) cnt[threadIdx.x] = 0ull;
+    __syncthreads();
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t kept = 0, pos = 0;
+    if (p < n_pairs) {
+        kept = maf_kept(T, slot_of[p], p) ? 1u : 0u;
+        flag[p] = kept;
+        if (kept) {
+            CsBytes t(text), u(text);
+            const MafLine R = lines[2ull * p], Q = lines[2ull * p + 1u];
+            pos = maf_same_bytes(t, R.strand_at, R.strand_len, u, Q.strand_at, Q.strand_len) ? 1u : 0u;
+        }
+    }
+    // (every lane of the workgroup comes here: the wavefront sums need them all)
+    const unsigned long long k = wave_sum((unsigned long long)kept), s = wave_sum((unsigned long long)pos);
+    if ((threadIdx.x & 63u) == 0) { if (k) atomicAdd(&cnt[0], k); if (s) atomicAdd(&cnt[1], s); }
+    __syncthreads();
+    if (threadIdx.x == 0) { if (cnt[0]) atomicAdd(&small[MAFS_ALIGNED], cnt[0]); if (cnt[1]) atomicAdd(&small[MAFS_POS], cnt[1]); }
+}
+__global__ void __launch_bounds__(256) k_maf_emit(uint64_t nbytes, const uint64_t *__restrict__ starts, const MafLine *__restrict__ lines, uint32_t n_pairs,
+                                                  const uint32_t *__restrict__ flag, const uint32_t *__restrict__ rank, MafOutLines *__restrict__ out_lines,
+                                                  MafOutRecord *__restrict__ out_records, MafOutFigures *__restrict__ out_figures) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pairs || !flag[p]) return;
+    const uint32_t k = rank[p];                                    // (< the number of kept pairs <= n_pairs: the arrays hold n_pairs)
+    const MafLine R = lines[2ull * p], Q = lines[2ull * p + 1u];
+    maf_emit(nbytes, starts[2ull * p], R, starts[2ull * p + 1u], Q, out_lines[k], out_records[k], out_figures[k]);
+}
+__global__ void __launch_bounds__(256) k_maf_names(const uint8_t *__restrict__ text, const MafLine *__restrict__ lines, MafTable T,
+                                                   const uint8_t *__restrict__ names, const uint64_t *__restrict__ names_off, uint32_t n_names,
+                                                   uint8_t *__restrict__ found) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_names) return;
+    CsBytes t(text), nb(names);
+    const uint64_t lo = names_off[i], n = names_off[i + 1u] - lo;
+    found[i] = n <= 0xffffffffull && maf_find(t, lines, T, nb, lo, (uint32_t)n) ? 1u : 0u;
 }

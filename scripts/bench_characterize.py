@@ -23,7 +23,14 @@ values of the single steps, so that the spread shows.
 histograms of the reference's fixture (7, 12 and 8 bins; tests/golden/reference_mixfit.json.gz) and on histograms of 1 000 bins: the
 kernel milliseconds per type (device events around each of the three calls) of every step, the evaluations the searches made, and the
 end-to-end time of fit_mixtures.
-    python scripts/bench_characterize.py --mixfit [--steps 3]"""
+    python scripts/bench_characterize.py --mixfit [--steps 3]
+--besthit: the best hit per read of a LAST MAF file (ns_maf_besthit) on a synthetic file built here: --alignments pairs of `s` lines over a
+third as many read names (sizes from a small range, so that ties occur), aligned sequences of --columns bytes (200 distinct ones,
+repeated), an `a score=` line and a blank line per pair.  Prints the kernel milliseconds of every step (device events from the first
+kernel to the last, the host's two waits inside the call included), that per 10^6 pairs and as GB/s over the bytes of the text, and the
+end-to-end time of besthit_call (the H2D copy of the text and the copies of the result included) next to the time the host needs to
+read the same file into memory — the parse-and-copy side of the call.
+    python scripts/bench_characterize.py --besthit [--alignments 200000] [--columns 1000] [--steps 3]"""
 import argparse
 import ctypes as C
 import json
@@ -45,6 +52,8 @@ ap.add_argument("--qualities", action="store_true")
 ap.add_argument("--homopolymers", action="store_true")
 ap.add_argument("--sam-pairs", action="store_true")
 ap.add_argument("--mixfit", action="store_true")
+ap.add_argument("--besthit", action="store_true")
+ap.add_argument("--columns", type=int, default=1000)
 ap.add_argument("--records", action="store_true")
 ap.add_argument("--host-walk", action="store_true")
 ap.add_argument("--dump-maf", default=None)
@@ -86,6 +95,50 @@ if a.mixfit:
     res["value"] = res["fixture"]["kernel_ms_all_three(median)"]
     print(json.dumps(res))
     eng.close()
+    sys.exit(0)
+if a.besthit:
+    rng = np.random.default_rng(SEED)
+    seqs = ["".join(rng.choice(list("ACGT-"), a.columns, p=[0.24, 0.24, 0.24, 0.24, 0.04]).tolist()) for _ in range(200)]
+    n_names = max(1, a.alignments // 3)
+    name_id, size = rng.integers(0, n_names, a.alignments).tolist(), rng.integers(a.columns // 2, a.columns // 2 + 50, a.alignments).tolist()
+    parts = ["# LAST version 1256\n"]
+    for i in range(a.alignments):
+        sq = seqs[i % 200]
+        parts.append("a score=%d\ns chr%d %9d %d + 248956422 %s\ns read_%08x %5d %d %s %d %s\n\n"
+                     % (size[i] * 6, i % 24, i * 13, a.columns, sq, name_id[i], i % 50, size[i], "+-"[i & 1], size[i] + 120, sq))
+    tmp = tempfile.mkdtemp(prefix="nsbest_")
+    path = os.path.join(tmp, "synthetic.maf")
+    with open(path, "w") as f:
+        f.write("".join(parts))
+    del parts
+    nbytes = os.path.getsize(path)
+    best = {}
+    for i in range(a.alignments):                             # the choice restated (G:14-39): how many pairs have to be kept
+        if best.get(name_id[i], -1) < size[i]:
+            best[name_id[i]] = size[i]
+    eng = E.Engine(0)
+    host_read_s = []
+    for _ in range(a.steps + 1):
+        t0 = time.perf_counter()
+        text = np.fromfile(path, dtype=np.uint8)
+        host_read_s.append(time.perf_counter() - t0)
+    r = characterize.besthit_call(eng, text)                  # warms up
+    assert int(r["raw"].n_pairs) == a.alignments and int(r["raw"].n_kept) == len(best) and r["raw"].first_bad_line == r["raw"].n_lines
+    ms, e2e = [], []
+    for _ in range(a.steps):
+        t0 = time.perf_counter()
+        r = characterize.besthit_call(eng, text)
+        e2e.append(time.perf_counter() - t0)
+        ms.append(float(r["raw"].ms_kernel))
+    med = float(np.median(ms))
+    print(json.dumps({"metric": "best hit per read of a MAF file, kernel ms per 10^6 pairs (ns_maf_besthit)", "value": med * 1e6 / a.alignments,
+                      "pairs": a.alignments, "names": len(best), "columns": a.columns, "text_bytes": nbytes, "steps": a.steps, "kernel_ms": ms,
+                      "kernel_gb_per_s(text bytes)": nbytes / (med * 1e-3) / 1e9, "kernel_frac_of_hbm_8tbs": nbytes / (med * 1e-3) / 1e9 / 8000.0,
+                      "besthit_call_end_to_end_s": e2e, "host_read_of_the_file_s": host_read_s[1:],
+                      "end_to_end_gb_per_s": nbytes / float(np.median(e2e)) / 1e9}))
+    eng.close()
+    os.remove(path)
+    os.rmdir(tmp)
     sys.exit(0)
 tmp = tempfile.mkdtemp(prefix="nschar_")
 prefix = os.path.join(tmp, "hg002_like")

@@ -40,6 +40,7 @@ TRAINING = {
     CSRC + "ns_em.h": ("tests/em_host.cpp", ["tests/test_quantify.py"]),
     CSRC + "ns_hp_hist.h": ("tests/hp_train_host.cpp", ["tests/test_hp_train.py"]),
     CSRC + "ns_ir_train.h": ("tests/ir_train_host.cpp", ["tests/test_ir_train.py"]),
+    CSRC + "ns_maf_best.h": ("tests/maf_best_host.cpp", ["tests/test_besthit.py"]),
     CSRC + "ns_qual_hist.h": ("tests/qual_hist_host.cpp", ["tests/test_basequal.py"]),
     CSRC + "ns_read_len.h": ("tests/read_len_host.cpp", ["tests/test_read_lengths.py", "tests/test_chimeric_train.py"]),
     CSRC + "ns_sam_pairs.h": ("tests/sam_pairs_host.cpp", ["tests/test_sam_pairs.py", "tests/test_read_lengths.py", "tests/test_chimeric_train.py"]),
