@@ -1683,6 +1683,28 @@ double nso_kde_sample(const double *data, uint64_t n, double bw, uint32_t w0, ui
     return kde_sample(&k, w);
 }
 double nso_pow10m1(double x) { return pow10m1(x); }
+/* the chain's table questions over n draws (tests/test_lookup_probe.py: the reference of tests/lookup_probe.hip) — the same calls
+ * nso_error_list makes, with p = u32_to_p(u) */
+void nso_ecdf_lookup_batch(const double *hi, const double *vhi, uint32_t nseg, double vlo0, const uint32_t *u, int64_t *out, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i) out[i] = nso_ecdf_lookup(hi, vhi, nseg, vlo0, u32_to_p(u[i]));
+}
+/* the next match length behind prev_match: the first bin with lo <= prev_match < hi, else the last (S:1891-1893), then its column */
+void nso_next_match_batch(const ns_model_tables *t, const int32_t *prev_match, const uint32_t *u, int64_t *out, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i) {
+        uint32_t b = 0;
+        for (; b < t->mm_nbins; ++b)
+            if (t->mm_bin_lo[b] <= prev_match[i] && prev_match[i] < t->mm_bin_hi[b]) break;
+        if (b >= t->mm_nbins) b = t->mm_nbins - 1;
+        const uint32_t o = t->mm_seg_off[b];
+        out[i] = nso_ecdf_lookup(t->mm_hi + o, t->mm_vhi + o, t->mm_seg_off[b + 1] - o, t->mm_vlo0[b], u32_to_p(u[i]));
+    }
+}
+void nso_run_length_batch(const ns_model_tables *t, const int32_t *type, const uint32_t *u_mix, const uint32_t *u_len, int64_t *out, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i) out[i] = run_length(t, type[i], u32_to_p(u_mix[i]), u32_to_p(u_len[i]));
+}
+void nso_trans_pick_batch(const ns_model_tables *t, const int32_t *state, const uint32_t *u, int64_t *out, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i) out[i] = trans_pick(t->trans[state[i]], u32_to_p(u[i]));
+}
 /* one scalar primitive over n inputs (tests/test_math_probe.py: the same ops as tests/math_probe.hip).  in / out: 8-byte elements,
  * read as double, or as uint64 for the draw ops (NORMINV_U: u = low 32 bits; U53: a = high, b = low 32 bits).  Returns 0, -1 for an
  * unknown op. */

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Mutation audit of the training side's walk headers ("What the mutation audit leaves"), on the CPU host build.
+"""Mutation audit of the training side's walk headers and of the event chains' packer and look-ups ("What the
+mutation audit leaves"), on the CPU host build.
 
 The GPU tests of the training calls compare the device with the host build of the SAME header, so a mistake in the shared walk is wrong
 on both sides at once; what pins the walk is the reference fixtures, the oracle and the hand cases.  This tool measures how tightly:
@@ -8,6 +9,7 @@ the mutants the tests did not notice.
 
     python scripts/mutation_audit.py nanosim_amd/csrc/ns_em.h tests/test_quantify.py
     python scripts/mutation_audit.py --all [--classes rel,lit,logic] [--jobs N] [--timeout S] [--log FILE]
+    python scripts/mutation_audit.py --chain            ns_pack.h and the thread-per-read part of ns_chain.h, on tests/chain_host.hip
 
 Mutation classes: rel   `<` <-> `<=`, `>` <-> `>=`                                   (the default)
                   lit   an integer literal inside a condition or an index expression, +1 and -1
@@ -15,7 +17,9 @@ Mutation classes: rel   `<` <-> `<=`, `>` <-> `>=`                              
 Per header it prints the number of mutants, how many were killed, and one line per survivor: `file:line col op | source line`.
 A mutant that runs into its time limit counts as killed (a flipped loop bound need not terminate).  A mutant the host compiler rejects
 is no mutant (a `<` of a template argument list, say) and is left out.  Text the host build never compiles — the true branch of an
-`#if` on __HIP_DEVICE_COMPILE__, or on __HIPCC__ where the header's unit is built by g++ — is listed apart as "device-only, not auditable on the host", and is not counted.
+`#if` on __HIP_DEVICE_COMPILE__, or on __HIPCC__ where the header's unit is built by g++, and the wave-per-read functions of ns_chain.h
+(`__device__` only: the host pass parses them and makes no code) — is listed apart as "device-only, not auditable on the host", and is
+not counted.
 
 Mutants run on the CPU host build only: a mutant is by construction code that may read or loop out of bounds.  Nothing here compiles
 for a GPU, imports an engine or runs a test marked gpu.  The working tree is never touched: every worker mutates its own copy."""
@@ -46,13 +50,23 @@ TRAINING = {
     CSRC + "ns_sam_pairs.h": ("tests/sam_pairs_host.cpp", ["tests/test_sam_pairs.py", "tests/test_read_lengths.py", "tests/test_chimeric_train.py"]),
     CSRC + "ns_mixfit.h": ("tests/mixfit_host.cpp", ["tests/test_mixfit.py"]),
 }
+# the event chains: the packer of the chain tables and the thread-per-read chains with their look-ups, compiled for the host by
+# tests/chain_host.hip (hipcc --cuda-host-only -DNS_HOST_TEST); the tests that decide AT the thresholds first (a mutant dies at the first failure)
+CHAIN_TESTS = ["tests/test_lookup_probe.py", "tests/test_chain_edges.py", "tests/test_chain_host.py", "tests/test_chain_guide.py"]
+CHAIN = {
+    CSRC + "ns_pack.h": ("tests/chain_host.hip", CHAIN_TESTS + ["tests/test_qual_probe.py"]),      # (+ the base-quality tables of the same header)
+    CSRC + "ns_chain.h": ("tests/chain_host.hip", CHAIN_TESTS),
+}
+UNITS = {**TRAINING, **CHAIN}
+# header -> the text from the first line that holds this marker to the end of the file is `__device__` only
+DEVICE_ONLY_FROM = {CSRC + "ns_chain.h": "// ---- cooperative unaligned_error_list"}
 SKIP_DIRS = {".git", "__pycache__", "_tmp", ".pytest_cache"}
 DEVICE_MACROS = ("__HIP_DEVICE_COMPILE__", "__HIPCC__")
 
 
 def host_defines(unit: str):
     """which of DEVICE_MACROS the host pass over `unit` defines: g++ none, hipcc --cuda-host-only __HIPCC__ (see syntax_check)"""
-    return ("__HIPCC__",) if unit.endswith("mixfit_host.cpp") else ()
+    return ("__HIPCC__",) if unit.endswith(("mixfit_host.cpp", ".hip")) else ()
 
 
 def blank_comments(text: str) -> str:
@@ -83,12 +97,18 @@ def blank_comments(text: str) -> str:
     return "".join(out)
 
 
-def device_only_lines(text: str, defined=()) -> set:
+def device_only_lines(text: str, defined=(), from_marker=None) -> set:
     """the (0-based) lines the host pass leaves out: the true branch of an `#if` on a device macro that pass does not define (or the
-    else branch of its negation), and the other branch for a macro it does define"""
+    else branch of its negation), and the other branch for a macro it does define; with from_marker, every line from the first one that
+    holds it"""
     dev, stack = set(), []                                    # stack of [is_left_out, tests_a_device_macro]
+    tail = False
     for ln, line in enumerate(text.split("\n")):
         s = line.strip()
+        tail = tail or (from_marker is not None and from_marker in line)
+        if tail:
+            dev.add(ln)
+            continue
         if s.startswith("#if"):
             m = any(k in s for k in DEVICE_MACROS)
             neg = m and ("!defined" in s.replace(" ", "") or s.startswith("#ifndef"))
@@ -170,12 +190,12 @@ def mutants_of(text: str, classes):
 
 def syntax_check(unit: str):
     """the command that tells whether a mutant is still a program"""
-    if unit.endswith("mixfit_host.cpp"):
+    if unit.endswith(("mixfit_host.cpp", ".hip")):
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         hipcc = hipcc if os.path.exists(hipcc) else shutil.which("hipcc")
         if not hipcc:
             raise SystemExit("%s needs hipcc for its host build" % unit)
-        return [hipcc, "--cuda-host-only", "-x", "hip", "-std=c++17", "-fsyntax-only", "-w", unit]
+        return [hipcc, "--cuda-host-only", "-x", "hip", "-std=c++17", "-fsyntax-only", "-w"] + (["-DNS_HOST_TEST"] if unit.endswith(".hip") else []) + [unit]
     return ["g++", "-std=c++17", "-fsyntax-only", "-w", unit]
 
 
@@ -224,7 +244,7 @@ def audit(header, unit, tests, classes, jobs, limit, base, emit):
     with open(os.path.join(ROOT, header)) as f:
         text = f.read()
     lines = text.split("\n")
-    dev = device_only_lines(text, host_defines(unit))
+    dev = device_only_lines(text, host_defines(unit), DEVICE_ONLY_FROM.get(header))
     where = lambda off: (text.count("\n", 0, off), off - (text.rfind("\n", 0, off) + 1) + 1)
     todo, device = [], []
     for mut in mutants_of(text, classes):
@@ -270,7 +290,8 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("header", nargs="?", help="the header to mutate, relative to the repository")
     ap.add_argument("tests", nargs="*", help="the test files to run against every mutant")
-    ap.add_argument("--all", action="store_true", help="the eight training headers with their CPU test files")
+    ap.add_argument("--all", action="store_true", help="the training headers with their CPU test files")
+    ap.add_argument("--chain", action="store_true", help="ns_pack.h and the thread-per-read part of ns_chain.h with the chain's CPU test files")
     ap.add_argument("--classes", default="rel", help="comma-separated: rel, lit, logic (default rel)")
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
     ap.add_argument("--timeout", type=float, default=300.0, help="seconds per mutant, at most (the limit in use follows the unmutated run's time)")
@@ -279,17 +300,17 @@ def main():
     classes = [c for c in a.classes.split(",") if c]
     if not classes or set(classes) - {"rel", "lit", "logic"}:
         ap.error("classes are rel, lit and logic")
-    if a.all == bool(a.header):
-        ap.error("give a header with its tests, or --all")
-    if a.all:
-        plan = [(h, u, t) for h, (u, t) in TRAINING.items()]
+    if (a.all or a.chain) == bool(a.header):
+        ap.error("give a header with its tests, or --all, or --chain")
+    if a.all or a.chain:
+        plan = [(h, u, t) for h, (u, t) in {**(TRAINING if a.all else {}), **(CHAIN if a.chain else {})}.items()]
     else:
         h = os.path.relpath(os.path.abspath(a.header), ROOT)
         if not a.tests:
             ap.error("no test file given")
-        unit = TRAINING[h][0] if h in TRAINING else None
+        unit = UNITS[h][0] if h in UNITS else None
         if unit is None:
-            ap.error("%s: no host translation unit known for it (TRAINING)" % h)
+            ap.error("%s: no host translation unit known for it (TRAINING, CHAIN)" % h)
         plan = [(h, unit, [os.path.relpath(os.path.abspath(t), ROOT) for t in a.tests])]
     log = open(a.log, "w") if a.log else None
 

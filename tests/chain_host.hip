@@ -61,3 +61,51 @@ int chost_error_list(const void *p, int variant, int staged, int32_t m_ref, uint
 }
 
 }  // extern "C"
+
+#ifdef CHAIN_HOST_MAIN
+// Stand-alone program for -fsanitize=address,undefined (tests/test_chain_edges.py): packs a model it makes up itself, every table in a heap
+// buffer of exactly its size, so that a read or a store of the packer one element behind a table is an error; then builds the bucket
+// table of one quality class into a buffer of exactly 1 024 entries.  Prints the image's size; exit status 0.
+#include <cstdio>
+int main() {
+    const uint32_t nb = 3, nseg[3] = {4, 1, 6};
+    std::vector<double> fm_hi{0.25, 0.5, 1.0}, fm_vhi{3, 9, 40};
+    std::vector<int64_t> lo{0, 2, 7}, hi{2, 7, 200};       // (previous matches 200 .. 255 fall through the bin search to the last bin)
+    std::vector<uint32_t> off{0, 4, 5, 11};
+    std::vector<double> mm_hi, mm_vhi, vlo0{0, 1, 2};
+    for (uint32_t b = 0; b < nb; ++b)
+        for (uint32_t s = 0; s < nseg[b]; ++s) {
+            mm_hi.push_back(s + 1 == nseg[b] ? (b == 2 ? 0.75 : 1.0) : (s + 1.0) / (nseg[b] + 1.0));       // (column 2: a last edge below the cut of every prefix)
+            mm_vhi.push_back(vlo0[b] + (s + 1) * (b + 1) * 3);
+        }
+    std::vector<double> cdf[3][2];
+    ns_model_tables *t = new ns_model_tables();
+    t->fm_nseg = 3; t->fm_hi = fm_hi.data(); t->fm_vhi = fm_vhi.data(); t->fm_vlo0 = 0;
+    t->mm_nbins = nb; t->mm_bin_lo = lo.data(); t->mm_bin_hi = hi.data(); t->mm_seg_off = off.data();
+    t->mm_hi = mm_hi.data(); t->mm_vhi = mm_vhi.data(); t->mm_vlo0 = vlo0.data();
+    for (int s = 0; s < 7; ++s) { t->trans[s][0] = 0.4; t->trans[s][1] = 0.7; t->trans[s][2] = 0.7; }
+    for (int ty = 0; ty < 3; ++ty) {
+        t->mix_w[ty] = 0.5;
+        for (int c = 0; c < 2; ++c) {
+            const uint32_t n = 1 + 3 * ty + c;
+            for (uint32_t j = 0; j < n; ++j) cdf[ty][c].push_back(j + 1 == n ? (c ? 0.5 : 1.0) : (j + 1.0) / (2.0 * n));     // (component 1 ends below 1)
+            t->mix_n[ty][c] = n; t->mix_cdf[ty][c] = cdf[ty][c].data();
+        }
+    }
+    size_t words = 0;
+    for (uint32_t force : {0u, 3u, 14u}) {
+        ChainTab ct; std::vector<uint64_t> blob; bool whole = false;
+        ns_pack_chain_tables(t, off[nb], ct, blob, whole, force);
+        if (!whole || ct.n_words != blob.size()) return 1;
+        words += blob.size();
+    }
+    std::vector<uint32_t> thr(NS_QUAL_LEVELS);
+    for (uint32_t j = 0; j < NS_QUAL_LEVELS; ++j) thr[j] = j * 500u;
+    std::vector<uint16_t> lut(1024);
+    if (ns_qual_thr_decrease(thr.data())) return 2;
+    ns_build_qual_lut(thr.data(), lut.data());
+    printf("%zu words, lut[1023] %u\n", words, (unsigned)lut[1023]);
+    delete t;
+    return 0;
+}
+#endif

@@ -550,7 +550,9 @@ def test_ecdf_segments_of_every_width(small_ref):
     """The LDS image of the chain answers an ECDF look-up without floating point where it can (ns_chain.h: ecdf_lookup_u): unit-wide
     segments by a flag, segments up to 15 units wide by a threshold list the host derives from the fp64 formula, wider ones (empty
     histogram bins merged, S:216-221) by the formula itself.  A model whose match-length columns mix all three, with edges that sit on
-    and next to the 2^-32 grid of the draws: same reads as the oracle (which only knows the fp64 formula)."""
+    and next to the 2^-32 grid of the draws: same reads as the oracle (which only knows the fp64 formula).  (Random draws land on a given
+    edge about once in 2^32: what the look-ups do AT a threshold is decided in tests/test_lookup_probe.py, tests/test_chain_edges.py and
+    tests/test_gpu_chain_edges.py.)"""
     import copy
     import os
     from tests.conftest import GOLDEN
