@@ -361,7 +361,7 @@ int ns_io_counters(ns_ctx *ctx, ns_io_stats *out, int reset);
  *   error_list   error transitions, row = mis, ins, del, mis0, ins0, del0 (the previous error, "0": no match in between), column = mis,
  *                ins, del; first_error: the first error of every alignment                   -> _error_markov_model
  * cs: the strings back to back, aln_off[n_aln + 1] their offsets (host memory; copied to the device).  The tables the reference writes
- * from these counts are text formatting on the host (nanosim_amd/characterize.py).  match_list is a dense cap x cap matrix in caller-owned
+ * from these counts are text formatting on the host (nanosim_amd/characterize/errors.py).  match_list is a dense cap x cap matrix in caller-owned
  * host memory: an add_match with an index >= cap is counted in n_match2d_overflow and max_match says how large the matrix has to be. */
 typedef struct ns_cs_hist {
     uint32_t cap_match2d;         /* in */
@@ -389,7 +389,7 @@ int ns_maf_histograms(ns_ctx *ctx, const uint8_t *ref_lines, const uint8_t *quer
  * replaces the collecting loops of src/model_base_qualities.py (M:23-79): for every query base of every primary alignment its class —
  * mismatch, insertion, match (from the cs string), head / tail (the soft clips), unmapped (every base of an unmapped read) — and its
  * quality, as a histogram per class.  The log-normal fit the reference runs on the collected values (M:82-96) is a closed form of the
- * histogram and is done on the host (nanosim_amd/characterize.py: fit_qualities).
+ * histogram and is done on the host (nanosim_amd/characterize/qualities.py: fit_qualities).
  * cs / qual: the cs strings and the QUAL strings (SAM text, Phred + 33; soft clips included, hard clips are not in QUAL) of the
  * alignments back to back in host memory, alignment a at cs_off[a] .. cs_off[a + 1] and qual_off[a] .. qual_off[a + 1]; aln[a]: its soft
  * clips.  head + tail must not exceed the alignment's quality length.  Added without an ABI change (a new function breaks no caller). */
@@ -416,7 +416,7 @@ int ns_qual_histograms(ns_ctx *ctx, const uint8_t *cs, uint64_t cs_bytes, const 
  *   records                       optional (NULL: none): one ns_hp_record per homopolymer, alignment by alignment in the order of the
  *                                 call and left to right inside an alignment.  n_hp is their number; when it exceeds cap_records none
  *                                 is written: call again with a larger buffer.
- * The fits the reference runs on these (H:142-201) are done on the host (nanosim_amd/characterize.py: fit_homopolymers).
+ * The fits the reference runs on these (H:142-201) are done on the host (nanosim_amd/characterize/homopolymers.py: fit_homopolymers).
  * ref_lines / query_lines / aln_off: as ns_maf_histograms; an alignment may have at most 2^24 - 1 columns.  Added without an ABI change. */
 typedef struct ns_hp_record {
     uint32_t aln;               /* index of the alignment in the call */
@@ -473,7 +473,7 @@ int ns_hp_histograms_sam(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *ciga
  * The objective is the largest |model CDF - cdf|; it is NaN when a parameter is not > 0 or p > 1 (scipy's argument checks).  The search is
  * scipy's minimize(f, x0, method='Nelder-Mead') with its defaults; objective, evaluation order and search are written down in
  * nanosim_amd/csrc/ns_mixfit.h.  NS_MIXFIT_EVALUATE returns the objective at each given point instead (fun = residual, nfev = 1, nit = 0).
- * Selecting among the starts and writing <prefix>_model_profile is done on the host (nanosim_amd/characterize.py: fit_mixtures).
+ * Selecting among the starts and writing <prefix>_model_profile is done on the host (nanosim_amd/characterize/mixfit.py: fit_mixtures).
  * Added without an ABI change. */
 enum { NS_MIXFIT_MISMATCH = 0, NS_MIXFIT_INDEL = 1 };
 enum { NS_MIXFIT_FIT = 0, NS_MIXFIT_EVALUATE = 1 };
@@ -566,7 +566,7 @@ int ns_chimeric_select(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_
  * Out: abundance[n_targets] in percent, count[n_targets] (base_count_tmp / read_count_tmp of the last executed iteration),
  * diff_trace[max_iter] (diff_tmp of iteration i; entries from n_iter on are 0), n_iter (iterations executed, 1 .. max_iter), n_nonfinite
  * (abundances of the last iteration that are NaN or infinite: the rest is then meaningless).  TPM and the file are the caller's
- * (nanosim_amd/characterize.py: em_quantify, format_quantification).  NS_EINVAL for n_targets == 0 and total == 0 (not > 0).
+ * (nanosim_amd/characterize/quantification.py: em_quantify, format_quantification).  NS_EINVAL for n_targets == 0 and total == 0 (not > 0).
  * Added without an ABI change. */
 typedef struct ns_em_problem {
     uint32_t n_targets, n_multi;

@@ -1,6 +1,6 @@
 // ns_qual_hist.h — training side, the base-quality model: what src/model_base_qualities.py collects per query base of
 // every primary alignment (M:23-79) — the base's class (mismatch / insertion / match / head-tail clip / unmapped read) and its quality —
-// as a 5 x 94 histogram; the log-normal fit of M:82-96 is a closed form of that histogram (nanosim_amd/characterize.py).
+// as a 5 x 94 histogram; the log-normal fit of M:82-96 is a closed form of that histogram (nanosim_amd/characterize/qualities.py).
 // M: = src/model_base_qualities.py of bcgsc/NanoSim v3.2.2.
 //
 // Two phases.  MARK: one walk per alignment over its cs string (the tokeniser of ns_cs_hist.h, cs_next_item — the regex of M:25 is the
