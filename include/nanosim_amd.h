@@ -662,6 +662,38 @@ typedef struct ns_maf_best_result {
 int ns_maf_besthit(ns_ctx *ctx, const uint8_t *text, uint64_t nbytes, const uint8_t *names, const uint64_t *names_off, uint32_t n_names,
                    ns_maf_best_result *out);
 
+/* ---- training side: BAM records to SAM text ----------------------------------------------------------------------------------------------------
+ * the records of a BAM file as `samtools view` prints them, byte for byte; nanosim_amd/csrc/ns_bam.h has the record layout, the rules of
+ * the text and how the kernels work.  bytes[nbytes]: inflated BAM that begins at a record boundary (the header is the caller's).  The call
+ * hops the block_size chain; `consumed` counts the bytes of the whole records.  A trailing partial record is left unconsumed when
+ * final == 0 and is a bad record (NS_BAM_BAD_TRUNCATED) when final != 0.  ref_names / ref_off / n_ref: the names of the header's reference
+ * dictionary one behind the other, name i the bytes ref_off[i] .. ref_off[i + 1] - 1.
+ * Out: text[n_text], the lines of the n_records records, each with its '\n'; line_off[n_records + 1], where they begin in text
+ * (line_off[n_records] == n_text).  Both belong to the context, lie in page-locked host memory and stay valid until the next ns_bam_to_sam
+ * on it or ns_destroy.  With a bad record the call returns NS_OK and emits nothing (n_records == n_text == consumed == 0): first_bad is its
+ * index among the records of this call (~0 without), first_bad_offset where its block_size stands in bytes, bad_reason why.
+ * NS_EINVAL for null arguments, offsets that do not ascend from 0 and 2^31 records or more, NS_ENOMEM when the device cannot hold the
+ * batch.  nbytes == 0 is valid.  ms_kernel: from the first kernel to the last, the waits of the host for the bad-record check, for the
+ * text of the floats and for the size of the text included.  Added without an ABI change. */
+enum { NS_BAM_OK = 0, NS_BAM_BAD_BLOCK_SIZE = 1, /* block_size is negative or smaller than what the record's own counts need */
+       NS_BAM_BAD_LSEQ = 2,                      /* l_seq < 0 */
+       NS_BAM_BAD_REFID = 3,                     /* refID or next_refID outside [-1, n_ref) */
+       NS_BAM_BAD_NAME = 4,                      /* the name is not NUL-terminated */
+       NS_BAM_BAD_TAG_TYPE = 5,                  /* a tag, or the elements of a B tag, of an unknown type */
+       NS_BAM_BAD_TAG_NUL = 6,                   /* a Z or H tag without a NUL inside the record */
+       NS_BAM_BAD_TAG_COUNT = 7,                 /* a B tag's count, or a tag's value, runs past the record */
+       NS_BAM_BAD_TRUNCATED = 8 };               /* final != 0 and the bytes end inside a record */
+typedef struct ns_bam_result {
+    const uint8_t *text;                         /* out, owned by the context */
+    const uint64_t *line_off;
+    uint64_t n_records, n_text, consumed;        /* out */
+    uint64_t first_bad, first_bad_offset;        /* out */
+    uint32_t bad_reason, reserved;
+    double ms_kernel;
+} ns_bam_result;
+int ns_bam_to_sam(ns_ctx *ctx, const uint8_t *bytes, uint64_t nbytes, int final, const uint8_t *ref_names, const uint64_t *ref_off, uint32_t n_ref,
+                  ns_bam_result *out);
+
 /* device address of a result buffer (for zero-copy consumers such as torch / RCCL); NULL if absent */
 const void *ns_device_ptr(ns_ctx *ctx, int which);
 

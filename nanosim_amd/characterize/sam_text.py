@@ -1,6 +1,6 @@
 """SAM text as the training stages read it: the one loop over the lines of a file (sam_lines), the look-up of an optional field
 (sam_tag) and the cs string of a record (cs_of, get_cs).  The seven readers of the stages are filters over sam_lines.
-Not covered: BAM input (pysam is not a dependency here: convert with ``samtools view -h``)."""
+BAM input: sam_lines takes the object characterize.read_bam returns (bam.py) wherever it takes a path."""
 import re
 
 _MD_TOKEN = re.compile(r'(\d+)|(\^[A-Za-z]+)|([A-Za-z])')
@@ -14,24 +14,47 @@ def _sam_refs(fld, refs):
         refs.append((tags["SN"], int(tags["LN"])))
 
 
-def sam_lines(path: str, min_fields: int, refs=None, header=None, drop: int = 0, lines: bool = False):
+class SamSource:
+    """something that is iterated like a SAM file opened for reading — its lines, each with its '\\n' — without being one: sam_lines
+    takes it in the place of a path (bam.BamText is the one there is; str() of it names the file, for messages)"""
+
+
+def _open_sam(path):
+    """the SAM text file at `path`, opened for reading; ValueError for a gzip / BGZF file, which a BAM file is"""
+    with open(path, "rb") as f:
+        if f.read(2) == b"\x1f\x8b":
+            raise ValueError("%s begins with the gzip magic: not SAM text.  A BAM file is read with characterize.read_bam(path, eng), "
+                             "whose result every reader takes in the place of the path" % path)
+    return open(path)
+
+
+def sam_lines(path, min_fields: int, refs=None, header=None, drop: int = 0, lines: bool = False):
     """The records of a SAM text file, in file order, each as the list of its fields, split once (with `lines` as (the line as it
     stands, that list), for the reader that writes lines out again).  The header lines stay out of the stream: `header`, a list, takes
     them as they stand and `refs`, a list, the (SN, LN) of every @SQ line that has both.  min_fields: records with fewer fields are
     dropped (11: a whole record, 6: up to the CIGAR); drop: so are records with one of these FLAG bits.  Nothing is converted and no
-    other rule applied: a reader's int() has to raise at the record the reader has come to, and a test here is paid by all seven."""
-    with open(path) as f:
-        for line in f:
-            if line[0] == "@":
-                if header is not None:
-                    header.append(line)
-                if refs is not None and line.startswith("@SQ\t"):
-                    _sam_refs(line.rstrip("\n").split("\t"), refs)
-                continue
-            fld = line.rstrip("\n").split("\t")
-            if len(fld) < min_fields or (drop and int(fld[1]) & drop):
-                continue
-            yield (line, fld) if lines else fld
+    other rule applied: a reader's int() has to raise at the record the reader has come to, and a test here is paid by all seven.
+    `path`: a SAM text file, or a SamSource (read_bam's BamText: the lines come from the GPU's decode of the BAM records)."""
+    if isinstance(path, SamSource):
+        yield from _sam_records(path, min_fields, refs, header, drop, lines)
+        return
+    with _open_sam(path) as f:
+        yield from _sam_records(f, min_fields, refs, header, drop, lines)
+
+
+def _sam_records(f, min_fields, refs, header, drop, lines):
+    """sam_lines over the lines `f` gives"""
+    for line in f:
+        if line[0] == "@":
+            if header is not None:
+                header.append(line)
+            if refs is not None and line.startswith("@SQ\t"):
+                _sam_refs(line.rstrip("\n").split("\t"), refs)
+            continue
+        fld = line.rstrip("\n").split("\t")
+        if len(fld) < min_fields or (drop and int(fld[1]) & drop):
+            continue
+        yield (line, fld) if lines else fld
 
 
 def sam_tag(fld, prefix: str):

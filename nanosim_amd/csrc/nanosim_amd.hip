@@ -16,7 +16,7 @@
 //   k_errlog            wave/read     _aligned_error_profile rows                           (S:2006-2008)
 // Metagenome worker calls run k_lengths / k_chain per PASS of the reference's while loop (S:844-1040) with k_meta_* around them; the lists of a
 // pass are launched before the host has walked the species quotas (assign_species), k_meta_tail does positions + acceptance afterwards.
-// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms, ns_sam_pairs_build, ns_mixture_fit, ns_read_lengths, ns_cigar_spans, ns_chimeric_select, ns_em_quantify, ns_ir_train, ns_maf_besthit: at the end of the host part) has its kernels in ns_train.h.
+// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms, ns_sam_pairs_build, ns_mixture_fit, ns_read_lengths, ns_cigar_spans, ns_chimeric_select, ns_em_quantify, ns_ir_train, ns_maf_besthit, ns_bam_to_sam: at the end of the host part) has its kernels in ns_train.h.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdio.h>
@@ -2225,6 +2225,8 @@ struct ns_ctx {
     DevBuf<uint64_t> ir_need, ir_off; DevBuf<uint8_t> spliced;
     uint64_t spliced_bytes = 0;
     std::vector<ns_maf_best_lines> maf_lines; std::vector<ns_maf_best_record> maf_records; std::vector<ns_maf_best_figures> maf_figures;   // the result of the last ns_maf_besthit
+    PinBuf bam_text, bam_line_off;                       // the result of the last ns_bam_to_sam, page-locked
+    std::vector<uint64_t> bam_rec_off, bam_flt_at; std::vector<uint32_t> bam_flt_first; std::vector<uint8_t> bam_slots;   // ... and its host-side lists
     uint8_t *pin_small = nullptr;    // page-locked slots for the scalar read-backs of a call (read_small)
     PinBuf pin_a, pin_b, pin_c;      // pinned host staging of the metagenome passes: draws (then species ids), sorted lengths, words
     uint32_t nspecies = 0;
@@ -4867,6 +4869,134 @@ int ns_maf_besthit(ns_ctx *ctx, const uint8_t *text, uint64_t nbytes, const uint
     }
     out->lines = ctx->maf_lines.data(); out->records = ctx->maf_records.data(); out->figures = ctx->maf_figures.data();
     out->n_kept = n_kept; out->pos_strand = small[MAFS_POS];
+    return NS_OK;
+}
+
+// BAM records to SAM text (include/nanosim_amd.h: ns_bam_result; ns_bam.h).  The host hops the block_size chain (one 4-byte read per
+// record) and waits three times inside the call: for the bad-record check and the number of floats, for the places of the floats when
+// there are any (their text is the C library's), and for the size of the text, which the page-locked result is grown to.
+int ns_bam_to_sam(ns_ctx *ctx, const uint8_t *bytes, uint64_t nbytes, int final, const uint8_t *ref_names, const uint64_t *ref_off, uint32_t n_ref,
+                  ns_bam_result *out) {
+    if (!ctx) return NS_EINVAL;
+    if (!out) return fail(ctx, NS_EINVAL, "ns_bam_to_sam: null argument");
+    static_assert(NS_BAM_BAD_BLOCK_SIZE == BAM_BAD_BLOCK_SIZE && NS_BAM_BAD_TAG_COUNT == BAM_BAD_TAG_COUNT && NS_BAM_BAD_TRUNCATED == BAM_BAD_TRUNCATED,
+                  "ns_bam.h mirrors the ABI's reasons");
+    out->text = nullptr; out->line_off = nullptr; out->n_records = out->n_text = out->consumed = 0; out->first_bad = ~0ull; out->first_bad_offset = ~0ull;
+    out->bad_reason = NS_BAM_OK; out->reserved = 0; out->ms_kernel = 0;
+    if ((nbytes && !bytes) || (n_ref && !ref_off)) return fail(ctx, NS_EINVAL, "ns_bam_to_sam: null argument");
+    const uint64_t name_bytes = n_ref ? ref_off[n_ref] : 0;
+    if (n_ref) {
+        if (ref_off[0]) return fail(ctx, NS_EINVAL, "ns_bam_to_sam: offsets not ascending / beyond the names");
+        if (int rc = check_offsets(ctx, "ns_bam_to_sam", "names", ref_off, n_ref, name_bytes)) return rc;
+        if (name_bytes && !ref_names) return fail(ctx, NS_EINVAL, "ns_bam_to_sam: null argument");
+    }
+    // ---- the records: the block_size chain ----
+    std::vector<uint64_t> &off = ctx->bam_rec_off;
+    off.clear();
+    uint64_t at = 0, host_bad = ~0ull;
+    uint32_t host_reason = NS_BAM_OK;
+    try {
+        while (nbytes - at >= 4u) {
+            int32_t bs;
+            memcpy(&bs, bytes + at, 4);
+            if (bs < 0) { host_bad = off.size(); host_reason = NS_BAM_BAD_BLOCK_SIZE; break; }
+            if ((uint64_t)bs > nbytes - at - 4u) break;                                   // a partial record
+            off.push_back(at);
+            at += 4ull + (uint64_t)bs;
+        }
+        if (host_bad == ~0ull && final && at < nbytes) { host_bad = off.size(); host_reason = NS_BAM_BAD_TRUNCATED; }
+        off.push_back(at);
+    } catch (const std::bad_alloc &) { return fail(ctx, NS_ENOMEM, "ns_bam_to_sam: no host memory for the record offsets"); }
+    const uint64_t n64 = off.size() - 1u;
+    if (n64 >= (1ull << 31)) return fail(ctx, NS_EINVAL, "ns_bam_to_sam: 2^31 records or more");
+    const uint32_t n = (uint32_t)n64;
+    auto bad = [&](uint64_t index, uint64_t where, uint32_t reason) { out->first_bad = index; out->first_bad_offset = where; out->bad_reason = reason; return NS_OK; };
+    if (!n) return host_bad != ~0ull ? bad(host_bad, at, host_reason) : NS_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    unsigned long long small[BAMS_WORDS] = {~0ull, 0ull, 0ull, 0ull};
+    CallScratch s(ctx, "ns_bam_to_sam");
+    const uint8_t *d_bytes = s.filled(bytes, (size_t)at, 16);
+    const uint64_t *d_off = s.filled(off.data(), (size_t)n + 1);
+    const BamRefs R{n_ref ? s.filled(ref_names, (size_t)name_bytes, 16) : nullptr, n_ref ? s.filled(ref_off, (size_t)n_ref + 1) : nullptr, n_ref};
+    BamRec *d_rec = s.alloc<BamRec>(n);
+    unsigned long long *d_len = s.zeroed<unsigned long long>((size_t)n + 1), *d_line_off = s.alloc<unsigned long long>((size_t)n + 1);
+    uint32_t *d_slices = s.zeroed<uint32_t>((size_t)n + 1), *d_slice_off = s.alloc<uint32_t>((size_t)n + 1);
+    uint64_t flt_cap = 4ull * n + 1024u;
+    unsigned long long *d_flt_at = s.alloc<unsigned long long>((size_t)flt_cap);
+    unsigned long long *d_small = s.filled(small, BAMS_WORDS);
+    if (int rc = s.upload()) return rc;
+    hipStream_t st = ctx->stream;
+    const unsigned rec_grid = (n + 3u) / 4u;
+    CALLCHK(s, hipEventRecord(ctx->evt[EV_HIST_BEGIN], st));
+    // ---- measure ----
+    k_bam_measure<<<dim3(rec_grid), dim3(256), 0, st>>>(d_bytes, d_off, n, R, d_rec, d_len, d_slices, d_flt_at, flt_cap, d_small);
+    CALLCHK(s, hipGetLastError());
+    CALLCHK(s, hipMemcpyAsync(small, d_small, sizeof small, hipMemcpyDeviceToHost, st));
+    CALLCHK(s, hipStreamSynchronize(st));
+    if (small[BAMS_FIRST_BAD] != ~0ull) return bad(small[BAMS_FIRST_BAD] >> 8, off[(size_t)(small[BAMS_FIRST_BAD] >> 8)], (uint32_t)(small[BAMS_FIRST_BAD] & 0xffu));
+    if (host_bad != ~0ull) return bad(host_bad, at, host_reason);
+    const uint64_t n_float = small[BAMS_N_FLOAT];
+    if (n_float >= (1ull << 32)) return fail(ctx, NS_EINVAL, "ns_bam_to_sam: 2^32 float values or more");
+    if (n_float > flt_cap) {                                                              // more floats than the list held: once more, with room for all
+        flt_cap = n_float;
+        d_flt_at = s.alloc<unsigned long long>((size_t)flt_cap);
+        if (s.rc) return s.rc;
+        CALLCHK(s, hipMemsetAsync(d_small + BAMS_N_FLOAT, 0, 8, st));
+        k_bam_measure<<<dim3(rec_grid), dim3(256), 0, st>>>(d_bytes, d_off, n, R, d_rec, d_len, d_slices, d_flt_at, flt_cap, d_small);
+        CALLCHK(s, hipGetLastError());
+    }
+    // ---- the floats: their places to the host, their text back ----
+    const uint32_t *d_flt_first = nullptr; const uint8_t *d_slots = nullptr;
+    if (n_float) {
+        try {
+            ctx->bam_flt_at.resize((size_t)n_float); ctx->bam_flt_first.assign((size_t)n + 1, 0u); ctx->bam_slots.assign((size_t)n_float * BAM_FLOAT_SLOT, 0);
+        } catch (const std::bad_alloc &) { return fail(ctx, NS_ENOMEM, "ns_bam_to_sam: no host memory for the floats"); }
+        std::vector<uint64_t> &fa = ctx->bam_flt_at;
+        CALLCHK(s, hipMemcpyAsync(fa.data(), d_flt_at, (size_t)n_float * 8, hipMemcpyDeviceToHost, st));
+        CALLCHK(s, hipStreamSynchronize(st));
+        std::sort(fa.begin(), fa.end());                                                  // the order of the records, and inside a record the order of its tags
+        uint32_t r = 0;
+        for (size_t k = 0; k < fa.size(); ++k) {
+            if (fa[k] > at - 4u) return fail(ctx, NS_EHIP, "ns_bam_to_sam: a float outside the records");
+            while (r < n && off[r + 1u] <= fa[k]) ctx->bam_flt_first[++r] = (uint32_t)k;
+            float f;
+            memcpy(&f, bytes + fa[k], 4);
+            char buf[32];
+            int l = snprintf(buf, sizeof buf, "%g", (double)f);
+            if (l < 0) l = 0;
+            if (l > (int)BAM_FLOAT_CHARS) l = (int)BAM_FLOAT_CHARS;
+            uint8_t *slot = ctx->bam_slots.data() + k * BAM_FLOAT_SLOT;
+            memcpy(slot, buf, (size_t)l);
+            slot[BAM_FLOAT_SLOT - 1u] = (uint8_t)l;
+        }
+        while (r < n) ctx->bam_flt_first[++r] = (uint32_t)fa.size();
+        d_flt_first = s.filled(ctx->bam_flt_first.data(), (size_t)n + 1);
+        d_slots = s.filled(ctx->bam_slots.data(), ctx->bam_slots.size());
+        if (int rc = s.upload()) return rc;
+        k_bam_float_len<<<dim3((n + 255u) / 256u), dim3(256), 0, st>>>(d_flt_first, d_slots, n, d_len);
+        CALLCHK(s, hipGetLastError());
+    }
+    // ---- the offsets, the text ----
+    if (int rc = scan_sum(ctx, d_len, d_line_off, (size_t)n + 1)) return fail(ctx, rc, std::string("ns_bam_to_sam: ") + ctx->err);
+    if (int rc = scan_sum(ctx, d_slices, d_slice_off, (size_t)n + 1)) return fail(ctx, rc, std::string("ns_bam_to_sam: ") + ctx->err);
+    unsigned long long n_text = 0;
+    uint32_t n_slices = 0;
+    CALLCHK(s, hipMemcpyAsync(&n_text, d_line_off + n, 8, hipMemcpyDeviceToHost, st));
+    CALLCHK(s, hipMemcpyAsync(&n_slices, d_slice_off + n, 4, hipMemcpyDeviceToHost, st));
+    CALLCHK(s, hipStreamSynchronize(st));
+    if (n_slices < n || n_slices >= (1u << 31)) return fail(ctx, n_slices < n ? NS_EHIP : NS_EINVAL, "ns_bam_to_sam: 2^31 slices or more");
+    uint8_t *d_text = s.alloc<uint8_t>((size_t)n_text, 16);
+    if (s.rc) return s.rc;
+    if (int rc = grow(ctx, ctx->bam_text, (size_t)n_text + 16)) return rc;
+    if (int rc = grow(ctx, ctx->bam_line_off, ((size_t)n + 1) * 8)) return rc;
+    k_bam_write<<<dim3((n_slices + 3u) / 4u), dim3(256), 0, st>>>(d_bytes, d_off, n, R, d_rec, d_line_off, d_slice_off, n_slices, d_flt_first, d_slots, d_text,
+                                                                 d_small);
+    CALLCHK(s, hipGetLastError());
+    if (int rc = timed_tail(s, {{small, d_small, sizeof small}, {ctx->bam_text.data(), d_text, (size_t)n_text},
+                                {ctx->bam_line_off.data(), d_line_off, ((size_t)n + 1) * 8}}, &out->ms_kernel)) return rc;
+    if (small[BAMS_MISMATCH]) return fail(ctx, NS_EHIP, "ns_bam_to_sam: the two walks of a record disagree about its line");
+    out->text = ctx->bam_text.data(); out->line_off = ctx->bam_line_off.view<uint64_t>();
+    out->n_records = n; out->n_text = n_text; out->consumed = at;
     return NS_OK;
 }
 

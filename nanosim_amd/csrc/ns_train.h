@@ -3,11 +3,11 @@
 // of SAM records (k_sam_scan, k_sam_lines), the fit of the error-length mixtures (k_mixfit), and the lengths behind the read-length
 // models (k_len_scan, k_len_flag, k_len_reduce), the split-alignment choice of chimeric reads (k_chim_scan, k_chim_select), the EM of
 // the abundance quantification (k_em_estep, k_em_accum, k_em_stop), the Markov counts of the intron-retention model (k_ir_walk), and the
-// best hit per read of a MAF file (k_maf_*).  The
+// best hit per read of a MAF file (k_maf_*), and the SAM text of BAM records (k_bam_*).  The
 // walks they run are ns_cs_hist.h, ns_qual_hist.h, ns_hp_hist.h, ns_sam_pairs.h, ns_mixfit.h, ns_read_len.h, ns_chimeric.h, ns_em.h,
-// ns_ir_train.h and ns_maf_best.h, which also compile for the host; the host side of the calls
+// ns_ir_train.h, ns_maf_best.h and ns_bam.h, which also compile for the host; the host side of the calls
 // (ns_cs_histograms / ns_maf_histograms, ns_qual_histograms, ns_hp_histograms / ns_hp_histograms_sam, ns_sam_pairs_build, ns_mixture_fit,
-// ns_read_lengths, ns_cigar_spans / ns_chimeric_select, ns_em_quantify, ns_ir_train, ns_maf_besthit) is at the end of nanosim_amd.hip.  Nothing here uses GenArgs or the simulation.
+// ns_read_lengths, ns_cigar_spans / ns_chimeric_select, ns_em_quantify, ns_ir_train, ns_maf_besthit, ns_bam_to_sam) is at the end of nanosim_amd.hip.  Nothing here uses GenArgs or the simulation.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,6 +22,7 @@
 #include "ns_em.h"
 #include "ns_ir_train.h"
 #include "ns_maf_best.h"
+#include "ns_bam.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // k_cs_hist: the counting loop of the characterisation stage (ns_cs_hist.h; src/besthit_to_histogram.py:316-365), one alignment per
@@ -711,4 +712,76 @@ __global__ void __launch_bounds__(256) k_maf_names(const uint8_t *__restrict__ t
     CsBytes t(text), nb(names);
     const uint64_t lo = names_off[i], n = names_off[i + 1u] - lo;
     found[i] = n <= 0xffffffffull && maf_find(t, lines, T, nb, lo, (uint32_t)n) ? 1u : 0u;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_bam_measure, k_bam_float_len, k_bam_write: BAM records to SAM text (ns_bam.h), one wavefront per record (measure) and per slice of a
+// record (write), four to a workgroup.
+// MEASURE: bam_measure; the line's length without its floats, the number of its slices and what the write pass needs of it (BamRec);
+// where a float stands goes to flt_at at a slot taken from small[BAMS_N_FLOAT] (beyond flt_cap it is only counted: the host runs the
+// kernel again with a list that holds them all); the smallest (index << 8 | reason) of a bad record by atomic min.
+// FLOAT_LEN, one record per thread, after the host has sorted the places, made the text of every float and found the first slot of
+// every record: the characters of the record's floats are added to the length of its line.
+// WRITE: wavefront g finds its record by bisection in the exclusive scan of the slice counts and writes slice g - slice_off[r] of it
+// (bam_write) at line_off[r]; a line that is not what MEASURE measured counts in small[BAMS_MISMATCH].
+// ---------------------------------------------------------------------------------------------------------
+enum { BAMS_FIRST_BAD = 0, BAMS_N_FLOAT = 1, BAMS_MISMATCH = 2, BAMS_WORDS = 4 };
+static_assert(BAM_ROUND_OPS == 64u && BAM_LANE_BYTES == sizeof(BamPiece) && BAM_SLICE_BASES % 2u == 0u, "a round is a wavefront, a piece one store");
+struct BamWaveDev {
+    static constexpr uint32_t LANES = 64u;
+    uint32_t lane;
+    unsigned long long *flt_at, *flt_n;
+    uint64_t flt_cap;
+    __device__ __forceinline__ uint32_t scan(uint32_t v, uint32_t &total) const {
+        uint32_t incl = v;
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t u = (uint32_t)__shfl_up((int)incl, o, 64); if (lane >= (uint32_t)o) incl += u; }
+        total = (uint32_t)__shfl((int)incl, 63, 64);
+        return incl - v;
+    }
+    __device__ __forceinline__ uint32_t first(bool pred) const { const unsigned long long m = __ballot(pred); return m ? (uint32_t)__ffsll(m) - 1u : 64u; }
+    __device__ __forceinline__ uint32_t bcast(uint32_t v, uint32_t src) const { return (uint32_t)__shfl((int)v, (int)src, 64); }
+    __device__ __forceinline__ uint64_t float_reserve(uint32_t n) const {
+        unsigned long long at = 0;
+        if (lane == 0) at = atomicAdd(flt_n, (unsigned long long)n);
+        return ((uint64_t)(uint32_t)__shfl((int)(at >> 32), 0, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)at, 0, 64);
+    }
+    __device__ __forceinline__ void float_put(uint64_t slot, uint64_t where) const { if (slot < flt_cap) flt_at[slot] = where; }
+};
+__global__ void __launch_bounds__(256) k_bam_measure(const uint8_t *__restrict__ bytes, const uint64_t *__restrict__ rec_off, uint32_t n_rec, BamRefs R,
+                                                     BamRec *__restrict__ rec, unsigned long long *__restrict__ line_len, uint32_t *__restrict__ slices,
+                                                     unsigned long long *__restrict__ flt_at, uint64_t flt_cap, unsigned long long *__restrict__ small) {
+    const uint32_t r = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (r >= n_rec) return;                                        // (a whole wavefront leaves)
+    BamWaveDev w{threadIdx.x & 63u, flt_at, &small[BAMS_N_FLOAT], flt_cap};
+    BamRec rc;
+    uint64_t len = 0;
+    uint32_t ns = 1;
+    const uint32_t reason = bam_measure(w, bytes, rec_off[r], rec_off[r + 1u], R, rc, len, ns);
+    if (w.lane) return;
+    if (reason) { atomicMin(&small[BAMS_FIRST_BAD], ((unsigned long long)r << 8) | reason); return; }
+    rec[r] = rc; line_len[r] = len; slices[r] = ns;
+}
+__global__ void __launch_bounds__(256) k_bam_float_len(const uint32_t *__restrict__ flt_first, const uint8_t *__restrict__ slots, uint32_t n_rec,
+                                                       unsigned long long *__restrict__ line_len) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rec) return;
+    unsigned long long add = 0;
+    for (uint32_t k = flt_first[r]; k < flt_first[r + 1u]; ++k) { const uint32_t l = slots[(uint64_t)k * BAM_FLOAT_SLOT + BAM_FLOAT_SLOT - 1u]; add += l > BAM_FLOAT_CHARS ? BAM_FLOAT_CHARS : l; }
+    if (add) line_len[r] += add;
+}
+__global__ void __launch_bounds__(256) k_bam_write(const uint8_t *__restrict__ bytes, const uint64_t *__restrict__ rec_off, uint32_t n_rec, BamRefs R,
+                                                   const BamRec *__restrict__ rec, const unsigned long long *__restrict__ line_off,
+                                                   const uint32_t *__restrict__ slice_off, uint32_t n_slices, const uint32_t *__restrict__ flt_first,
+                                                   const uint8_t *__restrict__ slots, uint8_t *__restrict__ text, unsigned long long *__restrict__ small) {
+    const uint32_t g = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (g >= n_slices) return;
+    uint32_t lo = 0, hi = n_rec - 1u;                              // the last record whose first slice is not behind g
+    while (lo < hi) { const uint32_t mid = lo + (hi - lo + 1u) / 2u; if (slice_off[mid] <= g) lo = mid; else hi = mid - 1u; }
+    const uint32_t r = lo;
+    BamWaveDev w{threadIdx.x & 63u, nullptr, nullptr, 0};
+    const BamRec rc = rec[r];
+    const uint64_t at = line_off[r];
+    const bool ok = bam_write(w, bytes, rec_off[r], rec_off[r + 1u], R, rc, g - slice_off[r], flt_first ? slots + (uint64_t)flt_first[r] * BAM_FLOAT_SLOT : nullptr,
+                              text + at, line_off[r + 1u] - at);
+    if (!ok && w.lane == 0) atomicAdd(&small[BAMS_MISMATCH], 1ull);
 }

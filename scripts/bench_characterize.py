@@ -30,7 +30,14 @@ repeated), an `a score=` line and a blank line per pair.  Prints the kernel mill
 kernel to the last, the host's two waits inside the call included), that per 10^6 pairs and as GB/s over the bytes of the text, and the
 end-to-end time of besthit_call (the H2D copy of the text and the copies of the result included) next to the time the host needs to
 read the same file into memory — the parse-and-copy side of the call.
-    python scripts/bench_characterize.py --besthit [--alignments 200000] [--columns 1000] [--steps 3]"""
+    python scripts/bench_characterize.py --besthit [--alignments 200000] [--columns 1000] [--steps 3]
+--bam: BAM input (ns_bam_to_sam, characterize.read_bam) on a synthetic file built here with the test-side writer (tests/bam_lib.py):
+--alignments records of 8 kb reads (200 distinct ones, repeated) with SEQ, QUAL, a CIGAR of ~1 500 ops and NM:i, ms:i, de:f, tp:A and cs:Z
+tags (the cs of the hg002-like error rates, ~2 KB).  Prints the kernel milliseconds of every step for all records in ONE call (device
+events from the first kernel to the last, the host's waits and its formatting of the floats included), that per 10^5 records, the text
+bytes written per second and against the 8 TB/s roofline; and, end to end, records/s of read_bam + cs_from_sam over the BAM file (BGZF
+inflate, batches of 64 MB, decode, the reader's loop) next to cs_from_sam over the SAM text of the same records (bam_to_sam wrote it).
+    python scripts/bench_characterize.py --bam [--alignments 20000] [--steps 3]"""
 import argparse
 import ctypes as C
 import json
@@ -54,6 +61,7 @@ ap.add_argument("--sam-pairs", action="store_true")
 ap.add_argument("--mixfit", action="store_true")
 ap.add_argument("--besthit", action="store_true")
 ap.add_argument("--columns", type=int, default=1000)
+ap.add_argument("--bam", action="store_true")
 ap.add_argument("--records", action="store_true")
 ap.add_argument("--host-walk", action="store_true")
 ap.add_argument("--dump-maf", default=None)
@@ -95,6 +103,76 @@ if a.mixfit:
     res["value"] = res["fixture"]["kernel_ms_all_three(median)"]
     print(json.dumps(res))
     eng.close()
+    sys.exit(0)
+if a.bam:
+    from concurrent.futures import ThreadPoolExecutor
+    from tests import bam_lib
+    rng = np.random.default_rng(SEED)
+    n = a.alignments if a.alignments != 200_000 else 20_000
+    distinct = []
+    for k in range(200):
+        l_seq = int(rng.integers(7600, 8400))
+        seq = "".join(rng.choice(list("ACGT"), l_seq).tolist())
+        qual = rng.integers(33 + 2, 33 + 40, l_seq).astype(np.uint8).tobytes().decode()
+        ops, cs, left = [], [], l_seq - 60
+        while left > 0:                                           # ~ one error per 11 bases: match runs with a mismatch, an insertion or a deletion between
+            m = int(min(left, rng.geometric(0.09)))
+            ops.append("%dM" % (m + 1)); cs.append(":%d*ag" % m); left -= m + 1
+            if left > 3 and rng.random() < 0.5:
+                e = int(rng.integers(1, 4))
+                if rng.random() < 0.5:
+                    ops.append("%dI" % e); cs.append("+" + "acg"[:e]); left -= e
+                else:
+                    ops.append("%dD" % e); cs.append("-" + "tgc"[:e])
+        cigar = "30S" + "".join(ops) + "30S"
+        tags = (bam_lib.tag_bytes("NM", "S", 700 + k) + bam_lib.tag_bytes("ms", "i", 9000 + k) + bam_lib.tag_bytes("de", "f", 0.08 + k * 1e-4) +
+                bam_lib.tag_bytes("tp", "A", "P") + bam_lib.tag_bytes("cs", "Z", "".join(cs)))
+        distinct.append(bam_lib.record("read_%06d/%s" % (k, "x" * (k % 16)), 16 * (k & 1), k % 24, 1 + k * 1013, 60, cigar, -1, 0, 0, seq, qual, tags))
+    refs = [("chr%d" % (i + 1), 250_000_000 - i * 1_000_000) for i in range(24)]
+    header = "@HD\tVN:1.6\tSO:unsorted\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % r for r in refs) + "@PG\tID:minimap2\tPN:minimap2\n"
+    records = b"".join(distinct[i % 200] for i in range(n))
+    n_ops = float(np.mean([int.from_bytes(r[16:18], "little") for r in distinct]))
+    tmp = tempfile.mkdtemp(prefix="nsbam_")
+    bam_path, sam_path = os.path.join(tmp, "synthetic.bam"), os.path.join(tmp, "synthetic.sam")
+    inflated = bam_lib.bam_header(header, refs) + records
+    with ThreadPoolExecutor(max_workers=16) as pool, open(bam_path, "wb") as f:
+        for blk in pool.map(lambda i: bam_lib.bgzf_block(inflated[i:i + 65280], level=1), range(0, len(inflated), 65280)):
+            f.write(blk)
+        f.write(bam_lib.EOF_BLOCK)
+    del inflated
+    eng = E.Engine(0)
+    names, off = characterize._pack([r[0] for r in refs])
+    r = characterize.bam_call(eng, records, True, names, off)    # warms up
+    assert int(r.n_records) == n and not r.bad_reason
+    n_text, ms, call_s = int(r.n_text), [], []
+    for _ in range(a.steps):
+        t0 = time.perf_counter()
+        r = characterize.bam_call(eng, records, True, names, off)
+        call_s.append(time.perf_counter() - t0)
+        ms.append(float(r.ms_kernel))
+    med = float(np.median(ms))
+    assert characterize.bam_to_sam(bam_path, sam_path, eng) == n and os.path.getsize(sam_path) == n_text + len(header)
+    from_bam, from_sam = [], []
+    for _ in range(a.steps):
+        t0 = time.perf_counter()
+        cs_bam = characterize.cs_from_sam(characterize.read_bam(bam_path, eng))
+        from_bam.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        cs_sam = characterize.cs_from_sam(sam_path)
+        from_sam.append(time.perf_counter() - t0)
+        assert cs_bam == cs_sam and len(cs_sam) == n
+    print(json.dumps({"metric": "BAM records to SAM text, kernel ms per 10^5 records of 8 kb reads with cs tags (ns_bam_to_sam)", "value": med * 1e5 / n,
+                      "records": n, "record_bytes": len(records), "text_bytes": n_text, "cigar_ops_per_record": n_ops, "steps": a.steps, "kernel_ms": ms,
+                      "text_gb_per_s": n_text / (med * 1e-3) / 1e9, "text_frac_of_hbm_8tbs": n_text / (med * 1e-3) / 1e9 / 8000.0,
+                      "moved_gb_per_s(records read + text written)": (len(records) + n_text) / (med * 1e-3) / 1e9,
+                      "bam_call_end_to_end_s": call_s, "bam_file_bytes": os.path.getsize(bam_path),
+                      "read_bam+cs_from_sam_s": from_bam, "cs_from_sam(sam text)_s": from_sam,
+                      "records_per_s(read_bam + cs_from_sam)": n / float(np.median(from_bam)),
+                      "records_per_s(cs_from_sam over SAM text)": n / float(np.median(from_sam))}))
+    eng.close()
+    os.remove(bam_path)
+    os.remove(sam_path)
+    os.rmdir(tmp)
     sys.exit(0)
 if a.besthit:
     rng = np.random.default_rng(SEED)
