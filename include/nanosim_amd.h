@@ -694,6 +694,38 @@ typedef struct ns_bam_result {
 int ns_bam_to_sam(ns_ctx *ctx, const uint8_t *bytes, uint64_t nbytes, int final, const uint8_t *ref_names, const uint64_t *ref_off, uint32_t n_ref,
                   ns_bam_result *out);
 
+/* ---- training side: cs and MD tags from the reference genome -----------------------------------------------------------------------------------
+ * the MD:Z text (samtools calmd's algorithm) and the short-form cs:Z text (minimap2 --cs) of n alignments from CIGAR, POS, SEQ and the
+ * reference set with ns_set_reference / ns_set_reference_device (the engine's normalised copy of it); nanosim_amd/csrc/ns_calmd.h has the
+ * rules of the text and how the kernels work.  Record i: the CIGAR text cigar[cigar_off[i] .. cigar_off[i + 1]), SEQ likewise, chrom[i] the
+ * index of its chromosome in the set reference, pos[i] its 1-based POS.
+ * Out: md[md_off[n]] and cs[cs_off[n]], the texts one behind the other without separators, text i at md_off[i] .. md_off[i + 1] - 1; all
+ * four belong to the context, lie in page-locked host memory and stay valid until the next ns_calmd on it or ns_destroy.  A bad record has
+ * empty texts; the call returns NS_OK and reports their number (n_bad), the index of the first (first_bad; ~0 without) and why that one is
+ * bad (bad_reason).  NS_EINVAL: no reference set, a null argument, offsets that do not ascend from 0, 2^31 records or more.  n == 0 is
+ * valid (md_off[0] == cs_off[0] == 0).  ms_kernel: from the first kernel to the last, the wait of the host for the sizes of the texts
+ * included.  Added without an ABI change. */
+enum { NS_CALMD_OK = 0, NS_CALMD_BAD_CIGAR = 1,  /* the CIGAR does not parse (a count of 0 or of 2^28 or more included) */
+       NS_CALMD_BAD_OP = 2,                      /* an op outside MIDSH=X */
+       NS_CALMD_BAD_CLIP = 3,                    /* an S that is not outermost inside the H ops (or an H inside) */
+       NS_CALMD_BAD_SEQ_LEN = 4,                 /* the length of SEQ is not the sum of its S/M/=/X/I ops */
+       NS_CALMD_BAD_SEQ_BYTE = 5,                /* a SEQ byte that is not a letter */
+       NS_CALMD_BAD_CHROM = 6,                   /* chrom outside the set reference */
+       NS_CALMD_BAD_POS = 7,                     /* POS 0 */
+       NS_CALMD_BAD_END = 8,                     /* the alignment runs past the end of its chromosome */
+       NS_CALMD_BAD_NO_COLUMN = 9 };             /* no M / = / X column at all */
+typedef struct ns_calmd_result {
+    const uint8_t *md;                           /* out, owned by the context */
+    const uint64_t *md_off;
+    const uint8_t *cs;
+    const uint64_t *cs_off;
+    uint64_t n_bad, first_bad;
+    uint32_t bad_reason, reserved;
+    double ms_kernel;
+} ns_calmd_result;
+int ns_calmd(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off, const uint8_t *seq, const uint64_t *seq_off,
+             const uint32_t *chrom, const uint32_t *pos, uint32_t n, ns_calmd_result *out);
+
 /* device address of a result buffer (for zero-copy consumers such as torch / RCCL); NULL if absent */
 const void *ns_device_ptr(ns_ctx *ctx, int which);
 

@@ -14,13 +14,14 @@ references, and every deviation from it.  Every name of a module is a name of th
     ir_model        characterize.intron_retention("training", "training_added_intron_final.gff3", "genome.sam", "transcriptome.sam", eng)
     maf_besthit     characterize.train_genome_from_maf("training", "last.maf", "reads.fasta", eng)
     bam             characterize.cs_from_sam(characterize.read_bam("training_primary.bam", eng))    # a BAM file wherever a reader takes a SAM path
+    calmd           characterize.cs_from_sam(characterize.with_reference("calls.sam", "genome.fa", eng))   # MD:Z and cs:Z from the reference genome
 
 Below them: chim_select (what chimeric_reads and quantification share), sam_text (the one loop over SAM text), _abi (marshalling)."""
 from __future__ import annotations
 
 from . import (_abi, sam_text, errors, qualities, homopolymers, sam_pairs, mixfit, lengths, chim_select, quantification, chimeric_reads,
-               ir_model, maf_besthit, bam)
+               ir_model, maf_besthit, bam, calmd)
 
 for _module in (_abi, sam_text, errors, qualities, homopolymers, sam_pairs, mixfit, lengths, chim_select, quantification, chimeric_reads,
-                ir_model, maf_besthit, bam):               # the underscore names too: tests and scripts use _pack, _qual_call, _strip_chr, ...
+                ir_model, maf_besthit, bam, calmd):             # the underscore names too: tests and scripts use _pack, _qual_call, _strip_chr, ...
     globals().update((k, v) for k, v in vars(_module).items() if not k.startswith("__"))

@@ -16,7 +16,7 @@
 //   k_errlog            wave/read     _aligned_error_profile rows                           (S:2006-2008)
 // Metagenome worker calls run k_lengths / k_chain per PASS of the reference's while loop (S:844-1040) with k_meta_* around them; the lists of a
 // pass are launched before the host has walked the species quotas (assign_species), k_meta_tail does positions + acceptance afterwards.
-// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms, ns_sam_pairs_build, ns_mixture_fit, ns_read_lengths, ns_cigar_spans, ns_chimeric_select, ns_em_quantify, ns_ir_train, ns_maf_besthit, ns_bam_to_sam: at the end of the host part) has its kernels in ns_train.h.
+// The training side (ns_cs_histograms, ns_qual_histograms, ns_hp_histograms, ns_sam_pairs_build, ns_mixture_fit, ns_read_lengths, ns_cigar_spans, ns_chimeric_select, ns_em_quantify, ns_ir_train, ns_maf_besthit, ns_bam_to_sam, ns_calmd: at the end of the host part) has its kernels in ns_train.h.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdio.h>
@@ -2227,6 +2227,7 @@ struct ns_ctx {
     std::vector<ns_maf_best_lines> maf_lines; std::vector<ns_maf_best_record> maf_records; std::vector<ns_maf_best_figures> maf_figures;   // the result of the last ns_maf_besthit
     PinBuf bam_text, bam_line_off;                       // the result of the last ns_bam_to_sam, page-locked
     std::vector<uint64_t> bam_rec_off, bam_flt_at; std::vector<uint32_t> bam_flt_first; std::vector<uint8_t> bam_slots;   // ... and its host-side lists
+    PinBuf calmd_md, calmd_md_off, calmd_cs, calmd_cs_off;  // the result of the last ns_calmd, page-locked
     uint8_t *pin_small = nullptr;    // page-locked slots for the scalar read-backs of a call (read_small)
     PinBuf pin_a, pin_b, pin_c;      // pinned host staging of the metagenome passes: draws (then species ids), sorted lengths, words
     uint32_t nspecies = 0;
@@ -4997,6 +4998,75 @@ int ns_bam_to_sam(ns_ctx *ctx, const uint8_t *bytes, uint64_t nbytes, int final,
     if (small[BAMS_MISMATCH]) return fail(ctx, NS_EHIP, "ns_bam_to_sam: the two walks of a record disagree about its line");
     out->text = ctx->bam_text.data(); out->line_off = ctx->bam_line_off.view<uint64_t>();
     out->n_records = n; out->n_text = n_text; out->consumed = at;
+    return NS_OK;
+}
+
+// cs and MD text from the reference genome (include/nanosim_amd.h: ns_calmd_result; ns_calmd.h).  The host waits once inside the call:
+// for the sizes of the two texts, which their device buffers and the page-locked result are grown to.
+int ns_calmd(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off, const uint8_t *seq, const uint64_t *seq_off, const uint32_t *chrom,
+             const uint32_t *pos, uint32_t n, ns_calmd_result *out) {
+    if (!ctx) return NS_EINVAL;
+    if (!out) return fail(ctx, NS_EINVAL, "ns_calmd: null argument");
+    static_assert(NS_CALMD_BAD_CIGAR == CALMD_BAD_CIGAR && NS_CALMD_BAD_SEQ_BYTE == CALMD_BAD_SEQ_BYTE && NS_CALMD_BAD_NO_COLUMN == CALMD_BAD_NO_COLUMN,
+                  "ns_calmd.h mirrors the ABI's reasons");
+    out->md = out->cs = nullptr; out->md_off = out->cs_off = nullptr; out->n_bad = 0; out->first_bad = ~0ull; out->bad_reason = NS_CALMD_OK;
+    out->reserved = 0; out->ms_kernel = 0;
+    if (!ctx->has_ref) return fail(ctx, NS_EINVAL, "ns_calmd: no reference set (ns_set_reference)");
+    if (!cigar_off || !seq_off || (n && (!chrom || !pos))) return fail(ctx, NS_EINVAL, "ns_calmd: null argument");
+    if (n >= (1u << 31)) return fail(ctx, NS_EINVAL, "ns_calmd: 2^31 records or more");
+    if (cigar_off[0] || seq_off[0]) return fail(ctx, NS_EINVAL, "ns_calmd: offsets not ascending from 0");
+    if (int rc = check_offsets(ctx, "ns_calmd", "CIGAR strings", cigar_off, n, cigar_off[n])) return rc;
+    if (int rc = check_offsets(ctx, "ns_calmd", "SEQ strings", seq_off, n, seq_off[n])) return rc;
+    const uint64_t cigar_bytes = cigar_off[n], seq_bytes = seq_off[n];
+    if ((cigar_bytes && !cigar) || (seq_bytes && !seq)) return fail(ctx, NS_EINVAL, "ns_calmd: null argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    if (int rc = grow(ctx, ctx->calmd_md_off, ((size_t)n + 1) * 8)) return rc;
+    if (int rc = grow(ctx, ctx->calmd_cs_off, ((size_t)n + 1) * 8)) return rc;
+    if (!n) {
+        *ctx->calmd_md_off.view<uint64_t>() = 0; *ctx->calmd_cs_off.view<uint64_t>() = 0;
+        if (int rc = grow(ctx, ctx->calmd_md, 16)) return rc;
+        if (int rc = grow(ctx, ctx->calmd_cs, 16)) return rc;
+        out->md = ctx->calmd_md.data(); out->cs = ctx->calmd_cs.data();
+        out->md_off = ctx->calmd_md_off.view<uint64_t>(); out->cs_off = ctx->calmd_cs_off.view<uint64_t>();
+        return NS_OK;
+    }
+    unsigned long long small[CALMDS_WORDS] = {~0ull, 0ull, 0ull, 0ull};
+    CallScratch s(ctx, "ns_calmd");
+    const uint8_t *d_cigar = s.filled(cigar, (size_t)cigar_bytes, 16), *d_seq = s.filled(seq, (size_t)seq_bytes, 16);
+    const uint64_t *d_cigar_off = s.filled(cigar_off, (size_t)n + 1), *d_seq_off = s.filled(seq_off, (size_t)n + 1);
+    const uint32_t *d_chrom = s.filled(chrom, (size_t)n), *d_pos = s.filled(pos, (size_t)n);
+    CalmdOp *d_ops = s.alloc<CalmdOp>((size_t)(cigar_bytes >> 1) + n + 1);
+    CalmdRec *d_rec = s.alloc<CalmdRec>(n);
+    unsigned long long *d_md_len = s.zeroed<unsigned long long>((size_t)n + 1), *d_cs_len = s.zeroed<unsigned long long>((size_t)n + 1);
+    unsigned long long *d_md_off = s.alloc<unsigned long long>((size_t)n + 1), *d_cs_off = s.alloc<unsigned long long>((size_t)n + 1);
+    unsigned long long *d_small = s.filled(small, CALMDS_WORDS);
+    if (int rc = s.upload()) return rc;
+    hipStream_t st = ctx->stream;
+    const CalmdRef G{ctx->ref.bases, ctx->ref.chrom_off, ctx->ref.nchrom};
+    const unsigned grid = (n + 3u) / 4u;
+    CALLCHK(s, hipEventRecord(ctx->evt[EV_HIST_BEGIN], st));
+    k_calmd_measure<<<dim3(grid), dim3(256), 0, st>>>(d_cigar, d_cigar_off, d_seq, d_seq_off, d_chrom, d_pos, n, G, d_ops, d_rec, d_md_len, d_cs_len, d_small);
+    CALLCHK(s, hipGetLastError());
+    if (int rc = scan_sum(ctx, d_md_len, d_md_off, (size_t)n + 1)) return fail(ctx, rc, std::string("ns_calmd: ") + ctx->err);
+    if (int rc = scan_sum(ctx, d_cs_len, d_cs_off, (size_t)n + 1)) return fail(ctx, rc, std::string("ns_calmd: ") + ctx->err);
+    unsigned long long n_md = 0, n_cs = 0;
+    CALLCHK(s, hipMemcpyAsync(&n_md, d_md_off + n, 8, hipMemcpyDeviceToHost, st));
+    CALLCHK(s, hipMemcpyAsync(&n_cs, d_cs_off + n, 8, hipMemcpyDeviceToHost, st));
+    CALLCHK(s, hipStreamSynchronize(st));
+    uint8_t *d_md = s.alloc<uint8_t>((size_t)n_md, 16), *d_cs = s.alloc<uint8_t>((size_t)n_cs, 16);
+    if (s.rc) return s.rc;
+    if (int rc = grow(ctx, ctx->calmd_md, (size_t)n_md + 16)) return rc;
+    if (int rc = grow(ctx, ctx->calmd_cs, (size_t)n_cs + 16)) return rc;
+    k_calmd_write<<<dim3(grid), dim3(256), 0, st>>>(d_cigar_off, d_seq, d_seq_off, d_chrom, d_pos, n, G, d_ops, d_rec, d_md_off, d_cs_off, d_md, d_cs, d_small);
+    CALLCHK(s, hipGetLastError());
+    if (int rc = timed_tail(s, {{small, d_small, sizeof small}, {ctx->calmd_md.data(), d_md, (size_t)n_md}, {ctx->calmd_cs.data(), d_cs, (size_t)n_cs},
+                                {ctx->calmd_md_off.data(), d_md_off, ((size_t)n + 1) * 8}, {ctx->calmd_cs_off.data(), d_cs_off, ((size_t)n + 1) * 8}},
+                            &out->ms_kernel)) return rc;
+    if (small[CALMDS_MISMATCH]) return fail(ctx, NS_EHIP, "ns_calmd: the two walks of a record disagree about its texts");
+    out->md = ctx->calmd_md.data(); out->cs = ctx->calmd_cs.data();
+    out->md_off = ctx->calmd_md_off.view<uint64_t>(); out->cs_off = ctx->calmd_cs_off.view<uint64_t>();
+    out->n_bad = small[CALMDS_N_BAD];
+    if (small[CALMDS_FIRST_BAD] != ~0ull) { out->first_bad = small[CALMDS_FIRST_BAD] >> 8; out->bad_reason = (uint32_t)(small[CALMDS_FIRST_BAD] & 0xffu); }
     return NS_OK;
 }
 

@@ -3,11 +3,12 @@
 // of SAM records (k_sam_scan, k_sam_lines), the fit of the error-length mixtures (k_mixfit), and the lengths behind the read-length
 // models (k_len_scan, k_len_flag, k_len_reduce), the split-alignment choice of chimeric reads (k_chim_scan, k_chim_select), the EM of
 // the abundance quantification (k_em_estep, k_em_accum, k_em_stop), the Markov counts of the intron-retention model (k_ir_walk), and the
-// best hit per read of a MAF file (k_maf_*), and the SAM text of BAM records (k_bam_*).  The
+// best hit per read of a MAF file (k_maf_*), the SAM text of BAM records (k_bam_*), and the MD and cs text of alignments from the
+// reference genome (k_calmd_*).  The
 // walks they run are ns_cs_hist.h, ns_qual_hist.h, ns_hp_hist.h, ns_sam_pairs.h, ns_mixfit.h, ns_read_len.h, ns_chimeric.h, ns_em.h,
-// ns_ir_train.h, ns_maf_best.h and ns_bam.h, which also compile for the host; the host side of the calls
+// ns_ir_train.h, ns_maf_best.h, ns_bam.h and ns_calmd.h, which also compile for the host; the host side of the calls
 // (ns_cs_histograms / ns_maf_histograms, ns_qual_histograms, ns_hp_histograms / ns_hp_histograms_sam, ns_sam_pairs_build, ns_mixture_fit,
-// ns_read_lengths, ns_cigar_spans / ns_chimeric_select, ns_em_quantify, ns_ir_train, ns_maf_besthit, ns_bam_to_sam) is at the end of nanosim_amd.hip.  Nothing here uses GenArgs or the simulation.
+// ns_read_lengths, ns_cigar_spans / ns_chimeric_select, ns_em_quantify, ns_ir_train, ns_maf_besthit, ns_bam_to_sam, ns_calmd) is at the end of nanosim_amd.hip.  Nothing here uses GenArgs or the simulation.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,6 +24,7 @@
 #include "ns_ir_train.h"
 #include "ns_maf_best.h"
 #include "ns_bam.h"
+#include "ns_calmd.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // k_cs_hist: the counting loop of the characterisation stage (ns_cs_hist.h; src/besthit_to_histogram.py:316-365), one alignment per
@@ -784,4 +786,63 @@ __global__ void __launch_bounds__(256) k_bam_write(const uint8_t *__restrict__ b
     const bool ok = bam_write(w, bytes, rec_off[r], rec_off[r + 1u], R, rc, g - slice_off[r], flt_first ? slots + (uint64_t)flt_first[r] * BAM_FLOAT_SLOT : nullptr,
                               text + at, line_off[r + 1u] - at);
     if (!ok && w.lane == 0) atomicAdd(&small[BAMS_MISMATCH], 1ull);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_calmd_measure, k_calmd_write: the MD and cs text of alignments from the reference genome (ns_calmd.h), one wavefront per record, four
+// to a workgroup, in both.
+// MEASURE: calmd_measure — the record is checked, its ops go to its table (at calmd_op_base), the lengths of its two texts to md_len and
+// cs_len; a bad record has lengths 0, counts in small[CALMDS_N_BAD] and gives the smallest (index << 8 | reason) by atomic min.
+// WRITE, after the exclusive scans of the lengths: calmd_text<true> at md_off[r] and cs_off[r]; a text that is not what MEASURE measured
+// counts in small[CALMDS_MISMATCH].
+// ---------------------------------------------------------------------------------------------------------
+enum { CALMDS_FIRST_BAD = 0, CALMDS_N_BAD = 1, CALMDS_MISMATCH = 2, CALMDS_WORDS = 4 };
+struct CalmdWaveDev {
+    static constexpr uint32_t LANES = 64u;
+    uint32_t lane;
+    __device__ __forceinline__ uint64_t ballot(bool pred) const { return __ballot(pred); }
+    __device__ __forceinline__ uint64_t scan(uint64_t v, uint64_t &total) const {
+        uint64_t incl = v;
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)incl, o, 64), hi = (uint32_t)__shfl_up((int)(uint32_t)(incl >> 32), o, 64);
+            if (lane >= (uint32_t)o) incl += ((uint64_t)hi << 32) | lo;
+        }
+        total = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(incl >> 32), 63, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)incl, 63, 64);
+        return incl - v;
+    }
+    __device__ __forceinline__ uint32_t bcast(uint32_t v, uint32_t src) const { return (uint32_t)__shfl((int)v, (int)src, 64); }
+    __device__ __forceinline__ void fence() const { __threadfence_block(); }
+};
+__global__ void __launch_bounds__(256) k_calmd_measure(const uint8_t *__restrict__ cigar, const uint64_t *__restrict__ cigar_off, const uint8_t *__restrict__ seq,
+                                                       const uint64_t *__restrict__ seq_off, const uint32_t *__restrict__ chrom, const uint32_t *__restrict__ pos,
+                                                       uint32_t n_rec, CalmdRef G, CalmdOp *ops, CalmdRec *__restrict__ rec,
+                                                       unsigned long long *__restrict__ md_len, unsigned long long *__restrict__ cs_len,
+                                                       unsigned long long *__restrict__ small) {
+    const uint32_t r = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (r >= n_rec) return;                                        // (a whole wavefront leaves)
+    CalmdWaveDev w{threadIdx.x & 63u};
+    CalmdRec R;
+    uint64_t ml = 0, cl = 0;
+    const uint64_t c0 = cigar_off[r], s0 = seq_off[r];
+    const uint32_t reason = calmd_measure(w, cigar + c0, cigar_off[r + 1u] - c0, seq + s0, seq_off[r + 1u] - s0, chrom[r], pos[r], G,
+                                          ops + calmd_op_base(cigar_off, r), R, ml, cl);
+    if (w.lane) return;
+    rec[r] = R; md_len[r] = ml; cs_len[r] = cl;
+    if (reason) { atomicMin(&small[CALMDS_FIRST_BAD], ((unsigned long long)r << 8) | reason); atomicAdd(&small[CALMDS_N_BAD], 1ull); }
+}
+__global__ void __launch_bounds__(256) k_calmd_write(const uint64_t *__restrict__ cigar_off, const uint8_t *__restrict__ seq, const uint64_t *__restrict__ seq_off,
+                                                     const uint32_t *__restrict__ chrom, const uint32_t *__restrict__ pos, uint32_t n_rec, CalmdRef G,
+                                                     const CalmdOp *__restrict__ ops, const CalmdRec *__restrict__ rec,
+                                                     const unsigned long long *__restrict__ md_off, const unsigned long long *__restrict__ cs_off,
+                                                     uint8_t *__restrict__ md, uint8_t *__restrict__ cs, unsigned long long *__restrict__ small) {
+    const uint32_t r = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (r >= n_rec) return;
+    const CalmdRec R = rec[r];
+    if (R.reason) return;                                          // (MEASURE has checked chrom and POS of the others)
+    CalmdWaveDev w{threadIdx.x & 63u};
+    const uint64_t ma = md_off[r], ca = cs_off[r];
+    uint64_t ml = 0, cl = 0;
+    const bool ok = calmd_text<true>(w, ops + calmd_op_base(cigar_off, r), R, seq + seq_off[r], G.bases + G.chrom_off[chrom[r]] + (pos[r] - 1u), md + ma,
+                                     md_off[r + 1u] - ma, cs + ca, cs_off[r + 1u] - ca, ml, cl);
+    if (!ok && w.lane == 0) atomicAdd(&small[CALMDS_MISMATCH], 1ull);
 }

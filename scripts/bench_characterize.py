@@ -37,7 +37,14 @@ tags (the cs of the hg002-like error rates, ~2 KB).  Prints the kernel milliseco
 events from the first kernel to the last, the host's waits and its formatting of the floats included), that per 10^5 records, the text
 bytes written per second and against the 8 TB/s roofline; and, end to end, records/s of read_bam + cs_from_sam over the BAM file (BGZF
 inflate, batches of 64 MB, decode, the reader's loop) next to cs_from_sam over the SAM text of the same records (bam_to_sam wrote it).
-    python scripts/bench_characterize.py --bam [--alignments 20000] [--steps 3]"""
+    python scripts/bench_characterize.py --bam [--alignments 20000] [--steps 3]
+--calmd: MD and cs text from the reference genome (ns_calmd, characterize.with_reference) on synthetic 8 kb reads over a random genome
+of 24 Mb: --alignments records (200 distinct ones, repeated; ~950 CIGAR ops each, a mismatch, an insertion or a deletion every ~11
+bases) in ONE call.  Prints the kernel milliseconds of every step (device events from the first kernel to the last, the host's wait for
+the sizes of the texts included), that per 10^5 records and as text bytes per second; the time of the SAME walk compiled for the host
+with one lane (tests/calmd_host.cpp, -O2) on one thread over the same records, and the ratios; and, end to end, records/s of iterating
+with_reference over the SAM text and over read_bam of the BAM file of the same records.
+    python scripts/bench_characterize.py --calmd [--alignments 20000] [--steps 3]"""
 import argparse
 import ctypes as C
 import json
@@ -62,6 +69,7 @@ ap.add_argument("--mixfit", action="store_true")
 ap.add_argument("--besthit", action="store_true")
 ap.add_argument("--columns", type=int, default=1000)
 ap.add_argument("--bam", action="store_true")
+ap.add_argument("--calmd", action="store_true")
 ap.add_argument("--records", action="store_true")
 ap.add_argument("--host-walk", action="store_true")
 ap.add_argument("--dump-maf", default=None)
@@ -172,6 +180,109 @@ if a.bam:
     eng.close()
     os.remove(bam_path)
     os.remove(sam_path)
+    os.rmdir(tmp)
+    sys.exit(0)
+if a.calmd:
+    import subprocess
+    import types
+    from concurrent.futures import ThreadPoolExecutor
+    from tests import bam_lib
+    rng = np.random.default_rng(SEED)
+    n = a.alignments if a.alignments != 200_000 else 20_000
+    n_chrom, chrom_len = 24, 1_000_000
+    ref = M.make_reference(["chr%d" % (i + 1) for i in range(n_chrom)],
+                           [np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, chrom_len)] for _ in range(n_chrom)])
+    distinct = []                                                 # (cigar, seq, chrom, pos)
+    for k in range(200):
+        ci, start = k % n_chrom, int(rng.integers(0, chrom_len - 10_000))
+        chrom = ref.chrom(ci).tobytes().decode()
+        want, r, ops, seq = int(rng.integers(7600, 8400)), start, [], ["A" * 30]
+        while len(ops) < 4 or sum(len(s) for s in seq) < want:   # ~ one error per 11 bases: match runs with a mismatch, an insertion or a deletion between
+            m = int(rng.geometric(0.09))
+            seq.append(chrom[r:r + m] + "ACGT"[("ACGT".index(chrom[r + m]) + 1) % 4]); ops.append("%dM" % (m + 1)); r += m + 1
+            if rng.random() < 0.5:
+                e = int(rng.integers(1, 4))
+                if rng.random() < 0.5:
+                    ops.append("%dI" % e); seq.append("acg"[:e])
+                else:
+                    ops.append("%dD" % e); r += e
+        seq.append(chrom[r:r + 5] + "C" * 30); ops.append("5M")
+        distinct.append(("30S" + "".join(ops) + "30S", "".join(seq), ci, start + 1))
+    recs = [distinct[i % 200] for i in range(n)]
+    cigars, seqs, chroms, poss = [x[0] for x in recs], [x[1] for x in recs], [x[2] for x in recs], [x[3] for x in recs]
+    n_ops = float(np.mean([x[0].count("M") + x[0].count("I") + x[0].count("D") + 2 for x in distinct]))
+    seq_bytes = sum(len(s) for s in seqs)
+    eng = E.Engine(0)
+    eng.set_reference(ref)
+    r = characterize.cs_md_call(eng, cigars, seqs, chroms, poss)    # warms up
+    n_text, ms, call_s = len(r["md"]) + len(r["cs"]), [], []
+    for _ in range(a.steps):
+        t0 = time.perf_counter()
+        r = characterize.cs_md_call(eng, cigars, seqs, chroms, poss)
+        call_s.append(time.perf_counter() - t0)
+        ms.append(r["ms_kernel"])
+    med = float(np.median(ms))
+    # the same walk, compiled for the host with one lane, on one thread over the same records
+    tmp = tempfile.mkdtemp(prefix="nscalmd_")
+    so = os.path.join(tmp, "libcalmd_host.so")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, os.path.join(ROOT, "tests", "calmd_host.cpp")])
+    HL = C.CDLL(so)
+    HL.calmd_host.restype = C.c_int
+    HL.calmd_host.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.c_uint32, C.c_void_p]
+    HL.calmd_host_set_reference.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]
+    assert HL.calmd_host_set_reference(ref.bases.ctypes.data, len(ref.bases), ref.chrom_off.ctypes.data, len(ref.names)) == 0
+
+    def host_check(rc):
+        assert rc == 0, rc
+    host = types.SimpleNamespace(ctx=None, _check=host_check, L=types.SimpleNamespace(ns_calmd=HL.calmd_host))
+    host_ms = []
+    for _ in range(a.steps):
+        h = characterize.cs_md_call(host, cigars, seqs, chroms, poss)
+        host_ms.append(h["ms_kernel"])
+    assert h["md"] == r["md"] and h["cs"] == r["cs"]
+    host_med = float(np.median(host_ms))
+    # end to end: with_reference over SAM text and over the BAM file of the same records
+    names = ref.names
+    header = "@HD\tVN:1.6\tSO:unsorted\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % (nm, chrom_len) for nm in names) + "@PG\tID:minimap2\tPN:minimap2\n"
+    quals = ["".join(chr(33 + 2 + (i * 7 + k) % 38) for i in range(len(x[1]))) for k, x in enumerate(distinct)]
+    sam_path, bam_path = os.path.join(tmp, "synthetic.sam"), os.path.join(tmp, "synthetic.bam")
+    with open(sam_path, "w") as f:
+        f.write(header)
+        for i in range(n):
+            c, s, ci, p = distinct[i % 200]
+            f.write("read_%06d\t%d\t%s\t%d\t60\t%s\t*\t0\t0\t%s\t%s\tNM:i:700\n" % (i, 16 * (i & 1), names[ci], p, c, s, quals[i % 200]))
+    packed = [bam_lib.record("read_%06d" % k, 16 * (k & 1), x[2], x[3], 60, x[0], -1, 0, 0, x[1].upper(), quals[k], bam_lib.tag_bytes("NM", "S", 700))
+              for k, x in enumerate(distinct)]
+    inflated = bam_lib.bam_header(header, [(nm, chrom_len) for nm in names]) + b"".join(packed[i % 200] for i in range(n))
+    with ThreadPoolExecutor(max_workers=16) as pool, open(bam_path, "wb") as f:
+        for blk in pool.map(lambda i: bam_lib.bgzf_block(inflated[i:i + 65280], level=1), range(0, len(inflated), 65280)):
+            f.write(blk)
+        f.write(bam_lib.EOF_BLOCK)
+    del inflated
+    over_sam, over_bam = [], []
+    for _ in range(a.steps):
+        t0 = time.perf_counter()
+        tagged = characterize.with_reference(sam_path, ref, eng)
+        got = sum(1 for line in tagged if line[0] != "@")
+        over_sam.append(time.perf_counter() - t0)
+        assert got == n == tagged.n_tagged
+        t0 = time.perf_counter()
+        tagged = characterize.with_reference(characterize.read_bam(bam_path, eng), ref, eng)
+        got = sum(1 for line in tagged if line[0] != "@")
+        over_bam.append(time.perf_counter() - t0)
+        assert got == n == tagged.n_tagged
+    print(json.dumps({"metric": "MD and cs text from the reference, kernel ms per 10^5 records of 8 kb reads (ns_calmd)", "value": med * 1e5 / n,
+                      "records": n, "seq_bytes": seq_bytes, "text_bytes": n_text, "cigar_ops_per_record": n_ops, "steps": a.steps, "kernel_ms": ms,
+                      "text_gb_per_s": n_text / (med * 1e-3) / 1e9, "bases_gb_per_s(SEQ + reference read, both walks)": 4.0 * seq_bytes / (med * 1e-3) / 1e9,
+                      "cs_md_call_end_to_end_s": call_s, "host_walk_one_thread_ms": host_ms, "host_walk_ms_per_1e5_records": host_med * 1e5 / n,
+                      "host_one_thread_over_gpu_kernel": host_med / med, "host_sixteen_threads_worth_over_gpu_kernel": host_med / 16.0 / med,
+                      "host_one_thread_over_gpu_call": host_med * 1e-3 / float(np.median(call_s)),
+                      "with_reference_over_sam_s": over_sam, "with_reference_over_bam_s": over_bam,
+                      "records_per_s(with_reference over SAM text)": n / float(np.median(over_sam)),
+                      "records_per_s(with_reference over read_bam)": n / float(np.median(over_bam))}))
+    eng.close()
+    for p in (so, sam_path, bam_path):
+        os.remove(p)
     os.rmdir(tmp)
     sys.exit(0)
 if a.besthit:

@@ -42,6 +42,7 @@ TRAINING = {
     CSRC + "ns_chimeric.h": ("tests/chimeric_host.cpp", ["tests/test_chimeric_train.py"]),
     CSRC + "ns_cs_hist.h": ("tests/cs_hist_host.cpp", ["tests/test_characterize.py", "tests/test_basequal.py"]),
     CSRC + "ns_bam.h": ("tests/bam_host.cpp", ["tests/test_bam.py"]),
+    CSRC + "ns_calmd.h": ("tests/calmd_host.cpp", ["tests/test_calmd.py"]),
     CSRC + "ns_em.h": ("tests/em_host.cpp", ["tests/test_quantify.py"]),
     CSRC + "ns_hp_hist.h": ("tests/hp_train_host.cpp", ["tests/test_hp_train.py"]),
     CSRC + "ns_ir_train.h": ("tests/ir_train_host.cpp", ["tests/test_ir_train.py"]),
