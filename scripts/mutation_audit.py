@@ -41,8 +41,10 @@ CSRC = "nanosim_amd/csrc/"
 TRAINING = {
     CSRC + "ns_chimeric.h": ("tests/chimeric_host.cpp", ["tests/test_chimeric_train.py"]),
     CSRC + "ns_cs_hist.h": ("tests/cs_hist_host.cpp", ["tests/test_characterize.py", "tests/test_basequal.py"]),
-    CSRC + "ns_bam.h": ("tests/bam_host.cpp", ["tests/test_bam.py"]),
-    CSRC + "ns_calmd.h": ("tests/calmd_host.cpp", ["tests/test_calmd.py"]),
+    # (the two headers written against an abstract wavefront: the one-lane build first, then 64 lanes in lock step, tests/wave64_host.h —
+    # 64 host threads per mutant, so few --jobs; a mutant whose lanes diverge ends with the wave's message, one that loops at its time limit)
+    CSRC + "ns_bam.h": ("tests/bam_host.cpp", ["tests/test_bam.py", "tests/test_bam_wave64.py"]),
+    CSRC + "ns_calmd.h": ("tests/calmd_host.cpp", ["tests/test_calmd.py", "tests/test_calmd_wave64.py"]),
     CSRC + "ns_em.h": ("tests/em_host.cpp", ["tests/test_quantify.py"]),
     CSRC + "ns_hp_hist.h": ("tests/hp_train_host.cpp", ["tests/test_hp_train.py"]),
     CSRC + "ns_ir_train.h": ("tests/ir_train_host.cpp", ["tests/test_ir_train.py"]),

@@ -1,6 +1,7 @@
 """Test-side of the cs / MD stage (nanosim_amd/csrc/ns_calmd.h, nanosim_amd/characterize/calmd.py), sharing no code with either:
 a generator of alignments over tests/golden/genome_small.fa that knows MD and cs by construction (from the events it draws, not from
-the columns), an independent column-by-column writer of the rules, and helpers that strip and re-tag SAM text."""
+the columns), an independent column-by-column writer of the rules, a plain restatement of the nine reasons a record is bad for with a
+generator of corrupted records, and helpers that strip and re-tag SAM text."""
 import os
 import re
 
@@ -76,12 +77,13 @@ def _other(rng, b):
 
 def alignment(rng, chroms, n_cols: int, kind: str, clips: bool = True, hard: bool = True, name: str = "r"):
     """one alignment of n_cols columns: dict(name, flag, chrom, pos, cigar, cigar_eqx, seq, md, cs).  kind: "clean" (no errors), "ont"
-    (about 12 % errors), "alternate" (every other column a mismatch).  The slice of the reference holds no N (a column on N is a
+    (about 12 % errors), "alternate" (every other column a mismatch), "dense" and "wide" (an I or a D op between any two M ops, which are
+    runs of 1-3 and of 60-70 columns).  The slice of the reference holds no N (a column on N is a
     mismatch whatever the read shows, which the hand-written cases cover)."""
     while True:
         ci = int(rng.integers(0, len(chroms)))
         chrom = chroms[ci]
-        span = n_cols + n_cols // 4 + 8
+        span = 4 * n_cols + 8 if kind == "dense" else n_cols + n_cols // 4 + 8         # (dense: up to three deleted letters per column)
         if span >= len(chrom):
             continue
         start = int(rng.integers(0, len(chrom) - span))
@@ -94,6 +96,13 @@ def alignment(rng, chroms, n_cols: int, kind: str, clips: bool = True, hard: boo
             step = ("=", n_cols - cols)
         elif kind == "alternate":
             step = ("X",) if cols % 2 else ("=", 1)
+        elif kind in ("dense", "wide"):                  # an I or a D op between any two M ops: M runs of 1-3 columns, or of 60-70
+            if events and events[-1][0] not in "ID":
+                step = ("I",) if rng.random() < 0.5 else ("D",)
+            else:
+                run = int(rng.integers(1, 4)) if kind == "dense" else int(rng.integers(60, 71))
+                k = min(run, n_cols - cols)
+                step = ("X",) if k == 1 and rng.random() < 0.3 else ("=", k)
         else:
             x = rng.random()
             step = ("=", min(int(rng.geometric(0.12)), n_cols - cols)) if x < 0.5 else ("X",) if x < 0.7 else ("I",) if x < 0.85 else ("D",)
@@ -226,3 +235,144 @@ def retagged(text: str, ref) -> str:
                     ("" if any(t.startswith("cs:Z:") for t in f[11:]) else "\tcs:Z:" + cs) + end)
         out.append(line)
     return "".join(out)
+
+
+# ---- bad records: the rules, one byte after the other ---------------------------------------------------------------------------------
+MAX_DIGITS, MAX_OPLEN, MAX_TOTAL = 9, 1 << 28, 1 << 31
+
+
+def bad_reason_at(cigar: str, seq, chrom: int, pos: int, chroms):
+    """(reason, the CIGAR byte that decides or None) of a record by the rules of the opening comment of ns_calmd.h, 0: a good record.
+    seq: bytes, or a str of code points below 256; chroms: as chromosomes() gives them.
+    chrom, then POS; then the CIGAR byte by byte, the lowest byte that has a reason decides — at one op letter: it does not parse, the op
+    is unknown, the order of the clips, the sums —, behind it digits at the end or no byte at all; then no column, the length of SEQ, the
+    end of the chromosome, a SEQ byte."""
+    sq = seq.encode("latin-1") if isinstance(seq, str) else bytes(seq)
+    if chrom >= len(chroms):
+        return 6, None
+    if pos == 0:
+        return 7, None
+    digits = ""
+    n_ops = 0
+    columns = seq_sum = ref_sum = 0
+    seen_aligned = lead_s = trail_s = closing_h = False                  # an M/I/D/=/X op; an S in front of them; one behind; an H that is not the first op
+    for at, c in enumerate(cigar):
+        if c.isascii() and c.isdigit():
+            digits += c
+            continue
+        if not (c == "=" or (c.isascii() and c.isalpha())):
+            return 1, at
+        if not digits or len(digits) > MAX_DIGITS or int(digits) == 0 or int(digits) >= MAX_OPLEN:
+            return 1, at
+        if c not in "MIDSH=X":
+            return 2, at
+        n = int(digits)
+        digits = ""
+        # the clips: H only as the first or the last op, S only with nothing but an H between it and the end it stands at
+        if closing_h:
+            return 3, at                                                 # (an op behind an H that was not the first op)
+        if c == "H":
+            closing_h = n_ops > 0
+        elif c == "S":
+            if (trail_s if seen_aligned else lead_s):
+                return 3, at
+            if seen_aligned:
+                trail_s = True
+            else:
+                lead_s = True
+        else:
+            if trail_s:
+                return 3, at
+            seen_aligned = True
+        columns += n if c in "M=X" else 0
+        seq_sum += n if c in "M=XIS" else 0
+        ref_sum += n if c in "M=XD" else 0
+        if max(columns, seq_sum, ref_sum) >= MAX_TOTAL:
+            return 1, at
+        n_ops += 1
+    if digits or not cigar:
+        return 1, len(cigar)
+    if not columns:
+        return 9, None
+    if seq_sum != len(sq):
+        return 4, None
+    if pos - 1 + ref_sum > len(chroms[chrom]):
+        return 8, None
+    if not all(65 <= (b & 0xdf) <= 90 for b in sq):
+        return 5, None
+    return 0, None
+
+
+def bad_reason(cigar: str, seq, chrom: int, pos: int, chroms) -> int:
+    return bad_reason_at(cigar, seq, chrom, pos, chroms)[0]
+
+
+CIGAR_NOISE, SEQ_NOISE = "0MIDSHNP=X,9m", "*=[`1"
+
+
+def corrupted_records(seed: int = 20261021, n: int = 3000, max_cols: int = 400):
+    """n records: good alignments of 1 .. max_cols columns with an indel between any two M runs ("dense" and "wide", in turn), each with
+    one or two changes — a CIGAR byte replaced by one of CIGAR_NOISE, a SEQ byte by one of SEQ_NOISE, a digit appended to the CIGAR, a clip
+    moved inward, POS pushed to the end of the chromosome; and, so that the set shows every reason, now and then the chromosome index set
+    to the number of chromosomes or POS to 0.  [dict(cigar, seq: bytes, chrom, pos, reason, at, two)]: reason and at from bad_reason_at;
+    two: the record has two changes in its CIGAR each of which alone is an error, of two different reasons at two different bytes."""
+    rng = np.random.default_rng(seed)
+    chroms = chromosomes(reference())
+    out = []
+
+    def cigar_byte(r):
+        at = int(rng.integers(0, len(r["cigar"])))
+        r["cigar"] = r["cigar"][:at] + CIGAR_NOISE[int(rng.integers(0, len(CIGAR_NOISE)))] + r["cigar"][at + 1:]
+
+    def seq_byte(r):
+        at = int(rng.integers(0, len(r["seq"])))
+        r["seq"] = r["seq"][:at] + SEQ_NOISE[int(rng.integers(0, len(SEQ_NOISE)))] + r["seq"][at + 1:]
+
+    def digit(r):
+        r["cigar"] += "0123456789"[int(rng.integers(0, 10))]
+
+    def clip(r):
+        ops = re.findall(r"\d+[^\d]", r["cigar"])
+        if len(ops) == len(re.findall(r"\d+[MIDSH=X]", r["cigar"])) and "".join(ops) == r["cigar"] and len(ops) >= 3:
+            s = [i for i, o in enumerate(ops) if o[-1] in "SH"]
+            i = s[int(rng.integers(0, len(s)))] if s else None
+            if i is not None:
+                o = ops.pop(i)
+                ops.insert(int(rng.integers(1, len(ops))), o)
+                r["cigar"] = "".join(ops)
+                return
+        cigar_byte(r)
+
+    def end(r):
+        span = sum(int(k) for k, o in re.findall(r"(\d+)([MD=X])", r["cigar"]))
+        r["pos"] = max(1, len(chroms[min(r["chrom"], len(chroms) - 1)]) - span + 1 + int(rng.integers(0, 3)))
+
+    def chrom(r):
+        r["chrom"] = len(chroms)
+
+    def pos0(r):
+        r["pos"] = 0
+    changes = [cigar_byte] * 10 + [seq_byte] * 3 + [digit] * 2 + [clip] * 2 + [end] * 2
+    for i in range(n):
+        cols = max(1, min(max_cols, int(round(10 ** rng.uniform(0, np.log10(max_cols))))))
+        a = alignment(rng, chroms, cols, ("dense", "wide")[i % 2], name="c%d" % i)
+        r = dict(cigar=a["cigar"], seq=a["seq"], chrom=a["chrom"], pos=a["pos"])
+        first = chrom if i % 97 == 5 else pos0 if i % 97 == 6 else changes[int(rng.integers(0, len(changes)))]
+        first(r)
+        alone = [dict(r)]
+        if rng.random() < 0.8:
+            second = cigar_byte if first is cigar_byte and rng.random() < 0.8 else changes[int(rng.integers(0, len(changes)))]
+            before = dict(r)
+            second(r)
+            if first is cigar_byte and second is cigar_byte and len(r["cigar"]) == len(a["cigar"]):
+                # the second change alone, on the good record
+                k = [j for j in range(len(r["cigar"])) if r["cigar"][j] != before["cigar"][j]]
+                if len(k) == 1:
+                    alone.append(dict(r, cigar=a["cigar"][:k[0]] + r["cigar"][k[0]] + a["cigar"][k[0] + 1:]))
+        r["reason"], r["at"] = bad_reason_at(r["cigar"], r["seq"], r["chrom"], r["pos"], chroms)
+        singles = [bad_reason_at(x["cigar"], x["seq"], x["chrom"], x["pos"], chroms) for x in alone]
+        r["two"] = (len(singles) == 2 and all(s[0] in (1, 2, 3) and s[1] is not None for s in singles) and singles[0][0] != singles[1][0] and
+                    singles[0][1] != singles[1][1])
+        r["seq"] = r["seq"].encode("latin-1")
+        out.append(r)
+    return out

@@ -31,22 +31,29 @@ class HostError(Exception):
     pass
 
 
-def build_host():
-    """an object that stands in for an Engine: its ns_bam_to_sam is the engine's per-wavefront code compiled for the host with one lane"""
+def build_host(lanes: int = 1):
+    """an object that stands in for an Engine: its ns_bam_to_sam is the engine's per-wavefront code compiled for the host with one lane
+    (or, lanes = 64, on the lock-step wavefront of tests/wave64_host.h)"""
     out = os.path.join(ROOT, "tests", "_tmp")
     os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "libbam_host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, os.path.join(ROOT, "tests", "bam_host.cpp")])
+    so = os.path.join(out, "libbam_host.so" if lanes == 1 else "libbam_host%d.so" % lanes)
+    mine = "%s.%d" % (so, os.getpid())                               # (built under a name of its own and moved: test processes may run side by side)
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-DBAM_HOST_LANES=%d" % lanes, "-o", mine,
+                           os.path.join(ROOT, "tests", "bam_host.cpp")])
+    os.replace(mine, so)
     L = C.CDLL(so)
     L.bam_host_to_sam.restype = C.c_int
     L.bam_host_to_sam.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    L.bam_host_guard.restype = C.c_int
+    L.bam_host_guard.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]
     L.bam_host_constant.restype = C.c_uint32
     L.bam_host_constant.argtypes = [C.c_int]
 
     def check(rc):
         if rc:
             raise HostError("bam_host_to_sam returned %d" % rc)
-    return types.SimpleNamespace(ctx=None, _check=check, L=types.SimpleNamespace(ns_bam_to_sam=L.bam_host_to_sam), constant=L.bam_host_constant)
+    return types.SimpleNamespace(ctx=None, _check=check, L=types.SimpleNamespace(ns_bam_to_sam=L.bam_host_to_sam), constant=L.bam_host_constant,
+                                 guard=L.bam_host_guard)
 
 
 @pytest.fixture(scope="module")
@@ -454,10 +461,16 @@ def malformed():
         ("n_cigar larger than the record", patched(4 + 12, "<H", 60000), 1),
         ("block_size below the fixed fields", struct.pack("<i", 20) + base[4:24], 1),
         ("block_size negative", struct.pack("<i", -5) + base[4:], 1),
+        ("block_size one below the fixed fields", struct.pack("<i", 31) + base[4:35] + good, 1),
+        ("block_size of the fixed fields alone: no name", struct.pack("<i", 32) + base[4:12] + b"\0" + base[13:16] + struct.pack("<H", 0) + base[18:20] +
+         struct.pack("<i", 0) + base[24:36], 4),
         ("l_seq negative", patched(4 + 16, "<i", -1), 2),
         ("refID == n_ref", patched(4, "<i", 3), 3),
         ("refID -2", patched(4, "<i", -2), 3),
+        ("next_refID -2", patched(4 + 20, "<i", -2), 3),
         ("next_refID beyond", patched(4 + 20, "<i", 1 << 30), 3),
+        ("next_refID == n_ref", patched(4 + 20, "<i", 3), 3),
+        ("refID == n_ref, next_refID the last", patched(4 + 20, "<i", 2, patched(4, "<i", 3)), 3),
         ("name without NUL", patched(4 + 32 + 3, "<B", 120), 4),
         ("l_read_name 0", record("", 0, 1, 1, 60, "*", 1, 5, 0, "*", "*")[:12] + b"\0" + record("", 0, 1, 1, 60, "*", 1, 5, 0, "*", "*")[13:], 4),
         ("tag type Q", with_tags(tag_bytes("NM", "C", 1) + b"XQQ\1"), 5),
@@ -469,6 +482,8 @@ def malformed():
         ("B count past the record", with_tags(b"XBBi" + struct.pack("<I", 3) + struct.pack("<ii", 1, 2)), 7),
         ("B count 2^32 - 1", with_tags(b"XBBc" + struct.pack("<I", 0xffffffff) + b"ab"), 7),
         ("B without count", with_tags(b"XBBc\1\0"), 7),
+        ("B with three bytes of count", with_tags(b"XBBc\0\0\0"), 7),
+        ("B with three bytes of count, a record behind", with_tags(b"XBBc\0\0\0") + good, 7),
         ("i with two bytes", with_tags(b"XIi\1\0"), 7),
         ("two stray bytes", with_tags(tag_bytes("NM", "C", 1) + b"XI"), 7),
     ]
@@ -495,6 +510,121 @@ def test_host_malformed_records(host):
     check_malformed(host)
 
 
+# ---- the edges of the rounds: what one lane cannot show (run on the one-lane build, on 64 lanes in lock step and on the GPU) ---------------
+Z_LENGTHS = (7, 8, 9, 511, 512, 513)                                 # around the bytes of a lane and of a wavefront in the search for a NUL
+ROUND_COUNTS = (63, 64, 65, 129)                                     # elements of a B array and ops of a CIGAR around the rounds
+
+
+def placed(rec: bytes, pos: int) -> bytes:
+    """the record at POS pos (1-based), its bin left as it is: beyond 2^29 the writer's reg2bin has no bin, and no line shows one"""
+    b = bytearray(rec)
+    struct.pack_into("<i", b, 4 + 4, pos - 1)
+    return bytes(b)
+
+
+def edge_cases():
+    """[(record bytes, its line)]"""
+    cases = [
+        (record("same0", 1, 0, 10, 60, "2M", 0, 90, 82, "AC", "II"), "same0\t1\tchr1\t10\t60\t2M\t=\t90\t82\tAC\tII\n"),
+        (record("other0", 1, 1, 10, 60, "2M", 0, 90, 82, "AC", "II"), "other0\t1\tchr2\t10\t60\t2M\tchr1\t90\t82\tAC\tII\n"),
+        (record("un0", 5, -1, 0, 0, "*", 0, 90, 0, "AC", "II"), "un0\t5\t*\t0\t0\t*\tchr1\t90\t0\tAC\tII\n"),
+        (record("last", 1, 2, 10, 60, "2M", 2, 90, 82, "AC", "II"), "last\t1\tchr3\t10\t60\t2M\t=\t90\t82\tAC\tII\n"),
+        (placed(record("ten", 1, 0, 1, 60, "2M", 1, 10 ** 9 - 1, -10 ** 9, "AC", "II", tag_bytes("BI", "B", ("I", [10 ** 9, 10 ** 9 - 1])) +
+                       tag_bytes("Bi", "B", ("i", [-10 ** 9, 10 ** 9, 10 ** 9 - 1, 1 - 10 ** 9])) + tag_bytes("XI", "I", 10 ** 9) + tag_bytes("Xi", "i", -10 ** 9)), 10 ** 9),
+         "ten\t1\tchr1\t1000000000\t60\t2M\tchr2\t999999999\t-1000000000\tAC\tII\tBI:B:I,1000000000,999999999\tBi:B:i,-1000000000,1000000000,999999999,-999999999"
+         "\tXI:i:1000000000\tXi:i:-1000000000\n"),
+        (placed(record("nine", 1, 0, 1, 60, "2M", 1, 10 ** 9, 10 ** 9, "AC", "II"), 10 ** 9 - 1), "nine\t1\tchr1\t999999999\t60\t2M\tchr2\t1000000000\t1000000000\tAC\tII\n"),
+        (record("tlen9", 1, 0, 1, 60, "2M", 1, 1, 10 ** 9 - 1, "AC", "II"), "tlen9\t1\tchr1\t1\t60\t2M\tchr2\t1\t999999999\tAC\tII\n"),
+        (record("op9", 0, 0, 1, 60, [(10 ** 8) << 4 | 2, (10 ** 8 - 1) << 4 | 3, 2 << 4], -1, 0, 0, "AC", "II"), "op9\t0\tchr1\t1\t60\t100000000D99999999N2M\t*\t0\t0\tAC\tII\n"),
+    ]
+    rng = np.random.default_rng(20261022)
+    for k, n in enumerate(Z_LENGTHS):                                # a Z value whose NUL is the very last byte of the record
+        z = rng.integers(33, 127, n).astype(np.uint8).tobytes().decode()
+        cases.append((record("z%d" % n, 0, 0, 1 + k, 60, "2M", -1, 0, 0, "AC", "II", tag_bytes("NM", "C", k) + tag_bytes("zz", "Z", z)),
+                      "z%d\t0\tchr1\t%d\t60\t2M\t*\t0\t0\tAC\tII\tNM:i:%d\tzz:Z:%s\n" % (n, 1 + k, k, z)))
+    limits = {"c": (-128, 128), "C": (0, 256), "s": (-32768, 32768), "S": (0, 65536), "i": (-2 ** 31, 2 ** 31), "I": (0, 2 ** 32)}
+    for n in ROUND_COUNTS:                                           # B arrays; behind each the bytes of the next tag, which are no element
+        tags, text = b"", ""
+        for sub in "cCsSiIf":
+            if sub == "f":
+                v = [float(np.float32(x)) for x in rng.standard_normal(n) * 10.0 ** rng.integers(-6, 7, n)]
+                shown = [g(x) for x in v]
+            else:
+                v = [int(x) for x in rng.integers(limits[sub][0], limits[sub][1], n)]
+                shown = ["%d" % x for x in v]
+            tags += tag_bytes("B" + sub, "B", (sub, v))
+            text += "\tB%s:B:%s,%s" % (sub, sub, ",".join(shown))
+        cases.append((record("b%d" % n, 0, 0, 1, 60, "2M", -1, 0, 0, "AC", "II", tags + tag_bytes("zz", "Z", "behind")),
+                      "b%d\t0\tchr1\t1\t60\t2M\t*\t0\t0\tAC\tII%s\tzz:Z:behind\n" % (n, text)))
+        cases.append((record("l%d" % n, 0, 0, 1, 60, "2M", -1, 0, 0, "AC", "II", tag_bytes("BS", "B", ("S", list(range(300, 300 + n))))),     # ... or the next record
+                      "l%d\t0\tchr1\t1\t60\t2M\t*\t0\t0\tAC\tII\tBS:B:S,%s\n" % (n, ",".join("%d" % x for x in range(300, 300 + n)))))
+    for n in ROUND_COUNTS:                                           # CIGARs; behind the ops the bytes of SEQ, which are no op
+        ops = [(int(rng.integers(1, 5000)), "MIDNSHP=X"[int(rng.integers(0, 9))]) for _ in range(n)]
+        cigar = "".join("%d%s" % o for o in ops)
+        cases.append((record("c%d" % n, 0, 0, 1, 60, cigar, -1, 0, 0, "TGCATGCATGCA", "IIIIIIIIIIII"),
+                      "c%d\t0\tchr1\t1\t60\t%s\t*\t0\t0\tTGCATGCATGCA\tIIIIIIIIIIII\n" % (n, cigar)))
+    return [(r, l.encode()) for r, l in cases]
+
+
+def edge_malformed():
+    """[(name, bytes, reason, the index of the bad record, its offset)]: a Z value without a NUL that ends its record, and directly
+    behind it a record whose first byte — the low byte of its block_size — is 0"""
+    behind = record("behind", 0, 0, 1, 60, "2M", -1, 0, 0, "AC", "II", tag_bytes("zz", "Z", "x" * 206))
+    assert len(behind) == 4 + 256 and behind[0] == 0
+    out = []
+    for n in Z_LENGTHS:
+        bad = record("bad", 0, 1, 1, 60, "2M1I", 1, 5, 0, "ACG", "III", tag_bytes("NM", "C", 1) + b"XZZ" + b"v" * n)
+        out.append(("Z without NUL of %d bytes, a 0 byte behind the record" % n, bad + behind, 6, 0, 0))
+        out.append(("... behind a good record", behind + bad + behind, 6, 1, len(behind)))
+    return out
+
+
+def check_edge_cases(eng):
+    cases = edge_cases()
+    got = lines_of(eng, [r for r, _ in cases])
+    for (_, want), line in zip(cases, got):
+        assert line == want
+    for r, want in cases:                                            # ... each alone, where its last byte is the last of the buffer
+        assert lines_of(eng, [r]) == [want]
+    behind = edge_malformed()[0][1][-260:]
+    for name, data, reason, index, offset in edge_malformed():
+        r = raw(eng, data, True)
+        assert (r["reason"], r["first_bad"], r["first_bad_offset"], r["n"], r["text"], r["consumed"]) == (reason, index, offset, 0, b"", 0), name
+    assert lines_of(eng, [behind]) == [b"behind\t0\tchr1\t1\t60\t2M\t*\t0\t0\tAC\tII\tzz:Z:" + b"x" * 206 + b"\n"]
+    return len(cases)
+
+
+def check_no_references(eng):
+    """a file without reference sequences: unmapped records decode, a refID or next_refID of 0 is outside the references"""
+    un = record("un", 4, -1, 0, 0, "*", -1, 0, 0, "AC", "II")
+    assert lines_of(eng, [un, un], refs=[]) == [b"un\t4\t*\t0\t0\t*\t*\t0\t0\tAC\tII\n"] * 2
+    for bad in (record("r0", 4, 0, 1, 0, "*", -1, 0, 0, "AC", "II"), record("n0", 4, -1, 0, 0, "*", 0, 1, 0, "AC", "II")):
+        r = raw(eng, un + bad + un, True, refs=[])
+        assert (r["reason"], r["first_bad"], r["first_bad_offset"], r["n"], r["text"]) == (3, 1, len(un), 0, b""), bad
+
+
+def check_store_guards(host):
+    """the host build alone (the engine has no such entry): bam_write on room that is shorter or longer than measured — short
+    lines cut at every byte, f and B:f bodies included; longer ones inside their tags, behind the first SEQ byte, of no byte — says so and stores nothing outside it"""
+    names, off = characterize._pack([n for n, _ in REFS])
+    done = 0
+    short = [record("g%d" % k, 0, 0, 1, 60, "2M1I", -1, 0, 0, "ACG", "III", tags) for k, tags in enumerate((                # lines cut at every byte
+        tag_bytes("de", "f", 0.25) + tag_bytes("zz", "Z", "behind"), tag_bytes("de", "f", -1.17549435e-38) + tag_bytes("fv", "B", ("f", [1e10, 0.5])),
+        tag_bytes("fv", "B", ("f", [1.5, -2.25, 1e-5])) + tag_bytes("XA", "A", "!"), tag_bytes("NM", "i", -7) + tag_bytes("de", "f", 3.0),
+        tag_bytes("Bs", "B", ("s", [-300, 7, 300])) + tag_bytes("HH", "H", "1AE3")))]
+    assert all(len(r) < 100 for r in short)
+    for rec in short + [r for r, _ in corner_cases() + edge_cases()]:
+        assert host.guard(rec, len(rec), names.ctypes.data, off.ctypes.data, len(REFS)) == 0
+        done += 1
+    assert done > 50 and sum(1 for _, line in corner_cases() + edge_cases() if b":f:" in line or b":B:f" in line) >= 6    # (f and B:f among them)
+
+
+def test_host_edges_of_the_rounds(host):
+    assert check_edge_cases(host) > 25
+    check_no_references(host)
+    check_store_guards(host)
+
+
 def test_host_code_is_clean_under_the_sanitizers(tmp_path):
     """the walks as a stand-alone program under -fsanitize=address,undefined: every malformed record gives its reason, the good files
     their text (n_text and the checksum of the text and the offsets)"""
@@ -518,7 +648,7 @@ def test_host_code_is_clean_under_the_sanitizers(tmp_path):
         for o in line_off:
             s = (s * 31 + o) & (2 ** 64 - 1)
         return s
-    for name, data, reason, index, offset in malformed():
+    for name, data, reason, index, offset in malformed() + edge_malformed():
         assert run(data) == ([0, 0, 0, index, offset, reason], 0), name
     cases = corner_cases()
     data, text = b"".join(r for r, _ in cases), b"".join(l for _, l in cases)

@@ -22,20 +22,23 @@ CHROMS = calmd_lib.chromosomes(REF)
 LANES = 64
 
 
-def build_host():
-    """an object that stands in for an Engine: its ns_calmd is the engine's per-wavefront code compiled for the host with one lane, its
-    set_reference keeps a copy normalised as the engine's"""
+def build_host(lanes: int = 1):
+    """an object that stands in for an Engine: its ns_calmd is the engine's per-wavefront code compiled for the host with one lane (or,
+    lanes = 64, on the lock-step wavefront of tests/wave64_host.h), its set_reference keeps a copy normalised as the engine's"""
     out = os.path.join(ROOT, "tests", "_tmp")
     os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "libcalmd_host.so")
+    so = os.path.join(out, "libcalmd_host.so" if lanes == 1 else "libcalmd_host%d.so" % lanes)
     mine = "%s.%d" % (so, os.getpid())                               # (built under a name of its own and moved: test processes may run side by side)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", mine, os.path.join(ROOT, "tests", "calmd_host.cpp")])
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-DCALMD_HOST_LANES=%d" % lanes, "-o", mine,
+                           os.path.join(ROOT, "tests", "calmd_host.cpp")])
     os.replace(mine, so)
     L = C.CDLL(so)
     L.calmd_host.restype = C.c_int
     L.calmd_host.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.c_uint32, C.c_void_p]
     L.calmd_host_set_reference.restype = C.c_int
     L.calmd_host_set_reference.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]
+    L.calmd_host_guard.restype = C.c_int
+    L.calmd_host_guard.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32]
     L.calmd_host_constant.restype = C.c_uint32
     L.calmd_host_constant.argtypes = [C.c_int]
 
@@ -48,7 +51,7 @@ def build_host():
     def set_reference(ref):
         check(L.calmd_host_set_reference(ref.bases.ctypes.data, len(ref.bases), ref.chrom_off.ctypes.data, len(ref.names)))
     return types.SimpleNamespace(ctx=None, _check=check, L=types.SimpleNamespace(ns_calmd=L.calmd_host), constant=L.calmd_host_constant,
-                                 set_reference=set_reference)
+                                 set_reference=set_reference, guard=L.calmd_host_guard)
 
 
 @pytest.fixture(scope="module")
@@ -277,6 +280,223 @@ def check_bad_records(eng):
 
 def test_host_bad_records(host):
     check_bad_records(host)
+
+
+# ---- the cross-lane arithmetic: what one lane cannot show (run on the one-lane build, on 64 lanes in lock step and on the GPU) ------------
+def built(ops, o, mis=(), chrom=0):
+    """(cigar, seq, chrom, pos) of the ops [(count, letter)] laid on chromosome `chrom` from offset o: the reference's letters in the
+    columns, but for the columns `mis`; `acgt...` in lower case for I and S"""
+    R = CHROMS[chrom]
+    r, col, seq = o, 0, []
+    for n, op in ops:
+        if op in "M=X":
+            seq.append("".join(mut(R[r + k]) if col + k in mis else R[r + k] for k in range(n)))
+            r += n
+            col += n
+        elif op == "D":
+            r += n
+        elif op in "IS":
+            seq.append(("acgt" * (n // 4 + 1))[:n])
+    return "".join("%d%s" % x for x in ops), "".join(seq), chrom, o + 1
+
+
+def ops_of(text):
+    return [(int(n), op) for n, op in re.findall(r"(\d+)([MIDSH=X])", text)]
+
+
+PAIRS15 = "1M1I" * 15                                                  # 60 bytes, 30 ops
+TAILS = {3: "10M", 4: "1M1D", 5: "10M1M", 6: "10M10M", 7: "10M1D1M", 8: "1M1D1M1D"}
+
+
+def cigar_of_length(n, shift=False):
+    """a dense good CIGAR of exactly n bytes; shift: with `10M` in front, so that its op letters stand at the other bytes"""
+    head = "10M" if shift else ""
+    pairs = (n - len(head) - 3) // 4
+    text = head + "1M1I" * pairs
+    return text + TAILS[n - len(text)]
+
+
+def wave_cases():
+    """[(name, cigar, seq, chrom, pos, reason or None)] — reason: written out where it can be counted by hand, 0 for a good record; None:
+    calmd_lib.bad_reason alone says.  The texts of the good ones are the independent writer's."""
+    R, last = CHROMS[0], CHROMS[2]
+    o = clean_window(R, 1200)
+    p = o + 1
+    c = []
+
+    def good(name, text, mis=()):
+        c.append((name,) + built(ops_of(text), o, mis) + (0,))
+    # ---- calmd_ops: rounds of 64 CIGAR bytes
+    for n in (63, 64, 65, 127, 128, 129):
+        for shift in (False, True):
+            text = cigar_of_length(n, shift)
+            assert len(text) == n
+            good("a CIGAR of %d bytes%s" % (n, ", shifted" if shift else ""), text)
+    a, b = PAIRS15 + "1M2D", PAIRS15 + "10M2D"
+    assert a[63] == "D" and b[64] == "D"
+    good("an op letter at byte 63", a + "5M")
+    good("an op letter at byte 64", b + "5M")
+    straddle = PAIRS15 + "2M123D5M"
+    assert straddle[62:66] == "123D"
+    good("a count across the boundary of a round", straddle)
+    s5 = R[o:o + 5]
+    big = 268435455                                                  # 2^28 - 1: eight of them are 2^31 - 8
+    c += [("nine digits, valid, a deletion past the end", "5M100000000D", s5, 0, p, 8),
+          ("nine digits, valid, SEQ too short", "100000000M", s5, 0, p, 4),
+          ("nine digits with zeros in front", "000000005M", s5, 0, p, 0),
+          ("SEQ bytes 2^31 - 1", "1M" + ("%dI" % big) * 8 + "6I", "A", 0, p, 4),
+          ("SEQ bytes 2^31", "1M" + ("%dI" % big) * 8 + "7I", "A", 0, p, 1),
+          ("SEQ bytes 2^31 in clips", "%dS" % big + ("%dI" % big) * 7 + "8S1M", "A", 0, p, 1),
+          ("reference letters 2^31 - 1", "1M" + ("%dD" % big) * 8 + "6D", R[o], 0, p, 8),
+          ("reference letters 2^31", "1M" + ("%dD" % big) * 8 + "7D", R[o], 0, p, 1),
+          ("columns 2^31 - 1", ("%dM" % big) * 8 + "7M", s5, 0, p, 4),
+          ("columns 2^31", ("%dM" % big) * 8 + "8M", s5, 0, p, 1),
+          ("columns 2^31 in = and X", ("%d=" % big) * 4 + ("%dX" % big) * 4 + "8=", s5, 0, p, 1)]
+    # the order of the clips, the clip in one round and the op that offends in the next (62 bytes in front)
+    lead = PAIRS15 + "1M"
+    for name, text in (("H between columns", lead + "2H3M"), ("an op behind a trailing S", lead + "2S3M"), ("two trailing S", lead + "2S1S"),
+                       ("an I behind a trailing S", lead + "2S1I"), ("S behind the closing H", lead + "2H1S"), ("H behind the closing H", lead + "2H1H")):
+        assert len(text) == 66 and text[63] in "HS"                  # (the clip closes round 0, the op that offends stands at bytes 64 and 65)
+        cg, sq, _, _ = built(ops_of(text), o)
+        c.append((name + " across a round", cg, sq, 0, p, 3))
+    good("S and a closing H across a round", lead + "2S3H")
+    good("leading H and S, the first column in a later round", "2H3S" + "1I1D" * 16 + "5M")
+    good("leading S, the first column in the third round", "3S" + "1D1I" * 32 + "5M2S1H")
+    c += [("two errors in one round, the op first", "5M2N3M0I", s5 + R[o + 5:o + 8], 0, p, 2),
+          ("two errors in one round, the count first", "5M0I2N3M", s5 + R[o + 5:o + 8], 0, p, 1),
+          ("a clip error in front of an unknown op", "2M1S1S2N", s5, 0, p, 3),
+          ("an unknown op behind a trailing S", "2M1S2N1S", s5, 0, p, 2),
+          ("an unknown op in front of a clip error", "2M2N1S2M", s5, 0, p, 2),
+          ("an unknown op in the first round, a parse error in the second", PAIRS15 + "1M2N" + "0M", s5, 0, p, 2),
+          ("a parse error in the second round only", PAIRS15 + "1M2M" + "0M", s5, 0, p, 1),
+          ("digits at the end behind a round", PAIRS15 + "1M2M" + "5", s5, 0, p, 1)]
+    # the densest op table there is, odd and even lengths next to each other (the tables lie at calmd_op_base)
+    for text in ("1M1I" * 64, "10M" + "1I1M" * 62, "10M" + "1D1M" * 62, "1M1D" * 64, "10M", "1M1I" * 64, "1M", "10M" + "1I1M" * 62):
+        good("dense, %d bytes" % len(text), text)
+    c += [("a good record in front of one that begins with a letter", "10M", R[o:o + 10], 0, p, 0), ("a letter first", "M5", s5, 0, p, 1),
+          ("a good record whose CIGAR fills its round, in front of a letter", cigar_of_length(64)) + built(ops_of(cigar_of_length(64)), o)[1:] + (0,),
+          ("a letter first, again", "M5", s5, 0, p, 1), ("a good record in front of an op", "7M", R[o:o + 7], 0, p, 0), ("the op", "5M", s5, 0, p, 0)]
+    # ---- calmd_text: steps of 64 columns
+    for n in (64, 128):
+        good("a trailing D behind %d columns" % n, "%dM2D" % n)
+        good("a trailing I behind %d columns" % n, "%dM2I" % n)
+        good("a trailing D and I behind %d columns" % n, "%dM2D1I" % n)
+        good("a trailing I and D behind %d columns, a mismatch in the last" % n, "%dM1I2D" % n, (n - 1,))
+    good("a mismatch in lane 63, a D in front of lane 0", "64M2D10M", (63,))
+    good("a mismatch in lane 63, an I in front of lane 0", "64M2I10M", (63,))
+    good("a mismatch in lane 63 and in lane 0, a D between", "64M1D10M", (63, 64))
+    good("D, I, D on a step boundary", "64M1D2I1D10M")
+    good("D, I, D on the second step boundary, mismatches around", "128M1D2I1D10M", (127, 128))
+    good("64 one-column ops in one step, a long op behind", "1M1D" * 64 + "100M", (70, 127, 128))
+    good("a step that begins in the middle of a long op", "1M1I" * 32 + "200M", (31, 32, 63, 64, 191))
+    good("one-column ops behind a long op", "100M" + "1D1M" * 70, (99, 100, 128))
+    for n in (64, 65, 300):
+        good("an insertion of %d" % n, "10M%dI10M" % n)
+        good("a deletion of %d" % n, "10M%dD10M" % n, (9, 10))
+        good("an insertion and a deletion of %d on a step boundary" % n, "64M%dI%dD64M" % (n, n))
+    # ---- calmd_seq_letters: 8 bytes per lane, 512 per round
+    for sn in (512, 513, 519):
+        for at in sorted(set((0, 7, 8, 511, 512, sn - 1))):
+            if at < sn:
+                sq = R[o:o + at] + "@[`{1*"[at % 6] + R[o + at + 1:o + sn]
+                c.append(("a bad SEQ byte at %d of %d" % (at, sn), "%dM" % sn, sq, 0, p, 5))
+        good("%d letters" % sn, "%dM" % sn, (sn - 1,))
+    return c
+
+
+def check_wave_cases(eng):
+    """the cases of wave_cases in one call, the bad ones among the good: every reason, the first bad record, the texts of the good ones"""
+    cases = wave_cases()
+    want = []
+    for name, cigar, seq, chrom, pos, reason in cases:
+        ref = calmd_lib.bad_reason(cigar, seq, chrom, pos, CHROMS)
+        assert reason is None or reason == ref, name
+        want.append(ref)
+    assert set(want) >= {0, 1, 2, 3, 4, 5, 8}
+    r = characterize.calmd_raw(eng, [c[1] for c in cases], [seq_bytes(c[2]) for c in cases], [c[3] for c in cases], [c[4] for c in cases])
+    md, cs = characterize.texts_of(r, "md"), characterize.texts_of(r, "cs")
+    first = next(i for i, w in enumerate(want) if w)
+    for i, (c, w) in enumerate(zip(cases, want)):
+        assert (md[i], cs[i]) == (("", "") if w else write_tags(c[1], c[4], c[2], CHROMS[c[3]])), c[0]
+        alone = characterize.calmd_raw(eng, [c[1]], [seq_bytes(c[2])], [c[3]], [c[4]])
+        assert (alone["n_bad"], alone["bad_reason"]) == ((1, w) if w else (0, 0)), c[0]
+        assert (alone["md"].decode(), alone["cs"].decode()) == (md[i], cs[i]), c[0]
+    assert (r["n_bad"], r["first_bad"], r["bad_reason"]) == (sum(1 for w in want if w), first, want[first])
+    return len(cases)
+
+
+def check_neighbours(eng):
+    """a good record between two records whose CIGARs begin with a letter, an op letter behind a count, `=` or digits: the lane behind the
+    last byte of a CIGAR, and the one in front of the first, take nothing of the neighbour"""
+    R = CHROMS[0]
+    o = clean_window(R, 1200)
+    for cigar in ("1M", "10M", cigar_of_length(63), cigar_of_length(64), cigar_of_length(65), cigar_of_length(128)):
+        rec = built(ops_of(cigar), o)
+        want = write_tags(rec[0], rec[3], rec[1], R)
+        for behind, reason in (("M5", 1), ("5M", 0), ("=", 1), ("15", 1), ("N", 1)):
+            got = characterize.calmd_raw(eng, [behind, rec[0], behind, rec[0]], [R[o:o + 5], rec[1], R[o:o + 5], rec[1]], [0] * 4, [o + 1] * 4)
+            texts = list(zip(characterize.texts_of(got, "md"), characterize.texts_of(got, "cs")))
+            assert texts[1] == texts[3] == want, (cigar, behind)
+            assert texts[0] == texts[2] == (("", "") if reason else ("5", ":5")), (cigar, behind)
+            assert (got["n_bad"], got["bad_reason"]) == ((2, reason) if reason else (0, 0)), (cigar, behind)
+
+
+def check_store_guard(host):
+    """the host build alone (the engine has no such entry): calmd_text<true> on room one byte shorter and one byte longer than
+    measured, for MD and for cs, says so and stores nothing outside — on records whose last store is a run, a mismatch, a deletion, an
+    insertion, and in a later step"""
+    cases = [c for c in hand_cases()[:24]] + [c for c in wave_cases() if c[5] == 0][::6]
+    assert len(cases) > 30
+    for c in cases:
+        cg, sq = c[1].encode(), seq_bytes(c[2])
+        assert host.guard(cg, len(cg), sq, len(sq), c[3], c[4]) == 0, c[0]
+    assert host.guard(b"M5", 2, b"ACGTA", 5, 0, 1) == 1
+
+
+def test_host_store_guard(host):
+    check_store_guard(host)
+
+
+def test_host_cross_lane_cases(host):
+    assert check_wave_cases(host) > 90
+    check_neighbours(host)
+
+
+_CORRUPTED = {}
+
+
+def corrupted_records():
+    """the generated corrupted set with what the references say of it, made once: bad_reason for all of them (checked against the 42
+    literal reasons of bad_cases first), write_tags for those that stayed good"""
+    if not _CORRUPTED:
+        for c in bad_cases():
+            assert calmd_lib.bad_reason(c[1], c[2], c[3], c[4], CHROMS) == c[5], c[0]
+        recs = calmd_lib.corrupted_records()
+        _CORRUPTED["records"] = recs
+        _CORRUPTED["texts"] = [("", "") if r["reason"] else write_tags(r["cigar"], r["pos"], r["seq"].decode("latin-1"), CHROMS[r["chrom"]]) for r in recs]
+    return _CORRUPTED
+
+
+def check_corrupted_records(eng, alone: int = 1):
+    """all of them in one call (the texts of those that stayed good, the count of the bad ones, the first), and every `alone`-th record
+    in a call of its own (its reason)"""
+    fx = corrupted_records()
+    recs, texts = fx["records"], fx["texts"]
+    assert len(recs) == 3000 and set(r["reason"] for r in recs) == set(range(10))
+    assert sum(1 for r in recs if r["two"]) >= 200                    # two errors in one CIGAR, of different reasons at different bytes
+    assert sum(1 for r in recs if r["reason"] in (1, 2, 3) and r["at"] >= LANES) >= 200
+    got = characterize.calmd_raw(eng, [r["cigar"] for r in recs], [r["seq"] for r in recs], [r["chrom"] for r in recs], [r["pos"] for r in recs])
+    first = next(i for i, r in enumerate(recs) if r["reason"])
+    assert (got["n_bad"], got["first_bad"], got["bad_reason"]) == (sum(1 for r in recs if r["reason"]), first, recs[first]["reason"])
+    assert list(zip(characterize.texts_of(got, "md"), characterize.texts_of(got, "cs"))) == texts
+    for r in recs[::alone]:
+        one = characterize.calmd_raw(eng, [r["cigar"]], [r["seq"]], [r["chrom"]], [r["pos"]])
+        assert (one["n_bad"], one["bad_reason"]) == ((1, r["reason"]) if r["reason"] else (0, 0)), (r["cigar"], r["chrom"], r["pos"])
+    return fx
+
+
+def test_host_corrupted_records(host):
+    check_corrupted_records(host)
 
 
 def checksum(md, md_off, cs, cs_off):
