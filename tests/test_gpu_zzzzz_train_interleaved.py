@@ -1,6 +1,6 @@
 """The training-side calls and the simulation on ONE context, interleaved.  The length sort of the counting calls (order_by_length) takes
 its temporary storage from the context's scan_tmp, which the scans and sorts of ns_generate use as well; everything else a counting call
-allocates is its own and gone when it returns (CallScratch, nanosim_amd.hip).  So: generate, count, generate, count ... on one engine,
+allocates is its own and gone when it returns (CallScratch, csrc/ns_train_calls.h).  So: generate, count, generate, count ... on one engine,
 with 65 alignments (the fewest that are sorted) and with 64 (the most that are visited in index order), and every result compared with
 the walk compiled for the host, with an engine that has done nothing else, and — the reads — with the oracle.  No new kernel runs here
 (k_* of csrc/ns_train.h are covered by tests/test_gpu_zz*), hence no child run."""
