@@ -726,6 +726,37 @@ typedef struct ns_calmd_result {
 int ns_calmd(ns_ctx *ctx, const uint8_t *cigar, const uint64_t *cigar_off, const uint8_t *seq, const uint64_t *seq_off,
              const uint32_t *chrom, const uint32_t *pos, uint32_t n, ns_calmd_result *out);
 
+/* ---- training side: the index of a SAM text ------------------------------------------------------------------------------------------------------
+ * where the lines, the fields and the tags cs:Z: MD:Z: NM:i: SA:Z: of a SAM text stand in its bytes, so that no reader splits a line;
+ * nanosim_amd/csrc/ns_sam_index.h has the rules (those of characterize.sam_text) and how the kernels work.  text[nbytes]: SAM text that
+ * begins at a line start.  A line begins at byte 0 or behind a '\n'; one whose first byte is `@` is a header line, wherever it stands;
+ * every other line, an empty one included, is a record.  Fields are what split("\t") gives.  Of the fields 11 onwards that begin with one
+ * of the four prefixes the last one is the tag.  FLAG, POS and the NM value are parsed when they are 1-10 decimal digits below 2^32;
+ * anything else only sets the row's NS_SAM_*_ODD bit, and the caller decides what the text means.
+ * Out: rows[n_records], one per record in the order of the text, and header[n_header], the header lines; both belong to the context and
+ * stay valid until the next ns_sam_index on it or ns_destroy.  n_odd: the bytes of the text that are '\r' or >= 0x80 (text mode is not
+ * restated: the caller turns such a text away).  n_cs / n_md: the records that carry the tag.
+ * NS_EINVAL for null arguments, a line of 2^32 bytes or more and 2^32 lines or more, NS_ENOMEM when the device cannot hold the text and
+ * the lists.  nbytes == 0 is valid and has no rows.  ms_kernel: from the first kernel to the last, the wait of the host for the number of
+ * lines and tabs included.  Added without an ABI change. */
+enum { NS_SAM_FLAG_ODD = 1, NS_SAM_POS_ODD = 2, NS_SAM_NM_ODD = 4,          /* ns_sam_row.bits: the number is not plain (flag / pos / nm are 0) */
+       NS_SAM_HAS_CS = 16, NS_SAM_HAS_MD = 32, NS_SAM_HAS_NM = 64, NS_SAM_HAS_SA = 128 };   /* ... the record has the tag */
+typedef struct ns_sam_row {             /* everything but begin and end is relative to begin */
+    uint64_t begin, end;                /* the line in text; end: its '\n' or nbytes */
+    uint32_t n_fields, bits;
+    uint32_t field_end[11];             /* where fields 0 .. 10 end; field k + 1 begins one behind; end - begin for a field the line has not */
+    uint32_t flag, pos, nm;
+    uint32_t tag_at[4], tag_len[4];     /* the values of cs, MD, NM, SA, behind their five prefix bytes (0, 0 without the tag) */
+} ns_sam_row;
+typedef struct ns_sam_span { uint64_t begin, end; } ns_sam_span;          /* a header line, without its '\n' */
+typedef struct ns_sam_index_result {
+    const ns_sam_row *rows;             /* out, owned by the context */
+    const ns_sam_span *header;
+    uint64_t n_records, n_header, n_odd, n_cs, n_md;                       /* out */
+    double ms_kernel;
+} ns_sam_index_result;
+int ns_sam_index(ns_ctx *ctx, const uint8_t *text, uint64_t nbytes, ns_sam_index_result *out);
+
 /* device address of a result buffer (for zero-copy consumers such as torch / RCCL); NULL if absent */
 const void *ns_device_ptr(ns_ctx *ctx, int which);
 

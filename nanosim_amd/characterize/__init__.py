@@ -16,12 +16,20 @@ references, and every deviation from it.  Every name of a module is a name of th
     bam             characterize.cs_from_sam(characterize.read_bam("training_primary.bam", eng))    # a BAM file wherever a reader takes a SAM path
     calmd           characterize.cs_from_sam(characterize.with_reference("calls.sam", "genome.fa", eng))   # MD:Z and cs:Z from the reference genome
 
+    sam_table       table = characterize.SamTable("training.sam", eng)    # the SAM text indexed on the GPU: every reader takes it for the path
+    training        characterize.train_genome("training", "aln.bam", "reads.fq", eng, chimeric_reads=True, homopolymer=True, fastq=True)
+                    characterize.train_metagenome("training", "aln.sam", "reads.fa", eng, quantification=True, expected={"spA": 60.0, "spB": 40.0})
+                    characterize.train_transcriptome("training", "t.sam", "g.sam", "reads.fa", eng, annotation="annot.gff3")
+                    characterize.quantify_reads("expression", "t.sam", eng, "trans")
+                    characterize.detect_ir("ir_info", "annot.gff3", "g.sam", "t.sam", eng)
+
+The five functions of `training` are the modes of ``python -m nanosim_amd.read_analysis``, which only parses their arguments.
 Below them: chim_select (what chimeric_reads and quantification share), sam_text (the one loop over SAM text), _abi (marshalling)."""
 from __future__ import annotations
 
-from . import (_abi, sam_text, errors, qualities, homopolymers, sam_pairs, mixfit, lengths, chim_select, quantification, chimeric_reads,
-               ir_model, maf_besthit, bam, calmd)
+from . import (_abi, sam_text, sam_table, errors, qualities, homopolymers, sam_pairs, mixfit, lengths, chim_select, quantification,
+               chimeric_reads, ir_model, maf_besthit, bam, calmd, training)
 
-for _module in (_abi, sam_text, errors, qualities, homopolymers, sam_pairs, mixfit, lengths, chim_select, quantification, chimeric_reads,
-                ir_model, maf_besthit, bam, calmd):             # the underscore names too: tests and scripts use _pack, _qual_call, _strip_chr, ...
+for _module in (_abi, sam_text, sam_table, errors, qualities, homopolymers, sam_pairs, mixfit, lengths, chim_select, quantification,
+                chimeric_reads, ir_model, maf_besthit, bam, calmd, training):             # the underscore names too: tests and scripts use _pack, _qual_call, _strip_chr, ...
     globals().update((k, v) for k, v in vars(_module).items() if not k.startswith("__"))

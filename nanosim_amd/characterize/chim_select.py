@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 from ._abi import _pack, arr, check_bad, ptr
+from .sam_table import SamTable
 from .sam_text import no_sq_line, sam_lines
 
 
@@ -54,6 +55,8 @@ def chimeric_records(path: str):
     `*`), header = the `@` lines as they stand.  ValueError where the reference stops or misbehaves: a primary record without NM:i (its
     get_tag raises outside the try, G:279), an SA entry without six fields (G:298), a reference name — of a record or of an SA entry —
     without an @SQ line, a supplementary or secondary record in front of the first primary (a NameError at G:400), no primary at all."""
+    if isinstance(path, SamTable):
+        return path.chimeric_records()
     refs, records, unaligned, header = [], [], [], []
     seen_primary = False
     for line, fld in sam_lines(path, 11, refs, header, lines=True):

@@ -46,7 +46,8 @@ def format_chimeric_info(n_gaps: int, num_aligned: int, beta=None) -> str:
     return text
 
 
-def chimeric(prefix: str, path: str, eng, species=None, abundance=None, primary_sam: bool = True, pickles=None, quantify=None, normalize: bool = True):
+def chimeric(prefix: str, path: str, eng, species=None, abundance=None, primary_sam: bool = True, pickles=None, quantify=None, normalize: bool = True,
+             selected=None):
     """primary_and_unaligned_chimeric (G:220-478): writes <prefix>_chimeric_info, adds gap_length —
     log10(gap + 1), bandwidth 0.01 (G:465-469) — to <prefix>_kde.npz next to the keys it holds (and writes <prefix>_gap_length.pkl by
     write_kde's rule), and, with primary_sam, <prefix>_primary.sam: the header and the selected lines, unchanged, in the reference's
@@ -55,6 +56,8 @@ def chimeric(prefix: str, path: str, eng, species=None, abundance=None, primary_
     quantify: None — no quantification, as before; "meta" — the EM over the species (species: the mapping, by default
     species_of_reference of every @SQ name) writes <prefix>_quantification.tsv and its abundances stand behind the shrinkage rate
     (abundance= next to it is a ValueError); "trans" — the EM over the transcripts writes the file (normalize: EM_trans').
+    selected: a list that takes the indices of the selected records among chimeric_records' records (SamTable.mapped_rows names
+    their rows), in the order of <prefix>_primary.sam.
     -> (refs, records, unaligned_len, strandness): read_lengths' arguments, the records being the selected ones."""
     if quantify not in (None, "meta", "trans"):
         raise ValueError("quantify must be None, 'meta' or 'trans'")
@@ -66,6 +69,8 @@ def chimeric(prefix: str, path: str, eng, species=None, abundance=None, primary_
     if quantify == "meta" and species is None:
         species = {name: species_of_reference(name) for name, _ in refs}
     sel = select_chimeric(eng, refs, records, species)
+    if selected is not None:
+        selected.extend(int(i) for i in sel["selected"])
     if quantify is not None:
         items = quant_items(records, sel, refs, species if quantify == "meta" else None)
         res = em_quantify(eng, items, quant_targets(refs, quantify, species), quantify, normalize)

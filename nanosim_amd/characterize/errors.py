@@ -16,6 +16,7 @@ import ctypes as C
 import numpy as np
 
 from ._abi import PackedPairs, _pack, _pack_pairs, write_text
+from .sam_table import SamTable
 from .sam_text import cs_of, sam_lines
 
 DICT_MAX = 1000                      # add_dict ignores larger values (B:15-16)
@@ -32,6 +33,8 @@ class NsCsHist(C.Structure):
 
 def cs_from_sam(path: str):
     """the cs string of every alignment of a SAM text file: the cs:Z tag, else from CIGAR + MD:Z (B:320-324)"""
+    if isinstance(path, SamTable):
+        return path.cs_from_sam()
     return [cs_of(fld) for fld in sam_lines(path, 11) if fld[5] != "*"]
 
 

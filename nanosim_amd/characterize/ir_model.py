@@ -16,6 +16,7 @@ import numpy as np
 
 from ..intron_retention import gff_features, parse_gff_attributes
 from ._abi import _pack, arr, ptr, write_text
+from .sam_table import SamTable
 from .sam_text import sam_lines
 
 
@@ -57,6 +58,8 @@ def ir_introns(gff_path: str) -> dict:
 
 def _mapped_records(path: str):
     """the fields of every record of a SAM text file that is not unmapped, in file order"""
+    if isinstance(path, SamTable):
+        return iter(path.mapped_records())
     return sam_lines(path, 6, drop=0x4)
 
 

@@ -18,6 +18,7 @@ import numpy as np
 
 from ._abi import _pack, arr, check_bad, ptr, write_text
 from .errors import s_line_pairs
+from .sam_table import SamTable
 from .sam_text import no_sq_line, sam_lines
 
 
@@ -39,6 +40,8 @@ def length_records(path: str):
     """(refs, records) of a SAM text file: refs = [(SN, LN)] of its @SQ lines, records = [(qname, flag, rname, pos, cigar)] of every
     record whose CIGAR is not `*`, in file order — the reference's `<prefix>_primary` file (A:127-134) as SAM text.  A record on a
     reference without an @SQ line raises ValueError (the reference stops with a KeyError, A:138, 156)."""
+    if isinstance(path, SamTable):
+        return path.length_records()
     refs, records = [], []
     for fld in sam_lines(path, 6, refs):
         if fld[5] != "*":
@@ -55,6 +58,8 @@ def primary_and_unaligned(path: str):
     (G:163-187): refs and records as length_records gives them, of the primary records (FLAG without 0x4, 0x100 and 0x800);
     unaligned_len: int64 array of len(SEQ), 0 for `*`, of the 0x4 records (query_length); strandness = records whose FLAG is 0 over the
     primary records.  No primary record raises ValueError (the reference divides by zero)."""
+    if isinstance(path, SamTable):
+        return path.primary_and_unaligned()
     refs, records, unaligned, pos_strand = [], [], [], 0
     for fld in sam_lines(path, 11, refs):
         flag = int(fld[1])

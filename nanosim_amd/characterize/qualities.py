@@ -15,6 +15,7 @@ import re
 import numpy as np
 
 from ._abi import _pack, write_text
+from .sam_table import SamTable
 from .sam_text import cs_of, sam_lines
 
 
@@ -41,6 +42,8 @@ def quals_from_sam(path: str, primary_only: bool = True):
     primary_only, without 0x800: what get_primary_sam keeps) — the cs:Z tag, else from CIGAR + MD:Z; head / tail: the leading / trailing
     soft clip (query_alignment_start, len - query_alignment_end; hard clips are not in QUAL).  unmapped: the QUAL strings of the flag 0x4
     records (src/get_primary_sam.py:172-175; a missing QUAL is skipped there, and is a ValueError on an aligned record)."""
+    if isinstance(path, SamTable):
+        return path.quals_from_sam(primary_only)
     aligned, unmapped = [], []
     drop = 0x100 | 0x800 if primary_only else 0x100
     for fld in sam_lines(path, 11):

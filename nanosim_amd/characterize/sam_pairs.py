@@ -15,6 +15,7 @@ import numpy as np
 
 from ._abi import PackedPairs, _pack, check_bad, ptr, write_text
 from .homopolymers import _hp_count, write_hp_files
+from .sam_table import SamTable
 from .sam_text import sam_lines, sam_tag
 
 
@@ -30,6 +31,8 @@ SAM_ALN_DTYPE = np.dtype([("head", "<u4"), ("tail", "<u4"), ("ref_len", "<u4"), 
 def sam_records(path: str):
     """[(qname, flag, rname, pos, cigar, md, seq)] of a SAM text file: the records pairwise2maf keeps — FLAG exactly 0 or 16 (P:46-51) —
     in file order.  A kept record without MD:Z, or with `H` in its CIGAR (the reference's int() stops there, P:59-67), raises ValueError."""
+    if isinstance(path, SamTable):
+        return path.sam_records()
     out = []
     for fld in sam_lines(path, 11):
         if fld[1] not in ("0", "16"):

@@ -2184,6 +2184,7 @@ struct __attribute__((visibility("hidden"))) TrainState {
     PinBuf bam_text, bam_line_off;                       // the result of the last ns_bam_to_sam, page-locked
     std::vector<uint64_t> bam_rec_off, bam_flt_at; std::vector<uint32_t> bam_flt_first; std::vector<uint8_t> bam_slots;   // ... and its host-side lists
     PinBuf calmd_md, calmd_md_off, calmd_cs, calmd_cs_off;  // the result of the last ns_calmd, page-locked
+    std::vector<ns_sam_row> sam_rows; std::vector<ns_sam_span> sam_header;   // the result of the last ns_sam_index
 };
 
 struct ns_ctx {

@@ -4,11 +4,11 @@
 // models (k_len_scan, k_len_flag, k_len_reduce), the split-alignment choice of chimeric reads (k_chim_scan, k_chim_select), the EM of
 // the abundance quantification (k_em_estep, k_em_accum, k_em_stop), the Markov counts of the intron-retention model (k_ir_walk), and the
 // best hit per read of a MAF file (k_maf_*), the SAM text of BAM records (k_bam_*), and the MD and cs text of alignments from the
-// reference genome (k_calmd_*).  The
+// reference genome (k_calmd_*), and the index of a SAM text (k_sam_sep_count, k_sam_sep_write, k_sam_tags, k_sam_rows).  The
 // walks they run are ns_cs_hist.h, ns_qual_hist.h, ns_hp_hist.h, ns_sam_pairs.h, ns_mixfit.h, ns_read_len.h, ns_chimeric.h, ns_em.h,
-// ns_ir_train.h, ns_maf_best.h, ns_bam.h and ns_calmd.h, which also compile for the host; the host side of the calls
+// ns_ir_train.h, ns_maf_best.h, ns_bam.h, ns_calmd.h and ns_sam_index.h, which also compile for the host; the host side of the calls
 // (ns_cs_histograms / ns_maf_histograms, ns_qual_histograms, ns_hp_histograms / ns_hp_histograms_sam, ns_sam_pairs_build, ns_mixture_fit,
-// ns_read_lengths, ns_cigar_spans / ns_chimeric_select, ns_em_quantify, ns_ir_train, ns_maf_besthit, ns_bam_to_sam, ns_calmd) is at the end of nanosim_amd.hip.  Nothing here uses GenArgs or the simulation.
+// ns_read_lengths, ns_cigar_spans / ns_chimeric_select, ns_em_quantify, ns_ir_train, ns_maf_besthit, ns_bam_to_sam, ns_calmd, ns_sam_index) is ns_train_calls.h.  Nothing here uses GenArgs or the simulation.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,6 +25,7 @@
 #include "ns_maf_best.h"
 #include "ns_bam.h"
 #include "ns_calmd.h"
+#include "ns_sam_index.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // k_cs_hist: the counting loop of the characterisation stage (ns_cs_hist.h; src/besthit_to_histogram.py:316-365), one alignment per
@@ -714,6 +715,133 @@ __global__ void __launch_bounds__(256) k_maf_names(const uint8_t *__restrict__ t
     CsBytes t(text), nb(names);
     const uint64_t lo = names_off[i], n = names_off[i + 1u] - lo;
     found[i] = n <= 0xffffffffull && maf_find(t, lines, T, nb, lo, (uint32_t)n) ? 1u : 0u;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_sam_sep_count, k_sam_sep_write, k_sam_tags, k_sam_rows: the index of a SAM text (ns_sam_index.h), from the bytes of the file.
+// SEP_COUNT / SEP_WRITE: a workgroup looks at SAM_SPAN consecutive bytes in SAM_LOADS loads; in load i lane t of the workgroup reads the
+// 16 bytes at 4096 i + 16 t of the span, so that a wavefront's load instruction covers 1 KiB of consecutive text.  COUNT sums the '\n',
+// the '\t' and the odd bytes of the span.  Behind the exclusive scans of the workgroups' two counts, WRITE repeats the masks and ranks
+// every separator in the order of the TEXT, which is (load, lane, byte) and not (lane, byte): an inclusive scan over the wavefront per
+// load, the wavefronts' totals per load in LDS, and a walk over the 16 totals.  The two counts travel packed in one word (16 bits each:
+// a span has at most 16384 of either).  A '\n' writes the start of the line behind it with its tab rank and whether that line is a
+// header line; a '\t' writes its position and its line (the number of '\n' in front of it).  Entry 0 and, behind a last line without
+// '\n', the closing entry are thread 0's.
+// TAGS, one tab per thread: sam_tag_offer, one atomicMax.  ROWS, one line per thread, in the NEXT kernel (the slots are settled by the
+// kernel boundary) and behind the exclusive scan of the header flags: a record goes to row l - (headers in front of it), a header line
+// to the header list.  small[]: SAMI_ODD, SAMI_CS, SAMI_MD (records with the tag), SAMI_LONG (lines of 2^32 bytes or more).
+// ---------------------------------------------------------------------------------------------------------
+enum { SAMI_ODD = 0, SAMI_CS = 1, SAMI_MD = 2, SAMI_LONG = 3, SAMI_WORDS = 4 };
+static_assert(SAM_SPAN == 256u * SAM_CHUNK * SAM_LOADS && SAM_SPAN <= 0xffffu, "a workgroup of the separator kernels is 256 threads; a count fits 16 bits");
+struct SamDevOps {
+    __device__ __forceinline__ void max32(uint32_t *w, uint32_t v) const { atomicMax(w, v); }
+};
+// where chunk (load, thread) of this workgroup begins in the text, and its masks (none beyond the text)
+__device__ __forceinline__ uint64_t sam_chunk_at(uint32_t load) {
+    return (uint64_t)blockIdx.x * SAM_SPAN + (uint64_t)load * (256u * SAM_CHUNK) + (uint64_t)threadIdx.x * SAM_CHUNK;
+}
+__device__ __forceinline__ SamChunk sam_load_chunk(const uint8_t *__restrict__ text, uint64_t nbytes, uint32_t load) {
+    const uint64_t at = sam_chunk_at(load);
+    if (at >= nbytes) return SamChunk{0u, 0u, 0u};
+    // (16-byte aligned: the text begins an allocation; its last chunk ends inside the NS_WINDOW_PAD bytes behind it)
+    const uint4 v = *reinterpret_cast<const uint4 *>(text + at);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    return sam_chunk(w, nbytes - at >= SAM_CHUNK ? SAM_CHUNK : (uint32_t)(nbytes - at));
+}
+__global__ void __launch_bounds__(256) k_sam_sep_count(const uint8_t *__restrict__ text, uint64_t nbytes, unsigned long long *__restrict__ wg_nl,
+                                                       unsigned long long *__restrict__ wg_tab, unsigned long long *__restrict__ small) {
+    __shared__ unsigned long long part[4];
+    unsigned long long n = 0;                                      // three counts of at most 2^14 each, 20 bits apart
+    for (uint32_t i = 0; i < SAM_LOADS; ++i) {
+        const SamChunk c = sam_load_chunk(text, nbytes, i);
+        n += (unsigned long long)__popc(c.nl) | (unsigned long long)__popc(c.tab) << 20 | (unsigned long long)__popc(c.odd) << 40;
+    }
+    n = wave_sum(n);
+    if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        n = part[0] + part[1] + part[2] + part[3];
+        wg_nl[blockIdx.x] = n & 0xfffffull;
+        wg_tab[blockIdx.x] = (n >> 20) & 0xfffffull;
+        if (n >> 40) atomicAdd(&small[SAMI_ODD], n >> 40);
+    }
+}
+__global__ void __launch_bounds__(256) k_sam_sep_write(const uint8_t *__restrict__ text, uint64_t nbytes, const unsigned long long *__restrict__ wg_nl_base,
+                                                       const unsigned long long *__restrict__ wg_tab_base, uint64_t n_nl, uint64_t n_tabs, uint64_t n_lines,
+                                                       uint64_t *__restrict__ line_start, uint64_t *__restrict__ line_rank, uint32_t *__restrict__ hdr_flag,
+                                                       uint64_t *__restrict__ tab_pos, uint32_t *__restrict__ tab_line) {
+    __shared__ uint32_t part[SAM_LOADS][4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    SamChunk c[SAM_LOADS];
+    uint32_t excl[SAM_LOADS];                                      // packed: '\n' in the low half, '\t' in the high half
+    for (uint32_t i = 0; i < SAM_LOADS; ++i) {
+        c[i] = sam_load_chunk(text, nbytes, i);
+        const uint32_t mine = (uint32_t)__popc(c[i].nl) | (uint32_t)__popc(c[i].tab) << 16;
+        uint32_t incl = mine;                                      // the inclusive scan over the wavefront
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t u = (uint32_t)__shfl_up((int)incl, o, 64); if (lane >= (uint32_t)o) incl += u; }
+        if (lane == 63u) part[i][wave] = incl;
+        excl[i] = incl - mine;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        CsBytes t(text);
+        line_start[0] = 0; line_rank[0] = 0; hdr_flag[0] = sam_is_header(t, nbytes, 0) ? 1u : 0u;
+        if (n_lines > n_nl) { line_start[n_lines] = nbytes + 1u; line_rank[n_lines] = n_tabs; }     // (the last line has no '\n')
+    }
+    const uint64_t nl_base = wg_nl_base[blockIdx.x], tab_base = wg_tab_base[blockIdx.x];
+    uint32_t before = 0;                                           // the separators of the loads in front of load i
+    CsBytes t(text);
+    for (uint32_t i = 0; i < SAM_LOADS; ++i) {
+        uint32_t in_front = before + excl[i];
+        for (uint32_t w = 0; w < 4u; ++w) { if (w < wave) in_front += part[i][w]; before += part[i][w]; }
+        const uint64_t at = sam_chunk_at(i), nl_at = nl_base + (in_front & 0xffffu), tab_at = tab_base + (in_front >> 16);
+        for (uint32_t m = c[i].tab; m; m &= m - 1u) {
+            const uint32_t k = (uint32_t)__ffs((int)m) - 1u;
+            const uint64_t j = tab_at + (uint32_t)__popc(sam_below(c[i].tab, k));
+            if (j < n_tabs) { tab_pos[j] = at + k; tab_line[j] = (uint32_t)(nl_at + (uint32_t)__popc(sam_below(c[i].nl, k))); }     // (j < n_tabs: the count kernel saw the same bytes)
+        }
+        for (uint32_t m = c[i].nl; m; m &= m - 1u) {
+            const uint32_t k = (uint32_t)__ffs((int)m) - 1u;
+            const uint64_t j = nl_at + (uint32_t)__popc(sam_below(c[i].nl, k)) + 1u;                  // the line behind this '\n'
+            if (j <= n_nl) {
+                line_start[j] = at + k + 1u;
+                line_rank[j] = tab_at + (uint32_t)__popc(sam_below(c[i].tab, k));
+                hdr_flag[j] = sam_is_header(t, nbytes, at + k + 1u) ? 1u : 0u;
+            }
+        }
+    }
+}
+__global__ void __launch_bounds__(256) k_sam_tags(const uint8_t *__restrict__ text, SamLists L, const uint32_t *__restrict__ tab_line, uint64_t n_tabs,
+                                                  uint32_t *__restrict__ slots) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_tabs) return;
+    CsBytes t(text);
+    SamDevOps ops;
+    sam_tag_offer(t, L, i, tab_line[i], slots, ops);
+}
+__global__ void __launch_bounds__(256) k_sam_rows(const uint8_t *__restrict__ text, SamLists L, const uint32_t *__restrict__ slots,
+                                                  const uint32_t *__restrict__ hdr_rank, SamRow *__restrict__ rows, SamSpan *__restrict__ header,
+                                                  unsigned long long *__restrict__ small) {
+    const uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long n = 0;                                      // SAMI_CS, SAMI_MD, SAMI_LONG, 20 bits apart
+    if (l < L.n_lines) {
+        CsBytes t(text);
+        SamRow R; SamSpan H;
+        const uint32_t h = hdr_rank[l];
+        const int what = sam_row(t, L, l, slots, R, H);
+        if (what == SAM_LINE_RECORD) {
+            rows[l - h] = R;
+            n = (R.bits & SAM_HAS_CS ? 1ull : 0ull) | (R.bits & SAM_HAS_MD ? 1ull << 20 : 0ull);
+        } else if (what == SAM_LINE_HEADER) header[h] = H;
+        else n = 1ull << 40;
+    }
+    // (every lane of the wavefront comes here: the sum needs them all)
+    n = wave_sum(n);
+    if ((threadIdx.x & 63u) == 0 && n) {
+        if (n & 0xfffffull) atomicAdd(&small[SAMI_CS], n & 0xfffffull);
+        if ((n >> 20) & 0xfffffull) atomicAdd(&small[SAMI_MD], (n >> 20) & 0xfffffull);
+        if (n >> 40) atomicAdd(&small[SAMI_LONG], n >> 40);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -786,6 +786,67 @@ int ns_maf_besthit(ns_ctx *ctx, const uint8_t *text, uint64_t nbytes, const uint
     return NS_OK;
 }
 
+// the index of a SAM text (include/nanosim_amd.h: ns_sam_index_result; ns_sam_index.h).  The host waits once inside the call, for the
+// numbers of '\n' and '\t' bytes, which size everything behind them.  Whether the text ends in '\n' — the one thing the number of lines
+// needs beyond the count — the host reads from its own copy.
+int ns_sam_index(ns_ctx *ctx, const uint8_t *text, uint64_t nbytes, ns_sam_index_result *out) {
+    if (!ctx) return NS_EINVAL;
+    if (!out) return fail(ctx, NS_EINVAL, "ns_sam_index: null argument");
+    static_assert(sizeof(SamRow) == sizeof(ns_sam_row) && sizeof(SamSpan) == sizeof(ns_sam_span), "ns_sam_index.h mirrors the ABI structs");
+    TrainState &keep = ctx->train;
+    keep.sam_rows.clear(); keep.sam_header.clear();
+    out->rows = nullptr; out->header = nullptr;
+    out->n_records = out->n_header = out->n_odd = out->n_cs = out->n_md = 0; out->ms_kernel = 0;
+    if (nbytes && !text) return fail(ctx, NS_EINVAL, "ns_sam_index: null argument");
+    if (!nbytes) return NS_OK;
+    const uint64_t n_wg = (nbytes + SAM_SPAN - 1u) / SAM_SPAN;
+    if (n_wg >= (1ull << 31)) return fail(ctx, NS_EINVAL, "ns_sam_index: 2^45 bytes of text or more");
+    HIPCHK(hipSetDevice(ctx->device));
+    unsigned long long small[SAMI_WORDS] = {0ull, 0ull, 0ull, 0ull};
+    CallScratch s(ctx, "ns_sam_index");
+    const uint8_t *d_text = s.filled(text, (size_t)nbytes, NS_WINDOW_PAD);
+    unsigned long long *d_wg_nl = s.zeroed<unsigned long long>((size_t)n_wg + 1), *d_wg_tab = s.zeroed<unsigned long long>((size_t)n_wg + 1);
+    unsigned long long *d_nl_base = s.alloc<unsigned long long>((size_t)n_wg + 1), *d_tab_base = s.alloc<unsigned long long>((size_t)n_wg + 1);
+    unsigned long long *d_small = s.filled(small, SAMI_WORDS);
+    if (int rc = s.upload()) return rc;
+    if (int rc = begin(s)) return rc;
+    // ---- the separators ----
+    launch(s, k_sam_sep_count, dim3((unsigned)n_wg), dim3(256), d_text, nbytes, d_wg_nl, d_wg_tab, d_small);
+    scan(s, d_wg_nl, d_nl_base, (size_t)n_wg + 1);
+    scan(s, d_wg_tab, d_tab_base, (size_t)n_wg + 1);
+    unsigned long long n_nl = 0, n_tabs = 0;
+    if (int rc = fetch(s, {{&n_nl, d_nl_base + n_wg, 8}, {&n_tabs, d_tab_base + n_wg, 8}})) return rc;
+    const uint64_t n_lines = n_nl + (text[nbytes - 1u] == '\n' ? 0u : 1u);
+    if (n_lines >= (1ull << 32)) return fail(ctx, NS_EINVAL, "ns_sam_index: 2^32 lines or more");
+    uint64_t *d_line_start = s.alloc<uint64_t>((size_t)n_lines + 1), *d_line_rank = s.alloc<uint64_t>((size_t)n_lines + 1);
+    uint32_t *d_hdr_flag = s.zeroed<uint32_t>((size_t)n_lines + 1), *d_hdr_rank = s.alloc<uint32_t>((size_t)n_lines + 1);
+    uint64_t *d_tab_pos = s.alloc<uint64_t>((size_t)n_tabs + 1);
+    uint32_t *d_tab_line = s.alloc<uint32_t>((size_t)n_tabs + 1), *d_slots = s.zeroed<uint32_t>((size_t)n_lines * SAM_TAGS);
+    SamRow *d_rows = s.alloc<SamRow>((size_t)n_lines);
+    SamSpan *d_header = s.alloc<SamSpan>((size_t)n_lines);
+    if (int rc = s.upload()) return rc;
+    // ---- the lists, the tags, the rows ----
+    const SamLists L{d_line_start, d_line_rank, d_tab_pos, n_lines, nbytes};
+    launch(s, k_sam_sep_write, dim3((unsigned)n_wg), dim3(256), d_text, nbytes, d_nl_base, d_tab_base, n_nl, n_tabs, n_lines, d_line_start, d_line_rank,
+           d_hdr_flag, d_tab_pos, d_tab_line);
+    scan(s, d_hdr_flag, d_hdr_rank, (size_t)n_lines + 1);
+    if (n_tabs) per_thread(s, k_sam_tags, n_tabs, d_text, L, d_tab_line, n_tabs, d_slots);
+    per_thread(s, k_sam_rows, n_lines, d_text, L, d_slots, d_hdr_rank, d_rows, d_header, d_small);
+    uint32_t n_header = 0;
+    if (int rc = finish(s, {{small, d_small, sizeof small}, {&n_header, d_hdr_rank + n_lines, 4}}, &out->ms_kernel)) return rc;
+    if (small[SAMI_LONG]) return fail(ctx, NS_EINVAL, "ns_sam_index: a line of 2^32 bytes or more");
+    if (n_header > n_lines) return fail(ctx, NS_EHIP, "ns_sam_index: the header lines and their ranks disagree");
+    const uint64_t n_records = n_lines - n_header;
+    try { keep.sam_rows.resize(n_records); keep.sam_header.resize(n_header); }
+    catch (const std::bad_alloc &) { return fail(ctx, NS_ENOMEM, "ns_sam_index: no host memory for the result"); }
+    if (int rc = fetch(s, {{keep.sam_rows.data(), d_rows, (size_t)n_records * sizeof(SamRow)},
+                          {keep.sam_header.data(), d_header, (size_t)n_header * sizeof(SamSpan)}})) return rc;
+    out->rows = keep.sam_rows.data(); out->header = keep.sam_header.data();
+    out->n_records = n_records; out->n_header = n_header;
+    out->n_odd = small[SAMI_ODD]; out->n_cs = small[SAMI_CS]; out->n_md = small[SAMI_MD];
+    return NS_OK;
+}
+
 // BAM records to SAM text (include/nanosim_amd.h: ns_bam_result; ns_bam.h).  The host hops the block_size chain (one 4-byte read per
 // record) and waits three times inside the call: for the bad-record check and the number of floats, for the places of the floats when
 // there are any (their text is the C library's), and for the size of the text, which the page-locked result is grown to.

@@ -27,7 +27,7 @@ EXPORTS = ("ns_abi_version", "ns_create", "ns_destroy", "ns_last_error", "ns_set
            "ns_sink_close", "ns_io_counters", "ns_cs_histograms", "ns_generate_step", "ns_step_context", "ns_maf_histograms",
            "ns_qual_histograms", "ns_hp_histograms", "ns_sam_pairs_build", "ns_hp_histograms_sam", "ns_mixture_fit", "ns_read_lengths",
            "ns_cigar_spans", "ns_chimeric_select", "ns_em_quantify", "ns_ir_train", "ns_maf_besthit", "ns_bam_to_sam",
-           "ns_calmd")
+           "ns_calmd", "ns_sam_index")
 
 
 class NsIoStats(C.Structure):
@@ -132,6 +132,8 @@ def load_library(path: str = LIB_PATH):
     L.ns_bam_to_sam.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.ns_calmd.restype = C.c_int
     L.ns_calmd.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.c_uint32, C.c_void_p]
+    L.ns_sam_index.restype = C.c_int
+    L.ns_sam_index.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     L.ns_generate_step.restype = C.c_int
     L.ns_generate_step.argtypes = [C.c_void_p, C.POINTER(NsParams), C.POINTER(NsParams), C.POINTER(NsBatchInfo)]
     L.ns_step_context.restype = C.c_int
