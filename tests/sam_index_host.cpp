@@ -3,7 +3,8 @@
 // the two lists, the tag choice, the rows and the host module around the call are checked without a GPU.  The chunks are visited in the
 // order of the text, span by span as the kernels cut it; the maximum — an atomic on the device — is a plain read and write, and the tabs
 // offer in the order sam_host_set_order chooses: 0 text order, 1 reversed (the outcome must not depend on it).  The text is copied to a
-// buffer of exactly its size: a read beyond it is an error under -fsanitize=address.
+// buffer of exactly its size: a read beyond it is an error under -fsanitize=address.  The bytes of the last chunk that lie behind the
+// text are filled with '\n', '\t', '\r' and 0xff in turn, not with zeros: on the device they are whatever the allocation held before.
 // Built by tests/test_sam_index.py with g++ into tests/_tmp/: as a shared library, and, with -DSAM_INDEX_MAIN, as a stand-alone program
 // for -fsanitize=address,undefined that takes a SAM file and prints `n_records n_header n_odd n_cs n_md` and a checksum of the rows.
 #include <stdint.h>
@@ -36,10 +37,16 @@ extern "C" int sam_host_index(void *, const uint8_t *text_in, uint64_t nbytes, n
     // the separators: chunk by chunk in the order of the text (a span's chunks (load, lane) are consecutive)
     std::vector<uint64_t> line_start{0}, line_rank{0}, tab_pos;
     std::vector<uint32_t> tab_line;
+    static const uint8_t dirty[4] = {'\n', '\t', '\r', 0xff};
+    static uint32_t g_turn = 0;
+    uint32_t turn = g_turn++;                                      // (every call begins with another of the four)
     for (uint64_t at = 0; at < nbytes; at += SAM_CHUNK) {
         const uint32_t valid = nbytes - at >= SAM_CHUNK ? SAM_CHUNK : (uint32_t)(nbytes - at);
-        uint32_t w[4] = {0u, 0u, 0u, 0u};
-        memcpy(w, text + at, valid);
+        uint8_t bytes[SAM_CHUNK];
+        uint32_t w[4];
+        memcpy(bytes, text + at, valid);
+        for (uint32_t k = valid; k < SAM_CHUNK; ++k) bytes[k] = dirty[turn++ & 3u];     // what the device may find there: only sam_chunk's `keep` hides it
+        memcpy(w, bytes, sizeof w);
         const SamChunk c = sam_chunk(w, valid);
         out->n_odd += (uint64_t)__builtin_popcount(c.odd);
         const uint64_t nl_at = line_start.size() - 1u, tab_at = tab_pos.size();

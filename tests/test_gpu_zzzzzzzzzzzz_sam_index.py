@@ -1,6 +1,8 @@
 """GPU parity of the index of a SAM text ("SAM text: one indexed pass and the CLI"): ns_sam_index (the k_sam_sep_*, k_sam_tags
 and k_sam_rows kernels of csrc/ns_train.h) against the restatement of tests/test_sam_index.py on the project's texts, on the hand-written
-text and at the borders of the spans; characterize.SamTable's readers against the path readers, returns and ValueErrors; twice on one
+text and at the borders of the spans; near misses of the four prefixes, records that end with their FLAG or POS, texts of nothing but
+separators at the sizes of a chunk, a wavefront's load, a load and a span, two separators at every pair of seams (what the ranking of
+k_sam_sep_count / k_sam_sep_write, which has no host build, is decided by); characterize.SamTable's readers against the path readers, returns and ValueErrors; twice on one
 engine and between other training calls; and a synthetic text of 20 000 records against the restatement and the path readers.  Every
 malformed input here is one the call answers with a status or a bit."""
 import os
@@ -11,8 +13,8 @@ import pytest
 from nanosim_amd import characterize
 from nanosim_amd import engine as EN
 from tests import test_besthit
-from tests.test_sam_index import (HAND, as_bytes, check_boundaries, check_errors, check_readers, check_rows, check_same_outcome, check_texts, composed_texts,
-                                  restate)
+from tests.test_sam_index import (HAND, as_bytes, check_arrays, check_boundaries, check_dense, check_errors, check_near_prefixes, check_readers, check_rows,
+                                  check_same_outcome, check_seam_pairs, check_short_records, check_tag_dense, check_texts, composed_texts, restate)
 
 pytestmark = pytest.mark.gpu
 SPAN = 16384                        # SAM_SPAN (tests/test_sam_index.py checks the number against the header)
@@ -34,6 +36,44 @@ def test_gpu_rows_equal_the_restatement(eng):
 
 def test_gpu_sizes_and_separators_at_the_borders_of_the_spans(eng):
     check_boundaries(eng, SPAN)
+
+
+def test_gpu_a_near_miss_of_a_prefix_is_no_tag(eng, tmp_path):
+    check_near_prefixes(eng, tmp_path)
+
+
+def test_gpu_records_that_end_with_their_flag_or_their_pos(eng):
+    check_short_records(eng)
+
+
+def test_gpu_texts_of_nothing_but_separators(eng):
+    check_dense(eng, SPAN)
+    r = characterize.sam_index_call(eng, np.full(2 * SPAN + 1, 10, dtype=np.uint8))
+    assert int(r["raw"].n_records) == 2 * SPAN + 1
+    print("ms_kernel %.3f for %d bytes, all of them line ends" % (r["raw"].ms_kernel, 2 * SPAN + 1))
+
+
+def test_gpu_tag_dense_lines_at_every_chunk_offset(eng):
+    check_tag_dense(eng, SPAN)
+
+
+def test_gpu_two_separators_at_every_pair_of_seams(eng):
+    assert check_seam_pairs(eng, SPAN) == 1860
+
+
+def test_gpu_the_spare_bytes_behind_the_text_are_no_text(eng):
+    """the last chunk's load reaches into the 16 spare bytes behind the text, which no copy writes: a text that ends 1 .. 15 bytes into a
+    chunk, each indexed directly behind a call whose text was line ends up to and beyond that place, is one record of one field.  Best
+    effort: whether the allocator hands the second call the memory of the first is its own business, and nothing here asserts that it
+    did; the host build decides the same thing with bytes it fills in itself (tests/sam_index_host.cpp)."""
+    L = SPAN + 32
+    line_ends = np.full(L, 10, dtype=np.uint8)
+    assert int(characterize.sam_index_call(eng, line_ends)["raw"].n_records) == L
+    for k in range(1, 16):
+        assert int(characterize.sam_index_call(eng, line_ends)["raw"].n_records) == L
+        r = check_arrays(eng, b"x" * (L - k), "%d bytes behind %d line ends" % (L - k, L))
+        assert len(r["rows"]) == 1 and len(r["header"]) == 0 and int(r["raw"].n_odd) == 0
+        assert (int(r["rows"][0]["n_fields"]), int(r["rows"][0]["begin"]), int(r["rows"][0]["end"])) == (1, 0, L - k)
 
 
 def test_gpu_every_table_reader_equals_its_path_reader(eng, tmp_path):

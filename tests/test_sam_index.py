@@ -2,9 +2,13 @@
 choice and rows (nanosim_amd/csrc/ns_sam_index.h, compiled for the host with the tabs offering one after the other; on the GPU the
 k_sam_sep_*, k_sam_tags and k_sam_rows kernels of ns_train.h run it) against a restatement written out here — line.split("\\t"),
 sam_tag, digits-only numbers — and characterize.SamTable, whose seven readers have to return or raise what the path readers do.
+Behind the fixed texts: near misses of the four prefixes, records that end with FLAG or POS, texts of nothing but separators and two
+separators at every pair of seams ("What the mutation audit leaves", says which mutant or device-only line each decides).
 The check_* functions take an engine: tests/test_gpu_zzzzzzzzzzzz_sam_index.py runs them on the real one."""
 import ctypes as C
+import functools
 import gzip
+import itertools
 import json
 import os
 import re
@@ -94,6 +98,36 @@ def plain_number(s: str):
     return int(s) if re.fullmatch("[0-9]{1,10}", s) and int(s) < 1 << 32 else None
 
 
+@functools.lru_cache(maxsize=1 << 16)
+def restate_line(line: str):
+    """what a row says of a record line apart from where the line stands: the tuple behind begin and end.  (Kept per distinct line: a
+    text of 30 000 equal lines is restated once.)"""
+    fld = line.split("\t")
+    ends, e = [], -1
+    for f in fld:
+        e += len(f) + 1
+        ends.append(e)
+    starts = [0] + [x + 1 for x in ends[:-1]]
+    field_end = tuple(ends[k] if k < len(fld) else len(line) for k in range(11))
+    bits = 0
+    flag = plain_number(fld[1]) if len(fld) > 1 else None
+    pos = plain_number(fld[3]) if len(fld) > 3 else None
+    bits |= (1 if flag is None else 0) | (2 if pos is None else 0)
+    tag_at, tag_len, nm = [0] * 4, [0] * 4, 0
+    for g, prefix in enumerate(PREFIXES):
+        value = characterize.sam_tag(fld, prefix)
+        if value is None:
+            continue
+        k = max(i for i in range(11, len(fld)) if fld[i].startswith(prefix))
+        assert fld[k][5:] == value
+        tag_at[g], tag_len[g] = starts[k] + 5, len(value)
+        bits |= 16 << g
+        if g == 2:
+            nm = plain_number(value)
+            bits |= 4 if nm is None else 0
+    return (len(fld), bits, field_end, flag or 0, pos or 0, nm or 0, tuple(tag_at), tuple(tag_len))
+
+
 def restate(text: str):
     """(rows, header) of a text by the rules written out: tuples in the order of SAM_ROW_DTYPE / SAM_SPAN_DTYPE"""
     rows, header, at = [], [], 0
@@ -106,31 +140,25 @@ def restate(text: str):
         if line[:1] == "@":
             header.append((begin, end))
             continue
-        fld = line.split("\t")
-        ends, e = [], -1
-        for f in fld:
-            e += len(f) + 1
-            ends.append(e)
-        starts = [0] + [x + 1 for x in ends[:-1]]
-        field_end = [ends[k] if k < len(fld) else len(line) for k in range(11)]
-        bits = 0
-        flag = plain_number(fld[1]) if len(fld) > 1 else None
-        pos = plain_number(fld[3]) if len(fld) > 3 else None
-        bits |= (1 if flag is None else 0) | (2 if pos is None else 0)
-        tag_at, tag_len, nm = [0] * 4, [0] * 4, 0
-        for g, prefix in enumerate(PREFIXES):
-            value = characterize.sam_tag(fld, prefix)
-            if value is None:
-                continue
-            k = max(i for i in range(11, len(fld)) if fld[i].startswith(prefix))
-            assert fld[k][5:] == value
-            tag_at[g], tag_len[g] = starts[k] + 5, len(value)
-            bits |= 16 << g
-            if g == 2:
-                nm = plain_number(value)
-                bits |= 4 if nm is None else 0
-        rows.append((begin, end, len(fld), bits, field_end, flag or 0, pos or 0, nm or 0, tag_at, tag_len))
+        n_fields, bits, field_end, flag, pos, nm, tag_at, tag_len = (restate_line if len(line) < 256 else restate_line.__wrapped__)(line)
+        rows.append((begin, end, n_fields, bits, list(field_end), flag, pos, nm, list(tag_at), list(tag_len)))
     return rows, header
+
+
+def restate_arrays(text):
+    """restate() as the arrays the call gives: (SAM_ROW_DTYPE rows, SAM_SPAN_DTYPE header spans, the number of odd bytes).  `text`: a str of
+    ASCII, or bytes, which are restated byte for byte (latin-1)"""
+    raw = text.encode("ascii") if isinstance(text, str) else bytes(text)
+    rows, header = restate(raw.decode("latin-1"))
+    want = np.zeros(len(rows), dtype=characterize.SAM_ROW_DTYPE)
+    for k, name in enumerate(characterize.SAM_ROW_DTYPE.names):
+        if rows:
+            want[name] = np.array([x[k] for x in rows], dtype=np.uint64)
+    spans = np.zeros(len(header), dtype=characterize.SAM_SPAN_DTYPE)
+    if header:
+        spans["begin"], spans["end"] = np.array(header, dtype=np.uint64).T
+    b = np.frombuffer(raw, dtype=np.uint8)
+    return want, spans, int(np.count_nonzero((b == 13) | (b >= 128)))
 
 
 def as_bytes(text) -> np.ndarray:
@@ -225,6 +253,169 @@ def check_boundaries(eng, S: int):
     # the empty text, header lines only, a single byte of each kind
     for text in ("", "@HD\tVN:1.6\n@SQ\tSN:chr1\tLN:5\n", "@HD", "\n", "\t", "x", "\n\n", "\t\n\t", "@\n@"):
         check_rows(eng, text)
+
+
+# ---- near misses, short records, dense separators ------------------------------------------------------------------------------------
+def check_arrays(eng, text, what=""):
+    """the call's rows, header spans and counts equal the restatement, compared as arrays (check_rows walks tuples: too slow for
+    30 000 rows); `text`: ASCII str or bytes; -> the call's dict"""
+    r = characterize.sam_index_call(eng, as_bytes(text))
+    want, spans, n_odd = restate_arrays(text)
+    assert (int(r["raw"].n_records), int(r["raw"].n_header)) == (len(want), len(spans)) == (len(r["rows"]), len(r["header"])), what
+    if r["rows"].tobytes() != want.tobytes():
+        for name in characterize.SAM_ROW_DTYPE.names:
+            differ = r["rows"][name] != want[name]
+            bad = np.flatnonzero(differ.reshape(len(want), -1).any(axis=1))
+            assert not len(bad), (what, name, int(bad[0]), len(bad), r["rows"][name][bad[0]].tolist(), want[name][bad[0]].tolist())
+        assert False, (what, "rows differ outside their fields")
+    bad = np.flatnonzero((r["header"]["begin"] != spans["begin"]) | (r["header"]["end"] != spans["end"]))
+    assert not len(bad), (what, "header", int(bad[0]), r["header"][bad[0]].tolist(), spans[bad[0]].tolist())
+    assert int(r["raw"].n_odd) == n_odd, (what, int(r["raw"].n_odd), n_odd)
+    assert (int(r["raw"].n_cs), int(r["raw"].n_md)) == (int(np.count_nonzero(want["bits"] & 16)), int(np.count_nonzero(want["bits"] & 32))), what
+    return r
+
+
+REAL_TAGS = ("cs:Z::4", "MD:Z:4", "NM:i:1", "SA:Z:chr1,5,+,4M,60,0;")
+NEIGHBOURS = ("cm:i:", "s1:i:", "s2:i:", "ms:i:", "nn:i:", "MC:Z:", "MM:Z:", "ML:B:", "NH:i:", "XA:Z:", "CS:Z:", "cs:z:", "md:Z:", "nm:i:", "sa:Z:")
+
+
+def near_prefixes():
+    """five-byte field starts next to the four prefixes: one letter, the type or one colon off (the four prefixes themselves are among
+    them), and the tags that stand next to them in real files"""
+    grid = [c0 + c1 + s2 + c3 + s4 for c0 in "cMNSx" for c1 in "sDMAx" for c3 in "Zix" for s2, s4 in ((":", ":"), (";", ":"), (":", ";"))]
+    return grid + list(NEIGHBOURS)
+
+
+def near_prefix_text() -> str:
+    """every candidate, with one value byte, three times: alone on an unmapped record (so that the readers go on to the end of the
+    text), behind the four real tags of a mapped record, in front of them"""
+    out = ["@SQ\tSN:chr1\tLN:1000\n"]
+    for k, c in enumerate(near_prefixes()):
+        out.append(rec("alone%d" % k, "4", c + "7", rname="*", pos="0", cigar="*"))
+        out.append(rec("behind%d" % k, "0", *REAL_TAGS, c + "7"))
+        out.append(rec("front%d" % k, "16", c + "7", *REAL_TAGS))
+    return "".join(out)
+
+
+def check_near_prefixes(eng, tmp_path):
+    """a field that only looks like a tag is none: the rows equal the restatement, a near miss sets no HAS bit and moves no real tag's
+    span, and the table readers do on this text what the path readers do"""
+    cands, text = near_prefixes(), near_prefix_text()
+    assert len(cands) == 225 + 15 and len(set(cands)) == 239          # (MM:Z: is in the grid and among the names)
+    assert [c for c in cands if c in PREFIXES] == ["cs:Z:", "MD:Z:", "NM:i:", "SA:Z:"]
+    r = check_arrays(eng, text, "near prefixes")
+    rows = r["rows"]
+    assert len(rows) == 3 * len(cands)
+    begin, tag_at, tag_len = rows["begin"].tolist(), rows["tag_at"].tolist(), rows["tag_len"].tolist()
+    for k, c in enumerate(cands):
+        if c in PREFIXES:
+            continue                                        # (a true prefix: the restatement has said what it does)
+        alone, behind, front = 3 * k, 3 * k + 1, 3 * k + 2
+        assert int(rows["bits"][alone]) >> 4 == 0 and tag_at[alone] == tag_len[alone] == [0] * 4 and int(rows["nm"][alone]) == 0, c
+        for j in (behind, front):
+            assert int(rows["bits"][j]) == 16 + 32 + 64 + 128 and int(rows["nm"][j]) == 1, (c, j)
+            assert [text[begin[j] + a:begin[j] + a + n] for a, n in zip(tag_at[j], tag_len[j])] == [t[5:] for t in REAL_TAGS], (c, j)
+    path = write_text(tmp_path, "near.sam", text)
+    table = characterize.SamTable(path, eng)
+    assert table.rows.tobytes() == rows.tobytes() and "".join(table) == text
+    seen = check_same_outcome(table, path)
+    assert len(seen) == len(test_sam_text.READERS) and all(v[0] == "returns" for v in seen.values()), {k: v[1:] for k, v in seen.items() if v[0] != "returns"}
+
+
+def short_lines():
+    """records of exactly 1 .. 5 fields: with plain FLAG and POS, with a FLAG or a POS that is not plain, of tabs only, and with FLAG
+    and POS both empty"""
+    whole = ["q", "16", "chr1", "7", "60"]
+    out = ["\t".join(whole[:n]) for n in (1, 2, 3, 4, 5)]
+    for bad in ("x", "-7", ""):
+        out += ["\t".join((whole[:1] + [bad] + whole[2:])[:n]) for n in (2, 3, 4, 5)]
+        out += ["\t".join((whole[:3] + [bad] + whole[4:])[:n]) for n in (4, 5)]
+    return out + ["\t", "\t\t", "\t\t\t", "\t\t\t\t", "q\t\tchr1\t\t60"]
+
+
+def check_short_records(eng):
+    """a record whose LAST field is FLAG or POS has that number; each short line in the middle of a text, as its last line without
+    '\\n', and all of them in one text"""
+    lines = short_lines()
+    assert {x.count("\t") + 1 for x in lines} == {1, 2, 3, 4, 5} and len(set(lines)) == len(lines)
+    for line in lines:
+        r = check_arrays(eng, rec("a") + line + "\n" + rec("b", "16", "NM:i:3"), repr(line))
+        assert int(r["rows"][1]["n_fields"]) == line.count("\t") + 1
+        r = check_arrays(eng, rec("a") + line, repr(line))
+        assert int(r["rows"][1]["end"]) == len(rec("a") + line)
+    check_arrays(eng, "\n".join(lines), "short lines")
+    r = check_arrays(eng, "\n".join(lines) + "\n", "short lines")
+    row = dict(zip(lines, r["rows"]))
+    say = lambda line: (int(row[line]["bits"]), int(row[line]["flag"]), int(row[line]["pos"]))
+    assert [say("\t".join(["q", "16", "chr1", "7", "60"][:n])) for n in (1, 2, 3, 4, 5)] == [(3, 0, 0), (2, 16, 0), (2, 16, 0), (0, 16, 7), (0, 16, 7)]
+    assert say("q\t-7") == (3, 0, 0) and say("q\t16\tchr1\t") == (2, 16, 0) and say("q\t\tchr1\t7") == (1, 0, 7) and say("\t\t\t") == (3, 0, 0)
+
+
+def dense_lengths(S: int):
+    """one lane's load is 16 bytes, a wavefront's 1 KiB, the workgroup's 4 KiB, the workgroup's span S; 2 S + 1: a third span of one byte"""
+    return (1, 15, 16, 17, 1023, 1024, 1025, 4095, 4096, 4097, S - 1, S, S + 1, 2 * S, 2 * S + 1)
+
+
+def dense_texts(n: int) -> dict:
+    cut = lambda unit: (unit * (n // len(unit) + 1))[:n]
+    return dict(nl=b"\n" * n, tab=b"\t" * n, tab_nl=cut(b"\t\n"), nl_tab=cut(b"\n\t"), cr=b"\r" * n, high=b"\xff" * n, headers=cut(b"@\n"), header_x=cut(b"@\nx\n"))
+
+
+def check_dense(eng, S: int):
+    """texts that are nothing but separators (or odd bytes, or header lines), at the sizes where the counting and ranking of
+    k_sam_sep_count / k_sam_sep_write change hands: the packed counts at their largest values"""
+    for n in dense_lengths(S):
+        got = {name: check_arrays(eng, text, "%s, %d bytes" % (name, n)) for name, text in dense_texts(n).items()}
+        count = lambda name: (len(got[name]["rows"]), len(got[name]["header"]), int(got[name]["raw"].n_odd))
+        assert count("nl") == (n, 0, 0) and count("tab") == (1, 0, 0) and count("cr") == count("high") == (1, 0, n)
+        assert count("tab_nl") == ((n + 1) // 2, 0, 0) and count("nl_tab") == (n // 2 + 1, 0, 0) and count("headers") == (0, (n + 1) // 2, 0)
+        assert count("header_x") == ((n + 1) // 4, (n + 3) // 4, 0)
+        assert int(got["tab"]["rows"]["n_fields"][0]) == n + 1 and np.all(got["nl"]["rows"]["n_fields"] == 1)
+        assert np.array_equal(got["nl"]["rows"]["begin"], np.arange(n, dtype=np.uint64))
+
+
+TAG_DENSE_LINE = "\t" * 11 + "\t".join(["cs:Z:a", "NM:i:7", "MD:Z:3", "SA:Z:x", "cs:Z:b", "NM:i:x"]) + "\n"
+
+
+def tag_dense_text(S: int, head: int) -> str:
+    """lines of eleven empty fields and six tags, two of them given twice, past 2 S, behind a header line of `head` bytes"""
+    return "@" + "x" * (head - 1) + "\n" + TAG_DENSE_LINE * (2 * S // len(TAG_DENSE_LINE) + 2)
+
+
+def check_tag_dense(eng, S: int):
+    """every line slides through every chunk offset: the last cs and the last NM, which is not plain, win on each"""
+    assert {(head + 1 + k * len(TAG_DENSE_LINE)) % 16 for head in range(1, 17) for k in range(16)} == set(range(16))
+    for head in range(1, 17):
+        text = tag_dense_text(S, head)
+        r = check_arrays(eng, text, "tag-dense text behind %d bytes" % head)
+        rows = r["rows"]
+        assert len(text) > 2 * S + 17 and len(rows) == text.count("\n") - 1 and len(r["header"]) == 1
+        assert np.all(rows["bits"] == 3 + 4 + 16 + 32 + 64 + 128) and np.all(rows["n_fields"] == 17) and np.all(rows["nm"] == 0)
+        at = lambda g: (rows["begin"] + rows["tag_at"][:, g]).astype(np.int64)
+        b = as_bytes(text)
+        assert np.all(rows["tag_len"] == 1) and bytes(b[at(0)]) == b"b" * len(rows) and bytes(b[at(2)]) == b"x" * len(rows)
+        assert bytes(b[at(1)]) == b"3" * len(rows) and np.all(b[at(0) - 6] == 9) and np.all(b[at(0) - 7] == ord("x"))
+
+
+def seam_positions(S: int):
+    """one in front of, at and one behind where a chunk, a wavefront's load, a load of the workgroup and a span begin, in a text of 2 S + 17 bytes"""
+    return sorted({c + d for c in (0, 16, 1024, 4096, 8192, 12288, S, S + 1024, S + 4096, 2 * S, 2 * S + 16) for d in (-1, 0, 1) if 0 <= c + d < 2 * S + 17})
+
+
+def check_seam_pairs(eng, S: int):
+    """two separators in a text of `x`, at every pair of seam positions and in every pair of kinds: where the order of the lanes and
+    the order of the text disagree (a tab at byte 4096 is load 1, lane 0; one at byte 16 is load 0, lane 1); -> the number of texts"""
+    P, n_texts = seam_positions(S), 0
+    assert len(P) == 31
+    text = bytearray(b"x" * (2 * S + 17))
+    for p, q in itertools.combinations(P, 2):
+        for a, b in itertools.product(b"\n\t", repeat=2):
+            text[p], text[q] = a, b
+            r = check_arrays(eng, bytes(text), "%r at %d, %r at %d" % (chr(a), p, chr(b), q))
+            assert len(r["rows"]) == 1 + (a == 10) + (b == 10) - (q == len(text) - 1 and b == 10)
+            n_texts += 1
+        text[p] = text[q] = ord("x")
+    return n_texts
 
 
 # ---- the readers -------------------------------------------------------------------------------------------------------------------------
@@ -413,6 +604,36 @@ def test_sizes_and_separators_at_the_borders_of_the_spans(host):
     check_boundaries(host, S)
 
 
+@pytest.mark.parametrize("order", [0, 1])
+def test_a_near_miss_of_a_prefix_is_no_tag_in_any_order_of_the_tabs(host, tmp_path, order):
+    host.order(order)
+    try:
+        check_near_prefixes(host, tmp_path)
+    finally:
+        host.order(0)
+
+
+def test_records_that_end_with_their_flag_or_their_pos(host):
+    check_short_records(host)
+
+
+def test_texts_of_nothing_but_separators(host):
+    check_dense(host, host.span)
+
+
+@pytest.mark.parametrize("order", [0, 1])
+def test_tag_dense_lines_at_every_chunk_offset_in_any_order_of_the_tabs(host, order):
+    host.order(order)
+    try:
+        check_tag_dense(host, host.span)
+    finally:
+        host.order(0)
+
+
+def test_two_separators_at_every_pair_of_seams(host):
+    assert check_seam_pairs(host, host.span) == 1860
+
+
 def test_every_table_reader_equals_its_path_reader(host, tmp_path):
     check_readers(host, tmp_path)
 
@@ -442,7 +663,9 @@ def test_host_code_is_clean_under_the_sanitizers(tmp_path):
     assert [int(v) for v in first.split()] == [len(rows), len(header), 0, sum(1 for x in rows if x[3] & 16), sum(1 for x in rows if x[3] & 32)]
     S = 16384
     edge = ["", "\n", "\t", "@", "x", "a\tcs:Z", "\t" * 11 + "cs:Z", "\t" * 11 + "cs:Z:", "\t" * 15, "\n" * 15, "q\t\r\n\xff", HAND + "\n", chim, pairs,
-            "@CO\t" + "x" * (S - 6) + "\t\n" + HAND, "x" * (S - 3) + "\t" * 11 + "cs:Z", "x" * (2 * S + 3)]
+            "@CO\t" + "x" * (S - 6) + "\t\n" + HAND, "x" * (S - 3) + "\t" * 11 + "cs:Z", "x" * (2 * S + 3),
+            near_prefix_text(), "\n".join(short_lines()), "\n".join(short_lines()) + "\n"] + [rec("a") + x for x in short_lines()] + \
+           [tag_dense_text(S, head) for head in (1, 8, 16)] + [tag_dense_text(S, 5)[:-k] for k in range(1, 8)]
     for k, text in enumerate(edge):
         p = os.path.join(str(tmp_path), "t%d.sam" % k)
         with open(p, "wb") as f:
