@@ -2621,9 +2621,7 @@ int ns_load_model(ns_ctx *ctx, const ns_model_tables *t) {
         ctx->chain_block = (ctx->lds_bytes + 8192 <= 32768 || ctx->lds_bytes + NS_CHAIN_BLOCK_BIG * 32u > 65536) ? NS_CHAIN_BLOCK : NS_CHAIN_BLOCK_BIG;
         const int v = ctx->knob.chain_block;
         if (v >= 64 && v <= NS_CHAIN_BLOCK_BIG && v % 64 == 0) ctx->chain_block = (uint32_t)v;
-        double vmax = 0;
-        for (uint32_t k2 = 0; k2 < nseg; ++k2) if (t->mm_vhi[k2] > vmax) vmax = t->mm_vhi[k2];
-        ctx->coop_ok = t->mm_nbins <= COOP_MAX_BINS && vmax < 65535.0;   // the cooperative chain keeps match lengths in 16 bits
+        ctx->coop_ok = ns_coop_ok(t, nseg);       // the cooperative chain keeps match lengths and run lengths in 16 bits (ns_pack.h)
     }
     for (int k = 0; k < NS_KDE_COUNT; ++k) {
         m.kde[k].n = t->kde[k].n; m.kde[k].bw = t->kde[k].bw;

@@ -7,8 +7,8 @@
 //   chain_unaligned_error_list  thread per read, unaligned reads and gaps
 //   coop_error_list, coop_unaligned_error_list   one read per wavefront (the longest aligned reads of a batch, gaps; lane = loop iteration)
 //   coopk_unaligned_error_list  one unaligned read per wavefront, K loop iterations per lane (all unaligned reads)
-// All produce the events of the oracle's error_list / unaligned_error_list bit for bit (tests/test_chain_host.py compiles this source
-// for the host; the -m gpu parity tests compare whole batches).
+// All produce the events of the oracle's error_list / unaligned_error_list bit for bit (tests/test_chain_host.py and tests/test_chain_wave64.py compile
+// this source for the host, the second on a lock-step wavefront of 64 host threads; the -m gpu parity tests compare whole batches).
 #pragma once
 #include "ns_device.h"
 
@@ -450,6 +450,28 @@ NS_DEV EList32 chain_unaligned_error_list(const Tabs &T, const ChainTab &c, int3
     return EList32{l_new, middle_ref};
 }
 
+// ---- the wave-per-read lists below and their cross-lane primitives ------------------------------------------------------------
+// The three lists that follow exchange values between the 64 lanes through NS_WAVE_*: in the product these are the builtins
+// themselves (same code as written in place).  A host build (-DNS_HOST_TEST, host pass only) that wants to RUN the lists defines all of
+// NS_WAVE_SCAN / _BALLOT / _SHFL / _READLANE / _FENCE and NS_POPCLL / NS_CLZLL before it includes this file, as functions of a
+// lock-step wavefront of host threads: every lane calls the list with its own sink, CoopLds is one object shared by the lanes, and
+// NS_WAVE_FENCE is the only primitive that orders memory.  A host build that does not define them leaves the lists out.
+#if !defined(NS_HOST_TEST) && !defined(NS_WAVE_SCAN)
+#define NS_WAVE_SCAN(v) wave_incl_scan(v)                                     // inclusive prefix sum over the lanes (ns_materialise.h)
+#define NS_WAVE_BALLOT(p) __ballot(p)
+#define NS_WAVE_SHFL(v, src) __shfl((v), (src))                               // the value of a lane computed per lane
+#define NS_WAVE_READLANE(v, n) __builtin_amdgcn_readlane((v), (n))            // the value of one lane, the same for all
+#define NS_WAVE_FENCE() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
+#define NS_POPCLL(x) __popcll(x)
+#define NS_CLZLL(x) __clzll(x)
+#endif
+#ifdef NS_WAVE_SCAN
+#ifdef NS_HOST_TEST
+#define NS_DEVW NS_DEV
+#else
+#define NS_DEVW __device__ inline                                             // (not NS_DEV: with __forceinline__ k_chain comes out as another ISA)
+#endif
+
 // ---- cooperative unaligned_error_list: one read (or gap) per wavefront, lane = loop iteration -------------------------
 // What iteration `it` of S:1797-1829 draws (type, run length) does not depend on the state of the loop, and the state is a running
 // sum: pos(it) = sum of the steps of the earlier non-insertion iterations, the loop runs while pos < m_ref.  So 64 iterations are
@@ -457,7 +479,7 @@ NS_DEV EList32 chain_unaligned_error_list(const Tabs &T, const ChainTab &c, int3
 // front of a non-insertion one), the event slots and the cumulative shifts; the events come out exactly as
 // chain_unaligned_error_list produces them.  A 20 kb unaligned read is 20 000 dependent iterations for one thread (tens of
 // milliseconds: it set the duration of the whole batch) and ~320 blocks of a few hundred instructions here.
-__device__ inline EList32 coop_unaligned_error_list(const Tabs &T, const ChainTab &c, int32_t m_ref, const ns_key &key, uint32_t seg,
+NS_DEVW EList32 coop_unaligned_error_list(const Tabs &T, const ChainTab &c, int32_t m_ref, const ns_key &key, uint32_t seg,
                                                     uint32_t attempt, EvSink32 &s, uint32_t lane) {
     int32_t l_new = m_ref, middle_ref = m_ref;
     if (m_ref <= 0) return EList32{l_new, middle_ref};
@@ -475,18 +497,18 @@ __device__ inline EList32 coop_unaligned_error_list(const Tabs &T, const ChainTa
         int type = type_n; uint32_t step = step_n;
         draw(it0 + 64 + lane, type_n, step_n);                   // the next block's draws and table reads run under this block's prefix sums
         const uint32_t adv = type == NS_INS ? 0u : step;
-        const uint32_t adv_incl = wave_incl_scan(adv);
+        const uint32_t adv_incl = NS_WAVE_SCAN(adv);
         const uint32_t pos = pos0 + adv_incl - adv;
         const bool exec = pos < (uint32_t)m_ref;                                                 // the loop is still running (a prefix of the lanes, >= 1)
-        const uint32_t n_exec = (uint32_t)__popcll(__ballot(exec));
+        const uint32_t n_exec = (uint32_t)NS_POPCLL(NS_WAVE_BALLOT(exec));
         if (!exec) { step = 0; type = 3; }
         const uint32_t ins = (exec && type == NS_INS) ? step : 0u, del = (exec && type == NS_DEL) ? step : 0u;
-        const uint32_t ins_incl = wave_incl_scan(ins);
+        const uint32_t ins_incl = NS_WAVE_SCAN(ins);
         // pending insertion in front of a non-insertion iteration: the insertion steps since the previous non-insertion one
         const bool nonins = exec && type != NS_INS;
-        const uint64_t NB = __ballot(nonins);
+        const uint64_t NB = NS_WAVE_BALLOT(nonins);
         const uint64_t below = NB & ((1ull << lane) - 1ull);
-        const uint32_t prev_ins = (uint32_t)__shfl((int)ins_incl, below ? 63 - __clzll((long long)below) : (int)lane);
+        const uint32_t prev_ins = (uint32_t)NS_WAVE_SHFL((int)ins_incl, below ? 63 - NS_CLZLL((long long)below) : (int)lane);
         const uint32_t L = nonins ? (below ? ins_incl - prev_ins : pend0 + ins_incl) : 0u;
         // the events of the iteration, at most three
         uint32_t ty0 = 0, ty1 = 0, ty2 = 0, ln0 = 0, ln1 = 0, ln2 = 0, ps0 = pos, ps1 = pos + 1, ps2 = pos + 1, n_ev = 0;
@@ -513,27 +535,27 @@ __device__ inline EList32 coop_unaligned_error_list(const Tabs &T, const ChainTa
         // insertion and deletion sums: no prefix sum of its own
         auto dsh = [](uint32_t ty, uint32_t ln) { return ty == NS_INS ? ln : ty == NS_DEL ? 0u - ln : 0u; };
         const uint32_t d0 = n_ev > 0 ? dsh(ty0, ln0) : 0u, d1 = n_ev > 1 ? dsh(ty1, ln1) : 0u;
-        const uint32_t dn_incl = wave_incl_scan(del | n_ev << 24);
+        const uint32_t dn_incl = NS_WAVE_SCAN(del | n_ev << 24);
         const uint32_t del_incl = dn_incl & 0xffffffu, n_incl = dn_incl >> 24;
         const uint32_t slot = s.n + n_incl - n_ev;
         const uint32_t sh = (uint32_t)s.shift + (pend0 + ins_incl - L) - (del_incl - del);       // (used by non-insertion lanes only)
         // (the shift in FRONT of every event must fit its field, as ev_push32 checks it)
         if ((n_ev > 0 && !ev_shift_fits((int32_t)sh)) || (n_ev > 1 && !ev_shift_fits((int32_t)(sh + d0))) || (n_ev > 2 && !ev_shift_fits((int32_t)(sh + d0 + d1)))) bad = true;
-        if (__ballot(bad)) s.range = true;
+        if (NS_WAVE_BALLOT(bad)) s.range = true;
         if (n_ev > 0) { if (slot < s.cap) { ns_event e; e.pos = ps0; e.info = ns_ev_pack(ln0, ty0, (int32_t)sh); s.ev[slot] = e; } }
         if (n_ev > 1) { if (slot + 1 < s.cap) { ns_event e; e.pos = ps1; e.info = ns_ev_pack(ln1, ty1, (int32_t)(sh + d0)); s.ev[slot + 1] = e; } }
         if (n_ev > 2) { if (slot + 2 < s.cap) { ns_event e; e.pos = ps2; e.info = ns_ev_pack(ln2, ty2, (int32_t)(sh + d0 + d1)); s.ev[slot + 2] = e; } }
-        const uint32_t n_blk = (uint32_t)__builtin_amdgcn_readlane((int)n_incl, 63);
+        const uint32_t n_blk = (uint32_t)NS_WAVE_READLANE((int)n_incl, 63);
         if (s.n + n_blk > s.cap) s.overflow = true;
         s.n += n_blk;
-        const uint32_t ins_tot = (uint32_t)__builtin_amdgcn_readlane((int)ins_incl, 63);
-        const uint32_t del_tot = (uint32_t)__builtin_amdgcn_readlane((int)del_incl, 63);
+        const uint32_t ins_tot = (uint32_t)NS_WAVE_READLANE((int)ins_incl, 63);
+        const uint32_t del_tot = (uint32_t)NS_WAVE_READLANE((int)del_incl, 63);
         l_new += (int32_t)ins_tot - (int32_t)del_tot;                                                      // S:1808-1815, 1820
         // pending insertion behind the last non-insertion iteration of the block
-        const uint32_t pend1 = NB ? ins_tot - (uint32_t)__shfl((int)ins_incl, 63 - __clzll((long long)NB)) : pend0 + ins_tot;
+        const uint32_t pend1 = NB ? ins_tot - (uint32_t)NS_WAVE_SHFL((int)ins_incl, 63 - NS_CLZLL((long long)NB)) : pend0 + ins_tot;
         s.shift = (int32_t)((uint32_t)s.shift + (pend0 + ins_tot - pend1) - del_tot);                     // the insertions filed - the deletions
         pend0 = pend1;
-        pos0 += (uint32_t)__builtin_amdgcn_readlane((int)adv_incl, (int)(n_exec - 1u));                   // positions advanced by the iterations that ran
+        pos0 += (uint32_t)NS_WAVE_READLANE((int)adv_incl, (int)(n_exec - 1u));                   // positions advanced by the iterations that ran
         if (n_exec < 64 || pos0 >= (uint32_t)m_ref) break;
     }
     if ((int32_t)pos0 > middle_ref) { l_new += (int32_t)pos0 - middle_ref; middle_ref = (int32_t)pos0; }      // S:1826-1828
@@ -548,7 +570,7 @@ __device__ inline EList32 coop_unaligned_error_list(const Tabs &T, const ChainTa
 // per lane: {positions advanced, insertions drawn, whether it has a non-insertion iteration, the insertions behind its last one}.
 // Same events, same order, same sink state as coop_unaligned_error_list.
 template <int K>
-__device__ inline EList32 coopk_unaligned_error_list(const Tabs &T, const ChainTab &c, int32_t m_ref, const ns_key &key, uint32_t seg,
+NS_DEVW EList32 coopk_unaligned_error_list(const Tabs &T, const ChainTab &c, int32_t m_ref, const ns_key &key, uint32_t seg,
                                                      uint32_t attempt, EvSink32 &s, uint32_t lane) {
     int32_t l_new = m_ref, middle_ref = m_ref;
     if (m_ref <= 0) return EList32{l_new, middle_ref};
@@ -574,7 +596,7 @@ __device__ inline EList32 coopk_unaligned_error_list(const Tabs &T, const ChainT
         uint32_t a_loc[K], a_lane = 0;
         #pragma unroll
         for (int k = 0; k < K; ++k) { a_loc[k] = a_lane; a_lane += type[k] == NS_INS ? 0u : step[k]; }
-        const uint32_t a_incl = wave_incl_scan(a_lane);
+        const uint32_t a_incl = NS_WAVE_SCAN(a_lane);
         const uint32_t pos_l = pos0 + a_incl - a_lane;
         // the iterations that still run (a prefix of the round), their insertions / deletions; within the lane: the insertions pending in
         // front of every non-insertion iteration since the previous one of the LANE (L_loc), whether it is the lane's first (`first`)
@@ -596,11 +618,11 @@ __device__ inline EList32 coopk_unaligned_error_list(const Tabs &T, const ChainT
             a_exec += (exec[k] && type[k] != NS_INS) ? step[k] : 0u;
             n_exec_l += exec[k] ? 1u : 0u;
         }
-        const uint32_t i_incl = wave_incl_scan(i_lane);
-        const uint64_t HAS = __ballot(seen);
+        const uint32_t i_incl = NS_WAVE_SCAN(i_lane);
+        const uint64_t HAS = NS_WAVE_BALLOT(seen);
         const uint64_t below = HAS & ((1ull << lane) - 1ull);
-        const int jb = below ? 63 - __clzll((long long)below) : (int)lane;
-        const uint32_t tail_b = (uint32_t)__shfl((int)run, jb), incl_b = (uint32_t)__shfl((int)i_incl, jb);
+        const int jb = below ? 63 - NS_CLZLL((long long)below) : (int)lane;
+        const uint32_t tail_b = (uint32_t)NS_WAVE_SHFL((int)run, jb), incl_b = (uint32_t)NS_WAVE_SHFL((int)i_incl, jb);
         const uint32_t pend_l = below ? tail_b + (i_incl - i_lane) - incl_b : pend0 + (i_incl - i_lane);       // pending in front of this lane
         // the events of every iteration, at most three each
         uint32_t ty[K][3], ln[K][3], ps[K][3], n_ev[K], n_loc[K], L[K], n_lane = 0;
@@ -632,8 +654,8 @@ __device__ inline EList32 coopk_unaligned_error_list(const Tabs &T, const ChainT
             n_ev[k] = ne; n_loc[k] = n_lane; n_lane += ne;
         }
         // deleted bases; event counts (<= 3 K per lane) and the iterations that ran (<= K) in one prefix sum
-        const uint32_t d_incl = wave_incl_scan(d_lane);
-        const uint32_t ne_incl = wave_incl_scan(n_lane | n_exec_l << 16);
+        const uint32_t d_incl = NS_WAVE_SCAN(d_lane);
+        const uint32_t ne_incl = NS_WAVE_SCAN(n_lane | n_exec_l << 16);
         const uint32_t d_front = d_incl - d_lane, n_front = (ne_incl & 0xffffu) - n_lane;
         auto dsh = [](uint32_t t, uint32_t l) { return t == NS_INS ? l : t == NS_DEL ? 0u - l : 0u; };
         #pragma unroll
@@ -649,26 +671,26 @@ __device__ inline EList32 coopk_unaligned_error_list(const Tabs &T, const ChainT
             if (n_ev[k] > 2 && slot + 2 < s.cap) { ns_event e; e.pos = ps[k][2]; e.info = ns_ev_pack(ln[k][2], ty[k][2], (int32_t)(sh + d0 + d1)); s.ev[slot + 2] = e; }
         }
         // ---- the state behind the round
-        const uint32_t ne_tot = (uint32_t)__builtin_amdgcn_readlane((int)ne_incl, 63);
+        const uint32_t ne_tot = (uint32_t)NS_WAVE_READLANE((int)ne_incl, 63);
         const uint32_t n_blk = ne_tot & 0xffffu, n_ran = ne_tot >> 16;
-        const uint32_t del_tot = (uint32_t)__builtin_amdgcn_readlane((int)d_incl, 63), ins_tot = (uint32_t)__builtin_amdgcn_readlane((int)i_incl, 63);
+        const uint32_t del_tot = (uint32_t)NS_WAVE_READLANE((int)d_incl, 63), ins_tot = (uint32_t)NS_WAVE_READLANE((int)i_incl, 63);
         // positions advanced by the iterations that ran: all of the round's, except in the round where the loop ends
-        uint32_t adv_tot = (uint32_t)__builtin_amdgcn_readlane((int)a_incl, 63);
-        if (n_ran < 64u * K) adv_tot = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(a_exec), 63);
+        uint32_t adv_tot = (uint32_t)NS_WAVE_READLANE((int)a_incl, 63);
+        if (n_ran < 64u * K) adv_tot = (uint32_t)NS_WAVE_READLANE((int)NS_WAVE_SCAN(a_exec), 63);
         if (s.n + n_blk > s.cap) s.overflow = true;
         s.n += n_blk;
         l_new += (int32_t)ins_tot - (int32_t)del_tot;                                                          // S:1808-1815, 1820
         uint32_t pend1 = pend0 + ins_tot;                          // pending behind the last non-insertion iteration of the round
         if (HAS) {
-            const int jl = 63 - __clzll((long long)HAS);
-            pend1 = (uint32_t)__shfl((int)run, jl) + ins_tot - (uint32_t)__shfl((int)i_incl, jl);
+            const int jl = 63 - NS_CLZLL((long long)HAS);
+            pend1 = (uint32_t)NS_WAVE_SHFL((int)run, jl) + ins_tot - (uint32_t)NS_WAVE_SHFL((int)i_incl, jl);
         }
         s.shift = (int32_t)((uint32_t)s.shift + (pend0 + ins_tot - pend1) - del_tot);
         pend0 = pend1;
         pos0 += adv_tot;
         if (n_ran < 64u * K || pos0 >= (uint32_t)m_ref) break;
     }
-    if (__ballot(bad)) s.range = true;
+    if (NS_WAVE_BALLOT(bad)) s.range = true;
     if ((int32_t)pos0 > middle_ref) { l_new += (int32_t)pos0 - middle_ref; middle_ref = (int32_t)pos0; }      // S:1826-1828
     return EList32{l_new, middle_ref};
 }
@@ -680,7 +702,6 @@ __device__ inline EList32 coopk_unaligned_error_list(const Tabs &T, const ChainT
 // (its Philox block and all table searches, including the fp64 interpolation) and leaves the results in LDS; the
 // dependent part that remains is a walk over 64 iterations of four small table reads each (~10x shorter critical
 // path than the thread-per-read chain).  Produces exactly the events of chain_error_list.
-#define COOP_MAX_BINS 16u
 struct CoopLds {
     uint32_t err_tab[64];                 // 2 bits per Markov state
     uint16_t step_tab[64][4];             // run length per error type
@@ -690,7 +711,7 @@ struct CoopLds {
 };
 
 // TM: the front of the blob (transition rows, run-length tables: n_words_mix words) — the wavefront's LDS copy when the launch gave it room
-__device__ inline EList32 coop_error_list(const Tabs &TM, const Tabs &T, const ChainTab &c, int32_t m_ref, const ns_key &key, uint32_t seg,
+NS_DEVW EList32 coop_error_list(const Tabs &TM, const Tabs &T, const ChainTab &c, int32_t m_ref, const ns_key &key, uint32_t seg,
                                           uint32_t attempt, EvSink32 &s, CoopLds &S, uint32_t lane) {
     int32_t l_new = m_ref, pos = 0, middle_ref = m_ref;
     int state = NS_ST_START;
@@ -766,8 +787,7 @@ __device__ inline EList32 coop_error_list(const Tabs &TM, const Tabs &T, const C
                 S.match_tab[lane][b] = (uint32_t)(uint16_t)v | bin_of(v) << 16 | bin_of(v == 0 ? 1 : v) << 24;
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        NS_WAVE_FENCE();
         // ---- sequential walk (uniform over the wavefront): four small LDS reads per iteration
         uint32_t nl = 0;                                           // events buffered in this block
         uint32_t i = 0;
@@ -806,16 +826,15 @@ __device__ inline EList32 coop_error_list(const Tabs &TM, const Tabs &T, const C
             else last_ins_pos = -1;
         }
         // ---- flush the block's events, one lane per event
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        NS_WAVE_FENCE();
         if (lane < nl) {
             if (s.n + lane < s.cap) s.ev[s.n + lane] = S.ev_buf[lane];
         }
         if (s.n + nl > s.cap) s.overflow = true;
         s.n += nl;
         it0 += i;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        NS_WAVE_FENCE();
     }
     return EList32{l_new, middle_ref};
 }
+#endif  // NS_WAVE_SCAN

@@ -27,6 +27,7 @@ enum NsStat : uint32_t {
 // copy `way` of the counters
 __host__ __device__ inline unsigned long long *ns_stats_way(unsigned long long *stats, uint32_t way) { return stats + NS_STAT_COUNT + NS_STAT_COUNT * way; }
 
+#define COOP_MAX_BINS 16u         // match-length columns the wave-per-read aligned chain keeps per iteration (CoopLds of ns_chain.h; ns_coop_ok of ns_pack.h)
 struct ChainTab {                 // offsets are in 8-byte words from the start of the blob (ns_pack.h describes the image)
     uint32_t n_words;
     uint32_t trans;               // 21 thresholds: rows start,mis,ins,del,mis0,ins0,del0 x (a, a+b, -)

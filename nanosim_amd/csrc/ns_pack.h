@@ -221,6 +221,23 @@ static inline void ns_pack_chain_tables(const ns_model_tables *t, uint32_t nseg,
     ct.n_words = (uint32_t)blob.size();
 }
 
+// May the wave-per-read aligned chain (coop_error_list, ns_chain.h) run this model?  It keeps, per future iteration, the next match of every
+// column in 16 bits of a word of COOP_MAX_BINS columns, and the run length of every error type in a uint16_t:
+//   - at most COOP_MAX_BINS columns;
+//   - every match length below 65 535 (nseg: the segments of all columns);
+//   - every run length at most 65 535: run_length_t answers up to the LENGTH of a run-length table (a draw above its last entry), and
+//     a table of 65 536 entries would come back from the uint16_t as a step of 0 — an event of length 0 and no `range`, where the
+//     thread-per-read chain files 65 536 and sets `range` (tests/test_chain_wave64.py has the case).
+// A model that fails a rule keeps every read on the thread-per-read chain.
+static inline bool ns_coop_ok(const ns_model_tables *t, uint32_t nseg) {
+    double vmax = 0;
+    for (uint32_t k = 0; k < nseg; ++k) if (t->mm_vhi[k] > vmax) vmax = t->mm_vhi[k];
+    uint32_t run_max = 0;
+    for (int ty = 0; ty < 3; ++ty)
+        for (int c = 0; c < 2; ++c) if (t->mix_n[ty][c] > run_max) run_max = t->mix_n[ty][c];
+    return t->mm_nbins <= COOP_MAX_BINS && vmax < 65535.0 && run_max <= 65535u;
+}
+
 // ---- base qualities (ns_model_tables.qual_thr, include/nanosim_amd.h) ------------------------------------------------------------------
 // The first level j in [1, NS_QUAL_LEVELS - 1) of one class's thresholds with thr[j] < thr[j - 1], or 0 when the table is non-decreasing
 // over j = 0..126 (thr[127] is never compared).  The count q = #{j : h >= thr[j]} only has one value for the bucket table, the binary search

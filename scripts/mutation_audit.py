@@ -10,6 +10,8 @@ the mutants the tests did not notice.
     python scripts/mutation_audit.py nanosim_amd/csrc/ns_em.h tests/test_quantify.py
     python scripts/mutation_audit.py --all [--classes rel,lit,logic] [--jobs N] [--timeout S] [--log FILE]
     python scripts/mutation_audit.py --chain            ns_pack.h and the thread-per-read part of ns_chain.h, on tests/chain_host.hip
+    python scripts/mutation_audit.py --chain-wave       the wave-per-read part of ns_chain.h, on tests/chain_wave_host.hip (64 host threads
+                                                        per mutant: --jobs 2)
 
 Mutation classes: rel   `<` <-> `<=`, `>` <-> `>=`                                   (the default)
                   lit   an integer literal inside a condition or an index expression, +1 and -1
@@ -17,9 +19,11 @@ Mutation classes: rel   `<` <-> `<=`, `>` <-> `>=`                              
 Per header it prints the number of mutants, how many were killed, and one line per survivor: `file:line col op | source line`.
 A mutant that runs into its time limit counts as killed (a flipped loop bound need not terminate).  A mutant the host compiler rejects
 is no mutant (a `<` of a template argument list, say) and is left out.  Text the host build never compiles — the true branch of an
-`#if` on __HIP_DEVICE_COMPILE__, or on __HIPCC__ where the header's unit is built by g++, and the wave-per-read functions of ns_chain.h
-(`__device__` only: the host pass parses them and makes no code) — is listed apart as "device-only, not auditable on the host", and is
-not counted.
+`#if` on __HIP_DEVICE_COMPILE__, or on __HIPCC__ where the header's unit is built by g++, and, under --chain, the wave-per-read functions
+of ns_chain.h (tests/chain_host.hip leaves them out) — is listed apart as "device-only, not auditable on the host", and is not counted.
+--chain-wave audits exactly that part of ns_chain.h, from the DEVICE_ONLY_FROM marker to the end of the file, on the build that runs
+it on a lock-step wavefront of 64 host threads (tests/chain_wave_host.hip); a mutant whose lanes diverge ends with the wave's message
+and counts as killed, like one that runs into its time limit.
 
 Mutants run on the CPU host build only: a mutant is by construction code that may read or loop out of bounds.  Nothing here compiles
 for a GPU, imports an engine or runs a test marked gpu.  The working tree is never touched: every worker mutates its own copy."""
@@ -63,6 +67,9 @@ CHAIN = {
     CSRC + "ns_pack.h": ("tests/chain_host.hip", CHAIN_TESTS + ["tests/test_qual_probe.py"]),      # (+ the base-quality tables of the same header)
     CSRC + "ns_chain.h": ("tests/chain_host.hip", CHAIN_TESTS),
 }
+# the wave-per-read chains (ns_chain.h from the DEVICE_ONLY_FROM marker on) on the lock-step wavefront of tests/wave64_host.h; the test file
+# has its edge tests first
+CHAIN_WAVE = {CSRC + "ns_chain.h": ("tests/chain_wave_host.hip", ["tests/test_chain_wave64.py"])}
 UNITS = {**TRAINING, **CHAIN}
 # header -> the text from the first line that holds this marker to the end of the file is `__device__` only
 DEVICE_ONLY_FROM = {CSRC + "ns_chain.h": "// ---- cooperative unaligned_error_list"}
@@ -246,14 +253,18 @@ class Worker:
                 f.write(text)
 
 
-def audit(header, unit, tests, classes, jobs, limit, base, emit):
+def audit(header, unit, tests, classes, jobs, limit, base, emit, tail_only=False):
+    """tail_only: the text from the header's DEVICE_ONLY_FROM marker to the end of the file, and nothing in front of it"""
     with open(os.path.join(ROOT, header)) as f:
         text = f.read()
     lines = text.split("\n")
-    dev = device_only_lines(text, host_defines(unit), DEVICE_ONLY_FROM.get(header))
+    tail = device_only_lines(text, (), DEVICE_ONLY_FROM[header]) - device_only_lines(text, ()) if tail_only else None
+    dev = device_only_lines(text, host_defines(unit), None if tail_only else DEVICE_ONLY_FROM.get(header))
     where = lambda off: (text.count("\n", 0, off), off - (text.rfind("\n", 0, off) + 1) + 1)
     todo, device = [], []
     for mut in mutants_of(text, classes):
+        if tail_only and where(mut[0])[0] not in tail:
+            continue
         (device if where(mut[0])[0] in dev else todo).append(mut)
     show = lambda mut: "%s:%d col %d %s -> %s | %s" % (header, where(mut[0])[0] + 1, where(mut[0])[1], mut[1], mut[2], lines[where(mut[0])[0]].strip()[:150])
     t0 = time.time()
@@ -298,6 +309,7 @@ def main():
     ap.add_argument("tests", nargs="*", help="the test files to run against every mutant")
     ap.add_argument("--all", action="store_true", help="the training headers with their CPU test files")
     ap.add_argument("--chain", action="store_true", help="ns_pack.h and the thread-per-read part of ns_chain.h with the chain's CPU test files")
+    ap.add_argument("--chain-wave", action="store_true", help="the wave-per-read part of ns_chain.h on the 64-lane host build, with tests/test_chain_wave64.py")
     ap.add_argument("--classes", default="rel", help="comma-separated: rel, lit, logic (default rel)")
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
     ap.add_argument("--timeout", type=float, default=300.0, help="seconds per mutant, at most (the limit in use follows the unmutated run's time)")
@@ -306,9 +318,13 @@ def main():
     classes = [c for c in a.classes.split(",") if c]
     if not classes or set(classes) - {"rel", "lit", "logic"}:
         ap.error("classes are rel, lit and logic")
-    if (a.all or a.chain) == bool(a.header):
-        ap.error("give a header with its tests, or --all, or --chain")
-    if a.all or a.chain:
+    if (a.all or a.chain or a.chain_wave) == bool(a.header):
+        ap.error("give a header with its tests, or --all, or --chain, or --chain-wave")
+    if a.chain_wave and (a.all or a.chain):
+        ap.error("--chain-wave audits the other part of a header --chain audits: run it on its own")
+    if a.chain_wave:
+        plan = [(h, u, t) for h, (u, t) in CHAIN_WAVE.items()]
+    elif a.all or a.chain:
         plan = [(h, u, t) for h, (u, t) in {**(TRAINING if a.all else {}), **(CHAIN if a.chain else {})}.items()]
     else:
         h = os.path.relpath(os.path.abspath(a.header), ROOT)
@@ -330,7 +346,7 @@ def main():
     tot = [0, 0, 0, 0]
     try:
         for h, u, t in plan:
-            for k, v in enumerate(audit(h, u, t, classes, a.jobs, a.timeout, base, emit)):
+            for k, v in enumerate(audit(h, u, t, classes, a.jobs, a.timeout, base, emit, tail_only=a.chain_wave)):
                 tot[k] += v
     finally:
         shutil.rmtree(base, ignore_errors=True)

@@ -25,6 +25,7 @@ void *chost_pack(const ns_model_tables *t) {
 void chost_free(void *p) { delete static_cast<ChainHost *>(p); }
 int chost_whole(const void *p) { return static_cast<const ChainHost *>(p)->whole ? 1 : 0; }
 uint32_t chost_lds_words(const void *p) { return static_cast<const ChainHost *>(p)->ct.n_words_lds; }
+int chost_coop_ok(const ns_model_tables *t) { return ns_coop_ok(t, t->mm_seg_off[t->mm_nbins]) ? 1 : 0; }       // the gate of ns_load_model
 uint32_t chost_tail_bits(const void *p) { return static_cast<const ChainHost *>(p)->ct.tail_bits; }
 
 // variant 0: chain_error_list   — the integer image k_chain<LDS> walks (T = the blob's first n_words_lds words)

@@ -156,8 +156,9 @@ def test_wave64_thread_sanitizer_refuses_the_walk_without_its_fence(tmp_path):
 
 
 def test_wave64_stops_with_a_message_when_the_lanes_diverge(tmp_path):
-    """the wave itself: its collectives on values that can be counted; lanes at different kinds of collective, and lanes that wait for
-    one that has left, end run() with their message at once, and the wave runs the next body as if nothing had been.  Built with a time
+    """the wave itself: its collectives on values that can be counted (the inclusive scan, the shuffle from a lane of one's own choice
+    and the read of one lane among them: tests/chain_wave_host.hip); lanes at different kinds of collective, lanes that read different
+    lanes in one readlane, and lanes that wait for one that has left, end run() with their message at once, and the wave runs the next body as if nothing had been.  Built with a time
     limit of 1 s, a lane that comes 1.5 s late finds the wave stopped by the lanes that waited for it."""
     src = os.path.join(str(tmp_path), "diverge.cpp")
     with open(src, "w") as f:
@@ -180,11 +181,18 @@ def test_wave64_stops_with_a_message_when_the_lanes_diverge(tmp_path):
                 '                                w.ballot(true); })) return 7;\n'
                 '    if (!strstr(g.error().c_str(), "waited 1000 ms at ballot for lane 9")) return 8;\n'
                 '#endif\n'
+                '    uint32_t c[64];\n'
+                '    if (!g.run([&](uint32_t l) { Wave64Lane w{&g, l}; c[l] = w.incl_scan(l + 1) + w.shfl(10 * l, 63 - l) + w.readlane(l * l, 7); w.fence(); })) return 13;\n'
+                '    for (uint32_t l = 0; l < 64; ++l) if (c[l] != (l + 1) * (l + 2) / 2 + 10 * (63 - l) + 49) return 14;\n'
+                '    if (g.run([&](uint32_t l) { Wave64Lane w{&g, l}; w.readlane(l, l == 9 ? 3 : 4); })) return 15;\n'
+                '    if (!strstr(g.error().c_str(), "diverged") || !strstr(g.error().c_str(), "readlane of lane")) return 16;\n'
+                '    if (g.run([&](uint32_t l) { Wave64Lane w{&g, l}; if (l == 9) w.shfl(l, 0); else w.readlane(l, 0); })) return 17;\n'
+                '    if (!strstr(g.error().c_str(), "diverged") || !strstr(g.error().c_str(), "shfl")) return 18;\n'
                 '    uint32_t n[64];\n'
                 '    if (!g.run([&](uint32_t l) { Wave64Lane w{&g, l}; n[l] = w.first(l > 40); })) return 9;\n'
                 '    for (uint32_t l = 0; l < 64; ++l) if (n[l] != 41) return 10;\n'
                 '    return 0;\n}\n')
-    for limit, messages in (("8000", 2), ("1000", 3)):
+    for limit, messages in (("8000", 4), ("1000", 5)):
         exe = os.path.join(str(tmp_path), "diverge" + limit)
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-pthread", "-DWAVE64_TIMEOUT_MS=" + limit, "-I", os.path.join(ROOT, "tests"), "-o", exe, src])
         done = subprocess.run([exe], capture_output=True, text=True)

@@ -2,14 +2,15 @@
 // wavefront W (nanosim_amd/csrc/ns_calmd.h, ns_bam.h).  Plain C++17 with threads, no HIP and no GPU: 64 host threads, one per lane, kept
 // for the life of the Wave64 object; run() hands all of them one body and returns when every lane has left it.
 //
-// Every collective — ballot, scan (32 and 64 bits), first, bcast, fence, and the two meetings of float_reserve — is a RENDEZVOUS: each
+// Every collective — ballot, scan (32 and 64 bits; incl_scan is scan + the lane's own value), first, bcast, shfl, readlane, fence, and the
+// two meetings of float_reserve — is a RENDEZVOUS: each
 // lane deposits its value, all 64 meet, each reads the deposits.  A deposit is two atomic words, each of which names its round and the
 // kind of the collective next to 32 bits of the value: a reader waits on a word until it names the round it is in, so a word is its
 // own proof of being the right one and nothing else has to be ordered.  The words are kept twice and used in turn: a lane can stand at
 // most one collective ahead of the slowest reader (it waits there for that reader's deposit), and that collective uses the other set.
 //
 // WHAT ORDERS MEMORY.  On the GPU a ballot, a prefix sum or a broadcast moves registers; it is no memory fence.  So here the deposits
-// of ballot, scan, first and bcast are RELAXED atomics: a lane learns the other lanes' values from them and nothing about what those
+// of ballot, scan, first, bcast, shfl and readlane are RELAXED atomics: a lane learns the other lanes' values from them and nothing about what those
 // lanes wrote to plain memory.  Only fence() deposits with release and reads with acquire (and so do the two meetings of float_reserve,
 // which stand in for an atomic add on a list the shim itself reallocates, and the hand-over of a body in run()).  Under
 // -fsanitize=thread a table that one lane writes and another reads with no fence() between the two — whatever other collectives lie
@@ -49,7 +50,7 @@
 class Wave64 {
 public:
     static constexpr uint32_t LANES = 64u;
-    enum Kind : uint32_t { BALLOT = 0, SCAN32, SCAN64, FIRST, BCAST, FENCE, RESERVE_IN, RESERVE_OUT, N_KINDS };
+    enum Kind : uint32_t { BALLOT = 0, SCAN32, SCAN64, FIRST, BCAST, FENCE, RESERVE_IN, RESERVE_OUT, SHFL, READLANE, N_KINDS };
     struct Stop {};                                                  // what a lane leaves a stopped wave with
 
     Wave64() {}
@@ -135,10 +136,13 @@ public:
         }
     }
 
+    // a lane that found the wave's lanes in disagreement at a collective of one kind
+    [[noreturn]] void diverged(uint32_t lane, const std::string &what) { fail("the lanes diverged: lane " + std::to_string(lane) + " at " + what); }
+
 private:
     struct Slot { std::atomic<uint64_t> lo{0}, hi{0}; };
     static const char *name(Kind k) {
-        static const char *const n[N_KINDS] = {"ballot", "scan (32 bits)", "scan (64 bits)", "first", "bcast", "fence", "float_reserve", "float_reserve (the result)"};
+        static const char *const n[N_KINDS] = {"ballot", "scan (32 bits)", "scan (64 bits)", "first", "bcast", "fence", "float_reserve", "float_reserve (the result)", "shfl", "readlane"};
         return k < N_KINDS ? n[k] : "?";
     }
     void stop(const std::string &why) {
@@ -215,6 +219,20 @@ struct Wave64Lane {
         uint64_t s[LANES];
         wave->meet(lane, Wave64::BCAST, v, s);
         return (uint32_t)s[src & (LANES - 1u)];
+    }
+    uint32_t incl_scan(uint32_t v) const { uint32_t total; return scan(v, total) + v; }     // inclusive prefix sum (32 bits, wraps like the GPU's)
+    uint32_t shfl(uint32_t v, uint32_t src) const {                 // v of lane src, a source PER LANE (bcast: one source for all)
+        uint64_t s[LANES];
+        wave->meet(lane, Wave64::SHFL, v, s);
+        return (uint32_t)s[src & (LANES - 1u)];
+    }
+    // v of lane n, n the same on every lane (an SGPR on the GPU): lanes that name different n have diverged, and the wave stops
+    uint32_t readlane(uint32_t v, uint32_t n) const {
+        uint64_t s[LANES];
+        wave->meet(lane, Wave64::READLANE, (uint64_t)(n & (LANES - 1u)) << 32 | v, s);
+        for (uint32_t l = 0; l < LANES; ++l)
+            if ((s[l] >> 32) != (n & (LANES - 1u))) wave->diverged(lane, "readlane of lane " + std::to_string(n & (LANES - 1u)) + ", lane " + std::to_string(l) + " reads lane " + std::to_string(s[l] >> 32));
+        return (uint32_t)s[n & (LANES - 1u)];
     }
     void fence() const { uint64_t s[LANES]; wave->meet(lane, Wave64::FENCE, 0u, s); }
 };
