@@ -757,6 +757,45 @@ typedef struct ns_sam_index_result {
 } ns_sam_index_result;
 int ns_sam_index(ns_ctx *ctx, const uint8_t *text, uint64_t nbytes, ns_sam_index_result *out);
 
+/* ---- compressed output: BGZF members, deflated on the GPU before the copy (nanosim_amd/csrc/ns_gz.h) ----
+ * A BGZF file is a series of independent gzip members of at most 64 KiB each; any concatenation of members is a valid .gz file.  Here
+ * every member holds at most NS_GZ_BLOCK_BYTES input bytes as ONE deflate block: a dynamic-Huffman block of literals only (no matches),
+ * or a stored block when that is smaller or when the code lacks a byte of the block.  One code serves a whole stream of blocks.
+ *
+ * ns_gz_code: a length-limited (<= 15 bits) canonical Huffman code over the byte values whose count is not 0, plus end-of-block
+ * (index 256).  len[v] == 0: the value has no code.  code[v]: the code bit-reversed, as deflate packs it (first bit of the code in bit
+ * 0).  header[]: the complete header of the dynamic block as a bit string of header_bits bits, first bit in bit 0 of header[0], zero
+ * behind the last bit: BFINAL = 1, BTYPE = 2, HLIT = 0 (257 codes), HDIST = 0 (one distance code of length 0: all literals), HCLEN, the
+ * lengths of the code-length code and the 258 run-length-coded lengths.  Its worst case is 3 + 5 + 5 + 4 bits, 19 x 3 bits, and at most
+ * 7 bits for every one of the 258 lengths (a repeat symbol with its extra bits, 14 bits at most, stands for three lengths or more):
+ * 17 + 57 + 1806 = 1880 bits = 235 bytes, kept in NS_GZ_HEADER_BYTES = 240 (whole 32-bit words).
+ * ns_gz_code_build needs no context and no GPU.  NS_EINVAL for a null argument. */
+#define NS_GZ_BLOCK_BYTES 16384u
+#define NS_GZ_HEADER_BYTES 240u
+typedef struct ns_gz_code {
+    uint8_t len[257];
+    uint16_t code[257];
+    uint32_t header_bits;
+    uint8_t header[NS_GZ_HEADER_BYTES];
+} ns_gz_code;
+int ns_gz_code_build(const uint64_t hist[256], ns_gz_code *out);
+/* an upper bound of what nbytes input bytes in n_ranges ranges compress to (every block stored, one short block more per range) */
+uint64_t ns_gz_bound(uint64_t nbytes, uint32_t n_ranges);
+/* the counts of the 256 byte values in the record image (which = NS_BUF_RECORDS) or the error-profile image (NS_BUF_ERRLOG) of the last batch */
+int ns_gz_histogram(ns_ctx *ctx, int which, uint64_t hist[256]);
+/* cuts[n_cuts]: ascending byte offsets into src[nbytes].  Every range [cuts[i], cuts[i + 1]) becomes a whole number of members, one
+ * behind the other in dst; gz_off[i], i < n_cuts - 1, is where the members of range i begin, gz_off[n_cuts - 1] where the last ones
+ * end.  An empty range has no bytes.  code == NULL: the code is built from the counts of src.  Host bytes in, host bytes out, on the
+ * kernels of ns_gz_result.  NS_EINVAL for null arguments, n_cuts == 0, cuts that do not ascend or lie beyond nbytes, and when dst_cap is
+ * smaller than the result (gz_off is filled then: gz_off[n_cuts - 1] is the size needed). */
+int ns_gz_bytes(ns_ctx *ctx, const uint8_t *src, uint64_t nbytes, const uint64_t *cuts, uint32_t n_cuts, const ns_gz_code *code,
+                uint8_t *dst, uint64_t dst_cap, uint64_t *gz_off);
+/* ... the same of the record image (which = NS_BUF_RECORDS) or the error-profile image (NS_BUF_ERRLOG) of the LAST batch, into the result
+ * buffer NS_BUF_RECORDS_GZ / NS_BUF_ERRLOG_GZ of the batch's result slot: ns_copy_out, ns_sink_write_range and ns_device_ptr take the two
+ * ids like the plain images, and the slot rule of the plain images holds for them.  NS_ESTATE without a batch. */
+enum { NS_BUF_RECORDS_GZ = 7, NS_BUF_ERRLOG_GZ = 8 };
+int ns_gz_result(ns_ctx *ctx, int which, const uint64_t *cuts, uint32_t n_cuts, const ns_gz_code *code, uint64_t *gz_off);
+
 /* device address of a result buffer (for zero-copy consumers such as torch / RCCL); NULL if absent */
 const void *ns_device_ptr(ns_ctx *ctx, int which);
 

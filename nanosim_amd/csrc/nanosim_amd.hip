@@ -44,6 +44,7 @@
 #include "ns_qual_hist.h"
 #include "ns_hp_hist.h"
 #include "ns_train.h"
+#include "ns_gz.h"
 
 // Reads per workgroup of the wave-per-read kernels.  One: read lengths vary by an order of magnitude inside a batch, and a wavefront
 // that is done cannot leave before the longest read of its workgroup is.
@@ -2211,6 +2212,8 @@ struct ns_ctx {
     ByteBuf scan_tmp;                  // temporary storage of the hipcub calls (with_tmp)
     ByteBuf rec_slot[2], err_slot[2];  // two result slots: the record / error-profile images of the last batch and of the one before (ns_io.h)
     int slot = 0;                      // slot of the last batch
+    ByteBuf gz_slot[2][2];             // [records, error profile][slot]: the BGZF image of the plain one, made by ns_gz_result (ns_gz.h)
+    uint64_t gz_bytes[2] = {0, 0};     // ... its size for the last batch (0: not made)
     IoEngine *io = nullptr;            // copy stream, staging slices, writer threads (created by the first ns_sink_open)
     std::vector<ns_sink *> sinks;
     ByteBuf ord_bins;                // k_order_*: histogram + cursors of the visiting-order bins, then n_multi and k_chain's priority thresholds
@@ -3845,6 +3848,7 @@ int ns_generate(ns_ctx *ctx, const ns_params *prm, ns_batch_info *info) {
     const size_t n = (size_t)prm->n_reads;
     memset(info, 0, sizeof *info);
     ctx->has_batch = false;
+    ctx->gz_bytes[0] = ctx->gz_bytes[1] = 0;
     if (!n) { ctx->last = *info; ctx->has_batch = true; return NS_OK; }
     GenArgs A;
     if ((rc = batch_args(ctx, prm, n, A))) return rc;
@@ -3939,6 +3943,8 @@ static int result_buf(ns_ctx *ctx, int which, const void **p, uint64_t *size) {
         case NS_BUF_ERRLOG: *p = ctx->err_slot[ctx->slot].data(); *size = b.errlog_bytes; return NS_OK;
         case NS_BUF_POLYA: *p = ctx->polya.data(); *size = ctx->polya.data() ? b.n_reads * 2 : 0; return NS_OK;
         case NS_BUF_SPLICED: *p = ctx->spliced.data(); *size = ctx->spliced_bytes; return NS_OK;
+        case NS_BUF_RECORDS_GZ: *p = ctx->gz_slot[0][ctx->slot].data(); *size = ctx->gz_bytes[0]; return NS_OK;
+        case NS_BUF_ERRLOG_GZ: *p = ctx->gz_slot[1][ctx->slot].data(); *size = ctx->gz_bytes[1]; return NS_OK;
         default: return NS_EINVAL;
     }
 }
@@ -4007,7 +4013,8 @@ int ns_sink_write_range(ns_ctx *ctx, ns_sink *s, int which, uint64_t offset, uin
     if (!ctx) return NS_EINVAL;
     if (!own_sink(ctx, s)) return fail(ctx, NS_EINVAL, "unknown sink");
     if (!ctx->has_batch) return fail(ctx, NS_ESTATE, "no batch to write");
-    if (which != NS_BUF_RECORDS && which != NS_BUF_ERRLOG) return fail(ctx, NS_EINVAL, "ns_sink_write: records or error profile only");
+    if (which != NS_BUF_RECORDS && which != NS_BUF_ERRLOG && which != NS_BUF_RECORDS_GZ && which != NS_BUF_ERRLOG_GZ)
+        return fail(ctx, NS_EINVAL, "ns_sink_write: records or error profile only");
     const void *p; uint64_t size;
     if (result_buf(ctx, which, &p, &size)) return fail(ctx, NS_EINVAL, "unknown buffer id");
     if (offset > size || nbytes > size - offset) return fail(ctx, NS_EINVAL, "ns_sink_write_range: range exceeds the buffer");
@@ -4084,3 +4091,4 @@ const void *ns_device_ptr(ns_ctx *ctx, int which) {
 }  // extern "C"
 
 #include "ns_train_calls.h"     // the training side: the host half of its calls, none of which the driver above uses
+#include "ns_gz_calls.h"        // compressed output: the host half of its calls

@@ -14,6 +14,10 @@ from .model import (EVENT_DTYPE, PIECE_DTYPE, READ_DTYPE, Model, NsBatchInfo, Ns
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NANOSIM_AMD_LIB") or os.path.join(_HERE, "libnanosim_amd.so")   # override: A/B builds only
 NS_BUF_RECORDS, NS_BUF_READS, NS_BUF_PIECES, NS_BUF_EVENTS, NS_BUF_ERRLOG, NS_BUF_POLYA, NS_BUF_SPLICED = 0, 1, 2, 3, 4, 5, 6
+NS_BUF_RECORDS_GZ, NS_BUF_ERRLOG_GZ = 7, 8          # the BGZF images that Batch.gz makes of the two plain ones
+GZ_OF = {NS_BUF_RECORDS: NS_BUF_RECORDS_GZ, NS_BUF_ERRLOG: NS_BUF_ERRLOG_GZ}
+NS_GZ_BLOCK_BYTES, NS_GZ_HEADER_BYTES = 16384, 240
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")      # the empty member that ends a BGZF file
 NS_SPLICED_BASE = 1 << 56
 NS_EINVAL, NS_ENODEV, NS_ENOMEM, NS_EHIP, NS_ESTATE, NS_EIO, NS_ESTEP_UNALIGNED = -1, -2, -3, -4, -5, -6, -7
 NS_KIND_ALIGNED, NS_KIND_UNALIGNED, NS_KIND_PERFECT = 0, 1, 2
@@ -27,12 +31,18 @@ EXPORTS = ("ns_abi_version", "ns_create", "ns_destroy", "ns_last_error", "ns_set
            "ns_sink_close", "ns_io_counters", "ns_cs_histograms", "ns_generate_step", "ns_step_context", "ns_maf_histograms",
            "ns_qual_histograms", "ns_hp_histograms", "ns_sam_pairs_build", "ns_hp_histograms_sam", "ns_mixture_fit", "ns_read_lengths",
            "ns_cigar_spans", "ns_chimeric_select", "ns_em_quantify", "ns_ir_train", "ns_maf_besthit", "ns_bam_to_sam",
-           "ns_calmd", "ns_sam_index")
+           "ns_calmd", "ns_sam_index", "ns_gz_code_build", "ns_gz_bound", "ns_gz_histogram", "ns_gz_bytes", "ns_gz_result")
 
 
 class NsIoStats(C.Structure):
     _fields_ = [("bytes", C.c_uint64), ("dma_ms", C.c_double), ("wait_staging_s", C.c_double), ("write_s", C.c_double),
                 ("slice_bytes", C.c_uint64), ("n_slices", C.c_uint32), ("n_threads", C.c_uint32)]
+
+
+class NsGzCode(C.Structure):
+    """ns_gz_code: one Huffman code of literals and end-of-block, and the header of its dynamic deflate block (include/nanosim_amd.h)"""
+    _fields_ = [("len", C.c_uint8 * 257), ("code", C.c_uint16 * 257), ("header_bits", C.c_uint32), ("header", C.c_uint8 * NS_GZ_HEADER_BYTES)]
+
 
 _lib = None
 
@@ -134,12 +144,47 @@ def load_library(path: str = LIB_PATH):
     L.ns_calmd.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.c_uint32, C.c_void_p]
     L.ns_sam_index.restype = C.c_int
     L.ns_sam_index.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.ns_gz_code_build.restype = C.c_int
+    L.ns_gz_code_build.argtypes = [C.c_void_p, C.POINTER(NsGzCode)]
+    L.ns_gz_bound.restype = C.c_uint64
+    L.ns_gz_bound.argtypes = [C.c_uint64, C.c_uint32]
+    L.ns_gz_histogram.restype = C.c_int
+    L.ns_gz_histogram.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.ns_gz_bytes.restype = C.c_int
+    L.ns_gz_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(NsGzCode), C.c_void_p, C.c_uint64, C.c_void_p]
+    L.ns_gz_result.restype = C.c_int
+    L.ns_gz_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(NsGzCode), C.c_void_p]
     L.ns_generate_step.restype = C.c_int
     L.ns_generate_step.argtypes = [C.c_void_p, C.POINTER(NsParams), C.POINTER(NsParams), C.POINTER(NsBatchInfo)]
     L.ns_step_context.restype = C.c_int
     L.ns_step_context.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     _lib = L
     return L
+
+
+def build_gz_code(hist) -> NsGzCode:
+    """The code of a compressed stream from the counts of its 256 byte values (ns_gz_code_build): no engine and no GPU."""
+    h = np.ascontiguousarray(hist, dtype=np.uint64)
+    if h.shape != (256,):
+        raise ValueError("a histogram has 256 counts")
+    code = NsGzCode()
+    rc = load_library().ns_gz_code_build(h.ctypes.data, C.byref(code))
+    if rc != 0:
+        raise EngineError("ns_gz_code_build failed with %d" % rc)
+    return code
+
+
+def gz_header_member(data: bytes) -> bytes:
+    """`data` (less than 64 KiB: a header line) as BGZF members made on the host, for what does not come from the device"""
+    import zlib
+    out = b""
+    for at in range(0, len(data), 0xff00):
+        chunk = data[at:at + 0xff00]
+        z = zlib.compressobj(6, zlib.DEFLATED, -15)
+        body = z.compress(chunk) + z.flush()
+        out += (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + (len(body) + 25).to_bytes(2, "little") + body
+                + zlib.crc32(chunk).to_bytes(4, "little") + len(chunk).to_bytes(4, "little"))
+    return out
 
 
 class Sink:
@@ -221,6 +266,20 @@ class Batch:
         rec, err = np.zeros(len(idx), dtype=np.uint64), np.zeros(len(idx), dtype=np.uint64)
         self.eng._check(self.eng.L.ns_record_offsets(self.eng.ctx, idx.ctypes.data, len(idx), rec.ctypes.data, err.ctypes.data))
         return rec, err
+
+    def gz_histogram(self, which: int) -> np.ndarray:
+        """the counts of the 256 byte values in the record image (NS_BUF_RECORDS) or the error-profile image (NS_BUF_ERRLOG)"""
+        h = np.zeros(256, dtype=np.uint64)
+        self.eng._check(self.eng.L.ns_gz_histogram(self.eng.ctx, which, h.ctypes.data))
+        return h
+
+    def gz(self, which: int, cuts, code: NsGzCode | None = None) -> np.ndarray:
+        """Makes the BGZF image of the plain image `which` (ns_gz_result): every range [cuts[i], cuts[i + 1]) of its bytes becomes whole
+        members.  Returns where the members of every range begin in the buffer GZ_OF[which]; the last entry is its size."""
+        c = np.ascontiguousarray(cuts, dtype=np.uint64)
+        off = np.zeros(len(c), dtype=np.uint64)
+        self.eng._check(self.eng.L.ns_gz_result(self.eng.ctx, which, c.ctypes.data, len(c), C.byref(code) if code is not None else None, off.ctypes.data))
+        return off
 
     def kernel_ms(self):
         return {KERNEL_NAMES[i]: float(self.info.ms_kernel[i]) for i in range(len(KERNEL_NAMES))}
@@ -382,6 +441,20 @@ class Engine:
         return dict(bytes=int(st.bytes), dma_ms=float(st.dma_ms), wait_staging_s=float(st.wait_staging_s), write_s=float(st.write_s),
                     d2h_gbs=(st.bytes / (st.dma_ms * 1e-3) / 1e9) if st.dma_ms > 0 else None,
                     slice_bytes=int(st.slice_bytes), n_slices=int(st.n_slices), n_threads=int(st.n_threads))
+
+    def gz_bytes(self, data, cuts=None, code: NsGzCode | None = None, cap: int | None = None):
+        """BGZF members of `data` (bytes or a uint8 array), deflated on the GPU (ns_gz_bytes): every range [cuts[i], cuts[i + 1]) becomes
+        whole members (default: one range, all of it).  Returns (the members, the offsets of the ranges' members with the size last).
+        cap: the room to offer (default ns_gz_bound)."""
+        src = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        c = np.ascontiguousarray([0, len(src)] if cuts is None else cuts, dtype=np.uint64)
+        if cap is None:
+            cap = int(self.L.ns_gz_bound(len(src), max(len(c), 1) - 1))
+        dst = np.empty(max(cap, 1), dtype=np.uint8)
+        off = np.zeros(len(c), dtype=np.uint64)
+        self._check(self.L.ns_gz_bytes(self.ctx, src.ctypes.data if len(src) else None, len(src), c.ctypes.data, len(c),
+                                       C.byref(code) if code is not None else None, dst.ctypes.data, cap, off.ctypes.data))
+        return dst[:int(off[-1]) if len(off) else 0].tobytes(), off
 
     def load_model(self, model: Model):
         t = model.to_c()

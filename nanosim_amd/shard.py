@@ -148,10 +148,12 @@ def part_path(path: str, rank: int) -> str:
 def subfile_path(path: str, tag) -> str:
     """sub-file `tag` of an output file, named as the reference names its workers' sub-files (S:1594-1595, 1650):
     <out>_aligned_reads<i>.fasta, <out>_error_profile<i> (without "aligned_"), <out>_unaligned_reads<i>.fasta"""
+    gz = ".gz" if path.endswith(".gz") else ""                   # (--gzip: the suffix stays last)
+    path = path[:len(path) - len(gz)]
     head, ext = (path[:-6], path[-6:]) if path.endswith((".fasta", ".fastq")) else (path, "")
     if head.endswith("_aligned_error_profile"):
         head = head[:-len("_aligned_error_profile")] + "_error_profile"
-    return "%s%s%s" % (head, tag, ext)
+    return "%s%s%s%s" % (head, tag, ext, gz)
 
 
 def clean_parts(paths, rank: int) -> None:

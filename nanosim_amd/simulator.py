@@ -8,7 +8,8 @@ loop running on MI355X through the C-ABI (include/nanosim_amd.h).
 Differences a user can see: ``--seed`` is honoured (the reference re-seeds from the OS in
 ``simulation()``, S:1591-1592, so its --seed has no effect); read numbers are the read's index (no gaps);
 ``-t K`` keeps the reference's meaning for the OUTPUT (K sub-files written side by side, then concatenated, S:1588-1639) while GPUs,
-not processes, do the work (run under ``torch.distributed.run`` for several GPUs).
+not processes, do the work (run under ``torch.distributed.run`` for several GPUs).  ``--gzip`` (not in the reference) writes every
+output as a BGZF ``.gz`` file whose bytes are deflated on the GPU before they are copied ("BGZF output").
 """
 from __future__ import annotations
 
@@ -39,6 +40,9 @@ def log(msg):
 MERGE_HELP = ("Not in the reference: with several ranks (one process per GPU) concatenate every rank's sub-files into ONE file per output, "
               "as the reference's workers do (S:1626-1639).  Off by default when WORLD_SIZE > 1: rank 0 would append terabytes through one "
               "inode at 6-10 GB/s after minutes of GPU work; <file>.subfiles lists the parts in order (cat $(cat <file>.subfiles) = <file>)")
+GZIP_HELP = ("Not in the reference: write BGZF-compressed outputs (<out>_aligned_reads.fasta.gz / .fastq.gz, <out>_unaligned_reads.*.gz, "
+             "<out>_aligned_error_profile.gz; sub-files likewise).  The bytes are deflated on the GPU before they cross PCIe; zcat, gzip, bgzip and "
+             "htslib read the files, and cat of the parts listed in <file>.subfiles is again one valid file")
 NO_MERGE_HELP = ("Not in the reference: with -t K > 1 (or several ranks) keep the sub-files the workers wrote side by side and list them in "
                  "<file>.subfiles (cat $(cat <file>.subfiles) = <file>) instead of concatenating them into one file as the reference does "
                  "(S:1626-1639).  Writes into ONE inode serialise in the kernel (5.7 GB/s on the measured box): the merge, not the GPU, sets "
@@ -81,6 +85,7 @@ def build_parser():
     g.add_argument('-t', '--num_threads', type=int, default=1, help='Number of threads for simulation (Default = 1)')
     g.add_argument('--no-merge', dest='no_merge', action='store_true', default=False, help=NO_MERGE_HELP)
     g.add_argument('--merge', dest='merge', action='store_true', default=False, help=MERGE_HELP)
+    g.add_argument('--gzip', dest='gzip', action='store_true', default=False, help=GZIP_HELP)
 
     t = sub.add_parser('transcriptome', help="Run the simulator on transcriptome mode")
     t.add_argument('-rt', '--ref_t', required=True)
@@ -104,6 +109,7 @@ def build_parser():
     t.add_argument('-t', '--num_threads', type=int, default=1)
     t.add_argument('--no-merge', dest='no_merge', action='store_true', default=False, help=NO_MERGE_HELP)
     t.add_argument('--merge', dest='merge', action='store_true', default=False, help=MERGE_HELP)
+    t.add_argument('--gzip', dest='gzip', action='store_true', default=False, help=GZIP_HELP)
     t.add_argument('--uracil', action='store_true', default=False)
 
     mg = sub.add_parser('metagenome', help="Run the simulator on metagenome mode")
@@ -127,6 +133,7 @@ def build_parser():
     mg.add_argument('-t', '--num_threads', type=int, default=1)
     mg.add_argument('--no-merge', dest='no_merge', action='store_true', default=False, help=NO_MERGE_HELP)
     mg.add_argument('--merge', dest='merge', action='store_true', default=False, help=MERGE_HELP)
+    mg.add_argument('--gzip', dest='gzip', action='store_true', default=False, help=GZIP_HELP)
     return parser, g, mg, t
 
 
@@ -317,8 +324,19 @@ def _run_phases(aligned, unaligned, rank, n_done, step_owner=None):
         sys.stdout.flush()
 
 
+def _gz_end_of_file(path, keep):
+    """--gzip, rank 0, once every part of `path` is in place: the 28-byte BGZF end-of-file block behind the last byte — of the merged
+    file, or of the last part that <path>.subfiles lists"""
+    last = path
+    if keep and os.path.exists(path + ".subfiles"):
+        names = [x for x in open(path + ".subfiles").read().split("\n") if x]
+        last = names[-1] if names else path
+    with open(last, "ab") as f:
+        f.write(E.BGZF_EOF)
+
+
 def _write_batches(eng, out_path, err_path, params, *, first, count, err_header=b"", dist=None, stripes=1, quiet=False, tag="",
-                   batch_reads=None, gen=None):
+                   batch_reads=None, gen=None, gz=False):
     """Reads [first, first + count) of this rank into out_path (and their error-profile rows into err_path), through the engine's output
     sinks (include/nanosim_amd.h: ns_sink_*): the images of batch i leave the GPU and reach the files while batch i + 1 is generated.
     params: what every worker call of the phase has in common, as keywords of E.make_params (seed, kind, lengths, mode flags).
@@ -331,7 +349,11 @@ def _write_batches(eng, out_path, err_path, params, *, first, count, err_header=
     Several ranks: a rank that is done publishes the list of its sub-files (shard.publish_parts); rank 0 appends them in rank order as they
     appear (shard.collect_parts) — no collective, and a rank that fails leaves a marker instead of a hanging peer.
     quiet: no progress line on stdout (the worker call that runs on the background context, _run_phases).
-    gen: what generates a batch from its parameters (StepPair.aligned / .unaligned); None: eng.generate."""
+    gen: what generates a batch from its parameters (StepPair.aligned / .unaligned); None: eng.generate.
+    gz (--gzip; the paths end in .gz): every range that would be queued is deflated on the GPU into whole BGZF members first (Batch.gz, with
+    the cuts of record_offsets) and the ranges of the compressed images are queued instead.  The code of an output is built once, from the
+    byte counts of the first batch that has bytes, and serves every later batch: a block it fits badly, or that has a byte it lacks, is
+    stored.  The error profile's header line is a member of its own, made on the host; rank 0 ends every file with the end-of-file block."""
     rank = dist.get_rank() if dist is not None else 0
     stripes = _cap_stripes(stripes, len([p for p in (out_path, err_path) if p]))
     world = dist.get_world_size() if dist is not None else 1
@@ -340,6 +362,17 @@ def _write_batches(eng, out_path, err_path, params, *, first, count, err_header=
     batch = min(getattr(eng, "_batch_reads", BATCH_READS), batch_reads or BATCH_READS)
     paths = [p for p in (out_path, err_path) if p]
     which = {out_path: E.NS_BUF_RECORDS, err_path: E.NS_BUF_ERRLOG}
+    codes = {}                                               # gz: the code of each output
+    if gz and err_header:
+        err_header = E.gz_header_member(err_header)
+
+    def gz_offsets(b, p, cuts):
+        """the compressed image of output p's plain one, cut at the byte offsets `cuts`: where the members of every range begin"""
+        if p not in codes:
+            h = b.gz_histogram(which[p])
+            if h.any():
+                codes[p] = E.build_gz_code(h)
+        return b.gz(which[p], cuts, codes.get(p))
     files = {p: [] for p in paths}                           # what holds this rank's bytes of p, in order
     open_now, prev = [], []                                  # (sink, fd) of the batch being queued / of the batch before it
     single = {}                                              # stripes == 1: the one sink per output
@@ -385,12 +418,22 @@ def _write_batches(eng, out_path, err_path, params, *, first, count, err_header=
                 batch = eng._batch_reads = max(1000, n // 2)
                 continue
             t1 = time.perf_counter()
+            sizes = {out_path: int(b.info.record_bytes), err_path: int(b.info.errlog_bytes)}
             if stripes == 1:
                 for p in paths:
-                    single[p].write(which[p])
+                    if gz:
+                        sizes[p] = int(gz_offsets(b, p, [0, sizes[p]])[-1])
+                        single[p].write(E.GZ_OF[which[p]])
+                    else:
+                        single[p].write(which[p])
             else:
                 cuts = sorted({k * n // stripes for k in range(stripes + 1)})
                 offs = dict(zip(paths, b.record_offsets(cuts)))
+                buf = which
+                if gz:
+                    offs = {p: gz_offsets(b, p, offs[p]) for p in paths}
+                    buf = {p: E.GZ_OF[which[p]] for p in paths}
+                    sizes = {p: int(offs[p][-1]) for p in paths}
                 for lo, hi in zip(range(len(cuts) - 1), range(1, len(cuts))):
                     for p in paths:
                         name = shard.subfile_path(p, n_sub if world == 1 else "%d_%d" % (rank, n_sub))
@@ -400,7 +443,7 @@ def _write_batches(eng, out_path, err_path, params, *, first, count, err_header=
                         files[p].append(name)
                         if p == err_path and err_header and rank == 0 and n_sub == 0:
                             sk.put(err_header)
-                        sk.write(which[p], int(offs[p][lo]), int(offs[p][hi] - offs[p][lo]))
+                        sk.write(buf[p], int(offs[p][lo]), int(offs[p][hi] - offs[p][lo]))
                     n_sub += 1
                 close_all(prev)                      # the batch before this one is in its files; this one's copies are under way
                 prev, open_now = open_now, []
@@ -410,7 +453,7 @@ def _write_batches(eng, out_path, err_path, params, *, first, count, err_header=
                 # slot, the wait for a slot whose last batch is still crossing PCIe); kernels: the sum of the kernel phases alone
                 sys.stderr.write("[cli%s] batch %d reads: generate %.1f ms (device %.1f, kernels %.1f), %.2f GB queued; so far %.2f GB copied at %s GB/s (DMA), copier waited "
                                  "%.2f s for staging, writers %.2f s in pwrite\n"
-                                 % (tag, n, (t1 - t0) * 1e3, b.info.ms_total, sum(float(x) for x in b.info.ms_kernel), (int(b.info.record_bytes) + int(b.info.errlog_bytes)) / 1e9, c["bytes"] / 1e9,
+                                 % (tag, n, (t1 - t0) * 1e3, b.info.ms_total, sum(float(x) for x in b.info.ms_kernel), sum(sizes[p] for p in paths) / 1e9, c["bytes"] / 1e9,
                                     "%.1f" % c["d2h_gbs"] if c["d2h_gbs"] else "-", c["wait_staging_s"], c["write_s"]))
             done += n
             if rank == 0 and not quiet:
@@ -441,6 +484,8 @@ def _write_batches(eng, out_path, err_path, params, *, first, count, err_header=
             sys.stdout.write('\n')
         for p in paths:
             shard.collect_parts(p, world, files[p], keep=keep)
+            if gz:
+                _gz_end_of_file(p, keep)
 
 
 class _Run:
@@ -468,7 +513,8 @@ class _Run:
         self.keep = None                                          # the broadcast bases on this GPU, while an engine may still copy them
 
     def outputs(self, base):
-        return [base + "_aligned_reads" + self.ext, base + "_aligned_error_profile", base + "_unaligned_reads" + self.ext]
+        gz = ".gz" if getattr(self.a, "gzip", False) else ""
+        return [base + "_aligned_reads" + self.ext + gz, base + "_aligned_error_profile" + gz, base + "_unaligned_reads" + self.ext + gz]
 
     def broadcast(self, ref, extra=None, outputs=(), error=None):
         """Rank 0's reference, its seed and the mode's small tables `extra` (a dict) for every rank: returns (ref, extra).  error: rank
@@ -551,11 +597,11 @@ class _Run:
         def aligned(gen=None):
             _write_batches(self.eng, out_al, out_err, dict(common, kind=E.NS_KIND_PERFECT if a.perfect else E.NS_KIND_ALIGNED, **aligned_only),
                            first=first + lo, count=hi - lo, err_header=ERR_HEADER, dist=self.dist, stripes=stripes, tag=" aligned",
-                           batch_reads=b_al, gen=gen)
+                           batch_reads=b_al, gen=gen, gz=getattr(a, "gzip", False))
 
         def unaligned(gen=None, quiet=True):                                                    # S:1642-1672
             _write_batches(self.eng_un, out_un, None, dict(common, kind=E.NS_KIND_UNALIGNED), first=first + n_al + ulo, count=uhi - ulo,
-                           dist=self.dist, stripes=stripes, quiet=quiet, tag=" unaligned", batch_reads=b_un, gen=gen)
+                           dist=self.dist, stripes=stripes, quiet=quiet, tag=" unaligned", batch_reads=b_un, gen=gen, gz=getattr(a, "gzip", False))
         if a.perfect:
             aligned()
         elif not side_by_side:
