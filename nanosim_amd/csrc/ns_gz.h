@@ -142,7 +142,7 @@ static inline int gz_code_build(const uint64_t hist[256], ns_gz_code *out) {
     uint32_t cl_used = 0;
     for (uint32_t t = 0; t < n_tok; ++t) cl_freq[tok[t]]++;
     for (uint32_t s = 0; s < 19; ++s) cl_used += cl_freq[s] != 0;
-    if (cl_used == 1) cl_freq[cl_freq[0] ? 1 : 0] = 1;               // (inflate wants a complete code-length code: a second symbol, never used)
+    if (cl_used == 1) cl_freq[cl_freq[0] ? 1 : 0] = 1;               // (inflate wants a complete code-length code: a second symbol, never used.  Not reached from here: end-of-block's length and the 0 of the distance code are always two tokens)
     gz_huff_lengths(cl_freq, 19, 7, cl_len);
     gz_canonical(cl_len, 19, 7, cl_code);
     static const uint8_t cl_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
@@ -310,6 +310,15 @@ template <class W> NS_CSH uint32_t gz_member(W &w, const GzTabs &T, const uint8_
     for (uint32_t j = head + 4u * words + w.lane; j < L.member; j += GZ_LANES) dst[j] = sb[j];
     return L.member;
 }
+// the blocks of a call (host and device: tests/gz_wave_host.cpp walks them on the CPU): range r = [cuts[r], cuts[r + 1]) has the blocks first[r] .. first[r + 1), NS_GZ_BLOCK_BYTES each but the last
+struct GzBlocks { const unsigned long long *cuts; const uint32_t *first; uint32_t n_ranges, n_blk; };
+NS_CSH void gz_block_at(const GzBlocks &B, uint32_t g, uint64_t &off, uint32_t &n) {
+    uint32_t lo = 0, hi = B.n_ranges - 1u;                           // the last range whose first block is not behind g
+    while (lo < hi) { const uint32_t mid = lo + (hi - lo + 1u) / 2u; if (B.first[mid] <= g) lo = mid; else hi = mid - 1u; }
+    off = B.cuts[lo] + (uint64_t)(g - B.first[lo]) * NS_GZ_BLOCK_BYTES;
+    const uint64_t left = B.cuts[lo + 1u] - off;
+    n = left < NS_GZ_BLOCK_BYTES ? (uint32_t)left : NS_GZ_BLOCK_BYTES;
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // the kernels
@@ -329,15 +338,6 @@ struct GzWaveDev {
     __device__ __forceinline__ uint32_t shfl(uint32_t v, uint32_t src) const { return (uint32_t)__shfl((int)v, (int)(src & 63u), 64); }
     __device__ __forceinline__ void fence() const { __threadfence_block(); }
 };
-// the blocks of a call: range r = [cuts[r], cuts[r + 1]) has the blocks first[r] .. first[r + 1), NS_GZ_BLOCK_BYTES each but the last
-struct GzBlocks { const unsigned long long *cuts; const uint32_t *first; uint32_t n_ranges, n_blk; };
-__device__ __forceinline__ void gz_block_at(const GzBlocks &B, uint32_t g, uint64_t &off, uint32_t &n) {
-    uint32_t lo = 0, hi = B.n_ranges - 1u;                           // the last range whose first block is not behind g
-    while (lo < hi) { const uint32_t mid = lo + (hi - lo + 1u) / 2u; if (B.first[mid] <= g) lo = mid; else hi = mid - 1u; }
-    off = B.cuts[lo] + (uint64_t)(g - B.first[lo]) * NS_GZ_BLOCK_BYTES;
-    const uint64_t left = B.cuts[lo + 1u] - off;
-    n = left < NS_GZ_BLOCK_BYTES ? (uint32_t)left : NS_GZ_BLOCK_BYTES;
-}
 // the counts of the byte values of src[0 .. n): 256 counters per workgroup in LDS, one global add per counter and workgroup.  src is
 // 4-byte aligned; every workgroup takes whole words at a grid stride, the last bytes go to the first thread
 __global__ void __launch_bounds__(256) k_gz_hist(const uint8_t *__restrict__ src, uint64_t n, unsigned long long *__restrict__ hist) {

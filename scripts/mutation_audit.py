@@ -12,6 +12,8 @@ the mutants the tests did not notice.
     python scripts/mutation_audit.py --chain            ns_pack.h and the thread-per-read part of ns_chain.h, on tests/chain_host.hip
     python scripts/mutation_audit.py --chain-wave       the wave-per-read part of ns_chain.h, on tests/chain_wave_host.hip (64 host threads
                                                         per mutant: --jobs 2)
+    python scripts/mutation_audit.py --gz               ns_gz.h (the code builder and the block walk of the compressed output) on
+                                                        tests/gz_wave_host.cpp, 64 host threads per mutant like --chain-wave
 
 Mutation classes: rel   `<` <-> `<=`, `>` <-> `>=`                                   (the default)
                   lit   an integer literal inside a condition or an index expression, +1 and -1
@@ -70,7 +72,10 @@ CHAIN = {
 # the wave-per-read chains (ns_chain.h from the DEVICE_ONLY_FROM marker on) on the lock-step wavefront of tests/wave64_host.h; the test file
 # has its edge tests first
 CHAIN_WAVE = {CSRC + "ns_chain.h": ("tests/chain_wave_host.hip", ["tests/test_chain_wave64.py"])}
-UNITS = {**TRAINING, **CHAIN}
+# the compressed output: the code builder and the block walk of ns_gz.h in the g++ program of tests/gz_wave_host.cpp (the kernels behind
+# `#if defined(__HIPCC__)` are listed apart); the builder's file first: it is the cheaper one and decides most mutants
+GZ = {CSRC + "ns_gz.h": ("tests/gz_wave_host.cpp", ["tests/test_gz_code_fuzz.py", "tests/test_gz_wave64.py"])}
+UNITS = {**TRAINING, **CHAIN, **GZ}
 # header -> the text from the first line that holds this marker to the end of the file is `__device__` only
 DEVICE_ONLY_FROM = {CSRC + "ns_chain.h": "// ---- cooperative unaligned_error_list"}
 SKIP_DIRS = {".git", "__pycache__", "_tmp", ".pytest_cache"}
@@ -310,6 +315,7 @@ def main():
     ap.add_argument("--all", action="store_true", help="the training headers with their CPU test files")
     ap.add_argument("--chain", action="store_true", help="ns_pack.h and the thread-per-read part of ns_chain.h with the chain's CPU test files")
     ap.add_argument("--chain-wave", action="store_true", help="the wave-per-read part of ns_chain.h on the 64-lane host build, with tests/test_chain_wave64.py")
+    ap.add_argument("--gz", action="store_true", help="ns_gz.h on the 64-lane host program, with tests/test_gz_code_fuzz.py and tests/test_gz_wave64.py")
     ap.add_argument("--classes", default="rel", help="comma-separated: rel, lit, logic (default rel)")
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
     ap.add_argument("--timeout", type=float, default=300.0, help="seconds per mutant, at most (the limit in use follows the unmutated run's time)")
@@ -318,21 +324,21 @@ def main():
     classes = [c for c in a.classes.split(",") if c]
     if not classes or set(classes) - {"rel", "lit", "logic"}:
         ap.error("classes are rel, lit and logic")
-    if (a.all or a.chain or a.chain_wave) == bool(a.header):
-        ap.error("give a header with its tests, or --all, or --chain, or --chain-wave")
+    if (a.all or a.chain or a.chain_wave or a.gz) == bool(a.header):
+        ap.error("give a header with its tests, or --all, or --chain, or --chain-wave, or --gz")
     if a.chain_wave and (a.all or a.chain):
         ap.error("--chain-wave audits the other part of a header --chain audits: run it on its own")
     if a.chain_wave:
         plan = [(h, u, t) for h, (u, t) in CHAIN_WAVE.items()]
-    elif a.all or a.chain:
-        plan = [(h, u, t) for h, (u, t) in {**(TRAINING if a.all else {}), **(CHAIN if a.chain else {})}.items()]
+    elif a.all or a.chain or a.gz:
+        plan = [(h, u, t) for h, (u, t) in {**(TRAINING if a.all else {}), **(CHAIN if a.chain else {}), **(GZ if a.gz else {})}.items()]
     else:
         h = os.path.relpath(os.path.abspath(a.header), ROOT)
         if not a.tests:
             ap.error("no test file given")
         unit = UNITS[h][0] if h in UNITS else None
         if unit is None:
-            ap.error("%s: no host translation unit known for it (TRAINING, CHAIN)" % h)
+            ap.error("%s: no host translation unit known for it (TRAINING, CHAIN, GZ)" % h)
         plan = [(h, unit, [os.path.relpath(os.path.abspath(t), ROOT) for t in a.tests])]
     log = open(a.log, "w") if a.log else None
 

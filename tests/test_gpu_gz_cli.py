@@ -11,6 +11,7 @@ import pytest
 from nanosim_amd import engine as E
 from nanosim_amd import simulator
 from nanosim_amd.characterize import bam
+from tests import gz_lib as G
 from tests import oracle_lib as O
 
 pytestmark = pytest.mark.gpu
@@ -112,3 +113,54 @@ def test_two_batches_on_one_engine_fill_both_slots(small_model, small_ref, tmp_p
         eng.close()
     assert gzip.decompress((tmp_path / "reads.gz").read_bytes()) == b"".join(want_r)
     assert gzip.decompress((tmp_path / "errors.gz").read_bytes()) == b"".join(want_e)
+
+
+def test_images_under_codes_that_do_not_fit_equal_the_plain_encoder(small_model, small_ref):
+    """ns_gz_result on the images of two batches, held byte for byte against gz_lib.ref_members over the oracle's bytes: under the code
+    of the image's own counts; under that code without the newline, so that every block with a line end is stored; under the code of a flat histogram; with cuts at 1, 2 and 3 modulo 4 and an empty range; and twice on one batch with other
+    cuts, where the second image takes the place of the first.  The device's counts are numpy's for both images of both batches."""
+    eng = E.Engine(0)
+    try:
+        eng.set_reference(small_ref)
+        eng.load_model(small_model)
+        for k, n in enumerate((110, 170)):
+            p = E.make_params(seed=11, first_read=1000 * k, n_reads=n, fastq=True, chimeric=True, max_len=small_ref.max_chrom, emit_errlog=True)
+            b = eng.generate(p)
+            exp = O.generate(small_model, small_ref, p)
+            for which, plain in ((E.NS_BUF_RECORDS, exp["records"].tobytes()), (E.NS_BUF_ERRLOG, exp["errlog"].tobytes())):
+                size = len(plain)
+                assert size == int(b.info.record_bytes if which == E.NS_BUF_RECORDS else b.info.errlog_bytes) > 4 * G.B
+                counts = np.bincount(np.frombuffer(plain, dtype=np.uint8), minlength=256).astype(np.uint64)
+                assert b.gz_histogram(which).tolist() == counts.tolist() and counts[10] > 0
+                no_newline = counts.copy()
+                no_newline[10] = 0
+                third = size // 3
+                cut_sets = [[0, third - third % 4 + 1, 2 * third - (2 * third) % 4 + 2, size - size % 4 - 1, size - size % 4 - 1, size],
+                            [0, size], [3, 2 * G.B + 2, size - 5]]
+                assert [c % 4 for c in cut_sets[0][1:4]] == [1, 2, 3]
+                saw, ref = set(), {}
+                for name, handed in (("own", E.build_gz_code(counts)), ("no_newline", E.build_gz_code(no_newline)),
+                                     ("flat", E.build_gz_code(np.full(256, 1000, dtype=np.uint64))), ("counted", None)):
+                    code = G.plain_code(handed if handed is not None else E.build_gz_code(counts))
+                    for cuts in cut_sets:                       # (every call on this batch replaces the image of the call before)
+                        off = b.gz(which, cuts, handed)
+                        got = b.copy_range(E.GZ_OF[which], 0, np.empty(int(off[-1]), dtype=np.uint8), int(off[-1])).tobytes()
+                        assert off[0] == 0 and len(got) == int(off[-1]) <= eng.L.ns_gz_bound(size, len(cuts) - 1)
+                        for i in range(len(cuts) - 1):
+                            key = (G.code_bytes(code), cuts[i], cuts[i + 1])       # ("own" and "counted" must be one code)
+                            if key not in ref:
+                                ref[key] = G.ref_members(code, plain[cuts[i]:cuts[i + 1]])
+                            want = ref[key]
+                            assert got[int(off[i]):int(off[i + 1])] == want, (name, which, cuts, i)
+                        if name == "no_newline" and len(cuts) == 2:         # every block with a line end is a stored one
+                            at = 0
+                            for lo in range(0, size, G.B):
+                                m = G.ref_member(code, plain[lo:lo + G.B])
+                                assert got[at:at + len(m)] == m
+                                if b"\n" in plain[lo:lo + G.B]:
+                                    assert got[at + 18] == 1 and len(m) == 31 + len(plain[lo:lo + G.B])
+                                    saw.add(True)
+                                at += len(m)
+                assert saw == {True}
+    finally:
+        eng.close()
